@@ -24,11 +24,16 @@ With N GPUs the job is frame-parallel (one frame per GPU per step, weak scaling)
 the one-to-many broadcast of the newest reconstructed reference (RCCL), the seam where the reference raises
 m_reconRowFlag (framefilter.cpp:664).  Every stage is parity-tested bit-exact against the oracle (tests/ -m gpu).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line with the contract fields.  A plain run sets up, warms up, times the K steps and prints it; with
+--dump-outputs DIR it also writes what the last timed step computed (the reconstructed Y / Cb / Cr planes and the stage outputs) as
+DIR/<name>.npy.  Everything else is measured only with --full, which adds to the line
   roofline     - dominant kernel (ME surface kernel): algorithmic bytes per launch /
                  HIP-event launch time vs 8 TB/s; `traffic` = HBM bytes from the committed rocprofv3 PMC passes
   stages_ms    - HIP-event time of each stage (a separate, untimed pass)
-  cpu_baseline - the oracle's restatement of the same pipeline on the host cores (bounded CTU sample).
+  cpu_baseline - the oracle's restatement of the same pipeline on the host cores (bounded CTU sample)
+  bit_exact    - one whole frame of the device pipeline against the oracle chain, stage by stage
+  encoder_summary - the real reference encoder with and without the seams (tier T3, tools/encoder_bench.py)
+and with N > 1 the `replicas` pass and the ring's band waits; the full record goes to bench_detail.json.
 """
 import argparse
 import importlib
@@ -37,18 +42,19 @@ import os
 import sys
 import time
 
-# The encoder-level leg calls x265hip_lowres_cost_host from several lookahead threads at once, each on its own stream; the HIP runtime
-# maps streams onto 4 hardware queues by default, which serialises those latency-bound launches (5.35 instead of 5.8 fps at 4K).  Read
-# when the runtime initialises, so it is set before torch is imported; a host encoder sets it in its environment.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# The encoder-level leg (--full) calls x265hip_lowres_cost_host from several lookahead threads at once, each on its own stream; with the
+# runtime's default number of hardware queues those latency-bound launches serialise (5.35 instead of 5.8 fps at 4K).  The queue count is
+# read when the runtime initialises: whoever runs the benchmark sets it in the environment, like a host encoder.
 
 import numpy as np
 
+T_START = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 CFG_DEPTH = {"cfg1": 8, "cfg2": 8, "cfg3": 8, "cfg4": 10, "cfg5": 10}
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec
+FULL_RUN_S = 540.0         # --full: the whole run (set-up, steps, stage pass, CPU baseline, encoder legs) stays below ten minutes
 
 
 def oracle_chain(F, clip, rng_r, subme, level, qp, depth, n, cores, avx2, ref_planes=None, cur_index=1, tu_flags=2, band=None, sao_rdo=None):
@@ -143,21 +149,77 @@ def device_outputs(pipe, cur, ref):
     import torch
     rec = pipe.run(cur, ref)
     torch.cuda.synchronize()
-    dt = cur.host.dtype
+    out = stage_outputs(pipe, cur.host.dtype)
+    out["recon"] = rec.cpu().numpy().view(cur.host.dtype).reshape(cur.host.shape)
+    return out
+
+
+def stage_outputs(pipe, dt):
+    """Every stage output of the frame the whole-picture device pipeline ran last, copied to the host; dt = the sample type of the
+    pictures.  The luma reconstruction is left to the caller (the value pipe.run returned)."""
     out = {"lowres_plane%d" % i: pipe.la.planes[i].cpu().numpy().view(dt) for i in range(4)}
     out.update({"intra_cost": pipe.la.intra_cost.cpu().numpy(), "intra_mode": pipe.la.intra_mode.cpu().numpy(),
                 "lowres_costs": pipe.la.lowres_costs.cpu().numpy().view(np.uint16),
                 "me_best": pipe.ms.best.cpu().numpy().view(np.uint64), "subpel_mv": pipe.sp.out.cpu().numpy().reshape(-1, 2),
                 "levels": pipe.rc.levels.cpu().numpy(), "num_sig": pipe.rc.num_sig.cpu().numpy(), "dist": pipe.rc.dist.cpu().numpy(),
                 "sao_count": pipe.sao.count.cpu().numpy(), "sao_offset_org": pipe.sao.offset_org.cpu().numpy(),
-                "sao_params": pipe.sao.params.cpu().numpy(),
-                "recon": rec.cpu().numpy().view(dt).reshape(cur.host.shape)})
+                "sao_params": pipe.sao.params.cpu().numpy()})
     for i in range(2):
         out["sao_params_c%d" % i] = pipe.sao_c[i].params.cpu().numpy()
         out["sao_count_c%d" % i] = pipe.sao_c[i].count.cpu().numpy()
         out["levels_c%d" % i] = pipe.rc_c[i].levels.cpu().numpy()
         out["recon_c%d" % i] = pipe.final_c[i].cpu().numpy().view(dt)
     return out
+
+
+DUMP_BYTES = 64_000_000 - (1 << 16)      # --dump-outputs: at most 64 MB in all (less room for the .npy headers)
+DUMP_SAMPLE = 1 << 16                    # a stage output larger than this many values is written as a fixed, seeded sample of them
+
+
+def _exact_float(a):
+    """An integer array as floats that hold every value exactly: float32 up to 16-bit integers, float64 for 32-bit ones, and
+    64-bit words (packed records) as their two 32-bit halves, low half first."""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f":
+        return a.astype(np.float64 if a.itemsize > 4 else np.float32)
+    if a.itemsize == 8:
+        a = a.view(np.uint32).reshape(a.shape + (2,))
+    return a.astype(np.float32 if a.itemsize <= 2 else np.float64)
+
+
+def _sample(a, n):
+    """a itself when it has at most n values, else n of its values (flattened) at indices that depend on a.size and n only."""
+    if a.size <= n:
+        return a
+    idx = np.sort(np.random.default_rng(265).choice(a.size, n, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def picture_planes(F, planes, pic, dt):
+    """[Y, Cb, Cr] device planes of a picture with pic's geometry -> the host arrays of the coded picture area (w64 x h64 luma,
+    4:2:0 chroma), the border margins around it left out."""
+    my, mx, cy, cx = F.MARGIN_Y, F.MARGIN_X, F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_X
+    out = {"recon_y": planes[0].cpu().numpy().view(dt).reshape(-1, pic.stride)[my:my + pic.h64, mx:mx + pic.w64]}
+    for name, p in zip(("recon_cb", "recon_cr"), planes[1:3]):
+        out[name] = p.cpu().numpy().view(dt).reshape(-1, pic.stride_c)[cy:cy + pic.h64 // 2, cx:cx + pic.w64 // 2]
+    return out
+
+
+def write_outputs(path, planes, stages):
+    """--dump-outputs: what the last timed step computed, as path/<name>.npy in float32 / float64 (exact), DUMP_BYTES at most: the stage
+    outputs first (each larger one as a DUMP_SAMPLE-value sample), then the reconstructed planes - whole when they fit in what is left,
+    else the same share of each as a sample."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: _sample(_exact_float(v), DUMP_SAMPLE) for k, v in stages.items()}
+    left = DUMP_BYTES - sum(a.nbytes for a in arrays.values())
+    pl = {k: _exact_float(v) for k, v in planes.items()}
+    total = sum(a.nbytes for a in pl.values())
+    if total > left:
+        pl = {k: _sample(a, int(a.size * left / total)) for k, a in pl.items()}
+    arrays.update(pl)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def compare_outputs(dev_out, cpu_out):
@@ -425,7 +487,7 @@ def encoder_leg(args, timeout_s=None):
     "encoder_summary": ..}."""
     import subprocess
     import tempfile
-    timeout_s = timeout_s or float(os.environ.get("X265HIP_ENCODER_TIMEOUT_S", "900"))
+    timeout_s = float(os.environ.get("X265HIP_ENCODER_TIMEOUT_S", timeout_s or 900))
     fd, path = tempfile.mkstemp(prefix="x265hip_encoder_", suffix=".json")
     os.close(fd)
     enc, err = {}, None
@@ -509,9 +571,10 @@ def _pick(d, keys):
     return {k: d[k] for k in keys if isinstance(d, dict) and k in d}
 
 
-def compact_line(out, minimal=False):
+def compact_line(out, minimal=False, detail=True):
     """The ONE line rank 0 prints: the contract's fields plus `roofline`, `cpu_baseline`, `bit_exact` and the encoder summary, numbers
-    and short labels only - below MAX_LINE_BYTES by construction (tests/test_bench_line.py).  `minimal` drops the optional objects."""
+    and short labels only - below MAX_LINE_BYTES by construction (tests/test_bench_line.py).  `minimal` drops the optional objects; `detail` =
+    the record was also written to bench_detail.json (--full)."""
     cfg = out.get("config", {})
     line = _pick(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"))
     c = {"workload": str(cfg.get("workload", ""))[:200], "parallelism": str(cfg.get("parallelism", ""))[:120]}
@@ -521,11 +584,12 @@ def compact_line(out, minimal=False):
     line["config"] = c
     if "replicas" in out:
         line["replicas"] = _pick(out["replicas"], ("value", "ms_per_step", "unit"))
-    r = out.get("roofline") or {}
-    rl = _pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "frac_traffic", "launch_ms"))
-    if isinstance(r.get("valu"), dict):
-        rl["valu"] = _pick(r["valu"], ("floor_ms", "frac"))
-    line["roofline"] = rl
+    if "roofline" in out:                     # --full
+        r = out["roofline"] or {}
+        rl = _pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "frac_traffic", "launch_ms"))
+        if isinstance(r.get("valu"), dict):
+            rl["valu"] = _pick(r["valu"], ("floor_ms", "frac"))
+        line["roofline"] = rl
     if "cpu_baseline" in out:
         cb = _pick(out["cpu_baseline"], ("value", "unit", "cores", "kind", "one_thread_value"))
         cb["sample"] = str(out["cpu_baseline"].get("sample", ""))[:160]
@@ -539,7 +603,8 @@ def compact_line(out, minimal=False):
             line["stages_ms"] = {k[:24]: v for k, v in list(out["stages_ms"].items())[:16]}
         if "encoder_summary" in out:
             line["encoder_summary"] = out["encoder_summary"]
-        line["detail"] = "bench_detail.json"
+        if detail:
+            line["detail"] = "bench_detail.json"
     return line
 
 
@@ -692,6 +757,15 @@ def main():
     ap.add_argument("--lookahead-probe", action="store_true",
                     help="instead of the pipeline line, time the lookahead P-frame cost estimate (x265hip_lowres_cost) for one picture and "
                          "for batches of independent pictures on separate streams, CPU restatement beside it (tools/lookahead_probe.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline: the per-stage HIP-event pass and the "
+                         "roofline, the CPU baseline and the bit-exact comparison with the oracle chain, the encoder-level leg, with N > 1 the "
+                         "replicas pass and the ring's band waits; the full record goes to bench_detail.json.  The --no-* switches above "
+                         "leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed - the reconstructed Y / Cb / Cr picture and (whole-picture pipeline, exhaustive "
+                         "search) every stage output - as DIR/<name>.npy, float32 / float64 holding the values exactly, 64 MB at most "
+                         "(larger outputs as fixed, seeded samples); the inputs are the same from run to run for the same arguments")
     args, rest = ap.parse_known_args()
     if args.prims or args.search_probe or args.lookahead_probe:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -856,7 +930,7 @@ def main():
     gc.disable()
     for i in range(args.warmup):
         step(i)
-    if banded and world > 1 and not stub:
+    if banded and world > 1 and not stub and args.full:
         ring.time_waits()                            # two device events per band: how long its stream waits for the reference rows it reads
     pipe.launch_lookahead_costs()                    # no lookahead work of the warm-up frames leaks into the timed region
     torch.cuda.synchronize()
@@ -879,8 +953,15 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed, written before anything below runs the pipeline again
+        sample_type = pics[0].host.dtype
+        stage_out = {}
+        if not banded and not stub and args.search == "full":
+            stage_out = {k: v for k, v in stage_outputs(pipe, sample_type).items() if not k.startswith("recon")}
+        write_outputs(args.dump_outputs, picture_planes(F, bp.final_planes() if banded else pipe.final_planes(), pics[0], sample_type), stage_out)
     replicas = None
-    if world > 1 and not gop and not args.no_replicas:
+    if args.full and world > 1 and not gop and not args.no_replicas:
         # the comparison line beside the ring (round-4 verdict, next 6): the same K steps with NO exchange - every rank its own closed
         # group of pictures (what --sharding gop times) - so the first hardware record shows ring and replicas side by side
         rp = [p.clone() for p in ref_pic.planes()]
@@ -910,22 +991,24 @@ def main():
                     "what": "--sharding gop: every rank its own closed group of pictures, no exchange - the upper bound the ring is compared with"}
     gc.enable()
     ring_wait = None
-    if banded and world > 1:                         # every rank: the maximum over ranks is a collective
+    if args.full and banded and world > 1:           # every rank: the maximum over ranks is a collective
         wms, _ = (0.0, 0) if stub else ring.wait_ms()
         wt = torch.tensor([wms / max(1, args.steps)], dtype=torch.float64, device=dev)
         dist.all_reduce(wt, op=dist.ReduceOp.MAX)
         ring_wait = round(float(wt.item()), 4)
-    if banded:
-        csum = {"recon_%s" % n: int(p.view(torch.uint8).to(torch.int64).sum().item()) for n, p in zip(("y", "cb", "cr"), bp.final_planes())}
-    else:
-        csum = pipe.checksum()
+    csum = None
+    if args.full:
+        if banded:
+            csum = {"recon_%s" % n: int(p.view(torch.uint8).to(torch.int64).sum().item()) for n, p in zip(("y", "cb", "cr"), bp.final_planes())}
+        else:
+            csum = pipe.checksum()
 
-    # ---- untimed pass: HIP-event time of every stage (events on the stream the kernels are launched on, recorded by the
+    # ---- --full, untimed pass: HIP-event time of every stage (events on the stream the kernels are launched on, recorded by the
     # pipeline's own stage hook, so exactly the launches of the timed loop are measured) ----
     ms = pipe.ms
     cur = pics[1]
     acc = {}
-    for _ in range(0 if stub else 5):
+    for _ in range(0 if stub or not args.full else 5):
         evs = [("start", torch.cuda.Event(enable_timing=True))]
         evs[0][1].record()
 
@@ -944,7 +1027,7 @@ def main():
     # (profiles/r03_search_star_stats.txt).  The exhaustive search (the default) does the same work for every pair.
     stages_note = None if args.search == "full" else ("data-dependent search: stages_ms is one frame pair (frame 1 vs the last reference), "
                                                       "ms_per_step averages the closed loop incl. the clip's wrap-around pairs")
-    if pipe.lcb:
+    if pipe.lcb and args.full:
         # the lookahead's cost estimate: one launch scores `lookahead_batch` pictures on its own stream, overlapped with the stages above
         b = pipe.lcb
         side = torch.cuda.Stream()
@@ -964,7 +1047,7 @@ def main():
         surf_mode = ms.surf is not None
         dom = "me"
         alg_bytes = ms.algorithmic_bytes(bpp=1 if args.depth == 8 else 2)
-        achieved = alg_bytes / (stages[dom] * 1e-3) / 1e9
+        achieved = alg_bytes / (stages[dom] * 1e-3) / 1e9 if args.full else None
         if args.search != "full":
             # a pattern search visits a data-dependent handful of the window's candidates: the exhaustive search's algorithmic bytes do not
             # describe it and no per-launch figure of its own exists - no fraction is printed (round-3 verdict, weak 6 ii)
@@ -1005,30 +1088,33 @@ def main():
                                           else "torch.distributed broadcast over one group of all ranks" if transport_name == "dist_bcast"
                                           else "torch.distributed point-to-point")),
                        "sharding": ("gop" if gop else "ring") if world > 1 else "none",
-                       "ctus_per_frame": ms.nctu, "checksum": csum,
+                       "ctus_per_frame": ms.nctu, **({"checksum": csum} if csum is not None else {}),
                        **({"band_rows": args.band_rows, "band_streams": args.band_streams,
                            "ring_model": "N pictures per max(step, N x lag), lag = the band periods until the reference rows a band's search window "
                                          "reaches are final + a hand-over (DESIGN.md section 6; band size chosen from N by pick_band_rows)"} if banded else {})},
-            "stages_ms": stages,
-            **({"stages_note": stages_note} if stages_note else {}),
-            "roofline": {"bound": "hbm", "kernel": "me_search_kernel" if args.search != "full" else
-                                   ((("me_ctu_c_kernel" if (ms.tiled or ms.blocked) else "me_ctu_q_kernel") if args.depth == 8 else "me_ctu_w_kernel") + "<surf,best>" if surf_mode
-                                    else minima_kernel_name(A, args.depth, args.range, stub)),
-                         "achieved": round(achieved, 2) if achieved is not None else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved is not None else None, "traffic": traffic, "traffic_source": tsrc,
-                         # the PHYSICAL fraction beside the contractual one: HBM bytes the counters saw / the live launch time / peak.
-                         # `frac` prices SURVEY 8(d)'s algorithmic bytes (window re-reads that LDS serves, 4 B per candidate where the
-                         # packed records hold 2.14) - it is the contract's number, this one is what the memory system really carries
-                         "frac_traffic": round(traffic / (stages[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
-                         "algorithmic_bytes_per_launch": alg_bytes, "output_bytes_per_launch": ms.hbm_floor_bytes(1 if args.depth == 8 else 2),
-                         "launch_ms": stages[dom],
-                         # what really bounds the kernel: the issue rate of its SAD instructions (the contract's `bound` can only say hbm | mfma)
-                         "valu": valu_bound(ms.nctu, args.range, args.depth, stages[dom]) if args.search == "full" else None,
-                         **({"note": "the launch keeps the per-PU minima only (default since round 4): its algorithmic bytes are the window reads + 8 bytes per PU; "
-                                     "rounds 1 - 3 quoted 0.90 - 0.92 on a launch that also wrote 11.9 GB (algorithmic) of SAD surfaces nothing in the loop read "
-                                     "(--surface brings it back)"} if args.search == "full" and not surf_mode else {})},
         }
-        if ring_wait is not None:
+        if args.full:
+            out.update({
+                "stages_ms": stages,
+                **({"stages_note": stages_note} if stages_note else {}),
+                "roofline": {"bound": "hbm", "kernel": "me_search_kernel" if args.search != "full" else
+                                       ((("me_ctu_c_kernel" if (ms.tiled or ms.blocked) else "me_ctu_q_kernel") if args.depth == 8 else "me_ctu_w_kernel") + "<surf,best>" if surf_mode
+                                        else minima_kernel_name(A, args.depth, args.range, stub)),
+                             "achieved": round(achieved, 2) if achieved is not None else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved is not None else None, "traffic": traffic, "traffic_source": tsrc,
+                             # the PHYSICAL fraction beside the contractual one: HBM bytes the counters saw / the live launch time / peak.
+                             # `frac` prices SURVEY 8(d)'s algorithmic bytes (window re-reads that LDS serves, 4 B per candidate where the
+                             # packed records hold 2.14) - it is the contract's number, this one is what the memory system really carries
+                             "frac_traffic": round(traffic / (stages[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
+                             "algorithmic_bytes_per_launch": alg_bytes, "output_bytes_per_launch": ms.hbm_floor_bytes(1 if args.depth == 8 else 2),
+                             "launch_ms": stages[dom],
+                             # what really bounds the kernel: the issue rate of its SAD instructions (the contract's `bound` can only say hbm | mfma)
+                             "valu": valu_bound(ms.nctu, args.range, args.depth, stages[dom]) if args.search == "full" else None,
+                             **({"note": "the launch keeps the per-PU minima only (default since round 4): its algorithmic bytes are the window reads + 8 bytes per PU; "
+                                         "rounds 1 - 3 quoted 0.90 - 0.92 on a launch that also wrote 11.9 GB (algorithmic) of SAD surfaces nothing in the loop read "
+                                         "(--surface brings it back)"} if args.search == "full" and not surf_mode else {})},
+            })
+        if banded and world > 1:                     # band_wait_ms_per_frame_max_over_ranks: --full
             flows = min(ring_gop, world - 1) if ring_gop else 1
             model_kw = dict(ctu_rows=(args.height + 63) // 64, lag_rows_luma=args.range + 16, depth=args.depth, width=args.width)
             out["config"]["ring"] = {"ranks_seen": ranks_seen, "transport": transport_name, "bands_per_frame": len(bp.bands), "refs": 1, "gop": ring_gop,
@@ -1042,14 +1128,14 @@ def main():
                                              "ranks_seen = all-reduce of ones over the job's process group"}
         if replicas is not None:
             out["replicas"] = replicas
-        sr = load_stage_traffic(args.width, args.height, args.depth)
+        sr = load_stage_traffic(args.width, args.height, args.depth) if args.full else None
         if sr:
             out["stages_roofline"] = sr
-        if banded:
+        if banded and args.full:
             out["roofline"]["note"] = ("stage times and roofline are whole-frame launches of rank 0 (untimed pass after the loop); the timed loop runs the "
                                        f"same stages band by band ({args.band_rows} CTU rows per band, row-walking search kernel per band)")
         bit_exact = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             dev_out = None
             if args.search == "full" and not args.no_verify:      # one more (untimed) frame: clip[1] searched in the SOURCE clip[0]
                 dev_out = device_outputs(pipe, pics[1], pics[0])
@@ -1057,11 +1143,13 @@ def main():
             if bit_exact is not None:
                 out["bit_exact"] = bit_exact["ok"]
                 out["bit_exact_detail"] = bit_exact
-        if world == 1 and not args.no_encoder and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_encoder and not args.no_cpu_baseline:
             write_detail(out, args)              # the headline is on disk before the long encoder legs start
-            out.update(encoder_leg(args))
-        write_detail(out, args)
-        line = json.dumps(compact_line(out), separators=(",", ":"))
+            # a --full run ends within FULL_RUN_S: the encoder legs get what is left of it (X265HIP_ENCODER_TIMEOUT_S overrides)
+            out.update(encoder_leg(args, timeout_s=max(60.0, FULL_RUN_S - (time.perf_counter() - T_START))))
+        if args.full:
+            write_detail(out, args)
+        line = json.dumps(compact_line(out, detail=args.full), separators=(",", ":"))
         if len(line) >= MAX_LINE_BYTES:          # never again a line the driver cannot parse (round-4 verdict): drop the optional objects, keep the contract
             line = json.dumps(compact_line(out, minimal=True), separators=(",", ":"))
         sys.stdout.flush()

@@ -456,7 +456,7 @@ def test_bench_py_gpus_n_runs_end_to_end_on_gloo_with_the_stage_stand_in(world, 
         env["X265HIP_RING_TRANSPORT"] = "bcast"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--width", "256", "--height", "256", "--range", "8",
-           "--sharding", sharding]
+           "--sharding", sharding, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -478,3 +478,62 @@ def test_bench_py_gpus_n_runs_end_to_end_on_gloo_with_the_stage_stand_in(world, 
         assert "ring" not in d["config"] and "replicas" not in d
     detail = json.load(open(tmp_path / "detail.json"))
     assert detail["config"]["checksum"]["recon_y"] > 0 and "parallelism_detail" in detail["config"]
+
+
+def test_bench_py_plain_run_prints_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (X265HIP_BENCH_STUB=1: CPU tensors, the stage stand-in) prints the contract fields and
+    nothing that needs a run of its own (--full), writes no detail file, and with --dump-outputs writes the last timed step's reconstructed
+    planes as float .npy files - the same values from run to run."""
+    import json
+    import subprocess
+    import numpy as np
+    env = dict(os.environ, X265HIP_BENCH_STUB="1", X265HIP_BENCH_DETAIL=str(tmp_path / "detail.json"), OMP_NUM_THREADS="1")
+    dumps = []
+    for run in range(2):
+        dump = tmp_path / f"dump{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "256", "--height", "256",
+               "--range", "8", "--dump-outputs", str(dump)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["dtype"] == "u8"
+        assert abs(d["value"] - 3 / (d["ms_per_step"] * 3e-3)) < 0.02 * d["value"]
+        for k in ("roofline", "stages_ms", "cpu_baseline", "bit_exact", "encoder_summary", "replicas", "detail"):
+            assert k not in d, k
+        assert not (tmp_path / "detail.json").exists()
+        files = sorted(p.name for p in dump.iterdir())
+        assert files == ["recon_cb.npy", "recon_cr.npy", "recon_y.npy"], files
+        arrays = {f: np.load(dump / f) for f in files}
+        assert arrays["recon_y.npy"].shape == (256, 256) and arrays["recon_cb.npy"].shape == (128, 128)
+        assert all(a.dtype == np.float32 for a in arrays.values()) and arrays["recon_y.npy"].max() > 0
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+def test_dump_keeps_values_exact_and_within_its_budget(tmp_path, monkeypatch):
+    """bench.write_outputs: integer outputs become floats that hold every value (64-bit words as two 32-bit halves), larger stage outputs a
+    fixed sample, and the planes shrink to what is left of the budget."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench as B
+    monkeypatch.setattr(B, "DUMP_BYTES", 600_000)
+    rng = np.random.default_rng(1)
+    words = rng.integers(0, 1 << 63, size=1000, dtype=np.uint64) | np.uint64(1 << 63)
+    big = rng.integers(-30000, 30000, size=B.DUMP_SAMPLE * 3, dtype=np.int16)
+    plane = rng.integers(0, 1024, size=(512, 512), dtype=np.uint16)
+    names = B.write_outputs(str(tmp_path), {"recon_y": plane}, {"words": words, "levels": big})
+    assert names == ["levels", "recon_y", "words"]
+    w = np.load(tmp_path / "words.npy")
+    assert w.dtype == np.float64 and w.shape == (1000, 2)
+    assert np.array_equal(w[:, 0].astype(np.uint64) | (w[:, 1].astype(np.uint64) << np.uint64(32)), words)
+    lv = np.load(tmp_path / "levels.npy")
+    assert lv.dtype == np.float32 and lv.shape == (B.DUMP_SAMPLE,) and np.all(np.isin(lv, big.astype(np.float32)))
+    B.write_outputs(str(tmp_path / "again"), {"recon_y": plane}, {"words": words, "levels": big})
+    assert np.array_equal(np.load(tmp_path / "again" / "levels.npy"), lv)
+    total = sum(os.path.getsize(tmp_path / (n + ".npy")) for n in names)
+    assert total <= 600_000 + 3 * 128 and np.load(tmp_path / "recon_y.npy").size < plane.size

@@ -4,8 +4,8 @@
 # Steps (each writes under gpurun_out/<tag>/ and prints a short tail):
 #   tests[:<pytest args>]   python -m pytest tests -m gpu -q [args]           -> pytest_N.log
 #   smoke                   __graft_entry__.smoke()                             -> smoke.log
-#   bench[:<args>]          python bench.py [args]                             -> bench[_N].json / .err
-#   stats[:<args>]          rocprofv3 --kernel-trace --stats of bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-encoder [args]
+#   bench[:<args>]          python bench.py --full [args]                      -> bench[_N].json / .err
+#   stats[:<args>]          rocprofv3 --kernel-trace --stats of bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-encoder [args]
 #                                                                                -> kernel_stats[_N].txt
 #   timeline[:<args>]       rocprofv3 --kernel-trace of the same command -> the dispatches of ONE steady-state step with start / end / idle gaps -> timeline_N.txt
 #   pmc[:<args>]            two PMC passes (FETCH_SIZE, WRITE_SIZE; --kernel-trace only) of the same command -> pmc[_N].txt
@@ -22,7 +22,7 @@ export TMPDIR=/tmp
 # the reference build under oracle/_ref travels with the snapshot (git-ignored, not gpurun-ignored): tests that need it FAIL instead of skipping when it is lost
 export X265HIP_EXPECT_REF=${X265HIP_EXPECT_REF:-1}
 n=0
-BENCH_PROF="--steps 10 --warmup 2 --no-cpu-baseline --no-encoder"
+BENCH_PROF="--full --steps 10 --warmup 2 --no-cpu-baseline --no-encoder"
 for step in "$@"; do
     n=$((n + 1))
     kind=${step%%:*}; arg=""; [ "$step" != "$kind" ] && arg=${step#*:}
@@ -36,7 +36,7 @@ for step in "$@"; do
     smoke)
         timeout 300 python -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' > "$OUT/smoke.log" 2>&1; tail -1 "$OUT/smoke.log" ;;
     bench)
-        timeout 1200 python bench.py $arg > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err"; echo "bench rc=$?"
+        timeout 1200 python bench.py --full $arg > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err"; echo "bench rc=$?"
         python - "$OUT/bench_$n.json" <<'PY'
 import json, sys
 try:
@@ -65,7 +65,7 @@ PY
         find "$OUT" -name '*.db' -delete
         grep -v "at::native\|rocclr" "$OUT/pmc_$n.txt" | cut -c1-60,92-200 | head -70 ;;
     variants)
-        run() { echo "# bench.py --no-cpu-baseline --no-encoder $*"; timeout 300 python bench.py --no-cpu-baseline --no-encoder --steps 50 --warmup 5 "$@" 2>/dev/null | python -c "
+        run() { echo "# bench.py --no-cpu-baseline --no-encoder $*"; timeout 300 python bench.py --full --no-cpu-baseline --no-encoder --steps 50 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({k:d[k] for k in ('value','unit','ms_per_step','stages_ms')}), json.dumps({k:d['roofline'][k] for k in ('kernel','achieved','frac','launch_ms')}))"; }

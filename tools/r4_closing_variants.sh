@@ -1,6 +1,6 @@
 #!/bin/bash
 # the closing library's step at the other BASELINE geometries / depths (the default line is 4K 8-bit): one line per variant
-run() { echo "# bench.py --no-cpu-baseline --no-encoder $*"; timeout 300 python bench.py --no-cpu-baseline --no-encoder --steps 50 --warmup 5 "$@" 2>/dev/null | python -c "
+run() { echo "# bench.py --no-cpu-baseline --no-encoder $*"; timeout 300 python bench.py --full --no-cpu-baseline --no-encoder --steps 50 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -1,4 +1,4 @@
-run() { echo "# bench.py --no-cpu-baseline --no-encoder $*"; timeout 300 python bench.py --no-cpu-baseline --no-encoder --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
+run() { echo "# bench.py --no-cpu-baseline --no-encoder $*"; timeout 300 python bench.py --full --no-cpu-baseline --no-encoder --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({k:d[k] for k in ('value','ms_per_step','stages_ms')}), json.dumps({k:d['roofline'][k] for k in ('kernel','frac','launch_ms')}))"; }

@@ -3,7 +3,7 @@
 OUT=gpurun_out/r5f; mkdir -p $OUT
 python -m pytest tests/test_gpu_me.py -m gpu -q -k "minima_only" > $OUT/me_variants.log 2>&1; tail -3 $OUT/me_variants.log
 R5_ME_FLAGS="254 446 256" bash tools/r5_me_ab.sh > $OUT/me_ab_lda.txt 2>&1; cat $OUT/me_ab_lda.txt
-run() { timeout 300 python bench.py --no-cpu-baseline --no-encoder --no-verify --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
+run() { timeout 300 python bench.py --full --no-cpu-baseline --no-encoder --no-verify --steps 60 --warmup 5 "$@" 2>/dev/null | python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('waves', os.environ.get('X265HIP_ME_BEST_WAVES'), sys.argv[1:], 'step', d['ms_per_step'], 'me', d['stages_ms']['me'])" "$@"; }
 for r in 1 2; do for w in 8 12 16; do X265HIP_ME_BEST_WAVES=$w run; done; done > $OUT/me_waves.txt 2>&1

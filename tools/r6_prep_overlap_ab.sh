@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 for r in 1 2 3; do
   for e in "" "X265HIP_PREP_OVERLAP=1"; do
-    env $e python bench.py --no-encoder --no-cpu-baseline --steps 200 2>/dev/null | python -c "
+    env $e python bench.py --full --no-encoder --no-cpu-baseline --steps 200 2>/dev/null | python -c "
 import sys,json,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('${e:-planes behind the search}', d['ms_per_step'], d.get('bit_exact'), flush=True)"
   done

@@ -15,7 +15,7 @@ BASE="--no-cpu-baseline --no-encoder --no-verify"
 prof() {          # key, bench args...
     local key=$1; shift
     echo "=== $key: $*"
-    ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt_$key" -o b -- python "$ROOT/bench.py" $BASE "$@" > "$OUT/bench_$key.json" 2> "$OUT/kt_$key.err" )
+    ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt_$key" -o b -- python "$ROOT/bench.py" --full $BASE "$@" > "$OUT/bench_$key.json" 2> "$OUT/kt_$key.err" )
     python tools/rocprof_summary.py kernel-trace $(find "$OUT/kt_$key" -name '*.db' | head -1) > "$OUT/kernel_stats_$key.txt" 2>&1
     for c in FETCH_SIZE WRITE_SIZE; do
         ( cd /tmp && timeout 600 rocprofv3 --pmc $c --kernel-trace -d "$OUT/pmc_${c}_$key" -o b -- python "$ROOT/bench.py" $BASE "$@" > /dev/null 2> "$OUT/pmc_${c}_$key.err" )

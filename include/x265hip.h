@@ -1020,7 +1020,9 @@ int x265hip_propagate_cost(int32_t* dst, const uint16_t* propagate_in, const int
  *   COST_C1C2            : costC1C2Flag.  bufs2 absCoeff, bufs4 baseCtxMod (updated); arg = {numC1Flag, ctxOffset}; result = packed
  *   RDOQ_NONPSY / _PSY / _PSY_1P / _PSY_2P : cu[].nonPsyRdoQuant / psyRdoQuant / psyRdoQuant_1p / _2p of ONE coefficient group.  bufs0 fenc's
  *                          transform, bufs1 the residual's transform (int16, block origin), bufs2 costUncoded (int64, block origin), bufs3
- *                          {totalUncodedCost, totalRdCost} (int64 [2], added to), bufs4 psyScale (int64); arg = {blkPos, log2TrSize, row stride or 0 = 1 << log2TrSize}; no result
+ *                          {totalUncodedCost, totalRdCost} (int64 [2], added to: jobs may share a pair - all coefficient groups of one TU adding
+ *                          into its totals, as rdoQuant does - the sums are exact in any order), bufs4 psyScale (int64);
+ *                          arg = {blkPos, log2TrSize, row stride or 0 = 1 << log2TrSize}; no result
  * costCoeffNxN / costC1C2Flag price bins with the HOST's per-state table: hand g_entropyBits (entropy.cpp:2611; x265_entropyStateBits is
  * accepted as well, its top byte is ignored) to x265hip_set_entropy_bits once - the table is the encoder's data, not this library's. */
 enum x265hip_coeff_kind

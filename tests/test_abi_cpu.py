@@ -214,3 +214,55 @@ def test_bit_cost_table_is_required_before_the_estimators_that_price_bins_run():
     src = open(os.path.join(root, "x265-yuuki-asuna_amd", "csrc", "frame_coeff_kernels.hip")).read()
     assert "were not handed in (x265hip_set_entropy_bits)" in src
     assert not re.search(r"0x[0-9A-Fa-f]{8}\s*,\s*0x[0-9A-Fa-f]{8}\s*,\s*0x[0-9A-Fa-f]{8}", src), "a packed constant table in the product"
+
+
+KIND_ENUMS = {"x265hip_cmp_kind": "CMP_", "x265hip_interp_kind": "IP_", "x265hip_tr_kind": "TR_", "x265hip_quant_kind": "Q_", "x265hip_intra_kind": "INTRA_",
+              "x265hip_blockop_kind": "OP_", "x265hip_lf_kind": "LF_", "x265hip_frame_kind": "FR_", "x265hip_coeff_kind": "CF_"}
+
+
+def _header_kind_enumerators(repo_root, tmp_path):
+    """{enumerator: value} of every batch-layer kind enum, as gcc evaluates include/x265hip.h (the enumerator names read from the header text)"""
+    import subprocess
+    hdr = open(os.path.join(repo_root, "include", "x265hip.h")).read()
+    names = {}
+    for enum in KIND_ENUMS:
+        m = re.search(r"enum\s+" + enum + r"\s*\{([^}]*)\}", hdr)
+        assert m, f"enum {enum} not found in include/x265hip.h"
+        names[enum] = re.findall(r"\b(X265HIP_\w+)\b", re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S))
+        assert names[enum], enum
+    lines = ['#include <stdio.h>', '#include "x265hip.h"', 'int main(void) {']
+    lines += [f'  printf("{e} {n} %d\\n", (int){n});' for e, ns in names.items() for n in ns]
+    lines += ['  return 0;', '}']
+    src = tmp_path / "kinds.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "kinds"
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(repo_root, "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    return [line.split() for line in out.splitlines()]
+
+
+def test_python_kind_constants_match_the_c_header(repo_root, tmp_path):
+    """Every enumerator of x265hip_{cmp,interp,tr,quant,intra,blockop,lf,frame,coeff}_kind has a constant of the same value in hipabi.py
+    (X265HIP_OP_SSIM_DIST -> A.OP_SSIM_DIST): a kind added to the header only, or a constant that drifted, fails here."""
+    A = importlib.import_module("x265-yuuki-asuna_amd.hipabi")
+    rows = _header_kind_enumerators(repo_root, tmp_path)
+    assert len(rows) == 5 + 8 + 5 + 7 + 3 + 23 + 17 + 9 + 9
+    for enum, name, val in rows:
+        py = name[len("X265HIP_"):]
+        assert py.startswith(KIND_ENUMS[enum]), (enum, name)
+        assert hasattr(A, py), f"hipabi.py has no constant {py} for {enum}::{name}"
+        assert getattr(A, py) == int(val), f"{py}: C says {val}, hipabi.py says {getattr(A, py)}"
+
+
+def test_every_kind_has_a_batch_level_test(repo_root, tmp_path):
+    """Every enumerator of the kind enums is named in tests/test_gpu_batch_kinds.py's COVERAGE table, and the test it names exists: a kind
+    added to the header without a batch-level test fails here, on a machine without a GPU."""
+    import test_gpu_batch_kinds as K
+    rows = _header_kind_enumerators(repo_root, tmp_path)
+    missing = [name for _, name, _ in rows if name not in K.COVERAGE]
+    assert not missing, f"kinds without a batch-level test in tests/test_gpu_batch_kinds.py COVERAGE: {missing}"
+    assert set(K.COVERAGE) == {name for _, name, _ in rows}, set(K.COVERAGE) - {name for _, name, _ in rows}
+    for name, where in K.COVERAGE.items():
+        module, test = where.split("::")
+        src = open(os.path.join(repo_root, "tests", module)).read()
+        assert re.search(r"^def " + test + r"\(", src, flags=re.M), f"{name}: {where} does not exist"

@@ -196,7 +196,7 @@ def test_rdoq_uncoded_cost_batch(depth, repo_root, tables):
             assert np.array_equal(back(d_tot, np.int64).reshape(-1, 2), want_tot), (name, log2)
 
 
-@pytest.mark.parametrize("depth", [8, 10])
+@pytest.mark.parametrize("depth", [8, 10, 12])
 def test_whole_plane_copies(depth, repo_root):
     """planecopy_cp / _sp / _sp_shl / _pp_shr and planeClipAndMax on 1080p-sized planes with odd widths, two planes per launch."""
     import torch
@@ -232,7 +232,7 @@ def test_whole_plane_copies(depth, repo_root):
         assert [tuple(r) for r in out.cpu().numpy().reshape(2, 2).tolist()] == res
 
 
-@pytest.mark.parametrize("depth", [8, 10])
+@pytest.mark.parametrize("depth", [8, 10, 12])
 def test_ssim_rows_lowres_and_cutree_rows(depth, repo_root):
     """The SSIM of a picture the way the reference walks it (encoder/framefilter.cpp calculateSSIM: rows of 4x4x2 moments, ssim_end_4 over
     groups of four windows), frameInitLowres of an odd-sized plane, propagateCost / fix8 rows."""

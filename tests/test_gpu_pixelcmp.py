@@ -1,5 +1,5 @@
 """GPU parity: batched pixel-compare kernels (x265hip_pixelcmp_batch) vs the oracle table slots
-(sad / satd / sa8d / sse_pp / psy_cost_pp), every PU / CU size, 8- and 10-bit, random + extremes."""
+(sad / satd / sa8d / sse_pp / psy_cost_pp), every PU / CU size, 8-, 10- and 12-bit, random + extremes."""
 import importlib
 
 import numpy as np
@@ -28,7 +28,7 @@ def _cases(depth, kind):
 KINDS = {"sad": A.CMP_SAD, "satd": A.CMP_SATD, "sa8d": A.CMP_SA8D, "sse_pp": A.CMP_SSE_PP, "psy_cost_pp": A.CMP_PSY_COST}
 
 
-@pytest.mark.parametrize("depth", [8, 10])
+@pytest.mark.parametrize("depth", [8, 10, 12])
 @pytest.mark.parametrize("kind", list(KINDS))
 def test_pixelcmp_batch_matches_oracle(depth, kind, repo_root):
     import torch

@@ -407,7 +407,9 @@ __global__ void __launch_bounds__(256) coeff_serial_kernel(CoeffArgs a)
     default:
     {   // the uncoded-cost pre-passes of one coefficient group (dct.cpp:988-1069): buf0 fenc's transform, buf1 the residual's transform (int16,
         // block origin), buf2 costUncoded (int64, block origin), buf3 {totalUncodedCost, totalRdCost} (int64 [2], added to), buf4 psyScale (int64);
-        // arg0 blkPos, arg1 log2TrSize, arg2 the row stride when it is not 1 << log2TrSize (a densely staged group).  The reference converts through double: exact, every term is below 2^53
+        // arg0 blkPos, arg1 log2TrSize, arg2 the row stride when it is not 1 << log2TrSize (a densely staged group).  The reference converts through double: exact, every term is below 2^53.
+        // The groups of one TU add into ONE totals pair (quant.cpp:716-808): the 16 terms are summed here and added with a 64-bit atomic - integer
+        // addition wraps the same in any order, so the totals equal the reference's serial += bit for bit however the jobs are scheduled
         const int16_t* fenc = (const int16_t*)a.buf[0] + jb.off[0];
         const int16_t* resi = (const int16_t*)a.buf[1] + jb.off[1];
         long long* cost = (long long*)a.buf[2] + jb.off[2];
@@ -417,7 +419,7 @@ __global__ void __launch_bounds__(256) coeff_serial_kernel(CoeffArgs a)
         const int log2 = jb.arg[1], transformShift = 15 - a.depth - log2, scaleBits = 15 - 2 * transformShift;
         const int psyShift = max(2 * transformShift + 1, 0);
         uint32_t blkPos = (uint32_t)jb.arg[0];
-        long long tu = tot[0], trd = tot[1];
+        long long tsum = 0;
         const uint32_t rowStride = jb.arg[2] ? (uint32_t)jb.arg[2] : 1u << log2;
         for (int y = 0; y < 4; y++, blkPos += rowStride)
             for (int x = 0; x < 4; x++)
@@ -426,9 +428,10 @@ __global__ void __launch_bounds__(256) coeff_serial_kernel(CoeffArgs a)
                 long long v = square ? (long long)(double)((cf * cf) << scaleBits) : cost[blkPos + x];
                 if (psy) v -= (long long)(double)((psyScale * ((long long)fenc[blkPos + x] - cf)) >> psyShift);
                 cost[blkPos + x] = v;
-                tu += v; trd += v;
+                tsum += v;
             }
-        tot[0] = tu; tot[1] = trd;
+        atomicAdd(reinterpret_cast<unsigned long long*>(tot), (unsigned long long)tsum);
+        atomicAdd(reinterpret_cast<unsigned long long*>(tot) + 1, (unsigned long long)tsum);
         break;
     }
     }

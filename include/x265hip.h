@@ -300,6 +300,21 @@ int x265hip_inter_recon_bi(const x265hip_recon_bi_params* p, void* stream);
  * plane's own weights (WeightParam of Cb or Cr) - with the conventions of x265hip_inter_recon_chroma: planes and strides of the chroma
  * plane, width / height = LUMA size, mv / mv1 = the luma stage's records, (n/2)^2 levels per block. */
 int x265hip_inter_recon_chroma_bi(const x265hip_recon_bi_params* p, void* stream);
+/* The TU-stage entries, as x265hip_tu_launch_grid names them. */
+enum x265hip_tu_entry
+{
+    X265HIP_TU_ENTRY_INTER = 0,          /* x265hip_inter_recon */
+    X265HIP_TU_ENTRY_INTER_BI,           /* x265hip_inter_recon_bi */
+    X265HIP_TU_ENTRY_INTER_CHROMA,       /* x265hip_inter_recon_chroma (nplanes 1) / _chroma_pair (nplanes 2) */
+    X265HIP_TU_ENTRY_INTER_CHROMA_BI,    /* x265hip_inter_recon_chroma_bi */
+    X265HIP_TU_ENTRY_INTRA               /* x265hip_intra_recon_batch (nblocks = njobs) */
+};
+/* grid.x of the launch `entry` makes for `nblocks` blocks (or jobs) of n x n transforms (n = the transform size: 8 << level for luma,
+ * 4 << level for chroma, intra n) at `depth`, with (tables != 0) or without a x265hip_tu_tables record, over `nplanes` planes.  The 16- and
+ * 32-point kernels are persistent - one resident set of single-wavefront workgroups, each walking blocks v, v + grid.x, ... - and get
+ * min(nblocks, resident set / nplanes); the smaller ones launch one workgroup per block and get nblocks.  A diagnostic for tests and
+ * tools: it launches nothing, but asks the current device.  Returns the grid, or X265HIP_EINVAL / X265HIP_ENODEV. */
+int x265hip_tu_launch_grid(int entry, int n, int depth, int tables, int nplanes, int nblocks);
 
 /* Picture border extension (reference extendPicBorder, pixel.cpp:1027-1041 = extendRowBorder slot,
  * ipfilter.cpp:59-77, + top/bottom row replication): `pic` points at pixel (0,0) of a plane that has

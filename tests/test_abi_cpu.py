@@ -220,12 +220,13 @@ KIND_ENUMS = {"x265hip_cmp_kind": "CMP_", "x265hip_interp_kind": "IP_", "x265hip
               "x265hip_blockop_kind": "OP_", "x265hip_lf_kind": "LF_", "x265hip_frame_kind": "FR_", "x265hip_coeff_kind": "CF_"}
 
 
-def _header_kind_enumerators(repo_root, tmp_path):
-    """{enumerator: value} of every batch-layer kind enum, as gcc evaluates include/x265hip.h (the enumerator names read from the header text)"""
+def _header_kind_enumerators(repo_root, tmp_path, enums=KIND_ENUMS):
+    """[enum, enumerator, value] of every enumerator of `enums` (default: the batch-layer kind enums), as gcc evaluates include/x265hip.h (the
+    enumerator names read from the header text)"""
     import subprocess
     hdr = open(os.path.join(repo_root, "include", "x265hip.h")).read()
     names = {}
-    for enum in KIND_ENUMS:
+    for enum in enums:
         m = re.search(r"enum\s+" + enum + r"\s*\{([^}]*)\}", hdr)
         assert m, f"enum {enum} not found in include/x265hip.h"
         names[enum] = re.findall(r"\b(X265HIP_\w+)\b", re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S))
@@ -266,3 +267,38 @@ def test_every_kind_has_a_batch_level_test(repo_root, tmp_path):
         module, test = where.split("::")
         src = open(os.path.join(repo_root, "tests", module)).read()
         assert re.search(r"^def " + test + r"\(", src, flags=re.M), f"{name}: {where} does not exist"
+
+
+def test_python_tu_entry_constants_match_the_c_header(repo_root, tmp_path):
+    """enum x265hip_tu_entry (the entries x265hip_tu_launch_grid names) has a constant of the same value in hipabi.py
+    (X265HIP_TU_ENTRY_INTER_BI -> A.TU_ENTRY_INTER_BI)."""
+    A = importlib.import_module("x265-yuuki-asuna_amd.hipabi")
+    rows = _header_kind_enumerators(repo_root, tmp_path, {"x265hip_tu_entry": "TU_ENTRY_"})
+    assert [name for _, name, _ in rows] == ["X265HIP_TU_ENTRY_INTER", "X265HIP_TU_ENTRY_INTER_BI", "X265HIP_TU_ENTRY_INTER_CHROMA",
+                                             "X265HIP_TU_ENTRY_INTER_CHROMA_BI", "X265HIP_TU_ENTRY_INTRA"]
+    for _, name, val in rows:
+        py = name[len("X265HIP_"):]
+        assert hasattr(A, py), f"hipabi.py has no constant {py} for x265hip_tu_entry::{name}"
+        assert getattr(A, py) == int(val), f"{py}: C says {val}, hipabi.py says {getattr(A, py)}"
+
+
+def test_tu_launch_grid_validates_before_touching_a_device():
+    """x265hip_tu_launch_grid rejects an unknown entry, a transform size the entry does not launch, a bad depth / plane count / block count
+    without a device; a valid query without a device fails with X265HIP_ENODEV instead of guessing a grid."""
+    import torch
+    A = importlib.import_module("x265-yuuki-asuna_amd.hipabi")
+    f = A.lib().x265hip_tu_launch_grid
+    f.argtypes = [ctypes.c_int] * 6
+    assert f(5, 16, 8, 0, 1, 100) == -2 and f(-1, 16, 8, 0, 1, 100) == -2          # entry
+    assert f(A.TU_ENTRY_INTER, 4, 8, 0, 1, 100) == -2                                # luma inter: 8, 16, 32
+    assert f(A.TU_ENTRY_INTER_BI, 64, 8, 0, 1, 100) == -2
+    assert f(A.TU_ENTRY_INTER_CHROMA, 32, 8, 0, 1, 100) == -2                        # chroma: 4, 8, 16
+    assert f(A.TU_ENTRY_INTER_CHROMA_BI, 32, 10, 0, 1, 100) == -2
+    assert f(A.TU_ENTRY_INTRA, 12, 8, 0, 1, 100) == -2
+    assert f(A.TU_ENTRY_INTER, 16, 9, 0, 1, 100) == -2                               # depth
+    assert f(A.TU_ENTRY_INTER, 16, 8, 0, 2, 100) == -2                               # two planes: the chroma pair only
+    assert f(A.TU_ENTRY_INTER_CHROMA, 16, 8, 0, 3, 100) == -2
+    assert f(A.TU_ENTRY_INTRA, 32, 8, 0, 1, 0) == -2                                 # no blocks
+    assert b"tu_launch_grid" in A.lib().x265hip_last_error()
+    if not torch.cuda.is_available():
+        assert f(A.TU_ENTRY_INTER_CHROMA, 16, 8, 1, 2, 100) == -1

@@ -24,11 +24,25 @@ def _oracle():
 def test_subpel_refine_matches_oracle(depth, subme, planes):
     """planes: the candidates are read from the reference picture's phase planes (x265hip_phase_planes) instead of being interpolated
     per candidate tile - the same decisions either way."""
+    _check_subpel(256, 128, depth, subme, planes, seed=40 + subme)
+
+
+@pytest.mark.parametrize("planes", [False, True])
+@pytest.mark.parametrize("width,height,depth,subme", [(384, 320, 8, 2), (576, 448, 8, 3), (576, 448, 10, 2)])
+def test_subpel_refine_xcd_ctu_order_matches_oracle(width, height, depth, subme, planes):
+    """The kernel takes CTU xcd_swizzle(blockIdx.x, gridDim.x): with 8 CTUs that is the identity map.  30 CTUs (6 x 5) and 63 CTUs (9 x 7):
+    each XCD gets a contiguous run of CTUs, and the last 6 / 7 CTUs form the tail past the last multiple of 8."""
+    nctu = (width // 64) * (height // 64)
+    assert nctu % 8 != 0 and nctu // 8 > 1, nctu
+    _check_subpel(width, height, depth, subme, planes, seed=90 + nctu + depth)
+
+
+def _check_subpel(width, height, depth, subme, planes, seed):
     import torch
     dev = torch.device("cuda:0")
     # sub-pel motion: frame 1 is frame 0 shifted by a non-integer amount (bilinear mix) plus noise
     rng = np.random.default_rng([41, depth, subme])
-    clip = F.synth_clip(256, 128, 2, depth=depth, seed=40 + subme)
+    clip = F.synth_clip(width, height, 2, depth=depth, seed=seed)
     y0 = clip[0][0].astype(np.float32)
     sh = np.roll(y0, (1, 2), axis=(0, 1))
     y1 = np.clip(np.rint(0.6 * y0 + 0.4 * sh + rng.normal(0, 1.0, size=y0.shape)), 0, (1 << depth) - 1).astype(clip[0][0].dtype)

@@ -1016,6 +1016,55 @@ static bool tu_raster_order(const bool chroma)
     return e[0] == '1' || (chroma ? e[0] == 'c' : e[0] == 'l');
 }
 
+// The persistent kernel (16 / 32 points) `entry` launches for n x n transforms, or NULL where it launches one workgroup per block
+template <typename Px, bool TB> static const void* tu_persistent_kernel(const int entry, const int n)
+{
+    switch (entry)
+    {
+    case X265HIP_TU_ENTRY_INTER:
+        return n == 16 ? (const void*)inter_recon_kernel<Px, 16, false, TB> : (n == 32 ? (const void*)inter_recon_kernel<Px, 32, false, TB> : nullptr);
+    case X265HIP_TU_ENTRY_INTER_BI:
+        return n == 16 ? (const void*)inter_recon_bi_kernel<Px, 16, false, TB> : (n == 32 ? (const void*)inter_recon_bi_kernel<Px, 32, false, TB> : nullptr);
+    case X265HIP_TU_ENTRY_INTER_CHROMA:
+        return n == 16 ? (const void*)inter_recon_kernel<Px, 16, true, TB> : nullptr;
+    case X265HIP_TU_ENTRY_INTER_CHROMA_BI:
+        return n == 16 ? (const void*)inter_recon_bi_kernel<Px, 16, true, TB> : nullptr;
+    default:
+        return n == 16 ? (const void*)intra_recon_kernel<Px, 16, false, TB> : (n == 32 ? (const void*)intra_recon_kernel<Px, 32, false, TB> : nullptr);
+    }
+}
+
+// grid.x of every TU-stage launch (x265hip_tu_launch_grid): the persistent kernels get exactly one resident set of single-wavefront
+// workgroups (a second partial round would double the time), split over `nplanes` rows of grid.y, never more workgroups than blocks;
+// the others one workgroup per block
+static int tu_launch_grid(const int entry, const int n, const int depth, const bool tables, const int nplanes, const int nblocks)
+{
+    const void* fn = depth == 8 ? (tables ? tu_persistent_kernel<uint8_t, true>(entry, n) : tu_persistent_kernel<uint8_t, false>(entry, n))
+                                : (tables ? tu_persistent_kernel<uint16_t, true>(entry, n) : tu_persistent_kernel<uint16_t, false>(entry, n));
+    if (!fn) return nblocks;
+    int dev = 0, cus = 256, per = 8;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 64, 0) != hipSuccess || per < 1) per = 8;
+    const long r = (long)cus * per / nplanes;
+    return (int)(nblocks < r ? nblocks : (r < 1 ? 1 : r));
+}
+
+extern "C" int x265hip_tu_launch_grid(int entry, int n, int depth, int tables, int nplanes, int nblocks)
+{
+    const bool chroma = entry == X265HIP_TU_ENTRY_INTER_CHROMA || entry == X265HIP_TU_ENTRY_INTER_CHROMA_BI;
+    if (entry < X265HIP_TU_ENTRY_INTER || entry > X265HIP_TU_ENTRY_INTRA) { set_error("tu_launch_grid: entry %d", entry); return X265HIP_EINVAL; }
+    const bool sizeOk = entry == X265HIP_TU_ENTRY_INTRA ? (n == 4 || n == 8 || n == 16 || n == 32)
+                                                        : (chroma ? (n == 4 || n == 8 || n == 16) : (n == 8 || n == 16 || n == 32));
+    if (!sizeOk) { set_error("tu_launch_grid: transform size %d for entry %d", n, entry); return X265HIP_EINVAL; }
+    if (depth != 8 && depth != 10 && depth != 12) { set_error("tu_launch_grid: depth %d", depth); return X265HIP_EINVAL; }
+    if (nplanes != 1 && !(nplanes == 2 && entry == X265HIP_TU_ENTRY_INTER_CHROMA)) { set_error("tu_launch_grid: %d planes for entry %d", nplanes, entry); return X265HIP_EINVAL; }
+    if (nblocks < 1) { set_error("tu_launch_grid: nblocks %d", nblocks); return X265HIP_EINVAL; }
+    int rc = ensure_device();
+    if (rc) return rc;
+    return tu_launch_grid(entry, n, depth, tables != 0, nplanes, nblocks);
+}
+
 extern "C" int x265hip_inter_recon(const x265hip_recon_params* p, void* stream)
 {
     int rc = ensure_device();
@@ -1041,19 +1090,11 @@ extern "C" int x265hip_inter_recon(const x265hip_recon_params* p, void* stream)
     const int npu = 64 >> (2 * p->level);
     hipStream_t s = (hipStream_t)stream;
     const int nblocks = nctu * npu;
-    auto resident = [&](const void* fn, const int threads)
-    {
-        int dev = 0, cus = 256, per = 8;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, threads, 0) != hipSuccess || per < 1) per = 8;
-        const long r = (long)cus * per;
-        return (int)(nblocks < r ? nblocks : r);
-    };
+    const int grid = tu_launch_grid(X265HIP_TU_ENTRY_INTER, 8 << p->level, p->depth, p->tables != nullptr, 1, nblocks);
 #define GO_T(PX, TB) do { \
-        if (p->level == 0) hipLaunchKernelGGL((inter_recon_kernel<PX, 8, false, TB>), dim3(nblocks), dim3(64), 0, s, aa, nblocks); \
-        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_kernel<PX, 16, false, TB>), dim3(resident((const void*)inter_recon_kernel<PX, 16, false, TB>, 64)), dim3(64), 0, s, aa, nblocks); \
-        else hipLaunchKernelGGL((inter_recon_kernel<PX, 32, false, TB>), dim3(resident((const void*)inter_recon_kernel<PX, 32, false, TB>, 64)), dim3(64), 0, s, aa, nblocks); } while (0)
+        if (p->level == 0) hipLaunchKernelGGL((inter_recon_kernel<PX, 8, false, TB>), dim3(grid), dim3(64), 0, s, aa, nblocks); \
+        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_kernel<PX, 16, false, TB>), dim3(grid), dim3(64), 0, s, aa, nblocks); \
+        else hipLaunchKernelGGL((inter_recon_kernel<PX, 32, false, TB>), dim3(grid), dim3(64), 0, s, aa, nblocks); } while (0)
 #define GO(PX) do { if (p->tables) GO_T(PX, true); else GO_T(PX, false); } while (0)
     if (p->depth == 8) GO(uint8_t); else GO(uint16_t);
 #undef GO_T
@@ -1099,23 +1140,16 @@ static int inter_recon_bi_impl(const x265hip_recon_bi_params* q, void* stream, c
     }
     const int nblocks = a.ctusW * (p->height / 64) * (64 >> (2 * p->level));
     hipStream_t s = (hipStream_t)stream;
-    auto resident = [&](const void* fn)
-    {
-        int dev = 0, cus = 256, per = 8;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 64, 0) != hipSuccess || per < 1) per = 8;
-        const long r = (long)cus * per;
-        return (int)(nblocks < r ? nblocks : r);
-    };
+    const int grid = tu_launch_grid(chroma ? X265HIP_TU_ENTRY_INTER_CHROMA_BI : X265HIP_TU_ENTRY_INTER_BI, (chroma ? 4 : 8) << p->level, p->depth,
+                                    p->tables != nullptr, 1, nblocks);
 #define GOB_T(PX, TB) do { \
-        if (p->level == 0) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 8, false, TB>), dim3(nblocks), dim3(64), 0, s, b, nblocks); \
-        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 16, false, TB>), dim3(resident((const void*)inter_recon_bi_kernel<PX, 16, false, TB>)), dim3(64), 0, s, b, nblocks); \
-        else hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 32, false, TB>), dim3(resident((const void*)inter_recon_bi_kernel<PX, 32, false, TB>)), dim3(64), 0, s, b, nblocks); } while (0)
+        if (p->level == 0) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 8, false, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); \
+        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 16, false, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); \
+        else hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 32, false, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); } while (0)
 #define GOBC_T(PX, TB) do { \
-        if (p->level == 0) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 4, true, TB>), dim3(nblocks), dim3(64), 0, s, b, nblocks); \
-        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 8, true, TB>), dim3(nblocks), dim3(64), 0, s, b, nblocks); \
-        else hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 16, true, TB>), dim3(resident((const void*)inter_recon_bi_kernel<PX, 16, true, TB>)), dim3(64), 0, s, b, nblocks); } while (0)
+        if (p->level == 0) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 4, true, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); \
+        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 8, true, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); \
+        else hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 16, true, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); } while (0)
 #define GOB(PX) do { if (chroma) { if (p->tables) GOBC_T(PX, true); else GOBC_T(PX, false); } else { if (p->tables) GOB_T(PX, true); else GOB_T(PX, false); } } while (0)
     if (p->depth == 8) GOB(uint8_t); else GOB(uint16_t);
 #undef GOB_T
@@ -1161,19 +1195,11 @@ static int inter_recon_chroma_planes(const x265hip_recon_params* const* pp, int 
     const int nctu = aa.p[0].ctusW * (p->height / 64);
     const int nblocks = nctu * (64 >> (2 * p->level));
     hipStream_t s = (hipStream_t)stream;
-    auto resident = [&](const void* fn)
-    {
-        int dev = 0, cus = 256, per = 8;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 64, 0) != hipSuccess || per < 1) per = 8;
-        const long r = (long)cus * per / nplanes;
-        return (int)(nblocks < r ? nblocks : (r < 1 ? 1 : r));
-    };
+    const int grid = tu_launch_grid(X265HIP_TU_ENTRY_INTER_CHROMA, 4 << p->level, p->depth, p->tables != nullptr, nplanes, nblocks);
 #define GOC_T(PX, TB) do { \
-        if (p->level == 0) hipLaunchKernelGGL((inter_recon_kernel<PX, 4, true, TB>), dim3(nblocks, nplanes), dim3(64), 0, s, aa, nblocks); \
-        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_kernel<PX, 8, true, TB>), dim3(nblocks, nplanes), dim3(64), 0, s, aa, nblocks); \
-        else hipLaunchKernelGGL((inter_recon_kernel<PX, 16, true, TB>), dim3(resident((const void*)inter_recon_kernel<PX, 16, true, TB>), nplanes), dim3(64), 0, s, aa, nblocks); } while (0)
+        if (p->level == 0) hipLaunchKernelGGL((inter_recon_kernel<PX, 4, true, TB>), dim3(grid, nplanes), dim3(64), 0, s, aa, nblocks); \
+        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_kernel<PX, 8, true, TB>), dim3(grid, nplanes), dim3(64), 0, s, aa, nblocks); \
+        else hipLaunchKernelGGL((inter_recon_kernel<PX, 16, true, TB>), dim3(grid, nplanes), dim3(64), 0, s, aa, nblocks); } while (0)
 #define GOC(PX) do { if (p->tables) GOC_T(PX, true); else GOC_T(PX, false); } while (0)
     if (p->depth == 8) GOC(uint8_t); else GOC(uint16_t);
 #undef GOC_T
@@ -1215,23 +1241,14 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
     a.levels = p->levels; a.numSig = p->num_sig; a.dist = (unsigned long long*)p->dist;
     a.tab = tu_tables_of(TABLES_OF(p));
     hipStream_t s = (hipStream_t)stream;
-    // 16 / 32: persistent single-wavefront workgroups, exactly one resident set (a second partial round would double the time);
-    // 4 / 8: nothing to amortise, one workgroup per job
-    auto resident = [&](const void* fn)
-    {
-        int dev = 0, cus = 256, per = 8;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 64, 0) != hipSuccess || per < 1) per = 8;
-        const long r = (long)cus * per;
-        return (int)(p->njobs < r ? p->njobs : r);
-    };
+    // 16 / 32: persistent single-wavefront workgroups, exactly one resident set; 4 / 8: nothing to amortise, one workgroup per job
+    const int grid = tu_launch_grid(X265HIP_TU_ENTRY_INTRA, p->n, p->depth, p->tables != nullptr, 1, p->njobs);
 #define GOI_T(PX, TB) do { \
-        if (p->n == 4 && !p->chroma) hipLaunchKernelGGL((intra_recon_kernel<PX, 4, true, TB>), dim3(p->njobs), dim3(64), 0, s, a); \
-        else if (p->n == 4) hipLaunchKernelGGL((intra_recon_kernel<PX, 4, false, TB>), dim3(p->njobs), dim3(64), 0, s, a); \
-        else if (p->n == 8) hipLaunchKernelGGL((intra_recon_kernel<PX, 8, false, TB>), dim3(p->njobs), dim3(64), 0, s, a); \
-        else if (p->n == 16) hipLaunchKernelGGL((intra_recon_kernel<PX, 16, false, TB>), dim3(resident((const void*)intra_recon_kernel<PX, 16, false, TB>)), dim3(64), 0, s, a); \
-        else hipLaunchKernelGGL((intra_recon_kernel<PX, 32, false, TB>), dim3(resident((const void*)intra_recon_kernel<PX, 32, false, TB>)), dim3(64), 0, s, a); } while (0)
+        if (p->n == 4 && !p->chroma) hipLaunchKernelGGL((intra_recon_kernel<PX, 4, true, TB>), dim3(grid), dim3(64), 0, s, a); \
+        else if (p->n == 4) hipLaunchKernelGGL((intra_recon_kernel<PX, 4, false, TB>), dim3(grid), dim3(64), 0, s, a); \
+        else if (p->n == 8) hipLaunchKernelGGL((intra_recon_kernel<PX, 8, false, TB>), dim3(grid), dim3(64), 0, s, a); \
+        else if (p->n == 16) hipLaunchKernelGGL((intra_recon_kernel<PX, 16, false, TB>), dim3(grid), dim3(64), 0, s, a); \
+        else hipLaunchKernelGGL((intra_recon_kernel<PX, 32, false, TB>), dim3(grid), dim3(64), 0, s, a); } while (0)
 #define GOI(PX) do { if (p->tables) GOI_T(PX, true); else GOI_T(PX, false); } while (0)
     if (p->depth == 8) GOI(uint8_t); else GOI(uint16_t);
 #undef GOI_T

@@ -35,6 +35,7 @@ class MEParams(ctypes.Structure):
 
 
 TU_INTRA_SLICE, TU_SIGN_HIDE = 1, 2        # X265HIP_TU_* flag bits of the TU stages' intra_slice field
+TU_ENTRY_INTER, TU_ENTRY_INTER_BI, TU_ENTRY_INTER_CHROMA, TU_ENTRY_INTER_CHROMA_BI, TU_ENTRY_INTRA = range(5)     # enum x265hip_tu_entry
 SURF_I32, SURF_PACKED, SURF_PACKED_T, SURF_PACKED_B = 0, 1, 2, 3
 SURF_GROUP_BYTES_I32, SURF_GROUP_BYTES_PACKED = 1360, 720
 
@@ -972,6 +973,14 @@ def intra_recon_batch(depth, n, fenc, fenc_stride, nb, recon, recon_stride, qp, 
     f = lib().x265hip_intra_recon_batch
     f.argtypes = [ctypes.POINTER(IntraReconParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_intra_recon_batch")
+
+
+def tu_launch_grid(entry, n, depth, tables, nplanes, nblocks):
+    """grid.x a TU-stage entry (TU_ENTRY_*) launches for `nblocks` blocks / jobs of n x n transforms (x265hip_tu_launch_grid): one resident
+    set of the persistent 16 / 32-point kernels (capped at nblocks; split over nplanes), nblocks for the one-workgroup-per-block sizes."""
+    f = lib().x265hip_tu_launch_grid
+    f.argtypes = [ctypes.c_int] * 6
+    return check(f(entry, n, depth, int(bool(tables)), nplanes, nblocks), "x265hip_tu_launch_grid")
 
 
 def interp_batch(kind, depth, taps, w, h, src, dst, jobs, njobs, stream=None):

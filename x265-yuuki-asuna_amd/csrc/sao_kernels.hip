@@ -8,9 +8,9 @@
 // Edge class of a sample c with neighbours a, b along the direction: s_eoTable[sign(c - a) + sign(c - b) + 2], table { 1, 2, 0,
 // 3, 4 } (sao.cpp:67); band = c >> (depth - 5).
 //
-// Statistics: one workgroup per CTU; the deblocked 66x66 neighbourhood is staged in LDS once, a thread walks 16 samples of a
-// row with a sliding 3x3 window and keeps the 4 x 5 edge accumulators packed (count << 20 | biased sum) in registers; the 32
-// bands go through per-wavefront LDS histograms.  HBM traffic is the two planes read once: 2 samples per pixel.
+// Statistics: one workgroup per CTU; the deblocked 66x66 neighbourhood is staged in LDS once, a thread walks 16 samples (4 of a
+// footprint up to 32x32) of a row with a sliding 3x3 window and keeps the edge accumulators packed in registers (sao_stats_walk);
+// the 32 bands go through per-wavefront LDS histograms.  HBM traffic is the two planes read once: 2 samples per pixel.
 #include "common.h"
 
 namespace x265hip {
@@ -31,6 +31,179 @@ __device__ __forceinline__ int sao_sign(int x) { return max(-1, min(1, x)); }   
 // workgroups each - three of them cost three times the latency, one launch with three times the workgroups costs it once.
 struct SaoStatsArgs3 { SaoStatsArgs p[3]; };
 
+// the sub-rectangles of a CTU the edge types / the bands are counted on (see sao_stats_kernel)
+struct SaoStatsGeo { int ctuW, ctuH, startX, endX0, startY, endY1, e0EndY, e1EndX, boEndX, boEndY; };
+
+// The walk over the staged CTU.  A lane owns SPL consecutive samples of one row, lanes are dealt to the rows of the NOMINAL footprint:
+// 16 samples for 64-wide footprints (four lanes per row, 64 rows), 4 samples for footprints up to 32x32 (eight lanes per row, 32 rows) -
+// with 16 samples per lane a 32x32 chroma footprint had a sample for 64 of the 256 lanes, and the other 192 waited for those.
+//
+// Result: acc[type][class] = count << 20 | sum of (source - deblocked + bias) of the lane's samples.
+//
+// 8-bit samples take the packed route - the launch is bound by the vector instructions of this loop, and the twenty
+// compare-select-add triples per sample (5 classes x 4 edge types) were more than half of them.  A sample is ONE 16-bit unit
+// u = 1 << 12 | (d + 256) (d + 256 = 1 .. 511); over at most 8 samples a class needs 4 bits of count and 12 bits of sum, so the classes 1 .. 4 of
+// an edge type are the four 16-bit fields of a 64-bit accumulator (one per run of 8 samples), and a sample is added by ONE 64-bit shift: the unit
+// sits in the top 16 bits and is shifted RIGHT by 48 / 32 / 16 / 0 into the field of its class - or by 63, which leaves nothing of it
+// (bit 15 of a unit is clear), for class 0 and for a sample the edge type does not count.  The shift comes out of a 5 x 6-bit table indexed
+// by the sum of the two signs; a lane whose ROW the edge type does not count uses a table of 63s, a sample outside the type's COLUMNS has
+// its unit cleared (one select for the three types that share the column range).  Class 0 is what the classes 1 .. 4 leave of the totals
+// of the counted samples, which cost one add per column range and sample.
+template <typename Px, int SPL>
+__device__ __forceinline__ void sao_stats_walk(const SaoStatsArgs& a, const SaoStatsGeo& g, const uint16_t* sRec, int (*sBoW)[32], int (*sEo)[20], const Px* fencCtu, int tid)
+{
+    constexpr int BPP = sizeof(Px), LW = 68;
+    uint32_t acc[4][5];
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int k = 0; k < 5; k++) acc[t][k] = 0;
+    static_assert(SPL == 16 || SPL == 4, "four lanes x 64 rows of a footprint up to 64x64, or eight lanes x 32 rows of one up to 32x32");
+    constexpr int lanesPerRow = SPL == 16 ? 4 : 8;
+    const int y = tid / lanesPerRow, x0 = (tid % lanesPerRow) * SPL;
+    const int bias = 1 << a.depth, boShift = a.depth - 5;
+    if (y < g.ctuH)
+    {
+        const Px* fe = fencCtu + (long)y * (a.fencStrideB / BPP);
+        // sliding window along the row: w[r][0..2] = columns x-1, x, x+1 of rows y-1, y, y+1 (LDS coordinates are shifted by one)
+        int w[3][3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) { w[r][1] = sRec[(y + r) * LW + x0]; w[r][2] = sRec[(y + r) * LW + x0 + 1]; }
+        const bool yE0 = y < g.e0EndY, yE1 = y >= g.startY && y < g.endY1, yBo = y < g.boEndY;
+        // the lane's source samples as packed dwords, a sample is extracted where it is used (a partial CTU reads into the padded margin):
+        // 8-bit samples up front, 16-bit samples four at a time inside the walk - eight more dwords do not fit the 64 registers of full occupancy
+        constexpr int FPD = 4 / BPP;                                               // samples per dword
+        uint32_t fevw[SPL / FPD];
+        const uint8_t* fp = reinterpret_cast<const uint8_t*>(fe + x0);
+        if (BPP == 1)
+        {
+#pragma unroll
+            for (int k = 0; k < SPL / FPD; k++) fevw[k] = ld_u32(fp + 4 * k);
+        }
+        // s_eoTable = { 1, 2, 0, 3, 4 }: class of edgeType e
+        auto cls = [](int e) { return (0x43021 >> (4 * e)) & 7; };                // nibble e of 0x43021
+        constexpr int HS = SPL < 8 ? SPL : 8, NH = SPL / HS;                        // packed route: samples per 64-bit accumulator, accumulators per type
+        constexpr uint32_t kShift = 48u | (32u << 6) | (63u << 12) | (16u << 18) | (0u << 24);      // right shift of edgeType 0 .. 4: classes 1, 2, (0: dropped), 3, 4
+        constexpr uint32_t kDrop = 63u | (63u << 6) | (63u << 12) | (63u << 18) | (63u << 24);
+        const uint32_t tab0 = yE0 ? kShift : kDrop, tab1 = yE1 ? kShift : kDrop;
+        unsigned long long pk[4][NH];
+        uint32_t tot[2][NH];                                                       // totals of the column ranges of types 0, 2, 3 / of type 1: count << 28 | sum << 16
+#pragma unroll
+        for (int h = 0; h < NH; h++) { pk[0][h] = pk[1][h] = pk[2][h] = pk[3][h] = 0; tot[0][h] = tot[1][h] = 0; }
+        int runBand = 0, runCnt = 0, runSum = 0;
+#pragma unroll
+        for (int i = 0; i < SPL; i++)
+        {
+            const int x = x0 + i;
+#pragma unroll
+            for (int r = 0; r < 3; r++) { w[r][0] = w[r][1]; w[r][1] = w[r][2]; w[r][2] = sRec[(y + r) * LW + x + 2]; }
+            // (tried: predication instead of this exit - every range below ends at ctuW or before it.  Without the branch the window reads of all
+            // sixteen samples are hoisted to the top of the walk: 104 registers instead of 56, half the occupancy)
+            if (x >= g.ctuW) break;
+            if (BPP == 2 && i % 4 == 0) { fevw[i / 2] = ld_u32(fp + 2 * i); fevw[i / 2 + 1] = ld_u32(fp + 2 * i + 4); }
+            const int c = w[1][1];
+            const int d = (int)__builtin_amdgcn_ubfe(fevw[i / FPD], (uint32_t)(8 * BPP * (i % FPD)), (uint32_t)(8 * BPP)) - c;
+            const bool xE = x >= g.startX && x < g.endX0, x1 = x < g.e1EndX;
+            const int sc_l = sao_sign(c - w[1][0]), sc_r = sao_sign(c - w[1][2]);
+            const int sc_u = sao_sign(c - w[0][1]), sc_d = sao_sign(c - w[2][1]);
+            const int sc_ul = sao_sign(c - w[0][0]), sc_dr = sao_sign(c - w[2][2]);
+            const int sc_ur = sao_sign(c - w[0][2]), sc_dl = sao_sign(c - w[2][0]);
+            if (BPP == 1)
+            {
+                const int h = i / HS;
+                const uint32_t unit = (uint32_t)(d + 0x1100) << 16;               // the 16-bit unit in the top half of a dword: the high dword of the 64-bit operand
+                const uint32_t uE = xE ? unit : 0u, u1 = x1 ? unit : 0u;
+                tot[0][h] += uE; tot[1][h] += u1;
+                auto put = [](unsigned long long& A, uint32_t hi, uint32_t tab, int signs)
+                {
+                    const uint32_t sh = __builtin_amdgcn_ubfe(tab, (uint32_t)(6 * signs + 12), 6u);
+                    A += ((unsigned long long)hi << 32) >> sh;
+                };
+                put(pk[0][h], uE, tab0, sc_l + sc_r);
+                put(pk[1][h], u1, tab1, sc_u + sc_d);
+                put(pk[2][h], uE, tab1, sc_ul + sc_dr);
+                put(pk[3][h], uE, tab1, sc_ur + sc_dl);
+            }
+            else
+            {
+                const uint32_t unit = (1u << 20) | (uint32_t)(d + bias);
+                const int k0 = (xE && yE0) ? cls(sc_l + sc_r + 2) : 7;
+                const int k1 = (x1 && yE1) ? cls(sc_u + sc_d + 2) : 7;
+                const int k2 = (xE && yE1) ? cls(sc_ul + sc_dr + 2) : 7;
+                const int k3 = (xE && yE1) ? cls(sc_ur + sc_dl + 2) : 7;
+#pragma unroll
+                for (int k = 0; k < 5; k++)
+                {
+                    acc[0][k] += k0 == k ? unit : 0u;
+                    acc[1][k] += k1 == k ? unit : 0u;
+                    acc[2][k] += k2 == k ? unit : 0u;
+                    acc[3][k] += k3 == k ? unit : 0u;
+                }
+            }
+            if (yBo && x < g.boEndX)
+            {
+                // neighbouring samples mostly share a band: accumulate the run in registers, touch the LDS histogram on a change
+                const int band = c >> boShift;
+                if (band != runBand)
+                {
+                    if (runCnt) { atomicAdd(&sBoW[0][runBand], runCnt); atomicAdd(&sBoW[1][runBand], runSum); }
+                    runBand = band; runCnt = 0; runSum = 0;
+                }
+                runCnt++; runSum += d;
+            }
+        }
+        if (runCnt) { atomicAdd(&sBoW[0][runBand], runCnt); atomicAdd(&sBoW[1][runBand], runSum); }
+        if (BPP == 1)
+        {
+            // the fields of the packed accumulators -> count << 20 | biased sum per class; class 0 from the totals
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+            {
+                uint32_t cs = 0, bs = 0, tc = 0, tb = 0;
+#pragma unroll
+                for (int k = 1; k < 5; k++)
+                {
+                    uint32_t cn = 0, b = 0;
+#pragma unroll
+                    for (int h = 0; h < NH; h++)
+                    {
+                        const uint32_t u = (uint32_t)(pk[t][h] >> (16 * (k - 1))) & 0xffffu;
+                        cn += u >> 12; b += u & 0xfffu;
+                    }
+                    acc[t][k] = (cn << 20) | b;
+                    cs += cn; bs += b;
+                }
+#pragma unroll
+                for (int h = 0; h < NH; h++) { const uint32_t v = tot[t == 1][h]; tc += v >> 28; tb += (v >> 16) & 0xfffu; }
+                if (!(t == 0 ? yE0 : yE1)) { tc = 0; tb = 0; }
+                acc[t][0] = ((tc - cs) << 20) | (tb - bs);
+            }
+        }
+    }
+    // every lane of the workgroup, also those without a row: reduce over the wavefront, then over the workgroup
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int k = 0; k < 5; k++)
+        {
+            // DPP row sums + four readlanes: no LDS round trips (the 40 butterfly reductions through ds_bpermute cost 8 us of the 44 us launch;
+            // halving the per-thread walk instead - 512 threads x 8 samples - changes nothing: the rest is the latency of one round of workgroups)
+            int cw, sw;
+            if (BPP == 1)
+            {   // 8 bits: a wavefront's 1024 samples fit the packed word (count < 2^11, biased sum < 2^20): one reduction instead of two
+                const uint32_t pw = (uint32_t)wave_sum_of_rows(row_sum((int)acc[t][k]));
+                cw = (int)(pw >> 20); sw = (int)(pw & 0xfffffu) - cw * bias;
+            }
+            else
+            {
+                const int cnt = (int)(acc[t][k] >> 20);
+                const int sum = (int)(acc[t][k] & 0xfffffu) - cnt * bias;
+                cw = wave_sum_of_rows(row_sum(cnt)); sw = wave_sum_of_rows(row_sum(sum));
+            }
+            if ((tid & 63) == 0 && cw) { atomicAdd(&sEo[0][t * 5 + k], cw); atomicAdd(&sEo[1][t * 5 + k], sw); }
+        }
+}
+
 template <typename Px>
 __global__ void __launch_bounds__(256) sao_stats_kernel(SaoStatsArgs3 aa)
 {
@@ -50,16 +223,18 @@ __global__ void __launch_bounds__(256) sao_stats_kernel(SaoStatsArgs3 aa)
     // the reference's sub-rectangles (sao.cpp:806-915): the right 5 columns / bottom 4 rows (3 / 2 for chroma) wait for the
     // neighbour's deblocking
     const int skipR = 5 - a.planeOffset, skipB = 4 - a.planeOffset;
-    const int boEndX = atRight ? ctuW : ctuW - skipR, boEndY = atBottom ? ctuH : ctuH - skipB;
-    const int startX = !lpelx, endX0 = atRight ? ctuW - 1 : ctuW - skipR;
-    const int startY = !tpely, endY1 = atBottom ? ctuH - 1 : ctuH - skipB;
-    const int e0EndY = ctuH - skipB, e1EndX = boEndX;
+    SaoStatsGeo g;
+    g.ctuW = ctuW; g.ctuH = ctuH;
+    g.boEndX = atRight ? ctuW : ctuW - skipR; g.boEndY = atBottom ? ctuH : ctuH - skipB;
+    g.startX = !lpelx; g.endX0 = atRight ? ctuW - 1 : ctuW - skipR;
+    g.startY = !tpely; g.endY1 = atBottom ? ctuH - 1 : ctuH - skipB;
+    g.e0EndY = ctuH - skipB; g.e1EndX = g.boEndX;
     for (int i = tid; i < 4 * 2 * 32; i += 256) (&sBo[0][0][0])[i] = 0;
     if (tid < 40) (&sEo[0][0])[tid] = 0;
     // stage rows -1..ctuH, columns -1..ctuW of the deblocked picture (the planes are padded, so the border reads are legal)
     const Px* rec = reinterpret_cast<const Px*>(a.rec) + lpelx + (long)tpely * (a.recStrideB / BPP);
     const long rst = a.recStrideB / BPP;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int wave = tid >> 6;
     {
         // packed loads: a thread fetches 4 samples (one dword, two for 16-bit pixels) of a staged row at a time
         const int qpr = (a.ctuW + 2 + 3) >> 2, nq = qpr * (a.ctuH + 2);
@@ -76,90 +251,9 @@ __global__ void __launch_bounds__(256) sao_stats_kernel(SaoStatsArgs3 aa)
         }
     }
     __syncthreads();
-    // a thread owns 16 consecutive samples of one row (four threads per row)
-    const int y = tid >> 2, x0 = (tid & 3) * 16;
-    const Px* fe = reinterpret_cast<const Px*>(a.fenc) + lpelx + (long)(tpely + y) * (a.fencStrideB / BPP);
-    const int bias = 1 << a.depth, boShift = a.depth - 5;
-    uint32_t acc[4][5];
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-        for (int k = 0; k < 5; k++) acc[t][k] = 0;
-    if (y < ctuH)
-    {
-        // sliding window along the row: w[r][0..2] = columns x-1, x, x+1 of rows y-1, y, y+1 (LDS coordinates are shifted by one)
-        int w[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) { w[r][1] = sRec[(y + r) * LW + x0]; w[r][2] = sRec[(y + r) * LW + x0 + 1]; }
-        const bool yE0 = y < e0EndY, yE1 = y >= startY && y < endY1, yBo = y < boEndY;
-        // the thread's 16 source samples, fetched as dwords up front (a partial CTU reads into the padded margin)
-        int fev[16];
-        {
-            const uint8_t* fp = reinterpret_cast<const uint8_t*>(fe + x0);
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-            {
-                if (BPP == 1) { const uint32_t w4 = ld_u32(fp + 4 * k); fev[4 * k] = w4 & 0xff; fev[4 * k + 1] = (w4 >> 8) & 0xff; fev[4 * k + 2] = (w4 >> 16) & 0xff; fev[4 * k + 3] = w4 >> 24; }
-                else { const uint32_t w0 = ld_u32(fp + 8 * k), w1 = ld_u32(fp + 8 * k + 4); fev[4 * k] = w0 & 0xffff; fev[4 * k + 1] = w0 >> 16; fev[4 * k + 2] = w1 & 0xffff; fev[4 * k + 3] = w1 >> 16; }
-            }
-        }
-        // s_eoTable = { 1, 2, 0, 3, 4 }: class of edgeType e
-        auto cls = [](int e) { return (0x43021 >> (4 * e)) & 7; };                // nibble e of 0x43021
-        int runBand = 0, runCnt = 0, runSum = 0;
-#pragma unroll
-        for (int i = 0; i < 16; i++)
-        {
-            const int x = x0 + i;
-#pragma unroll
-            for (int r = 0; r < 3; r++) { w[r][0] = w[r][1]; w[r][1] = w[r][2]; w[r][2] = sRec[(y + r) * LW + x + 2]; }
-            if (x >= ctuW) break;
-            const int c = w[1][1];
-            const int d = fev[i] - c;
-            const uint32_t unit = (1u << 20) | (uint32_t)(d + bias);
-            const bool xE = x >= startX && x < endX0;
-            const int sc_l = sao_sign(c - w[1][0]), sc_r = sao_sign(c - w[1][2]);
-            const int sc_u = sao_sign(c - w[0][1]), sc_d = sao_sign(c - w[2][1]);
-            const int sc_ul = sao_sign(c - w[0][0]), sc_dr = sao_sign(c - w[2][2]);
-            const int sc_ur = sao_sign(c - w[0][2]), sc_dl = sao_sign(c - w[2][0]);
-            const int k0 = (xE && yE0) ? cls(sc_l + sc_r + 2) : 7;
-            const int k1 = (x < e1EndX && yE1) ? cls(sc_u + sc_d + 2) : 7;
-            const int k2 = (xE && yE1) ? cls(sc_ul + sc_dr + 2) : 7;
-            const int k3 = (xE && yE1) ? cls(sc_ur + sc_dl + 2) : 7;
-#pragma unroll
-            for (int k = 0; k < 5; k++)
-            {
-                acc[0][k] += k0 == k ? unit : 0u;
-                acc[1][k] += k1 == k ? unit : 0u;
-                acc[2][k] += k2 == k ? unit : 0u;
-                acc[3][k] += k3 == k ? unit : 0u;
-            }
-            if (yBo && x < boEndX)
-            {
-                // neighbouring samples mostly share a band: accumulate the run in registers, touch the LDS histogram on a change
-                const int band = c >> boShift;
-                if (band != runBand)
-                {
-                    if (runCnt) { atomicAdd(&sBo[wave][0][runBand], runCnt); atomicAdd(&sBo[wave][1][runBand], runSum); }
-                    runBand = band; runCnt = 0; runSum = 0;
-                }
-                runCnt++; runSum += d;
-            }
-        }
-        if (runCnt) { atomicAdd(&sBo[wave][0][runBand], runCnt); atomicAdd(&sBo[wave][1][runBand], runSum); }
-    }
-    // unpack, reduce over the wavefront, then over the workgroup
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-        for (int k = 0; k < 5; k++)
-        {
-            const int cnt = (int)(acc[t][k] >> 20);
-            const int sum = (int)(acc[t][k] & 0xfffffu) - cnt * bias;
-            // DPP row sums + four readlanes: no LDS round trips (the 40 butterfly reductions through ds_bpermute cost 8 us of the 44 us launch;
-            // halving the per-thread walk instead - 512 threads x 8 samples - changes nothing: the rest is the latency of one round of workgroups)
-            const int cw = wave_sum_of_rows(row_sum(cnt)), sw = wave_sum_of_rows(row_sum(sum));
-            if ((tid & 63) == 0 && cw) { atomicAdd(&sEo[0][t * 5 + k], cw); atomicAdd(&sEo[1][t * 5 + k], sw); }
-        }
+    const Px* fencCtu = reinterpret_cast<const Px*>(a.fenc) + lpelx + (long)tpely * (a.fencStrideB / BPP);
+    if (a.ctuW <= 32 && a.ctuH <= 32) sao_stats_walk<Px, 4>(a, g, sRec, sBo[wave], sEo, fencCtu, tid);
+    else sao_stats_walk<Px, 16>(a, g, sRec, sBo[wave], sEo, fencCtu, tid);
     __syncthreads();
     int32_t* cnt = a.count + (size_t)addr * 160;
     int32_t* org = a.offsetOrg + (size_t)addr * 160;

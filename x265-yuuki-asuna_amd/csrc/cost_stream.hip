@@ -13,82 +13,23 @@
 // One worker thread, one HIP stream: uploads, weighting, interpolation and the table chain of a round are stream-ordered; the round ends
 // with one synchronisation, then the flags of its bands are raised.  Readers never wait and never lock (ready[row] before AND after the
 // read); whatever is not served is the host primitive's to compute - the same integers.
-#include "common.h"
+#include "row_pictures.h"
 
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <thread>
-#include <vector>
 
 using namespace x265hip;
-
-namespace {
-
-// primitives.weight_pp (common/pixel.cpp:518-543) over whole buffer lines; round / shift include the 14 - depth correction
-template <typename Px>
-__global__ void __launch_bounds__(256) cs_weight_lines_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t ndw, int w0, int round, int shift,
-                                                              int offset, int correction, int maxVal)
-{
-    constexpr int PER = 4 / (int)sizeof(Px), BITS = 8 * (int)sizeof(Px);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ndw; i += (size_t)gridDim.x * blockDim.x)
-    {
-        const uint32_t v = src[i];
-        uint32_t o = 0;
-#pragma unroll
-        for (int k = 0; k < PER; k++)
-        {
-            const int px = (int)((v >> (k * BITS)) & ((1u << BITS) - 1));
-            const int val = (int)(int16_t)(px << correction);
-            o |= (uint32_t)clip3(0, maxVal, ((w0 * val + round) >> shift) + offset) << (k * BITS);
-        }
-        dst[i] = o;
-    }
-}
-
-// centre of every CTU's window = the displacement of its 64x64 block's minimum SAD in the +-big search, clamped to +-maxX / [-maxY, maxYDown] (downwards the
-// candidates must stay inside the reference rows that exist when the row is computed)
-__global__ void cs_centre_kernel(const unsigned long long* __restrict__ best, int16_t* __restrict__ centres, int nctu, int big, int maxX, int maxY, int maxYDown)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nctu) return;
-    const uint32_t idx = (uint32_t)best[(size_t)i * 85 + 84];
-    const int ncb = 2 * big + 1;
-    const int mx = (int)(idx % ncb) - big, my = (int)(idx / ncb) - big;
-    centres[2 * i] = (int16_t)clip3(-maxX, maxX, mx);
-    centres[2 * i + 1] = (int16_t)clip3(-maxY, maxYDown, my);
-}
-
-double cs_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-} // namespace
 
 struct x265hip_cost_stream
 {
     x265hip_cost_stream_params prm;
-    int bpp, device, ctusW, ctuRows, nplanes, bandRows, npu, recBytes, maxCx, maxCy, maxCyDown;
-    size_t planeBytes[2], pitch[2], ctuBytes, rowBytes;
-    int rows[2], margin[2], ctuLines[2], nph[2];
+    PlaneGeometry geo;
+    int device, ctusW, bandRows, npu, recBytes, maxCx, maxCy, maxCyDown;
+    size_t ctuBytes, rowBytes;
     hipStream_t stream = nullptr;
-    struct Pic
-    {
-        uint64_t key = 0; bool used = false; uint32_t epoch = 0; uint64_t stamp = 0; int busy = 0;
-        uint8_t* stage[3] = { nullptr, nullptr, nullptr };      // pinned planes, rows staged by the host threads
-        uint8_t* dSrc[3] = { nullptr, nullptr, nullptr };
-        std::vector<uint8_t> staged;                            // per CTU row
-        int nextRow = 0;                                        // rows [0, nextRow) are uploaded (or queued on the stream)
-    };
-    struct View
+    struct View : x265hip::View
     {
         bool used = false; uint64_t stamp = 0; int busy = 0;          // busy: launches of the running round read it
-        int pic = -1; uint32_t picEpoch = 0; bool active = false;      // active: still growing behind its picture
-        unsigned mask = 0; x265hip_weight w[3] = {};
-        uint8_t* dW[3] = { nullptr, nullptr, nullptr };         // the picture's planes weighted (only the planes of the mask)
-        uint8_t* dOut[3] = { nullptr, nullptr, nullptr };       // every phase plane
-        int rowsSeen = 0; int done[2] = { 0, 0 };
     };
     struct Slot
     {
@@ -100,107 +41,57 @@ struct x265hip_cost_stream
         int bandLimit = 1;                                      // rows of the pair's next band: 1, 2, 4 ... band_rows - the first rows of EVERY open pair land before anybody's last ones
         uint16_t* hMvCost = nullptr; uint16_t* dMvCost = nullptr; bool hasCost = false;      // the pair's vector-cost table (pinned staging, device copy); !hasCost: rank by SAD alone
     };
-    std::vector<Pic> pics;
+    PicturePool pool;
     std::vector<View> views;
     std::vector<Slot> slots;
     // one band's scratch
     uint8_t* dSurf = nullptr; unsigned long long* dBest = nullptr; uint16_t* dZeroCost = nullptr; int16_t* dCentres = nullptr; int16_t* dCand = nullptr; uint8_t* dTables = nullptr;
-    uint64_t clock = 0;
-    std::mutex mu;
-    std::condition_variable cv;
-    bool stop = false, dirty = false;
-    std::thread worker;
+    RowWorker w;
     std::atomic<uint64_t> pairsOpened{0}, pairsCompleted{0}, bands{0}, rowsServed{0}, rowsUploaded{0}, failed{0}, stalePairs{0}, viewsOpened{0}, viewsShared{0}, linesWeighted{0};
-    std::atomic<uint64_t> usBusy{0}, bytesDown{0}, bytesUp{0};
-    char workerError[256] = "";
+    std::atomic<uint64_t> bytesDown{0}, bytesUp{0};
 };
 
 namespace {
 
 typedef x265hip_cost_stream CS;
 
-// buffer lines [y0, y1) of plane kind k (0 luma, 1 chroma) that CTU rows [r0, r0 + n) occupy; margins travel with the first / last row
-inline void cs_lines(const CS* s, int k, int r0, int n, int& y0, int& y1)
-{
-    y0 = r0 == 0 ? 0 : s->margin[k] + r0 * s->ctuLines[k];
-    y1 = r0 + n == s->ctuRows ? s->rows[k] : s->margin[k] + (r0 + n) * s->ctuLines[k];
-}
-
-struct Upload { int pic, r0, r1; };
-struct ViewJob { int view, pic, r0, r1; int done[2]; unsigned mask; x265hip_weight w[3]; };
 struct Band { int slot, gen, r0, r1, fenc, view; bool hasCost; };
 
-int run_round(CS* s, const std::vector<Upload>& ups, const std::vector<ViewJob>& jobs, const std::vector<Band>& bands)
+int run_round(CS* s, const std::vector<RowUpload>& ups, const std::vector<ViewJob>& jobs, const std::vector<Band>& bands)
 {
+    const PlaneGeometry& g = s->geo;
     X265HIP_TRY(hipSetDevice(s->device));
     apply_wait_policy(s->device);
-    for (const Upload& u : ups)
-        for (int pl = 0; pl < s->nplanes; pl++)
-        {
-            const int k = pl ? 1 : 0;
-            int y0, y1;
-            cs_lines(s, k, u.r0, u.r1 - u.r0, y0, y1);
-            X265HIP_TRY(hipMemcpyAsync(s->pics[u.pic].dSrc[pl] + (size_t)y0 * s->pitch[k], s->pics[u.pic].stage[pl] + (size_t)y0 * s->pitch[k],
-                                       (size_t)(y1 - y0) * s->pitch[k], hipMemcpyHostToDevice, s->stream));
-            s->bytesUp += (size_t)(y1 - y0) * s->pitch[k];
-            if (!pl) s->rowsUploaded += u.r1 - u.r0;
-        }
+    int rc;
+    for (const RowUpload& u : ups)
+    {
+        if ((rc = upload(g, s->pool.pics[u.pic], u.r0, u.r1, s->stream, s->bytesUp))) return rc;
+        s->rowsUploaded += u.r1 - u.r0;
+    }
     for (const ViewJob& job : jobs)
     {
-        CS::View& v = s->views[job.view];
-        for (int pl = 0; pl < s->nplanes; pl++)
-        {
-            const int k = pl ? 1 : 0;
-            int y0, y1;
-            cs_lines(s, k, job.r0, job.r1 - job.r0, y0, y1);
-            const uint8_t* src = s->pics[job.pic].dSrc[pl];
-            if (job.mask & (1u << pl))
-            {
-                const size_t off = (size_t)y0 * s->pitch[k], ndw = (size_t)(y1 - y0) * s->pitch[k] / 4;
-                const x265hip_weight& w = job.w[pl];
-                const int correction = 14 - s->prm.depth, maxVal = (1 << s->prm.depth) - 1;
-                size_t blocks = (ndw + 255) / 256;
-                if (blocks > 8192) blocks = 8192;
-                if (s->bpp == 1)
-                    hipLaunchKernelGGL(cs_weight_lines_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), 0, s->stream, (const uint32_t*)(src + off), (uint32_t*)(v.dW[pl] + off),
-                                       ndw, w.w0, w.round, w.shift, w.offset, correction, maxVal);
-                else
-                    hipLaunchKernelGGL(cs_weight_lines_kernel<uint16_t>, dim3((unsigned)blocks), dim3(256), 0, s->stream, (const uint32_t*)(src + off), (uint32_t*)(v.dW[pl] + off),
-                                       ndw, w.w0, w.round, w.shift, w.offset, correction, maxVal);
-                X265HIP_TRY(hipGetLastError());
-                s->linesWeighted += (uint64_t)(y1 - y0);
-                src = v.dW[pl];
-            }
-            // producible now: lines [max(done, 4), y1 - 8) - a line needs 3 source lines above and up to 8 below it
-            const int b0 = job.done[k] < 4 ? 4 : job.done[k], b1 = y1 - 8;
-            if (b1 - b0 < 4) continue;
-            const size_t lineOff = (size_t)(b0 - 4) * s->pitch[k];
-            int rc = phase_planes_launch(s->prm.depth, k, src + lineOff, v.dOut[pl] + lineOff, k ? s->prm.stride_c : s->prm.stride, b1 - b0 + 12, s->planeBytes[k], s->stream);
-            if (rc) return rc;
-        }
+        LineRange made[2];              // the worker has advanced the view's done[] by the same rule
+        if ((rc = grow_view(g, s->pool.pics[job.pic], s->views[job.view], job, s->stream, made, s->linesWeighted))) return rc;
     }
-    const size_t org = ((size_t)s->prm.margin_y * s->prm.stride + s->prm.margin_x) * s->bpp;
+    const size_t org = ((size_t)s->prm.margin_y * s->prm.stride + s->prm.margin_x) * g.bpp;
     for (const Band& b : bands)
     {
         CS::Slot& sl = s->slots[b.slot];
         const CS::View& v = s->views[b.view];
         const int n = b.r1 - b.r0 + 1, nctuBand = n * s->ctusW;
-        const size_t bandOff = (size_t)b.r0 * 64 * s->pitch[0];
-        const uint8_t* refL = (v.mask & 1) ? v.dW[0] : s->pics[v.pic].dSrc[0];
+        const size_t bandOff = (size_t)b.r0 * 64 * g.pitch[0];
+        const uint8_t* refL = (v.mask & 1) ? v.dW[0] : s->pool.pics[v.pic].dSrc[0];
         x265hip_me_params p;
         memset(&p, 0, sizeof(p));
         p.depth = s->prm.depth; p.width = s->prm.width; p.height = n * 64;
-        p.fenc = s->pics[b.fenc].dSrc[0] + org + bandOff; p.fenc_stride = s->prm.stride;
+        p.fenc = s->pool.pics[b.fenc].dSrc[0] + org + bandOff; p.fenc_stride = s->prm.stride;
         p.fref = refL + org + bandOff; p.fref_stride = s->prm.stride;
-        int rc;
         if (s->prm.centre_range)
         {
             if ((rc = x265hip_me_best_reset((uint64_t*)s->dBest, (size_t)nctuBand * 85, s->stream))) return rc;
             p.range = s->prm.centre_range; p.best = (uint64_t*)s->dBest; p.cost_x = p.cost_y = s->dZeroCost;
             if ((rc = x265hip_me_fullsearch(&p, s->stream))) return rc;
-            hipLaunchKernelGGL(cs_centre_kernel, dim3((nctuBand + 63) / 64), dim3(64), 0, s->stream, (const unsigned long long*)s->dBest, s->dCentres, nctuBand,
-                               s->prm.centre_range, s->maxCx, s->maxCy, s->maxCyDown);
-            X265HIP_TRY(hipGetLastError());
+            if ((rc = centres_launch((const unsigned long long*)s->dBest, s->dCentres, nctuBand, s->prm.centre_range, s->maxCx, s->maxCy, s->maxCyDown, s->stream))) return rc;
             p.best = nullptr; p.cost_x = p.cost_y = nullptr;
         }
         else
@@ -221,13 +112,13 @@ int run_round(CS* s, const std::vector<Upload>& ups, const std::vector<ViewJob>&
         memset(&t, 0, sizeof(t));
         t.depth = s->prm.depth; t.width = s->prm.width; t.stride = s->prm.stride; t.margin_x = s->prm.margin_x; t.margin_y = s->prm.margin_y;
         t.stride_c = s->prm.stride_c; t.margin_y_c = s->prm.margin_y_c; t.ctu_row0 = b.r0; t.ctu_rows = n;
-        for (int pl = 0; pl < s->nplanes; pl++)
+        for (int pl = 0; pl < g.nplanes; pl++)
         {
-            t.fenc[pl] = s->pics[b.fenc].dSrc[pl];
-            t.ref[pl] = (v.mask & (1u << pl)) ? v.dW[pl] : s->pics[v.pic].dSrc[pl];
+            t.fenc[pl] = s->pool.pics[b.fenc].dSrc[pl];
+            t.ref[pl] = (v.mask & (1u << pl)) ? v.dW[pl] : s->pool.pics[v.pic].dSrc[pl];
             t.phases[pl] = v.dOut[pl];
         }
-        t.plane_bytes = s->planeBytes[0]; t.plane_bytes_c = s->planeBytes[1];
+        t.plane_bytes = g.planeBytes[0]; t.plane_bytes_c = g.planeBytes[1];
         t.shapes = s->prm.shapes; t.candidates = s->prm.candidates; t.subme = s->prm.subme; t.chroma = s->prm.chroma; t.sad_costs = s->prm.sad_costs;
         t.cand = s->dCand; t.tables = s->dTables;
         if ((rc = x265hip_cost_tables(&t, s->stream))) return rc;
@@ -237,14 +128,14 @@ int run_round(CS* s, const std::vector<Upload>& ups, const std::vector<ViewJob>&
     X265HIP_TRY(hipStreamSynchronize(s->stream));
     if (!bands.empty())
     {
-        std::lock_guard<std::mutex> lk(s->mu);                    // against pair_open: a reopened slot keeps its cleared flags
+        std::lock_guard<std::mutex> lk(s->w.mu);                    // against pair_open: a reopened slot keeps its cleared flags
         for (const Band& b : bands)
         {
             CS::Slot& sl = s->slots[b.slot];
             if (sl.generation == b.gen)
             {
                 for (int r = b.r0; r <= b.r1; r++) sl.ready[r].store(b.gen, std::memory_order_release);
-                if (b.r1 == s->ctuRows - 1) s->pairsCompleted++;
+                if (b.r1 == g.ctuRows - 1) s->pairsCompleted++;
             }
             s->bands++; s->rowsServed += b.r1 - b.r0 + 1;
         }
@@ -254,105 +145,69 @@ int run_round(CS* s, const std::vector<Upload>& ups, const std::vector<ViewJob>&
 
 void cs_worker(CS* s)
 {
+    const int ctuRows = s->geo.ctuRows;
     for (;;)
     {
-        std::vector<Upload> ups;
+        std::vector<RowUpload> ups;
         std::vector<ViewJob> jobs;
         std::vector<Band> bands;
+        Pins pins;
         {
-            std::unique_lock<std::mutex> lk(s->mu);
-            s->cv.wait(lk, [s] { return s->stop || s->dirty; });
-            if (s->stop) return;
-            s->dirty = false;
-            for (int i = 0; i < (int)s->pics.size(); i++)
-            {
-                CS::Pic& pc = s->pics[i];
-                if (!pc.used) continue;
-                int r1 = pc.nextRow;
-                while (r1 < s->ctuRows && pc.staged[r1]) r1++;          // views grow top to bottom: only a contiguous prefix is useful
-                if (r1 > pc.nextRow) { ups.push_back({ i, pc.nextRow, r1 }); pc.nextRow = r1; pc.busy++; }
-            }
+            std::unique_lock<std::mutex> lk(s->w.mu);
+            if (!worker_wait(s->w, lk)) return;
+            take_staged_prefixes(s->pool, ctuRows, ups, pins);
             for (int i = 0; i < (int)s->views.size(); i++)
             {
                 CS::View& v = s->views[i];
-                if (!v.used || !v.active) continue;
-                const CS::Pic& pc = s->pics[v.pic];
-                if (!pc.used || pc.epoch != v.picEpoch) { v.active = false; continue; }      // the picture went away: what is finished stays valid
-                if (pc.nextRow > v.rowsSeen)
+                ViewJob job;
+                if (!v.used || !take_view_job(s->pool, ctuRows, v, i, job)) continue;
+                jobs.push_back(job);
+                pin(pins, s->pool.pics[job.pic].busy); pin(pins, v.busy);
+                // the lines this job will have produced (the launches are stream-ordered before any band of this round)
+                for (int k = 0; k < (s->geo.nplanes > 1 ? 2 : 1); k++)
                 {
-                    ViewJob job = { i, v.pic, v.rowsSeen, pc.nextRow, { v.done[0], v.done[1] }, v.mask, { v.w[0], v.w[1], v.w[2] } };
-                    jobs.push_back(job);
-                    s->pics[v.pic].busy++; v.busy++;
-                    // the lines this job will have produced (the launches are stream-ordered before any band of this round)
-                    for (int k = 0; k < (s->nplanes > 1 ? 2 : 1); k++)
-                    {
-                        int y0, y1;
-                        cs_lines(s, k, v.rowsSeen, pc.nextRow - v.rowsSeen, y0, y1);
-                        const int b0 = v.done[k] < 4 ? 4 : v.done[k], b1 = y1 - 8;
-                        if (b1 - b0 >= 4) v.done[k] = b1;
-                    }
-                    v.rowsSeen = pc.nextRow;
-                    if (v.rowsSeen == s->ctuRows) v.active = false;
+                    int b0, b1;
+                    if (producible_lines(s->geo, k, job.r0, job.r1, v.done[k], b0, b1)) v.done[k] = b1;
                 }
             }
             for (int i = 0; i < (int)s->slots.size(); i++)
             {
                 CS::Slot& sl = s->slots[i];
                 if (!sl.active) continue;
-                const CS::Pic& pf = s->pics[sl.fenc];
+                const Pic& pf = s->pool.pics[sl.fenc];
                 const CS::View& v = s->views[sl.view];
                 if (!pf.used || pf.epoch != sl.fencEpoch || !v.used || v.stamp != sl.viewStamp ||
-                    (v.rowsSeen < s->ctuRows && (!s->pics[v.pic].used || s->pics[v.pic].epoch != v.picEpoch)))
+                    (v.rowsSeen < ctuRows && (!s->pool.pics[v.pic].used || s->pool.pics[v.pic].epoch != v.picEpoch)))
                 { sl.active = false; s->stalePairs++; continue; }
                 int r1 = sl.nextRow - 1;
-                while (r1 + 1 < s->ctuRows && r1 + 1 - sl.nextRow < sl.bandLimit)
+                while (r1 + 1 < ctuRows && r1 + 1 - sl.nextRow < sl.bandLimit)
                 {
                     const int r = r1 + 1;
-                    const int need = r + 2 > s->ctuRows ? s->ctuRows : r + 2;          // the candidates of row r reach <= 44 luma lines below it (maxCyDown + window + 2)
+                    const int need = r + 2 > ctuRows ? ctuRows : r + 2;          // the candidates of row r reach <= 44 luma lines below it (maxCyDown + window + 2)
                     if (pf.nextRow <= r || v.rowsSeen < need) break;
                     r1 = r;
                 }
                 if (r1 < sl.nextRow) continue;
                 bands.push_back({ i, sl.generation, sl.nextRow, r1, sl.fenc, sl.view, sl.hasCost });
-                s->pics[sl.fenc].busy++; s->pics[v.pic].busy++; s->views[sl.view].busy++;
+                pin(pins, s->pool.pics[sl.fenc].busy); pin(pins, s->pool.pics[v.pic].busy); pin(pins, s->views[sl.view].busy);
                 sl.nextRow = r1 + 1;
                 sl.bandLimit = sl.bandLimit * 2 > s->bandRows ? s->bandRows : sl.bandLimit * 2;
-                if (sl.nextRow == s->ctuRows) sl.active = false;
-                else s->dirty = true;
+                if (sl.nextRow == ctuRows) sl.active = false;
+                else s->w.dirty = true;
             }
         }
         if (ups.empty() && jobs.empty() && bands.empty()) continue;
-        const double t0 = cs_now_us();
-        if (run_round(s, ups, jobs, bands))
-        {
-            s->failed += bands.size() + 1;
-            snprintf(s->workerError, sizeof(s->workerError), "%s", x265hip_last_error());
-            (void)hipStreamSynchronize(s->stream);                      // nothing queued may still read a picture whose pin goes below
-        }
-        {
-            std::lock_guard<std::mutex> lk(s->mu);
-            for (const Upload& u : ups) s->pics[u.pic].busy--;
-            for (const ViewJob& j : jobs) { s->pics[j.pic].busy--; s->views[j.view].busy--; }
-            for (const Band& b : bands) { s->pics[b.fenc].busy--; s->pics[s->views[b.view].pic].busy--; s->views[b.view].busy--; }
-        }
-        s->usBusy += (uint64_t)(cs_now_us() - t0);
+        const double t0 = now_us();
+        const int rc = run_round(s, ups, jobs, bands);
+        if (rc) s->failed += bands.size() + 1;
+        worker_round_end(s->w, s->stream, rc, pins, t0);
     }
 }
 
 void cs_free(CS* s)
 {
-    for (auto& pc : s->pics)
-        for (int i = 0; i < 3; i++)
-        {
-            if (pc.stage[i]) (void)hipHostFree(pc.stage[i]);
-            if (pc.dSrc[i]) (void)hipFree(pc.dSrc[i]);
-        }
-    for (auto& v : s->views)
-        for (int i = 0; i < 3; i++)
-        {
-            if (v.dW[i]) (void)hipFree(v.dW[i]);
-            if (v.dOut[i]) (void)hipFree(v.dOut[i]);
-        }
+    pool_free(s->pool);
+    for (auto& v : s->views) view_free(v);
     for (auto& sl : s->slots) { if (sl.tables) (void)hipHostFree(sl.tables); if (sl.hMvCost) (void)hipHostFree(sl.hMvCost); if (sl.dMvCost) (void)hipFree(sl.dMvCost); delete[] sl.ready; }
     if (s->dSurf) (void)hipFree(s->dSurf);
     if (s->dBest) (void)hipFree(s->dBest);
@@ -365,7 +220,7 @@ void cs_free(CS* s)
 
 bool cs_pic_held(const CS* s, int i)
 {
-    const CS::Pic& p = s->pics[i];
+    const Pic& p = s->pool.pics[i];
     for (const auto& v : s->views)
         if (v.used && v.pic == i && v.picEpoch == p.epoch)
         {
@@ -377,27 +232,14 @@ bool cs_pic_held(const CS* s, int i)
     return false;
 }
 
-// index of the picture named `key`, created when it is new: least recently used entry nothing is still fed from; -1 = all held
-int cs_find_or_make_picture(CS* s, uint64_t key)
+// lock held: the entry of picture `key` (find_or_make); cs_pic_held() entries are not recycled
+int cs_picture(CS* s, uint64_t key)
 {
-    for (int i = 0; i < (int)s->pics.size(); i++)
-        if (s->pics[i].used && s->pics[i].key == key) { s->pics[i].stamp = ++s->clock; return i; }
-    int victim = -1;
-    for (int i = 0; i < (int)s->pics.size(); i++)
-    {
-        CS::Pic& p = s->pics[i];
-        if (!p.used) { victim = i; break; }
-        if (p.busy || cs_pic_held(s, i)) continue;
-        if (victim < 0 || p.stamp < s->pics[victim].stamp) victim = i;
-    }
-    if (victim < 0) return -1;
-    CS::Pic& p = s->pics[victim];
-    // views of the recycled entry are void: their unweighted planes are the picture's own
-    for (auto& v : s->views) if (v.used && v.pic == victim && v.picEpoch == p.epoch) { v.used = false; v.active = false; }
-    p.used = true; p.key = key; p.epoch++; p.stamp = ++s->clock; p.busy = 0;
-    std::fill(p.staged.begin(), p.staged.end(), (uint8_t)0);
-    p.nextRow = 0;
-    return victim;
+    const int i = find_or_make(s->pool, key, [s](int i) { return cs_pic_held(s, i); });
+    // views of a recycled entry (they carry its previous epoch) are void: their unweighted planes are the picture's own
+    if (i >= 0)
+        for (auto& v : s->views) if (v.used && v.pic == i && v.picEpoch != s->pool.pics[i].epoch) { v.used = false; v.active = false; }
+    return i;
 }
 
 bool same_w(const x265hip_weight& a, const x265hip_weight& b) { return a.w0 == b.w0 && a.round == b.round && a.shift == b.shift && a.offset == b.offset; }
@@ -405,7 +247,7 @@ bool same_w(const x265hip_weight& a, const x265hip_weight& b) { return a.w0 == b
 // the view of (pic, weights): an existing one (shared) or a new one in the least recently used entry no active pair reads; -1 = all held
 int cs_find_or_make_view(CS* s, int pic, const x265hip_weight* w, unsigned mask)
 {
-    const CS::Pic& pc = s->pics[pic];
+    const Pic& pc = s->pool.pics[pic];
     for (int i = 0; i < (int)s->views.size(); i++)
     {
         CS::View& v = s->views[i];
@@ -425,10 +267,8 @@ int cs_find_or_make_view(CS* s, int pic, const x265hip_weight* w, unsigned mask)
     }
     if (victim < 0) return -1;
     CS::View& v = s->views[victim];
-    v.used = true; v.stamp = ++s->clock; v.busy = 0; v.pic = pic; v.picEpoch = pc.epoch; v.active = true;
-    v.mask = mask;
-    for (int c = 0; c < 3; c++) v.w[c] = (mask & (1u << c)) ? w[c] : x265hip_weight{ 0, 0, 0, 0 };
-    v.rowsSeen = 0; v.done[0] = v.done[1] = 0;
+    v.used = true; v.stamp = ++s->pool.clock; v.busy = 0;
+    view_reset(v, pic, pc.epoch, w, mask);
     s->viewsOpened++;
     return victim;
 }
@@ -468,11 +308,12 @@ int x265hip_cost_stream_create(x265hip_cost_stream** out, const x265hip_cost_str
     CS* s = new (std::nothrow) CS;
     if (!s) { set_error("cost_stream_create: out of memory"); return X265HIP_EINVAL; }
     s->prm = *p;
-    s->bpp = p->depth == 8 ? 1 : 2;
-    s->ctusW = p->width / 64; s->ctuRows = p->height / 64;
-    s->nplanes = hasC ? 3 : 1;
+    s->geo = plane_geometry(p->depth, p->stride, p->stride_c, p->height + 2 * p->margin_y, hasC ? p->height / 2 + 2 * p->margin_y_c : 0, p->margin_y, p->margin_y_c);
+    const PlaneGeometry& g = s->geo;
+    const int ctuRows = g.ctuRows;
+    s->ctusW = p->width / 64;
     s->bandRows = p->band_rows > 0 ? p->band_rows : 8;
-    if (s->bandRows > s->ctuRows) s->bandRows = s->ctuRows;
+    if (s->bandRows > ctuRows) s->bandRows = ctuRows;
     s->npu = x265hip_cost_pu_count(p->shapes);
     s->recBytes = x265hip_cost_record_bytes(p->subme, p->sad_costs);
     s->ctuBytes = x265hip_cost_ctu_bytes(p->subme, p->shapes, p->candidates, p->sad_costs);
@@ -481,45 +322,23 @@ int x265hip_cost_stream_create(x265hip_cost_stream** out, const x265hip_cost_str
     if (p->centre_range && (s->maxCx > p->centre_range)) s->maxCx = p->centre_range;
     if (p->centre_range && (s->maxCy > p->centre_range)) s->maxCy = p->centre_range;
     s->maxCyDown = maxCyDownRaw < s->maxCy ? maxCyDownRaw : s->maxCy;
-    s->pitch[0] = (size_t)p->stride * s->bpp; s->pitch[1] = (size_t)p->stride_c * s->bpp;
-    s->rows[0] = p->height + 2 * p->margin_y; s->rows[1] = hasC ? p->height / 2 + 2 * p->margin_y_c : 0;
-    s->planeBytes[0] = s->pitch[0] * s->rows[0]; s->planeBytes[1] = s->pitch[1] * s->rows[1];
-    s->margin[0] = p->margin_y; s->margin[1] = p->margin_y_c;
-    s->ctuLines[0] = 64; s->ctuLines[1] = 32;
-    s->nph[0] = 15; s->nph[1] = 63;
     if (hipGetDevice(&s->device) != hipSuccess) s->device = 0;
-#define CS_TRY(expr) do { if (check_hip((expr), #expr)) { cs_free(s); delete s; return X265HIP_ENODEV; } } while (0)
+    auto fail = [s] { cs_free(s); delete s; return X265HIP_ENODEV; };
+#define CS_TRY(expr) do { if (check_hip((expr), #expr)) return fail(); } while (0)
     CS_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    s->pics = std::vector<CS::Pic>(p->pictures);
-    for (auto& pc : s->pics)
-    {
-        pc.staged.assign(s->ctuRows, 0);
-        for (int i = 0; i < s->nplanes; i++)
-        {
-            const int k = i ? 1 : 0;
-            CS_TRY(hipHostMalloc((void**)&pc.stage[i], s->planeBytes[k], hipHostMallocDefault));
-            CS_TRY(hipMalloc((void**)&pc.dSrc[i], s->planeBytes[k] + 256));
-            CS_TRY(hipMemset(pc.dSrc[i], 0, s->planeBytes[k] + 256));
-        }
-    }
+    if (pool_alloc(s->pool, g, p->pictures)) return fail();
     s->views = std::vector<CS::View>(p->views);
     for (auto& v : s->views)
-        for (int i = 0; i < s->nplanes; i++)
-        {
-            const int k = i ? 1 : 0;
-            CS_TRY(hipMalloc((void**)&v.dW[i], s->planeBytes[k] + 256));
-            CS_TRY(hipMemset(v.dW[i], 0, s->planeBytes[k] + 256));
-            CS_TRY(hipMalloc((void**)&v.dOut[i], s->planeBytes[k] * s->nph[k] + 256));
-        }
+        if (view_alloc(v, g, 256)) return fail();
     s->slots = std::vector<CS::Slot>(p->slots);
     for (auto& sl : s->slots)
     {
-        CS_TRY(hipHostMalloc((void**)&sl.tables, s->rowBytes * s->ctuRows, hipHostMallocDefault));
+        CS_TRY(hipHostMalloc((void**)&sl.tables, s->rowBytes * ctuRows, hipHostMallocDefault));
         CS_TRY(hipHostMalloc((void**)&sl.hMvCost, (2 * (size_t)p->window + 1) * sizeof(uint16_t), hipHostMallocDefault));
         CS_TRY(hipMalloc((void**)&sl.dMvCost, (2 * (size_t)p->window + 1) * sizeof(uint16_t)));
-        sl.ready = new (std::nothrow) std::atomic<int>[s->ctuRows];
+        sl.ready = new (std::nothrow) std::atomic<int>[ctuRows];
         if (!sl.ready) { set_error("cost_stream_create: out of memory"); cs_free(s); delete s; return X265HIP_EINVAL; }
-        for (int r = 0; r < s->ctuRows; r++) sl.ready[r].store(0);
+        for (int r = 0; r < ctuRows; r++) sl.ready[r].store(0);
     }
     const size_t nctuBand = (size_t)s->bandRows * s->ctusW;
     CS_TRY(hipMalloc((void**)&s->dSurf, nctuBand * x265hip_surf_ctu_bytes(X265HIP_SURF_I32, p->window) + 256));
@@ -529,11 +348,9 @@ int x265hip_cost_stream_create(x265hip_cost_stream** out, const x265hip_cost_str
     CS_TRY(hipMalloc((void**)&s->dCentres, nctuBand * 4));
     CS_TRY(hipMalloc((void**)&s->dCand, nctuBand * s->npu * p->candidates * 4));
     CS_TRY(hipMalloc((void**)&s->dTables, nctuBand * s->ctuBytes));
-
-    // the device memsets are queued on the null stream and the worker's stream is non-blocking: wait for the fills here, once
-    CS_TRY(hipDeviceSynchronize());
 #undef CS_TRY
-    s->worker = std::thread(cs_worker, s);
+    if (wait_for_fills()) return fail();
+    s->w.thread = std::thread(cs_worker, s);
     *out = s;
     return 0;
 }
@@ -541,83 +358,62 @@ int x265hip_cost_stream_create(x265hip_cost_stream** out, const x265hip_cost_str
 void x265hip_cost_stream_destroy(x265hip_cost_stream* s)
 {
     if (!s) return;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        s->stop = true;
-    }
-    s->cv.notify_all();
-    if (s->worker.joinable()) s->worker.join();
-    (void)hipStreamSynchronize(s->stream);
+    worker_stop(s->w, s->stream);
     cs_free(s);
     delete s;
 }
 
 int x265hip_cost_stream_picture_rows(x265hip_cost_stream* s, uint64_t key, const void* luma_buf, const void* cb_buf, const void* cr_buf, int ctu_row0, int ctu_rows)
 {
-    if (!s || !luma_buf || (s->nplanes > 1 && (!cb_buf || !cr_buf)) || ctu_row0 < 0 || ctu_rows < 1 || ctu_row0 + ctu_rows > s->ctuRows)
+    if (!s || !luma_buf || (s->geo.nplanes > 1 && (!cb_buf || !cr_buf)) || ctu_row0 < 0 || ctu_rows < 1 || ctu_row0 + ctu_rows > s->geo.ctuRows)
     { set_error("cost_stream_picture_rows: bad argument"); return X265HIP_EINVAL; }
     int idx;
     {
-        std::lock_guard<std::mutex> lk(s->mu);
-        idx = cs_find_or_make_picture(s, key);
-        if (idx < 0) { set_error("cost_stream_picture_rows: every picture entry is still read (pictures = %d)", (int)s->pics.size()); return X265HIP_EBUSY; }
-        s->pics[idx].busy++;
+        std::lock_guard<std::mutex> lk(s->w.mu);
+        idx = cs_picture(s, key);
+        if (idx < 0) { set_error("cost_stream_picture_rows: every picture entry is still read (pictures = %d)", (int)s->pool.pics.size()); return X265HIP_EBUSY; }
+        s->pool.pics[idx].busy++;
     }
-    CS::Pic& pc = s->pics[idx];
     const void* bufs[3] = { luma_buf, cb_buf, cr_buf };
-    for (int pl = 0; pl < s->nplanes; pl++)
-    {
-        const int k = pl ? 1 : 0;
-        int y0, y1;
-        cs_lines(s, k, ctu_row0, ctu_rows, y0, y1);
-        memcpy(pc.stage[pl] + (size_t)y0 * s->pitch[k], (const uint8_t*)bufs[pl] + (size_t)y0 * s->pitch[k], (size_t)(y1 - y0) * s->pitch[k]);
-    }
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        pc.busy--;
-        if (pc.used && pc.key == key)
-            for (int r = ctu_row0; r < ctu_row0 + ctu_rows; r++) pc.staged[r] = 1;
-        s->dirty = true;
-    }
-    s->cv.notify_one();
+    stage_rows(s->w, s->geo, s->pool.pics[idx], key, bufs, ctu_row0, ctu_rows);
     return 0;
 }
 
 int x265hip_cost_stream_pair_open(x265hip_cost_stream* s, int slot, uint64_t fenc_key, uint64_t ref_key, const x265hip_weight* w, unsigned planes_weighted, const uint16_t* mv_cost)
 {
     if (!s || slot < 0 || slot >= (int)s->slots.size()) { set_error("cost_stream_pair_open: bad slot"); return X265HIP_EINVAL; }
-    unsigned mask = w ? planes_weighted & ((1u << s->nplanes) - 1) : 0;
-    for (int c = 0; c < s->nplanes; c++)
-        if ((mask & (1u << c)) && (w[c].shift < 14 - s->prm.depth || w[c].shift > 31))
+    unsigned mask = w ? planes_weighted & ((1u << s->geo.nplanes) - 1) : 0;
+    for (int c = 0; c < s->geo.nplanes; c++)
+        if ((mask & (1u << c)) && !weight_shift_ok(s->prm.depth, w[c].shift))
         { set_error("cost_stream_pair_open: plane %d shift %d (it includes the 14 - depth correction of weight_pp)", c, w[c].shift); return X265HIP_EINVAL; }
     int gen;
     {
-        std::lock_guard<std::mutex> lk(s->mu);
+        std::lock_guard<std::mutex> lk(s->w.mu);
         CS::Slot& sl = s->slots[slot];
         const bool was = sl.active;
         sl.active = false;                                    // the slot's previous pair no longer holds anything
-        const int fenc = cs_find_or_make_picture(s, fenc_key);
-        if (fenc >= 0) s->pics[fenc].busy++;                  // not the victim of the next line
-        const int ref = fenc < 0 ? -1 : cs_find_or_make_picture(s, ref_key);
-        if (fenc >= 0) s->pics[fenc].busy--;
+        const int fenc = cs_picture(s, fenc_key);
+        if (fenc >= 0) s->pool.pics[fenc].busy++;                  // not the victim of the next line
+        const int ref = fenc < 0 ? -1 : cs_picture(s, ref_key);
+        if (fenc >= 0) s->pool.pics[fenc].busy--;
         const int view = ref < 0 ? -1 : cs_find_or_make_view(s, ref, w, mask);
         if (view < 0)
         {
             sl.active = was;
-            set_error("cost_stream_pair_open: no %s entry free (pictures = %d, views = %d)", ref < 0 ? "picture" : "view", (int)s->pics.size(), (int)s->views.size());
+            set_error("cost_stream_pair_open: no %s entry free (pictures = %d, views = %d)", ref < 0 ? "picture" : "view", (int)s->pool.pics.size(), (int)s->views.size());
             return X265HIP_EBUSY;
         }
         if (++sl.generation <= 0) sl.generation = 1;
-        for (int r = 0; r < s->ctuRows; r++) sl.ready[r].store(0, std::memory_order_release);      // before anything is rewritten
-        sl.fenc = fenc; sl.fencEpoch = s->pics[fenc].epoch; sl.view = view; sl.viewStamp = s->views[view].stamp;
+        for (int r = 0; r < s->geo.ctuRows; r++) sl.ready[r].store(0, std::memory_order_release);      // before anything is rewritten
+        sl.fenc = fenc; sl.fencEpoch = s->pool.pics[fenc].epoch; sl.view = view; sl.viewStamp = s->views[view].stamp;
         sl.nextRow = 0; sl.active = true; sl.bandLimit = 1;
         sl.hasCost = mv_cost != nullptr;
         if (mv_cost) memcpy(sl.hMvCost, mv_cost, (2 * (size_t)s->prm.window + 1) * sizeof(uint16_t));
         gen = sl.generation;
         s->pairsOpened++;
-        s->dirty = true;
+        s->w.dirty = true;
     }
-    s->cv.notify_one();
+    s->w.cv.notify_one();
     return gen;
 }
 
@@ -633,8 +429,8 @@ int x265hip_cost_stream_stats(x265hip_cost_stream* s, x265hip_cost_stream_stats_
     if (!s || !st) { set_error("cost_stream_stats: NULL"); return X265HIP_EINVAL; }
     st->pairs_opened = s->pairsOpened; st->pairs_completed = s->pairsCompleted; st->bands = s->bands; st->rows_served = s->rowsServed; st->rows_uploaded = s->rowsUploaded;
     st->failed = s->failed; st->stale_pairs = s->stalePairs; st->views_opened = s->viewsOpened; st->views_shared = s->viewsShared; st->lines_weighted = s->linesWeighted;
-    st->us_busy = s->usBusy; st->bytes_downloaded = s->bytesDown; st->bytes_uploaded = s->bytesUp; st->table_bytes = s->rowBytes * s->ctuRows;
-    if (s->failed) set_error("cost_stream worker: %s", s->workerError);
+    st->us_busy = s->w.usBusy; st->bytes_downloaded = s->bytesDown; st->bytes_uploaded = s->bytesUp; st->table_bytes = s->rowBytes * s->geo.ctuRows;
+    if (s->failed) set_error("cost_stream worker: %s", s->w.error);
     return 0;
 }
 

@@ -12,7 +12,6 @@
 #include "common.h"
 
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -62,11 +61,6 @@ struct x265hip_me_cache
 };
 
 namespace {
-
-double now_us()
-{
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // A batch = the (source, reference) pairs that were queued together (normally all references of one picture): every pair is
 // uploaded and searched (one launch each), then the surfaces come down CTU ROW BY CTU ROW ACROSS THE PAIRS - row 0 of every pair,

@@ -32,7 +32,7 @@
 // Readers never wait and never lock: surface rows are valid when ready[row] == the pair's generation, checked BEFORE and AFTER the
 // read (a slot that was reopened in between has its flags cleared before any of its rows can be rewritten).  Everything a lookup
 // cannot serve is answered by the host's own primitive with identical values, so the bitstream cannot change.
-#include "common.h"
+#include "row_pictures.h"
 
 #include <atomic>
 #include <chrono>
@@ -96,43 +96,6 @@ __global__ void __launch_bounds__(256) surf_planes_kernel(const uint8_t* __restr
             *reinterpret_cast<uint4*>(base + (size_t)(80 - pu0) * planeS + (size_t)(pu - 80) * planeW + ((size_t)row * pitch + 4 * g) * 4) = make_uint4(v[0], v[1], v[2], v[3]);
     }
 }
-
-// centre of every CTU's window = the displacement of its 64x64 block's minimum SAD in the +-big search, clamped to +-maxX / +-maxY
-__global__ void centre_kernel(const unsigned long long* __restrict__ best, int16_t* __restrict__ centres, int nctu, int big, int maxX, int maxY)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nctu) return;
-    const uint32_t idx = (uint32_t)best[(size_t)i * 85 + 84];
-    const int ncb = 2 * big + 1;
-    const int mx = (int)(idx % ncb) - big, my = (int)(idx / ncb) - big;
-    centres[2 * i] = (int16_t)clip3(-maxX, maxX, mx);
-    centres[2 * i + 1] = (int16_t)clip3(-maxY, maxY, my);
-}
-
-// primitives.weight_pp (common/pixel.cpp:518-543) over whole buffer lines, margins included: the plane MotionReference::applyWeight
-// builds row by row (encoder/reference.cpp:119-178: weight_pp on the picture, then the borders replicated) is the reconstructed
-// plane weighted sample by sample - a replicated border sample weights to the replicated weighted sample.
-template <typename Px>
-__global__ void __launch_bounds__(256) weight_lines_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t ndw, int w0, int round, int shift, int offset,
-                                                           int correction, int maxVal)
-{
-    constexpr int PER = 4 / (int)sizeof(Px), BITS = 8 * (int)sizeof(Px);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ndw; i += (size_t)gridDim.x * blockDim.x)
-    {
-        const uint32_t v = src[i];
-        uint32_t o = 0;
-#pragma unroll
-        for (int k = 0; k < PER; k++)
-        {
-            const int px = (int)((v >> (k * BITS)) & ((1u << BITS) - 1));
-            const int val = (int)(int16_t)(px << correction);                       // "simulating pixel to short conversion" (pixel.cpp:535)
-            o |= (uint32_t)clip3(0, maxVal, ((w0 * val + round) >> shift) + offset) << (k * BITS);
-        }
-        dst[i] = o;
-    }
-}
-
-double ms_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 enum { ROW_NONE = 0, ROW_STAGED = 1, ROW_ON_DEVICE = 2 };
 
@@ -209,16 +172,9 @@ int run_round(S* s, const std::vector<Upload>& ups, const std::vector<Weigh>& we
     {
         long y0, y1;
         row_lines(s, q.r0, q.n, y0, y1);
-        const size_t off = (size_t)y0 * s->linePitch, ndw = (size_t)(y1 - y0) * s->linePitch / 4;
-        const x265hip_weight& w = s->pics[q.pic].w;
-        const int correction = 14 - s->prm.depth, maxVal = (1 << s->prm.depth) - 1;
-        size_t blocks = (ndw + 255) / 256;
-        if (blocks > 8192) blocks = 8192;
-        const uint32_t* src = (const uint32_t*)(s->pics[q.parent].dev + off);
-        uint32_t* dst = (uint32_t*)(s->pics[q.pic].dev + off);
-        if (s->bpp == 1) hipLaunchKernelGGL(weight_lines_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), 0, s->compute, src, dst, ndw, w.w0, w.round, w.shift, w.offset, correction, maxVal);
-        else hipLaunchKernelGGL(weight_lines_kernel<uint16_t>, dim3((unsigned)blocks), dim3(256), 0, s->compute, src, dst, ndw, w.w0, w.round, w.shift, w.offset, correction, maxVal);
-        X265HIP_TRY(hipGetLastError());
+        const size_t off = (size_t)y0 * s->linePitch;
+        int rc = weight_lines_launch(s->prm.depth, s->pics[q.parent].dev + off, s->pics[q.pic].dev + off, (size_t)(y1 - y0) * s->linePitch / 4, s->pics[q.pic].w, s->compute);
+        if (rc) return rc;
         s->rowsWeighted += q.n;
     }
     const size_t org = ((size_t)s->prm.margin_y * s->prm.stride + s->prm.margin_x) * s->bpp;
@@ -241,9 +197,8 @@ int run_round(S* s, const std::vector<Upload>& ups, const std::vector<Weigh>& we
             p.range = s->centreRange; p.best = (uint64_t*)s->dBest; p.cost_x = p.cost_y = s->dZeroCost;
             rc = x265hip_me_fullsearch(&p, s->compute);
             if (rc) return rc;
-            hipLaunchKernelGGL(centre_kernel, dim3((nctuBand + 63) / 64), dim3(64), 0, s->compute, (const unsigned long long*)s->dBest,
-                               sl.dCentres + (size_t)b.r0 * s->ctusW * 2, nctuBand, s->centreRange, s->maxCx, s->maxCy);
-            X265HIP_TRY(hipGetLastError());
+            rc = centres_launch((const unsigned long long*)s->dBest, sl.dCentres + (size_t)b.r0 * s->ctusW * 2, nctuBand, s->centreRange, s->maxCx, s->maxCy, s->maxCy, s->compute);
+            if (rc) return rc;
             p.best = nullptr; p.cost_x = p.cost_y = nullptr;
             p.centres = sl.dCentres + (size_t)b.r0 * s->ctusW * 2;
         }
@@ -400,7 +355,7 @@ void worker_main(S* s)
             }
         }
         if (ups.empty() && weighs.empty() && bands.empty()) continue;
-        const double t0 = ms_now_us();
+        const double t0 = now_us();
         bool failedRound = false;
         if (run_round(s, ups, weighs, bands))
         {
@@ -435,7 +390,7 @@ void worker_main(S* s)
             for (const Weigh& q : weighs) { s->pics[q.pic].busy--; s->pics[q.parent].busy--; }
             for (const Band& b : bands) { s->pics[b.fenc].busy--; s->pics[b.ref].busy--; }
         }
-        s->usBusy += (uint64_t)(ms_now_us() - t0);
+        s->usBusy += (uint64_t)(now_us() - t0);
     }
 }
 
@@ -676,7 +631,7 @@ int x265hip_me_stream_pair_open_weighted(x265hip_me_stream* s, int slot, uint64_
 {
     if (!s || slot < 0 || slot >= (int)s->slots.size()) { set_error("me_stream_pair_open: bad slot"); return X265HIP_EINVAL; }
     if (fenc_key == ref_key) { set_error("me_stream_pair_open: source and reference picture carry the same key"); return X265HIP_EINVAL; }
-    if (w && (w->shift < 14 - s->prm.depth || w->shift > 31 || w->w0 < -128 * 64 || w->w0 > 128 * 64))
+    if (w && (!weight_shift_ok(s->prm.depth, w->shift) || w->w0 < -128 * 64 || w->w0 > 128 * 64))
     { set_error("me_stream_pair_open: weight (w0 %d, shift %d) out of range (shift includes the 14 - depth correction of weight_pp)", w->w0, w->shift); return X265HIP_EINVAL; }
     int gen;
     {

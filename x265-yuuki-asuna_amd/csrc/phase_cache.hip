@@ -9,7 +9,6 @@
 #include "common.h"
 
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <cstring>
 #include <deque>
@@ -49,14 +48,12 @@ struct x265hip_phase_cache
 
 namespace {
 
-double pc_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 int run_plane(x265hip_phase_cache* c, x265hip_phase_cache::Slot& s, int plane, double& usK, double& usD)
 {
     const bool chroma = plane != 0;
     const size_t srcBytes = chroma ? c->chromaBytes : c->lumaBytes;
     const int nph = chroma ? 63 : 15;
-    const double t0 = pc_now_us();
+    const double t0 = now_us();
     X265HIP_TRY(hipMemcpyAsync(c->dSrc + c->guardLo, s.stage[plane], srcBytes, hipMemcpyHostToDevice, c->stream));
     x265hip_phase_planes_params p;
     p.depth = c->prm.depth; p.chroma = chroma; p.src = c->dSrc + c->guardLo; p.dst = c->dOut;
@@ -64,10 +61,10 @@ int run_plane(x265hip_phase_cache* c, x265hip_phase_cache::Slot& s, int plane, d
     int rc = x265hip_phase_planes(&p, c->stream);
     if (rc) return rc;
     X265HIP_TRY(hipStreamSynchronize(c->stream));
-    const double t1 = pc_now_us();
+    const double t1 = now_us();
     X265HIP_TRY(hipMemcpyAsync(s.out[plane], c->dOut, srcBytes * nph, hipMemcpyDeviceToHost, c->stream));
     X265HIP_TRY(hipStreamSynchronize(c->stream));
-    usK += t1 - t0; usD += pc_now_us() - t1;
+    usK += t1 - t0; usD += now_us() - t1;
     c->bytesDown += srcBytes * nph;
     return 0;
 }

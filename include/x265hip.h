@@ -300,6 +300,38 @@ int x265hip_inter_recon_bi(const x265hip_recon_bi_params* p, void* stream);
  * plane's own weights (WeightParam of Cb or Cr) - with the conventions of x265hip_inter_recon_chroma: planes and strides of the chroma
  * plane, width / height = LUMA size, mv / mv1 = the luma stage's records, (n/2)^2 levels per block. */
 int x265hip_inter_recon_chroma_bi(const x265hip_recon_bi_params* p, void* stream);
+/* The bidirectional decision of a B picture: for every NxN block (N = 8 << level, the block grid of the TU stages) which list(s) it is
+ * predicted from - the bidirectional part of Search::predInterSearch (search.cpp:2473-2640: luma-only cost of the averaged prediction
+ * :2498-2510, the zero-vector candidate :2515-2577, the selection :2581-2640 without the merge arm) with predInterLumaPixel
+ * (predict.cpp:245-265: rounded, clipped pixels), pixelavg_pp and pu[].satd.  With rec0 / rec1 = the block's records of the two
+ * x265hip_subpel_refine passes (entry base(level) + z of [ctu][85]) and mvc(q) = cost_q[qoff + qx] + cost_q[qoff + qy]:
+ *     c0  = rec0.cost + dir_cost[0]          c1 = rec1.cost + dir_cost[1]
+ *     cbi = satd(fenc, (P0 + P1 + 1) >> 1) + mvc(mv0) + mvc(mv1) + dir_cost[2]
+ *     if (mv0 != 0 || mv1 != 0) { cz = satd(fenc, (fref0[block] + fref1[block] + 1) >> 1) + 4 * cost_q[qoff] + dir_cost[2];
+ *                                 if (cz < cbi) cbi = cz, mv0 = mv1 = 0; }
+ *     dir = (cbi < c0 && cbi < c1) ? 3 : (c0 <= c1 ? 1 : 2)
+ * Each list is searched around one predictor, (0,0) (what cost_q is indexed with), so the reference's predictor range check of the zero
+ * candidate always passes and checkBestMVP has nothing to choose.  dir_cost = lambda * m_listSelBits of getBlkBits (search.cpp:2649-2656:
+ * 3, 3, 5 bits for a B slice's 2Nx2N).  Luma only: no chroma SATD, no sa8d / motion-compensated twin (checkBidir2Nx2N), no merge.
+ *   mv0_out / mv1_out : a used list gets { winning cost, final vector } (zero where the zero candidate won), an unused list
+ *                       { that list's own c_l, 0 }; only the level's entries are written
+ *   fref0 / fref1     : margins as x265hip_subpel_refine wants them */
+typedef struct x265hip_bidir_params
+{
+    int depth, width, height, level;                 /* width / height multiples of 64, level 0..2 */
+    const void* fenc;  intptr_t fenc_stride;
+    const void* fref0; const void* fref1; intptr_t fref_stride;      /* sample (0,0) of the list-0 / list-1 reference */
+    const int32_t* mv0; const int32_t* mv1;          /* [ctu*85][2] records of the two refinements */
+    const uint16_t* cost_q; int qoff;
+    int32_t dir_cost[3];
+    int ref_id0, ref_id1;                            /* picture ids written into ref0 / ref1 (what x265hip_deblock_bs_inter compares) */
+    const void* phase_planes0; const void* phase_planes1; intptr_t phase_plane_samples;   /* optional (both or none): each list's planes as x265hip_subpel_params takes them */
+    uint8_t* dir;                                    /* [ctu][blocks]: 1 / 2 / 3, the `dir` of x265hip_recon_bi_params */
+    int8_t* ref0; int8_t* ref1;                      /* optional [ctu][blocks]: ref_id or -1 (list unused) */
+    int32_t* mv0_out; int32_t* mv1_out;              /* [ctu*85][2]; must not alias mv0 / mv1 or each other */
+    int32_t* cost_out;                               /* optional [ctu][blocks][4] = { c0, c1, bidir at the refined vectors, cz or -1 if not tried } */
+} x265hip_bidir_params;
+int x265hip_bidir_decide(const x265hip_bidir_params* p, void* stream);
 /* The TU-stage entries, as x265hip_tu_launch_grid names them. */
 enum x265hip_tu_entry
 {

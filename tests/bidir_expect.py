@@ -1,0 +1,301 @@
+"""Expected results of the bidirectional decision (x265hip_bidir_decide), assembled from the oracle's pieces.
+
+The decision itself is not a function of the oracle library, so the expectation is put together here from what the oracle does provide:
+O.me_fullsearch / O.subpel_refine give the two lists' records, O.phase_planes gives predInterLumaPixel's samples (the plane of phase
+yFrac * 4 + xFrac read at the vector's integer part IS luma_hpp / luma_vpp / luma_hvpp of the block, rounded and clipped), and
+pixelavg_pp / satd are the oracle table's own slots pu[LUMA_NxN].pixelavg_pp / pu[LUMA_NxN].satd - where the real reference build is
+present its slots are called too and must agree.  The arithmetic that remains here is the handful of integer additions and comparisons
+of Search::predInterSearch (search.cpp:2498-2510, 2515-2577, 2581-2640)."""
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import oracle_api as O          # noqa: E402
+import harness                  # noqa: E402
+
+F = importlib.import_module("x265-yuuki-asuna_amd.frames")
+spec = importlib.import_module("x265-yuuki-asuna_amd.table_spec")
+
+LEVEL_BASE = (0, 64, 80)
+DIR_COST = (12, 12, 20)         # lambda 4 x m_listSelBits (3, 3, 5) of a B slice's 2Nx2N (search.cpp:2649-2656)
+OUTCOMES = ("dir1", "dir2", "dir3_refined", "dir3_zero", "not_tried", "tie01")
+
+
+def zorder(z):
+    return (z & 1) | ((z >> 1) & 2) | ((z >> 2) & 4), ((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4)
+
+
+def six_stripe_lumas(depth, w=768, h=192, seed=21):
+    """[list 0, cur, list 1] luma pictures whose six vertical stripes make every outcome of the decision occur: (a) plain motion,
+    (b) only list 0 matches, (c) only list 1 matches, (d) flat + noise (spurious vectors: the zero candidate competes), (e) opposite
+    patterns that only the coincident average cancels, (f) three identical pictures (zero vectors, nothing tried, c0 == c1)."""
+    clip = F.synth_clip(w, h, 3, depth=depth, seed=seed)
+    other = F.synth_clip(w, h, 3, depth=depth, seed=seed + 1000)
+    ys = [c[0].copy() for c in clip]
+    r = np.random.default_rng([seed, depth])
+    q = w // 6
+    sc = 1 << (depth - 8)
+    mx = (1 << depth) - 1
+    ys[2][:, q:2 * q] = other[0][0][:, q:2 * q]
+    ys[0][:, 2 * q:3 * q] = other[2][0][:, 2 * q:3 * q]
+    for i in range(3):
+        ys[i][:, 3 * q:4 * q] = np.clip(np.rint(128 * sc + r.normal(0, 3.0 * sc, size=(h, q))), 0, mx).astype(ys[i].dtype)
+    E = np.rint(r.normal(0, 20.0 * sc, size=(h, q)))
+    ys[0][:, 4 * q:5 * q] = np.clip(128 * sc + E, 0, mx).astype(ys[0].dtype)
+    ys[2][:, 4 * q:5 * q] = np.clip(128 * sc - E, 0, mx).astype(ys[0].dtype)
+    ys[1][:, 4 * q:5 * q] = np.clip(np.rint(128 * sc + r.normal(0, 1.0 * sc, size=(h, q))), 0, mx).astype(ys[0].dtype)
+    ys[0][:, 5 * q:] = ys[1][:, 5 * q:]
+    ys[2][:, 5 * q:] = ys[1][:, 5 * q:]
+    return ys
+
+
+def oracle_records(depth, cur, ref, stride, org, w64, h64, rng_r, subme, lam=4.0):
+    """{cost, qmvx | qmvy << 16} [nctu * 85, 2] of cur searched in and refined against ref (padded host planes)."""
+    nctu = (w64 // 64) * (h64 // 64)
+    cost = F.mv_cost_table(rng_r, lam)
+    cq, qoff = F.qpel_cost_table(rng_r, lam)
+    _, best = O.me_fullsearch(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False)
+    return O.subpel_refine(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, best, cq, qoff, subme)
+
+
+def phases_of(depth, ref, stride):
+    """[16, rows, stride]: the reference plane itself (phase 0) and its 15 fractional-phase planes."""
+    ph = O.phase_planes(depth, ref.reshape(-1), stride, ref.shape[0])
+    return np.ascontiguousarray(np.concatenate([ref.reshape(1, ref.shape[0], stride), ph], axis=0))
+
+
+def unpack_mv(word):
+    w = int(word) & 0xffffffff
+    qx, qy = w & 0xffff, w >> 16
+    return qx - 0x10000 if qx & 0x8000 else qx, qy - 0x10000 if qy & 0x8000 else qy
+
+
+class Slots:
+    """pixelavg_pp and satd of the N x N luma PU from the oracle's table - and from the real reference's where it is built: both are
+    called on every block and must agree."""
+
+    def __init__(self, depth, n, with_reference=True):
+        idx = spec.LUMA_PU_INDEX[f"{n}x{n}"]
+        tabs = [harness.load_oracle(depth, ROOT)]
+        ref = harness.load_reference(depth, ROOT) if with_reference else None
+        if ref is not None:
+            tabs.append(ref)
+        self.keep = tabs
+        self.avg = [t.fn(f"pu[{idx}].pixelavg_pp[0]") for t in tabs]
+        self.satd = [t.fn(f"pu[{idx}].satd") for t in tabs]
+        assert all(self.avg) and all(self.satd)
+        self.n, self.dt = n, harness.pix_dtype(depth)
+        self.tables = len(tabs)
+
+    def satd_of_average(self, fenc_ptr, fenc_stride, a_ptr, b_ptr, ref_stride):
+        out = []
+        for avg, satd in zip(self.avg, self.satd):
+            tmp = np.zeros((self.n, self.n), self.dt)
+            avg(tmp.ctypes.data, self.n, a_ptr, ref_stride, b_ptr, ref_stride, 32)
+            out.append(satd(fenc_ptr, fenc_stride, tmp.ctypes.data, self.n))
+        assert len(set(out)) == 1, f"oracle and reference slots disagree: {out}"
+        return out[0]
+
+
+def expect(depth, cur, stride, org, w64, h64, level, recs, phases, cq, qoff, dir_cost=DIR_COST, ref_ids=(0, 1), with_reference=True):
+    """The decision for every block of `level`: recs = (list 0, list 1) records [nctu * 85, 2], phases = (list 0, list 1) phases_of().
+    Returns dict: dir uint8 [nctu * nb], ref0 / ref1 int8, mv0 / mv1 int32 [nctu * nb, 2] (the level's entries of mv*_out, block order),
+    cost int32 [nctu * nb, 4], and the boolean outcome masks of OUTCOMES."""
+    n, nb, base = 8 << level, (64 >> (3 + level)) ** 2, LEVEL_BASE[level]
+    cw = w64 // 64
+    nctu = cw * (h64 // 64)
+    slots = Slots(depth, n, with_reference)
+    es = cur.itemsize
+    tot = nctu * nb
+    d = np.zeros(tot, np.uint8)
+    ref0, ref1 = np.zeros(tot, np.int8), np.zeros(tot, np.int8)
+    mvo = [np.zeros((tot, 2), np.int32), np.zeros((tot, 2), np.int32)]
+    cost = np.zeros((tot, 4), np.int32)
+    masks = {k: np.zeros(tot, bool) for k in OUTCOMES}
+    cqi = cq.astype(np.int64)
+    for ctu in range(nctu):
+        cx, cy = (ctu % cw) * 64, (ctu // cw) * 64
+        for z in range(nb):
+            bx, by = zorder(z)
+            off = org + (cy + by * n) * stride + cx + bx * n           # element offset of the block in every padded plane
+            b = ctu * nb + z
+            ptrs, zptrs, mvc, words, cl = [], [], [], [], []
+            for l in (0, 1):
+                c, word = recs[l][ctu * 85 + base + z]
+                qx, qy = unpack_mv(word)
+                p = (qy & 3) * 4 + (qx & 3)
+                ptrs.append(phases[l].ctypes.data + ((p * phases[l].shape[1] * stride) + off + (qy >> 2) * stride + (qx >> 2)) * es)
+                zptrs.append(phases[l].ctypes.data + off * es)
+                mvc.append(int(cqi[qoff + qx]) + int(cqi[qoff + qy]))
+                words.append(int(word))
+                cl.append(int(c) + dir_cost[l])
+            fp = cur.ctypes.data + off * es
+            cref = slots.satd_of_average(fp, stride, ptrs[0], ptrs[1], stride) + mvc[0] + mvc[1] + dir_cost[2]
+            cbi, cz, m = cref, -1, list(words)
+            tried = words[0] != 0 or words[1] != 0
+            if tried:
+                cz = slots.satd_of_average(fp, stride, zptrs[0], zptrs[1], stride) + 4 * int(cqi[qoff]) + dir_cost[2]
+                if cz < cbi:
+                    cbi, m = cz, [0, 0]
+            dd = 3 if (cbi < cl[0] and cbi < cl[1]) else (1 if cl[0] <= cl[1] else 2)
+            d[b] = dd
+            ref0[b] = ref_ids[0] if dd & 1 else -1
+            ref1[b] = ref_ids[1] if dd & 2 else -1
+            if dd == 3:
+                mvo[0][b], mvo[1][b] = (cbi, m[0]), (cbi, m[1])
+            else:
+                mvo[0][b] = (cl[0], m[0] if dd == 1 else 0)
+                mvo[1][b] = (cl[1], m[1] if dd == 2 else 0)
+            cost[b] = (cl[0], cl[1], cref, cz)
+            masks["dir1"][b], masks["dir2"][b] = dd == 1, dd == 2
+            masks["dir3_refined"][b] = dd == 3 and not (tried and cz < cref)
+            masks["dir3_zero"][b] = dd == 3 and tried and cz < cref
+            masks["not_tried"][b] = not tried
+            masks["tie01"][b] = cl[0] == cl[1]
+    return dict(dir=d, ref0=ref0, ref1=ref1, mv0=mvo[0], mv1=mvo[1], cost=cost, masks=masks, tables=slots.tables)
+
+
+def full_mv_out(level, nctu, level_entries, prefill):
+    """The whole [nctu * 85, 2] mv*_out buffer a launch leaves: `prefill` everywhere but the level's entries."""
+    nb, base = (64 >> (3 + level)) ** 2, LEVEL_BASE[level]
+    out = np.full((nctu, 85, 2), prefill, np.int32)
+    out[:, base:base + nb] = level_entries.reshape(nctu, nb, 2)
+    return out.reshape(-1, 2)
+
+
+class SixStripe:
+    """The six-stripe case on the host: padded planes, both lists' records and phases."""
+
+    def __init__(self, depth, subme, rng_r=12, w=768, h=192, seed=21, lam=4.0):
+        self.depth, self.subme, self.range = depth, subme, rng_r
+        self.ys = six_stripe_lumas(depth, w, h, seed)
+        pl = [F.pad_plane(y) for y in self.ys]
+        self.cur, self.stride, self.org, self.w64, self.h64 = pl[1]
+        self.refs = (pl[0][0], pl[2][0])
+        self.nctu = (self.w64 // 64) * (self.h64 // 64)
+        self.cq, self.qoff = F.qpel_cost_table(rng_r, lam)
+        self.recs = [oracle_records(depth, self.cur, r, self.stride, self.org, self.w64, self.h64, rng_r, subme, lam) for r in self.refs]
+        self.phases = [phases_of(depth, r, self.stride) for r in self.refs]
+
+    def expect(self, level, dir_cost=DIR_COST, **kw):
+        return expect(self.depth, self.cur, self.stride, self.org, self.w64, self.h64, level, self.recs, self.phases, self.cq, self.qoff, dir_cost, **kw)
+
+
+def b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, subme, level, qp, sao_rdo=None, dir_cost=DIR_COST, tu_flags=2,
+            cores=0, avx2=False, with_reference=False):
+    """One B picture through the oracle, stage by stage (the CPU twin of stages.BFramePipeline.run with chroma, deblocking and SAO applied):
+    *_planes = padded (Y [rows, stride], Cb, Cr) host planes of the source picture and of the two reference pictures.  sao_rdo: the record
+    FramePipeline takes (x265hip_sao_rdo's host inputs) or None = the distortion-only stand-in.  Returns every stage output by name."""
+    S = importlib.import_module("x265-yuuki-asuna_amd.stages")
+    _, _, stride, rows, org = F.padded_dims(w64, h64)
+    cur, r0, r1 = cur_planes[0], ref0_planes[0], ref1_planes[0]
+    nctu = (w64 // 64) * (h64 // 64)
+    cost = F.mv_cost_table(rng_r)
+    cq, qoff = F.qpel_cost_table(rng_r)
+    out, recs, phases = {}, [], []
+    for l, ref in enumerate((r0, r1)):
+        _, best = O.me_fullsearch(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False, nthreads=cores, avx2=avx2)
+        mv = O.subpel_refine(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, best, cq, qoff, subme, nthreads=cores, avx2=avx2)
+        out["me_best%d" % l], out["subpel_mv%d" % l] = best, mv
+        recs.append(mv)
+        phases.append(phases_of(depth, ref, stride))
+    e = expect(depth, cur, stride, org, w64, h64, level, recs, phases, cq, qoff, dir_cost, with_reference=with_reference)
+    del phases
+    mv0, mv1 = full_mv_out(level, nctu, e["mv0"], 0), full_mv_out(level, nctu, e["mv1"], 0)
+    out.update({"dir": e["dir"], "ref0": e["ref0"], "ref1": e["ref1"], "mv0_out": mv0, "mv1_out": mv1, "cost_out": e["cost"]})
+    rec, lev, ns, dist = O.inter_recon_bi(depth, cur.reshape(-1), stride, org, r0.reshape(-1), r1.reshape(-1), w64, h64, level, mv0, mv1, qp,
+                                          dir_flags=e["dir"], intra_slice=tu_flags, nthreads=cores, avx2=avx2)
+    out.update({"levels": lev, "num_sig": ns, "dist": dist})
+    cuqp = max(qp - 6 * (depth - 8), 0)
+    bv, bh = O.deblock_bs_b(depth, w64, h64, level, mv0, mv1, e["ref0"], e["ref1"], ns, slice_b=True, avx2=avx2)
+    out.update({"bs_ver": bv, "bs_hor": bh})
+    dbk = O.deblock_luma(depth, rec.reshape(-1), stride, org, w64, h64, bv, bh, cuqp, avx2=avx2)
+    cnt, off = O.sao_stats(depth, cur.reshape(-1), dbk.reshape(-1), stride, org, w64, h64, nthreads=cores, avx2=avx2)
+    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
+    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
+    qpc = S.chroma_quant_qp(qp, depth)
+    crec = [O.inter_recon_chroma_bi(depth, cur_planes[c].reshape(-1), ref0_planes[c].reshape(-1), ref1_planes[c].reshape(-1), sc, oc, w64, h64, level, mv0, mv1,
+                                    qpc, dir_flags=e["dir"], intra_slice=tu_flags, nthreads=cores, avx2=avx2) for c in (1, 2)]
+    cdb = O.deblock_chroma(depth, crec[0][0].reshape(-1), crec[1][0].reshape(-1), sc, oc, w64, h64, bv, bh, cuqp, avx2=avx2)
+    cstat = [O.sao_stats(depth, cur_planes[1 + i].reshape(-1), cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, nthreads=cores, avx2=avx2, ctu=(32, 32), plane_offset=2)
+             for i in range(2)]
+    if sao_rdo is not None:
+        lam = np.tile(np.array(sao_rdo["lambdas"], np.int64), (nctu, 1))
+        pars, _ = O.sao_rdo(depth, [cnt, cstat[0][0], cstat[1][0]], [off, cstat[0][1], cstat[1][1]], w64 // 64, h64 // 64, lam, sao_rdo["ctx_merge"],
+                            sao_rdo["ctx_type"], sao_rdo["entropy_bits"], avx2=avx2)
+        par, cpars = pars[0].reshape(-1), [pars[1].reshape(-1), pars[2].reshape(-1)]
+    else:
+        _, par = O.sao_decide(depth, cnt, off, avx2=avx2)
+        cpars = [O.sao_decide(depth, cstat[i][0], cstat[i][1], avx2=avx2)[1] for i in range(2)]
+    fin = O.sao_apply(depth, dbk.reshape(-1), stride, org, w64, h64, par, nthreads=cores, avx2=avx2).reshape(rows, stride)
+    out.update({"sao_count": cnt, "sao_offset_org": off, "sao_params": par})
+    inner = fin[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
+    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
+    for i in range(2):
+        cf = O.sao_apply(depth, cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, cpars[i], nthreads=cores, avx2=avx2, ctu=(32, 32))
+        out["levels_c%d" % i], out["num_sig_c%d" % i], out["sao_count_c%d" % i], out["sao_params_c%d" % i] = crec[i][1], crec[i][2], cstat[i][0], cpars[i]
+        ci = cf.reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
+        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
+    return out
+
+
+def b_device_outputs(pipe, dt):
+    """The same names from a stages.BFramePipeline after run() (chroma, deblocking, SAO applied, want_cost)."""
+    out = {}
+    for l in range(2):
+        out["me_best%d" % l] = pipe.msl[l].best.cpu().numpy().view(np.uint64)
+        out["subpel_mv%d" % l] = pipe.spl[l].out.cpu().numpy().reshape(-1, 2)
+    bd = pipe.bd
+    out.update({"dir": bd.dir.cpu().numpy(), "ref0": bd.ref0.cpu().numpy(), "ref1": bd.ref1.cpu().numpy(), "mv0_out": bd.mv0_out.cpu().numpy().reshape(-1, 2),
+                "mv1_out": bd.mv1_out.cpu().numpy().reshape(-1, 2), "cost_out": bd.cost_out.cpu().numpy().reshape(-1, 4),
+                "levels": pipe.rc.levels.cpu().numpy(), "num_sig": pipe.rc.num_sig.cpu().numpy(), "dist": pipe.rc.dist.cpu().numpy(),
+                "bs_ver": pipe.db.bs_ver.cpu().numpy(), "bs_hor": pipe.db.bs_hor.cpu().numpy(),
+                "sao_count": pipe.sao.count.cpu().numpy(), "sao_offset_org": pipe.sao.offset_org.cpu().numpy(), "sao_params": pipe.sao.params.cpu().numpy(),
+                "recon": pipe.final.cpu().numpy().view(dt)})
+    for i in range(2):
+        out["levels_c%d" % i], out["num_sig_c%d" % i] = pipe.rc_c[i].levels.cpu().numpy(), pipe.rc_c[i].num_sig.cpu().numpy()
+        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = pipe.sao_c[i].count.cpu().numpy(), pipe.sao_c[i].params.cpu().numpy()
+        out["recon_c%d" % i] = pipe.final_c[i].cpu().numpy().view(dt)
+    return out
+
+
+def compare(dev_out, cpu_out):
+    """Stage by stage, equal or not (no tolerance: everything is integer arithmetic).  Returns the list of stages that differ."""
+    bad = []
+    for k, e in cpu_out.items():
+        g, e = np.asarray(dev_out[k]).reshape(-1), np.asarray(e).reshape(-1)
+        if g.dtype != e.dtype:
+            g, e = g.astype(np.int64), e.astype(np.int64)
+        if g.shape != e.shape:
+            bad.append(f"{k}: shape {g.shape} vs {e.shape}")
+        elif not np.array_equal(g, e):
+            bad.append(f"{k}: {int(np.count_nonzero(g != e))} of {e.size} values differ")
+    return bad
+
+
+def padded_planes(yuv):
+    """(Y, Cb, Cr) pictures -> the padded host planes b_chain takes (and w64, h64)."""
+    y, stride, org, w64, h64 = F.pad_plane(yuv[0])
+    return (y, F.pad_chroma(yuv[1], w64, h64)[0], F.pad_chroma(yuv[2], w64, h64)[0]), w64, h64
+
+
+def occluded_clip(width, height, nframes, depth, seed):
+    """frames.synth_clip with two vertical bands (the second and third quarter of the width, all three planes) that change content in the
+    middle of the clip: band A shows other content AFTER picture nframes // 2, band B BEFORE it - so a B picture finds band A in its
+    earlier reference only or band B in its later reference only, wherever the change lies between it and that reference, and plain
+    motion everywhere else: all three prediction directions occur."""
+    clip = [tuple(p.copy() for p in f) for f in F.synth_clip(width, height, nframes, depth=depth, seed=seed)]
+    other = F.synth_clip(width, height, nframes, depth=depth, seed=seed + 1000)
+    mid, q = nframes // 2, width // 4
+    for k in range(nframes):
+        for c in range(3):
+            s = 1 if c == 0 else 2
+            if k > mid:
+                clip[k][c][:, q // s:2 * q // s] = other[k][c][:, q // s:2 * q // s]
+            if k < mid:
+                clip[k][c][:, 2 * q // s:3 * q // s] = other[k][c][:, 2 * q // s:3 * q // s]
+    return clip

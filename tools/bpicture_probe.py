@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""Time the B-picture step (stages.BFramePipeline) on one GPU: picture 1 of a synthetic clip between pictures 0 and 2, the bench's settings.
+
+  python tools/bpicture_probe.py --steps 20 --subpel-planes 1          # one JSON line: ms per B step, per-stage event times through mark()
+  rocprofv3 --kernel-trace --stats -d DIR -o b -- python tools/bpicture_probe.py --steps 20     # + tools/rocprof_summary.py kernel-trace DIR/.../b_results.db
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--depth", type=int, default=8, choices=[8, 10])
+    ap.add_argument("--range", type=int, default=57)
+    ap.add_argument("--subme", type=int, default=3)
+    ap.add_argument("--level", type=int, default=2)
+    ap.add_argument("--qp", type=int, default=27)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--subpel-planes", type=int, default=1, choices=[0, 1])
+    a = ap.parse_args()
+    import torch
+    F = importlib.import_module("x265-yuuki-asuna_amd.frames")
+    P = importlib.import_module("x265-yuuki-asuna_amd.pipeline")
+    S = importlib.import_module("x265-yuuki-asuna_amd.stages")
+    HT = importlib.import_module("x265-yuuki-asuna_amd.host_tables")
+    dev = torch.device("cuda:0")
+    qp = a.qp + 12 * (a.depth == 10)
+    clip = F.synth_clip(a.width, a.height, 3, depth=a.depth, seed=265)
+    cur, r0, r1 = (P.DevicePicture(clip[i][0], dev, clip[i][1], clip[i][2]) for i in (1, 0, 2))
+    tabs = HT.load()
+    cu_qp = max(qp - 6 * (a.depth - 8), 0)
+    cm, ct = HT.sao_contexts(HT.SLICE_B, cu_qp)
+    srdo = {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
+    pipe = S.BFramePipeline(cur.w64, cur.h64, a.depth, dev, rng=a.range, subme=a.subme, level=a.level, qp=qp, deblock=True, sao=True, chroma=True,
+                            sao_apply=True, sign_hide=True, subpel_planes=bool(a.subpel_planes), sao_rdo=srdo)
+    for _ in range(a.warmup):
+        pipe.run(cur, r0, r1)
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(a.steps):
+        pipe.run(cur, r0, r1)
+    t1.record()
+    torch.cuda.synchronize()
+    ms = t0.elapsed_time(t1) / a.steps
+    # per-stage times: one event after every stage, averaged over the same number of steps
+    stages = {}
+    for _ in range(a.steps):
+        evs = [("start", torch.cuda.Event(enable_timing=True))]
+        evs[0][1].record()
+
+        def mark(name):
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            evs.append((name, e))
+        pipe.run(cur, r0, r1, mark=mark)
+        torch.cuda.synchronize()
+        for (_, e0), (name, e1) in zip(evs, evs[1:]):
+            stages[name] = stages.get(name, 0.0) + e0.elapsed_time(e1) / a.steps
+    d = pipe.bd.dir.cpu().numpy()
+    print(json.dumps({"what": "BFramePipeline.run", "width": a.width, "height": a.height, "depth": a.depth, "range": a.range, "subme": a.subme,
+                      "level": a.level, "subpel_planes": a.subpel_planes, "steps": a.steps, "ms_per_b_step": round(ms, 4),
+                      "stages_ms": {k: round(v, 4) for k, v in stages.items()}, "stages_ms_sum": round(sum(stages.values()), 4),
+                      "dir_counts": [int((d == k).sum()) for k in (1, 2, 3)], "checksum": pipe.checksum()}))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,184 @@
+// bidir_kernels.hip - the bidirectional decision of a B picture's blocks, on gfx950: which list(s) every NxN block is predicted from.
+//
+// Reference semantics: the bidirectional part of Search::predInterSearch (source/encoder/search.cpp:2473-2640) - the luma-only branch
+// of the averaged prediction's cost (:2498-2510), the zero-vector candidate (bTryZero, :2515-2577, luma branch :2544-2551, strict '<'
+// at :2566) and the selection between list 0, list 1 and both (:2581-2640, without the merge arm) - with Predict::predInterLumaPixel
+// (source/common/predict.cpp:245-265: luma_hpp / luma_vpp / luma_hvpp / copy, i.e. ROUNDED AND CLIPPED pixels, not the 14-bit
+// intermediates addAvg combines), pixelavg_pp ((a + b + 1) >> 1, source/common/pixel.cpp) and pu[].satd (pixel.cpp:210-297; tiled in
+// 4x4s here - every 4x4's coefficient sum is even, so the tiling does not change the total).
+//
+// The pipeline searches each list around ONE predictor, (0,0) - that is what cost_q is indexed with everywhere - so the reference's
+// predictor range check of the zero candidate (:2520-2528) always passes, and checkBestMVP (:2563-2564) has nothing to choose between:
+// the zero candidate's vector cost is 4 * cost_q[qoff] (two components per list, both lists).
+//
+// Mapping: one workgroup of 256 threads per CTU, thread = one 4x4 tile of one block, a block's 4 / 16 / 64 tiles on consecutive lanes
+// (the geometry of the sub-pel stage), the tile's source samples in registers.  Each thread forms its tile of both lists' predictions
+// (tile_predict: the exact interpolation; with phase planes four dword loads per list instead), takes the SATD of the averaged
+// prediction and of the zero candidate, and the two partial costs are summed over the block's lanes with DPP moves - a block never
+// straddles a wavefront, so there is no LDS and no barrier.  One lane per block decides and writes.  No atomics.
+#include "common.h"
+#include "tile_interp.h"
+
+namespace x265hip {
+
+struct BidirArgs
+{
+    const uint8_t* fenc; long fencStrideB;
+    const uint8_t* fref[2]; long frefStrideB;
+    int ctusW, depth;
+    const int2* mv[2];                   // {cost, qx | qy << 16} per PU, [ctu][85]
+    const uint16_t* costQ; int qoff;
+    int dirCost[3];
+    int refId[2];
+    const uint8_t* planes[2]; long planeBytes;       // sample (0,0) of phase 1 of each list's reference; NULL = interpolate
+    uint8_t* dir;
+    int8_t* ref[2];
+    int2* mvOut[2];
+    int* costOut;                        // [ctu][blocks][4]
+};
+
+template <int LEVEL> struct BdGeom
+{
+    static constexpr int N = 8 << LEVEL, NPU = 64 >> (2 * LEVEL);
+    static constexpr int TSHIFT = 2 * LEVEL + 2, NTILES = 1 << TSHIFT, TPR = N >> 2;     // 4x4 tiles per block; NPU * NTILES = 256
+    static constexpr int LBASE = LEVEL == 0 ? 0 : (LEVEL == 1 ? 64 : 80);
+};
+
+template <typename Px, int LEVEL, bool PL>
+__global__ void __launch_bounds__(256) bidir_decide_kernel(BidirArgs a)
+{
+    typedef BdGeom<LEVEL> G;
+    constexpr int BPP = sizeof(Px), N = G::N;
+    const int ctu = xcd_swizzle(blockIdx.x, gridDim.x);
+    const int cx = (ctu % a.ctusW) * 64, cy = (ctu / a.ctusW) * 64;
+    const int tid = threadIdx.x;
+    const int pu = tid >> G::TSHIFT, tile = tid & (G::NTILES - 1);
+    const int bxz = (pu & 1) | ((pu >> 1) & 2) | ((pu >> 2) & 4), byz = ((pu >> 1) & 1) | ((pu >> 2) & 2) | ((pu >> 3) & 4);
+    const int ty = tile / G::TPR, tx = tile % G::TPR;
+    const int px = cx + bxz * N + tx * 4, py = cy + byz * N + ty * 4;
+
+    int src[4][4];
+    tile_predict<BPP>(a.fenc + (long)py * a.fencStrideB + (long)px * BPP, a.fencStrideB, 0, 0, a.depth, src);
+
+    const size_t rec = (size_t)ctu * 85 + G::LBASE + pu;
+    const int2 r0 = a.mv[0][rec], r1 = a.mv[1][rec];
+    const long tileOff = (long)py * a.frefStrideB + (long)px * BPP;
+
+    // P0 + P1 at the refined vectors and at (0,0): one pass per list, the interpolation code exists once
+    int sumP[4][4] = {}, sumZ[4][4] = {};
+#pragma unroll 1
+    for (int l = 0; l < 2; l++)
+    {
+        const int w = l ? r1.y : r0.y;
+        const int qx = (int16_t)(w & 0xffff), qy = w >> 16;
+        const int xf = qx & 3, yf = qy & 3, ph = yf * 4 + xf;
+        const uint8_t* z = a.fref[l] + tileOff;
+        const uint8_t* org = ((PL && ph) ? a.planes[l] + (long)(ph - 1) * a.planeBytes + tileOff : z)
+                             + (long)(qy >> 2) * a.frefStrideB + (long)(qx >> 2) * BPP;
+        int d[4][4];
+        tile_predict<BPP>(org, a.frefStrideB, PL ? 0 : xf, PL ? 0 : yf, a.depth, d);
+#pragma unroll
+        for (int y = 0; y < 4; y++)
+#pragma unroll
+            for (int x = 0; x < 4; x++) sumP[y][x] += d[y][x];
+        tile_predict<BPP>(z, a.frefStrideB, 0, 0, a.depth, d);
+#pragma unroll
+        for (int y = 0; y < 4; y++)
+#pragma unroll
+            for (int x = 0; x < 4; x++) sumZ[y][x] += d[y][x];
+    }
+#pragma unroll
+    for (int y = 0; y < 4; y++)
+#pragma unroll
+        for (int x = 0; x < 4; x++)
+        {
+            sumP[y][x] = src[y][x] - ((sumP[y][x] + 1) >> 1);
+            sumZ[y][x] = src[y][x] - ((sumZ[y][x] + 1) >> 1);
+        }
+    int sBi = tile_satd4(sumP), sZ = tile_satd4(sumZ);
+    // sum over the block's NTILES consecutive lanes (every lane takes part)
+    sBi = quad_sum(sBi); sZ = quad_sum(sZ);
+    if (G::NTILES >= 16) { sBi = row_sum_of_quads(sBi); sZ = row_sum_of_quads(sZ); }
+    if (G::NTILES >= 64) { sBi = wave_sum_of_rows(sBi); sZ = wave_sum_of_rows(sZ); }
+
+    if (tile == 0)
+    {
+        auto mvc = [&](const int w) { return (int)a.costQ[a.qoff + (int16_t)(w & 0xffff)] + (int)a.costQ[a.qoff + (w >> 16)]; };
+        const int c0 = r0.x + a.dirCost[0], c1 = r1.x + a.dirCost[1];
+        const int cRef = sBi + mvc(r0.y) + mvc(r1.y) + a.dirCost[2];
+        int cbi = cRef, cz = -1, m0 = r0.y, m1 = r1.y;
+        if (m0 != 0 || m1 != 0)                                      // bTryZero
+        {
+            cz = sZ + 4 * (int)a.costQ[a.qoff] + a.dirCost[2];
+            if (cz < cbi) { cbi = cz; m0 = 0; m1 = 0; }
+        }
+        const int dir = (cbi < c0 && cbi < c1) ? 3 : (c0 <= c1 ? 1 : 2);
+        const size_t blk = (size_t)ctu * G::NPU + pu;
+        a.dir[blk] = (uint8_t)dir;
+        if (a.ref[0]) a.ref[0][blk] = (int8_t)((dir & 1) ? a.refId[0] : -1);
+        if (a.ref[1]) a.ref[1][blk] = (int8_t)((dir & 2) ? a.refId[1] : -1);
+        a.mvOut[0][rec] = dir == 3 ? make_int2(cbi, m0) : make_int2(c0, dir == 1 ? m0 : 0);
+        a.mvOut[1][rec] = dir == 3 ? make_int2(cbi, m1) : make_int2(c1, dir == 2 ? m1 : 0);
+        if (a.costOut) { int* co = a.costOut + blk * 4; co[0] = c0; co[1] = c1; co[2] = cRef; co[3] = cz; }
+    }
+}
+
+template <typename Px, bool PL>
+static void bidir_launch(int level, int nctu, hipStream_t s, const BidirArgs& a)
+{
+    switch (level)
+    {
+    case 0: hipLaunchKernelGGL((bidir_decide_kernel<Px, 0, PL>), dim3(nctu), dim3(256), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((bidir_decide_kernel<Px, 1, PL>), dim3(nctu), dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((bidir_decide_kernel<Px, 2, PL>), dim3(nctu), dim3(256), 0, s, a); break;
+    }
+}
+
+} // namespace x265hip
+
+using namespace x265hip;
+
+extern "C" int x265hip_bidir_decide(const x265hip_bidir_params* p, void* stream)
+{
+    // argument checks first: they need no device
+    if (!p || !p->fenc || !p->fref0 || !p->fref1 || !p->mv0 || !p->mv1 || !p->cost_q || !p->dir || !p->mv0_out || !p->mv1_out)
+    { set_error("bidir_decide: NULL operand"); return X265HIP_EINVAL; }
+    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("bidir_decide: depth %d", p->depth); return X265HIP_EINVAL; }
+    if (p->level < 0 || p->level > 2) { set_error("bidir_decide: level %d out of [0,2]", p->level); return X265HIP_EINVAL; }
+    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("bidir_decide: width/height must be multiples of 64"); return X265HIP_EINVAL; }
+    const int nctu = (p->width / 64) * (p->height / 64);
+    {
+        // the decision reads both lists' records of a block after other blocks' outputs may have been written: outputs must be buffers of their own
+        const uintptr_t len = (uintptr_t)nctu * 85 * 8;
+        const uintptr_t in[2] = { (uintptr_t)p->mv0, (uintptr_t)p->mv1 }, out[2] = { (uintptr_t)p->mv0_out, (uintptr_t)p->mv1_out };
+        bool alias = out[0] < out[1] + len && out[1] < out[0] + len;
+        for (int i = 0; i < 2; i++)
+            for (int j = 0; j < 2; j++) alias = alias || (out[i] < in[j] + len && in[j] < out[i] + len);
+        if (alias) { set_error("bidir_decide: mv0_out / mv1_out must not alias mv0 / mv1 or each other"); return X265HIP_EINVAL; }
+    }
+    const bool planes = p->phase_planes0 || p->phase_planes1;
+    if (planes && (!p->phase_planes0 || !p->phase_planes1 || p->phase_plane_samples <= 0))
+    { set_error("bidir_decide: phase planes of both lists and phase_plane_samples are needed together"); return X265HIP_EINVAL; }
+    int rc = ensure_device();
+    if (rc) return rc;
+
+    const int bpp = p->depth == 8 ? 1 : 2;
+    BidirArgs a;
+    a.fenc = (const uint8_t*)p->fenc; a.fencStrideB = (long)p->fenc_stride * bpp;
+    a.fref[0] = (const uint8_t*)p->fref0; a.fref[1] = (const uint8_t*)p->fref1; a.frefStrideB = (long)p->fref_stride * bpp;
+    a.ctusW = p->width / 64; a.depth = p->depth;
+    a.mv[0] = (const int2*)p->mv0; a.mv[1] = (const int2*)p->mv1;
+    a.costQ = p->cost_q; a.qoff = p->qoff;
+    for (int i = 0; i < 3; i++) a.dirCost[i] = p->dir_cost[i];
+    a.refId[0] = p->ref_id0; a.refId[1] = p->ref_id1;
+    a.planes[0] = (const uint8_t*)p->phase_planes0; a.planes[1] = (const uint8_t*)p->phase_planes1;
+    a.planeBytes = (long)p->phase_plane_samples * bpp;
+    a.dir = p->dir; a.ref[0] = p->ref0; a.ref[1] = p->ref1;
+    a.mvOut[0] = (int2*)p->mv0_out; a.mvOut[1] = (int2*)p->mv1_out;
+    a.costOut = p->cost_out;
+    hipStream_t s = (hipStream_t)stream;
+    if (planes) { if (bpp == 1) bidir_launch<uint8_t, true>(p->level, nctu, s, a); else bidir_launch<uint16_t, true>(p->level, nctu, s, a); }
+    else { if (bpp == 1) bidir_launch<uint8_t, false>(p->level, nctu, s, a); else bidir_launch<uint16_t, false>(p->level, nctu, s, a); }
+    X265HIP_TRY(hipGetLastError());
+    return 0;
+}

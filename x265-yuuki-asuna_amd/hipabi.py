@@ -51,6 +51,22 @@ class SubpelParams(ctypes.Structure):
     ]
 
 
+class BidirParams(ctypes.Structure):
+    """x265hip_bidir_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("fenc", ctypes.c_void_p), ("fenc_stride", ctypes.c_ssize_t),
+        ("fref0", ctypes.c_void_p), ("fref1", ctypes.c_void_p), ("fref_stride", ctypes.c_ssize_t),
+        ("mv0", ctypes.c_void_p), ("mv1", ctypes.c_void_p),
+        ("cost_q", ctypes.c_void_p), ("qoff", ctypes.c_int),
+        ("dir_cost", ctypes.c_int32 * 3),
+        ("ref_id0", ctypes.c_int), ("ref_id1", ctypes.c_int),
+        ("phase_planes0", ctypes.c_void_p), ("phase_planes1", ctypes.c_void_p), ("phase_plane_samples", ctypes.c_ssize_t),
+        ("dir", ctypes.c_void_p), ("ref0", ctypes.c_void_p), ("ref1", ctypes.c_void_p),
+        ("mv0_out", ctypes.c_void_p), ("mv1_out", ctypes.c_void_p), ("cost_out", ctypes.c_void_p),
+    ]
+
+
 class LowresInitParams(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_int), ("src", ctypes.c_void_p), ("src_stride", ctypes.c_ssize_t),
                 ("plane", ctypes.c_void_p * 4), ("stride", ctypes.c_ssize_t),
@@ -217,6 +233,29 @@ def subpel_refine(depth, width, height, rng, subme, fenc, fenc_stride, fref, fre
     f = lib().x265hip_subpel_refine
     f.argtypes = [ctypes.POINTER(SubpelParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_subpel_refine")
+
+
+def bidir_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, mv0, mv1, cost_q, qoff, dir_cost, dir_out, mv0_out, mv1_out,
+                 ref0=None, ref1=None, cost_out=None, ref_ids=(0, 1), fenc_off=0, fref_off=0, phase_planes=None, stream=None):
+    """x265hip_bidir_decide: list 0 / list 1 / both for every block of a B picture from the two refinements' records.  fref0 / fref1:
+    tensors of one geometry (sample (0,0) at element fref_off); phase_planes: (list 0, list 1) byte tensors of x265hip_phase_planes."""
+    es = 1 if depth == 8 else 2
+    p = BidirParams()
+    p.depth, p.width, p.height, p.level = depth, width, height, level
+    p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
+    p.fref0, p.fref1, p.fref_stride = fref0.data_ptr() + fref_off * es, fref1.data_ptr() + fref_off * es, fref_stride
+    p.mv0, p.mv1, p.cost_q, p.qoff = mv0.data_ptr(), mv1.data_ptr(), cost_q.data_ptr(), qoff
+    p.dir_cost[0], p.dir_cost[1], p.dir_cost[2] = (int(c) for c in dir_cost)
+    p.ref_id0, p.ref_id1 = ref_ids
+    if phase_planes is not None:
+        p.phase_planes0, p.phase_planes1 = (t.data_ptr() + fref_off * es for t in phase_planes)
+        p.phase_plane_samples = fref0.numel() * fref0.element_size() // es
+    p.dir, p.ref0, p.ref1 = dir_out.data_ptr(), _p(ref0), _p(ref1)
+    p.mv0_out, p.mv1_out, p.cost_out = mv0_out.data_ptr(), mv1_out.data_ptr(), _p(cost_out)
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_bidir_decide
+    f.argtypes = [ctypes.POINTER(BidirParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_bidir_decide")
 
 
 def lowres_init(depth, src, src_stride, src_off, planes, stride, org, width, lines, margin_x, margin_y, stream=None):

@@ -269,6 +269,12 @@ class Deblock:
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv, num_sig, self.bs_ver, self.bs_hor)
         hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp)
 
+    def run_b(self, plane, pic: DevicePicture, mv0, mv1, ref0, ref1, num_sig):
+        """A B picture: the boundary strengths compare (ref0, ref1) x (mv0, mv1) per block (deblock.cpp:217-247); ref0 / ref1 = int8 picture
+        ids per block, -1 = list unused (what BidirDecide leaves)."""
+        hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv0, num_sig, self.bs_ver, self.bs_hor, slice_b=True, mv1=mv1, ref0=ref0, ref1=ref1)
+        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp)
+
 
 class Sao:
     """Sample adaptive offset of the deblocked luma picture: the two pixel passes on device (x265hip_sao_stats /
@@ -1191,3 +1197,181 @@ class BandedFramePipeline:
 
     def final_planes(self):
         return list(self.planes)
+
+
+class BidirDecide:
+    """The bidirectional decision of a B picture (x265hip_bidir_decide; reference Search::predInterSearch, search.cpp:2473-2640): from the
+    two lists' refined records, per block of the TU stages' grid, list 0 / list 1 / both.  Owns dir uint8 [ctu][blocks] (what InterReconBi
+    takes), ref0 / ref1 int8 [ctu][blocks] (what Deblock.run_b takes), mv0_out / mv1_out int32 [ctu*85][2] (the level's entries) and,
+    with want_cost, cost_out int32 [ctu][blocks][4]."""
+
+    def __init__(self, nctu, w64, h64, depth, level, device, dir_cost=(12, 12, 20), ref_ids=(0, 1), want_cost=False):
+        """dir_cost: lambda x the list-selection bits of a B slice's 2Nx2N (3, 3, 5; search.cpp:2649-2656) - (12, 12, 20) at the pipeline's lambda 4."""
+        import torch
+        self.nctu, self.w64, self.h64, self.depth, self.level = nctu, w64, h64, depth, level
+        self.nblk = (64 // (8 << level)) ** 2
+        self.dir_cost, self.ref_ids = tuple(int(c) for c in dir_cost), tuple(ref_ids)
+        self.dir = torch.zeros(nctu * self.nblk, dtype=torch.uint8, device=device)
+        self.ref0 = torch.zeros(nctu * self.nblk, dtype=torch.int8, device=device)
+        self.ref1 = torch.zeros(nctu * self.nblk, dtype=torch.int8, device=device)
+        self.mv0_out = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device)
+        self.mv1_out = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device)
+        self.cost_out = torch.zeros(nctu * self.nblk * 4, dtype=torch.int32, device=device) if want_cost else None
+
+    def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mv0, mv1, cost_q, qoff, phase_planes=None, stream=None):
+        """mv0 / mv1: the two SubpelRefine outputs; phase_planes: (list 0, list 1) planes of x265hip_phase_planes or None (interpolate)."""
+        assert ref0.stride == ref1.stride and ref0.org == ref1.org
+        hipabi.bidir_decide(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, ref0.t, ref1.t, ref0.stride, mv0, mv1, cost_q, qoff,
+                            self.dir_cost, self.dir, self.mv0_out, self.mv1_out, ref0=self.ref0, ref1=self.ref1, cost_out=self.cost_out,
+                            ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org, phase_planes=phase_planes, stream=stream)
+
+    def checksum(self):
+        import torch
+        return {"dir": int(self.dir.to(torch.int64).sum().item()), "mv0_out": int(self.mv0_out.to(torch.int64).sum().item()),
+                "mv1_out": int(self.mv1_out.to(torch.int64).sum().item())}
+
+
+class BFramePipeline:
+    """One B picture on the device, the stages of FramePipeline.run with two reference lists:
+        per list: exhaustive search (best mv) -> sub-pel refinement;  bidirectional decision (BidirDecide);  bi-predictive luma + 4:2:0
+        chroma reconstruction with the decided dir / vectors;  B-picture boundary strengths + luma / chroma deblocking;  SAO (statistics,
+        x265hip_sao_rdo or the distortion-only stand-in, application);  border extension.
+    The constructor switches mean what they mean in FramePipeline.  A B picture is not referenced here; final_planes() are its output."""
+
+    def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
+                 sign_hide=False, subpel_planes=False, sao_rdo=None, dir_cost=(12, 12, 20), want_cost=False):
+        import torch
+        from .pipeline import MotionSearch, SubpelRefine
+        self.depth, self.qp, self.chroma = depth, qp, chroma
+        self.msl = [MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True) for _ in range(2)]
+        self.spl = [SubpelRefine(m, subme, device, phase_planes=subpel_planes) for m in self.msl]
+        self.ms = self.msl[0]                # geometry (nctu, w64, h64) for the helpers shared with FramePipeline
+        self.bd = BidirDecide(self.ms.nctu, w64, h64, depth, level, device, dir_cost=dir_cost, want_cost=want_cost)
+        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
+        self.rc = InterReconBi(self.ms.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        self.db = Deblock(w64, h64, depth, level, max(qp - 6 * (depth - 8), 0), device) if deblock else None
+        self.sao = Sao(w64, h64, depth, device) if sao else None
+        self.recon, self.recon_c, self.out, self.out_c = None, None, None, None
+        if chroma:
+            qpc = chroma_quant_qp(qp, depth)
+            self.rc_c = [InterReconChromaBi(self.ms.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
+            self.sao_c = [Sao(w64 // 2, h64 // 2, depth, device, ctu=(32, 32), plane_offset=2) for _ in range(2)] if sao else None
+        self.sao_apply = bool(sao and sao_apply)
+        self.sao_rdo = sao_rdo if (sao and sao_apply) else None
+        if self.sao_rdo is not None:
+            self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
+            self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
+
+    def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mark=None):
+        """ref0 / ref1: the list-0 / list-1 reference pictures (extended borders; with chroma=True also their Cb / Cr planes).  Returns the
+        luma plane of the coded picture; mark(name), if given, is called after every stage."""
+        import torch
+        mark = mark or (lambda name: None)
+        if self.recon is None:
+            self.recon = torch.zeros_like(cur.t)
+        for l, ref in enumerate((ref0, ref1)):
+            self.msl[l].reset()
+            self.msl[l].search(cur, ref)
+            mark("me%d" % l)
+            self.spl[l].run(cur, ref)
+            mark("subpel%d" % l)
+        phases = (self.spl[0].planes, self.spl[1].planes) if self.spl[0].use_planes else None      # what the two refinements just prepared
+        self.bd.run(cur, ref0, ref1, self.spl[0].out, self.spl[1].out, self.spl[0].cost_q, self.spl[0].qoff, phase_planes=phases)
+        mark("bidir")
+        mv0, mv1, dirs = self.bd.mv0_out, self.bd.mv1_out, self.bd.dir
+        self.rc.run(cur, ref0, ref1, self.recon, mv0, mv1, dir_flags=dirs)
+        mark("recon")
+        if self.chroma:
+            if self.recon_c is None:
+                self.recon_c = [torch.zeros_like(p) for p in cur.c]
+            for i in range(2):
+                self.rc_c[i].run(cur.c[i], ref0.c[i], ref1.c[i], self.recon_c[i], cur.stride_c, cur.org_c, mv0, mv1, dir_flags=dirs)
+            mark("recon_chroma")
+        if self.db is not None:
+            self.db.run_b(self.recon, cur, mv0, mv1, self.bd.ref0, self.bd.ref1, self.rc.num_sig)
+            if self.chroma:
+                hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
+                                      self.db.bs_ver, self.db.bs_hor, self.db.qp)
+            mark("deblock")
+        final, final_c = self.recon, self.recon_c
+        if self.sao is not None and self.sao_apply and self.out is None:
+            self.out = torch.zeros_like(cur.t)
+            self.out_c = [torch.zeros_like(p) for p in cur.c] if self.chroma else None
+        if self.sao_rdo is not None:
+            planes = FramePipeline._sao_planes(self, cur)
+            hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes])
+            mark("sao_stats")
+            FramePipeline._sao_rdo(self)
+            mark("sao_rdo")
+            hipabi.sao_apply_planes(self.depth, planes)
+            final, final_c = self.out, self.out_c
+            mark("sao_apply")
+        elif self.sao is not None:
+            self.sao.stats(cur, self.recon, cur.stride, cur.org)
+            if self.chroma:
+                for i in range(2):
+                    self.sao_c[i].stats(None, self.recon_c[i], cur.stride_c, cur.org_c, src_plane=cur.c[i])
+            mark("sao_stats")
+            if self.sao_apply:
+                self.sao.decide()
+                self.sao.apply(self.recon, cur.stride, cur.org, self.out)
+                final = self.out
+                if self.chroma:
+                    for i in range(2):
+                        self.sao_c[i].decide()
+                        self.sao_c[i].apply(self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i])
+                    final_c = self.out_c
+                mark("sao_apply")
+        extend_border_picture([final] + (list(final_c) if self.chroma else []), cur)
+        mark("border")
+        self.final, self.final_c = final, final_c
+        return final
+
+    def final_planes(self):
+        """[Y, Cb, Cr] (or [Y]) of the picture run() coded last."""
+        return [self.final] + (list(self.final_c) if self.chroma else [])
+
+    def checksum(self):
+        import torch
+        out = {}
+        for l in range(2):
+            out.update({"%s%d" % (k, l): v for k, v in self.msl[l].checksum().items()})
+            out.update({"%s%d" % (k, l): v for k, v in self.spl[l].checksum().items()})
+        out.update(self.bd.checksum())
+        out.update(self.rc.checksum())
+        if self.chroma:
+            for i in range(2):
+                out.update({"%s_c%d" % (k, i): v for k, v in InterRecon.checksum(self.rc_c[i]).items()})
+        out["recon"] = int(self.final.to(torch.int64).sum().item())
+        return out
+
+
+class MiniGop:
+    """Display order in, coding order inside: anchor pictures 0, gop, 2 gop, ... form the P chain (each coded by p_step.run from the
+    previous anchor's OUTPUT), and the pictures between two anchors are B pictures coded by b_step.run(cur, previous anchor, this
+    anchor) once the later anchor is done.  B pictures are not referenced.  p_step: a FramePipeline, b_step: a BFramePipeline of the same
+    geometry and chroma setting."""
+
+    def __init__(self, p_step, b_step, gop):
+        assert gop >= 1
+        self.p, self.b, self.gop = p_step, b_step, int(gop)
+
+    def run(self, pictures):
+        """pictures: DevicePictures in display order; picture 0 is the first anchor and is taken as it is (an intra picture is not this
+        pipeline's business).  Pictures behind the last anchor are left out.  Returns (coding order as display indices, {display index:
+        [Y, Cb, Cr] planes of the coded picture (clones)})."""
+        def keep(planes):
+            return [p.clone() for p in planes]
+        prev = pictures[0]
+        out, order = {0: keep(prev.planes())}, [0]
+        for a in range(self.gop, len(pictures), self.gop):
+            self.p.run(pictures[a], prev)
+            out[a] = keep(self.p.final_planes())
+            order.append(a)
+            anchor = pictures[a].like(out[a])
+            for k in range(a - self.gop + 1, a):
+                self.b.run(pictures[k], prev, anchor)
+                out[k] = keep(self.b.final_planes())
+                order.append(k)
+            prev = anchor
+        return order, out

@@ -7,6 +7,8 @@ import sys
 import numpy as np
 import pytest
 
+import subpel_cases as SC
+
 pytestmark = pytest.mark.gpu
 
 F = importlib.import_module("x265-yuuki-asuna_amd.frames")
@@ -57,6 +59,28 @@ def test_inter_recon_matches_oracle(depth, level, qp, flags):
         assert (ens > 1).any()
     if qp == 45:
         assert (ens == 0).any()
+
+
+@pytest.mark.parametrize("case,level,qp", SC.RECON_CASES, ids=lambda v: v.id if isinstance(v, SC.Case) else str(v))
+def test_inter_recon_clipping_content_matches_oracle(case, level, qp):
+    """The prediction and reconstruction clips: `edges` / `inverse` pictures (tests/subpel_cases.py) predicted with the oracle's refined vectors,
+    anywhere in a +-57 window.  tests/test_subpel_cases_cpu.py asserts that the oracle codes at least 30 % of these blocks and that its
+    reconstruction sits at 0 and at max, each for at least 1 % of the samples, where the source does not."""
+    import torch
+    dev = torch.device("cuda:0")
+    c = SC.build(*case.build)
+    mv = SC.refined(case)
+    cur, ref = P.DevicePicture(c.cur_img, dev), P.DevicePicture(c.ref_img, dev)
+    st = S.InterRecon(c.nctu, c.w64, c.h64, c.depth, level, qp, dev)
+    recon = torch.zeros_like(cur.t)
+    st.run(cur, ref, recon, torch.from_numpy(mv.reshape(-1).copy()).to(dev))
+    torch.cuda.synchronize()
+    erec, elev, ens, edist = _oracle().inter_recon(c.depth, c.cur, c.stride, c.org, c.ref, c.stride, c.org, c.w64, c.h64, level, mv, qp)
+    assert np.array_equal(st.num_sig.cpu().numpy().view(np.uint32), ens), "numSig differs"
+    assert np.array_equal(st.levels.cpu().numpy(), elev), "quantised levels differ"
+    grec = recon.cpu().numpy().view(c.cur.dtype).reshape(c.cur.shape)
+    assert np.array_equal(grec, erec), f"recon differs at {np.count_nonzero(grec != erec)} samples"
+    assert np.array_equal(st.dist.cpu().numpy().view(np.uint64), edist), "SSE differs"
 
 
 @pytest.mark.parametrize("depth,level,qp", [(8, 2, 24), (8, 1, 30), (8, 0, 20), (10, 2, 36), (10, 0, 30), (12, 1, 44)])

@@ -8,6 +8,8 @@ import sys
 import numpy as np
 import pytest
 
+import subpel_cases as SC
+
 pytestmark = pytest.mark.gpu
 
 F = importlib.import_module("x265-yuuki-asuna_amd.frames")
@@ -44,6 +46,9 @@ def _check(depth, method, width, height, seed, njobs, submes, meranges, extreme=
     y0, y1 = clip[0][0], clip[1][0]
     if extreme == "flat":
         y0 = np.zeros_like(y0); y1 = np.full_like(y1, (1 << depth) - 1)
+    if extreme == "edges":                                    # tests/subpel_cases.py: 0 / max cells and planted sub-pel motion - tile_clip16 at both ends
+        c = SC.build(depth, width, height, 57, "edges", seed)
+        y0, y1 = c.ref_img, c.cur_img
     cur, ref = P.DevicePicture(y1, dev), P.DevicePicture(y0, dev)
     rng = np.random.default_rng([seed, depth, METHODS[method]])
     for subme in submes:
@@ -81,6 +86,14 @@ def test_full_search_driver(depth):
 def test_search_extremes():
     _check(8, "hex", 128, 128, seed=43, njobs=32, submes=(2,), meranges=(16,), extreme="flat")
     _check(8, "star", 128, 128, seed=43, njobs=32, submes=(3,), meranges=(57,), extreme="flat")
+
+
+@pytest.mark.parametrize("depth", [8, 10])
+def test_search_on_clipping_content(depth):
+    """`edges` pictures: the interpolation of the search drivers' sub-pel part (tile_interp.h) overshoots 0 and max in the h, v and hv paths."""
+    seed = {8: 1, 10: 2}[depth]                              # the pictures of SC.PLANTED_CASES: their phase planes sit at 0 and at max for 15 - 25 % of the samples each
+    _check(depth, "hex", 256, 128, seed=seed, njobs=64, submes=(3, 7), meranges=(16,), extreme="edges")
+    _check(depth, "star", 256, 128, seed=seed, njobs=64, submes=(3, 7), meranges=(57,), extreme="edges")
 
 
 SEA_UNSUPPORTED = {(8, 4), (4, 8), (32, 8), (8, 32)}

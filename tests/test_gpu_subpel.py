@@ -7,6 +7,8 @@ import sys
 import numpy as np
 import pytest
 
+import subpel_cases as SC
+
 pytestmark = pytest.mark.gpu
 
 F = importlib.import_module("x265-yuuki-asuna_amd.frames")
@@ -62,3 +64,59 @@ def _check_subpel(width, height, depth, subme, planes, seed):
     # the refinement must actually move some vectors off the integer grid
     frac = (exp[:, 1] & 3) | ((exp[:, 1] >> 16) & 3)
     assert np.count_nonzero(frac) > exp.shape[0] // 10
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Hostile content with records written by the test (tests/subpel_cases.py; what every case reaches is asserted, with the oracle alone,
+# in tests/test_subpel_cases_cpu.py): clipped samples, zero-cost keys, vectors anywhere in a +-57 window.
+SENTINEL = -0x5a5a5a5b
+
+
+def _refine_on_device(case, planes, wide_fenc=False):
+    """x265hip_subpel_refine on a builder case, the records uploaded into a MotionSearch's `best` (no search runs).  wide_fenc: the current
+    picture sits in a buffer 64 samples wider than the reference's, at another origin - hipabi.subpel_refine with its own fenc_stride / fenc_off."""
+    import torch
+    A = importlib.import_module("x265-yuuki-asuna_amd.hipabi")
+    dev = torch.device("cuda:0")
+    c = SC.build(*case.build)
+    cur, ref = P.DevicePicture(c.cur_img, dev), P.DevicePicture(c.ref_img, dev)
+    assert (cur.stride, cur.org) == (c.stride, c.org) and np.array_equal(cur.host, c.cur) and np.array_equal(ref.host, c.ref)
+    ms = P.MotionSearch(c.w64, c.h64, c.R, c.depth, dev, want_surf=False)
+    ms.best.copy_(torch.from_numpy(c.best.view(np.int64).copy()))
+    sp = P.SubpelRefine(ms, case.subme, dev, phase_planes=planes)
+    sp.out.fill_(SENTINEL)
+    if not wide_fenc:
+        sp.run(cur, ref)
+    else:
+        rows, stride = c.cur.shape[0] + 5, c.stride + 64
+        org = 3 * stride + 40 + c.org // c.stride * stride + c.org % c.stride          # the padded plane's corner at row 3, column 40
+        wide = np.full((rows, stride), (1 << c.depth) - 1 if c.depth > 8 else 0x5a, c.cur.dtype)
+        wide[3:3 + c.cur.shape[0], 40:40 + c.stride] = c.cur
+        wide_t = torch.from_numpy(wide if c.depth == 8 else wide.view(np.int16)).to(dev)
+        sp.prepare(ref)
+        A.subpel_refine(c.depth, c.w64, c.h64, c.R, case.subme, wide_t, stride, ref.t, ref.stride, ms.best, sp.cost_q, sp.qoff, sp.out,
+                        fenc_off=org, fref_off=ref.org, phase_planes=sp.planes)
+    torch.cuda.synchronize()
+    return sp.out.cpu().numpy().reshape(-1, 2)
+
+
+def _assert_records(got, exp, what):
+    bad = np.nonzero((got != exp).any(axis=1))[0]
+    assert bad.size == 0, (f"{what}: {bad.size} of {got.shape[0]} PUs differ, first {bad[:5]} (ctu {bad[:5] // 85}, record {bad[:5] % 85}): "
+                           f"{got[bad[:3]].tolist()} vs {exp[bad[:3]].tolist()}")
+
+
+@pytest.mark.parametrize("planes", [False, True])
+@pytest.mark.parametrize("case", SC.SUBPEL_CASES, ids=lambda c: c.id)
+def test_subpel_refine_hostile_content_matches_oracle(case, planes):
+    """Every one of the nctu * 85 records, bit for bit, over a sentinel-filled output: `edges` / `noise` / `inverse` pictures clip the h, v and
+    hv filters at both ends, three keys in ten cost zero (the shortcut, at every level), the vectors fill a +-57 (13, 8) window up to its
+    edge, `inverse` at 12 bits feeds the packed Hadamard differences of full amplitude, the flat pairs leave the decision to the mv cost."""
+    _assert_records(_refine_on_device(case, planes), SC.refined(case), case.id)
+
+
+@pytest.mark.parametrize("planes", [False, True])
+@pytest.mark.parametrize("case", SC.STRIDE_CASES, ids=lambda c: c.id)
+def test_subpel_refine_with_a_source_stride_of_its_own(case, planes):
+    """fenc_stride != fref_stride: DevicePicture gives both planes one stride, so a mix-up of the two would otherwise go unseen."""
+    _assert_records(_refine_on_device(case, planes, wide_fenc=True), SC.refined(case), case.id)

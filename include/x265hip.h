@@ -1483,6 +1483,60 @@ int x265hip_comm_unique_id(void* id128);
 int x265hip_comm_init(void** comm, int nranks, const void* id128, int rank);
 int x265hip_comm_destroy(void* comm);
 
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * One I picture on the block grid of the TU stages (csrc/intra_picture.h): every NxN block (N = 8 << level) is a 2Nx2N intra CU with one
+ * TU; CTUs are coded in raster order, blocks in z-order inside a CTU; one slice, no constrained intra prediction.  Per block:
+ *   neighbours : Predict::initIntraNeighbors / fillReferenceSamples (predict.cpp:664-876, I-slice arm) from the RECON plane - a 4-sample
+ *                unit of above-left, above, above-right, left or below-left is available iff it lies inside the picture and its block
+ *                precedes the current one in coding order; nothing available = 1 << (depth - 1), partly available = the substitution
+ *                walk (bottom of below-left up the left column, then along the top row).  Unavailable samples are never read.
+ *   filtering  : Predict::initAdiPattern, ALL_IDX arm (:600-650): for 32x32 with strong_intra_smoothing the bilinear form when both
+ *                threshold tests at 1 << (depth - 5) pass, else cu[].intra_filter's [1 2 1]
+ *   decision   : Search::checkIntraInInter without bEnableFastIntra (search.cpp:1344-1446): DC (unfiltered, edge smoothing for N <= 16),
+ *                planar (filtered), angular 2..34 (the array g_intraFilterFlags[mode] & N selects); sad = cu[].sa8d(fenc, pred),
+ *                cost = sad + ((bits * lambda8 + 128) >> 8) (rdcost.h:148-153), strict '<' in the order DC, planar, 2, 3, ..., 34
+ *   mode bits  : the three most probable modes of CUData::getIntraDirLumaPredictor (cudata.cpp:910-953: the left block's mode if that
+ *                block is inside the picture, the above block's only inside the same CTU, else DC); bits = mode_bits[0] for preds[0],
+ *                mode_bits[1] for preds[1] / preds[2], mode_bits[2] otherwise - bitsIntraModeMPM / bitsIntraModeNonMPM at the host's
+ *                context state (entropy.h:196-197); (2, 3, 6) prices both bin values at one bit
+ *   coding     : the winner through the contract of x265hip_intra_recon_batch (predIntraLumaAng, residual, transformNxN with the
+ *                X265HIP_TU_* bits of `flags` - the mode-dependent scan for luma 8x8 under sign hiding -, inverse, reconstruction,
+ *                SSE); the reconstruction goes into `recon`, where later blocks read it
+ *   chroma     : optional (fenc_cb / fenc_cr / recon_cb / recon_cr and the Cb / Cr outputs all given, or none): 4:2:0, per block Cb and
+ *                Cr blocks of N/2 with the luma mode (DM_CHROMA), unfiltered neighbours of the plane's own reconstruction
+ *                (initAdiPatternChroma, predict.cpp:652-662), predIntraChromaAng, DCT for 4x4; qp_cb / qp_cr = the planes' quantiser QPs
+ *                as x265hip_inter_recon_chroma takes them
+ * Outputs: mode uint8 [ctu][blocks]; levels / num_sig / dist laid out as x265hip_inter_recon lays them out (chroma: (N/2)^2 levels per
+ * block); cost (optional) int32 [ctu][blocks][2] = { winning sad, winning cost }.
+ * Schedule: CTU (cx, cy) runs in wave cx + 2 cy; the entry issues one launch per wave (x265hip_intra_picture_waves of them) on `stream`,
+ * nothing else - no host synchronisation, capturable into a graph.  recon must not alias fenc; the margins of recon are not written.
+ * tables: scaling lists / the denoiser are NOT supported by this stage - a non-NULL pointer is refused with X265HIP_EINVAL.
+ * Also refused: flag bits other than the two X265HIP_TU_* ones, strides below the plane's width, recon_cb == recon_cr, mode_bits outside
+ * [0, 4096] and lambda8 outside [0, 2^24] (the bounds that keep the winning cost inside the int32 of `cost`). */
+typedef struct x265hip_intra_picture_params
+{
+    int depth, width, height, level;                 /* width / height multiples of 64, level 0..2 */
+    int qp, qp_cb, qp_cr;                            /* quantiser QPs (+ QP_BD_OFFSET) of the three planes */
+    int flags;                                       /* X265HIP_TU_INTRA_SLICE | X265HIP_TU_SIGN_HIDE */
+    int strong_intra_smoothing;                      /* sps.bUseStrongIntraSmoothing (x265 default: 1) */
+    int lambda8;                                     /* 256 x lambda: RDCost::m_lambda */
+    int32_t mode_bits[3];
+    const void* fenc;  intptr_t fenc_stride;         /* sample (0,0) of the source luma plane */
+    const void* fenc_cb; const void* fenc_cr; intptr_t fenc_stride_c;
+    void* recon;       intptr_t recon_stride;
+    void* recon_cb; void* recon_cr; intptr_t recon_stride_c;
+    uint8_t* mode;
+    int16_t* levels; uint32_t* num_sig; uint64_t* dist;
+    int16_t* levels_cb; uint32_t* num_sig_cb; uint64_t* dist_cb;
+    int16_t* levels_cr; uint32_t* num_sig_cr; uint64_t* dist_cr;
+    int32_t* cost;
+    const x265hip_tu_tables* tables;                 /* must be NULL */
+} x265hip_intra_picture_params;
+int x265hip_intra_picture(const x265hip_intra_picture_params* p, void* stream);
+/* launches x265hip_intra_picture issues for a picture of this size: width / 64 + 2 * (height / 64 - 1).  Host arithmetic, needs no device. */
+int x265hip_intra_picture_waves(int width, int height);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1256,3 +1256,6 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
     X265HIP_TRY(hipGetLastError());
     return 0;
 }
+
+// the I-picture stage (x265hip_intra_picture): its kernel codes blocks with tu_chain / TuOpsFor above
+#include "intra_picture.h"

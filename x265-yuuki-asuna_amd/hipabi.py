@@ -67,6 +67,25 @@ class BidirParams(ctypes.Structure):
     ]
 
 
+class IntraPictureParams(ctypes.Structure):
+    """x265hip_intra_picture_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("qp", ctypes.c_int), ("qp_cb", ctypes.c_int), ("qp_cr", ctypes.c_int),
+        ("flags", ctypes.c_int), ("strong_intra_smoothing", ctypes.c_int), ("lambda8", ctypes.c_int),
+        ("mode_bits", ctypes.c_int32 * 3),
+        ("fenc", ctypes.c_void_p), ("fenc_stride", ctypes.c_ssize_t),
+        ("fenc_cb", ctypes.c_void_p), ("fenc_cr", ctypes.c_void_p), ("fenc_stride_c", ctypes.c_ssize_t),
+        ("recon", ctypes.c_void_p), ("recon_stride", ctypes.c_ssize_t),
+        ("recon_cb", ctypes.c_void_p), ("recon_cr", ctypes.c_void_p), ("recon_stride_c", ctypes.c_ssize_t),
+        ("mode", ctypes.c_void_p),
+        ("levels", ctypes.c_void_p), ("num_sig", ctypes.c_void_p), ("dist", ctypes.c_void_p),
+        ("levels_cb", ctypes.c_void_p), ("num_sig_cb", ctypes.c_void_p), ("dist_cb", ctypes.c_void_p),
+        ("levels_cr", ctypes.c_void_p), ("num_sig_cr", ctypes.c_void_p), ("dist_cr", ctypes.c_void_p),
+        ("cost", ctypes.c_void_p), ("tables", ctypes.c_void_p),
+    ]
+
+
 class LowresInitParams(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_int), ("src", ctypes.c_void_p), ("src_stride", ctypes.c_ssize_t),
                 ("plane", ctypes.c_void_p * 4), ("stride", ctypes.c_ssize_t),
@@ -256,6 +275,40 @@ def bidir_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, f
     f = lib().x265hip_bidir_decide
     f.argtypes = [ctypes.POINTER(BidirParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_bidir_decide")
+
+
+def intra_picture_waves(width, height):
+    """x265hip_intra_picture_waves: launches of the I-picture schedule (CTU (cx, cy) runs in wave cx + 2 cy).  Needs no device."""
+    f = lib().x265hip_intra_picture_waves
+    f.argtypes = [ctypes.c_int, ctypes.c_int]
+    return check(f(width, height), "x265hip_intra_picture_waves")
+
+
+def intra_picture(depth, width, height, level, qp, flags, lambda8, mode_bits, fenc, fenc_stride, fenc_off, recon, mode, levels, num_sig, dist,
+                  chroma=None, cost=None, strong_intra_smoothing=True, stream=None):
+    """x265hip_intra_picture: one I picture (mode decision + coding of every block, wave by wave).  fenc / recon: luma tensors of one
+    geometry (sample (0,0) at element fenc_off).  chroma: None or a dict - fenc (Cb, Cr), recon (Cb, Cr) tensors with `stride` samples per
+    row and sample (0,0) at element `org`, qp (Cb, Cr) and per plane levels / num_sig / dist tensors."""
+    es = 1 if depth == 8 else 2
+    p = IntraPictureParams()
+    p.depth, p.width, p.height, p.level, p.qp, p.flags = depth, width, height, level, qp, flags
+    p.strong_intra_smoothing, p.lambda8 = int(bool(strong_intra_smoothing)), int(lambda8)
+    p.mode_bits[0], p.mode_bits[1], p.mode_bits[2] = (int(b) for b in mode_bits)
+    p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
+    p.recon, p.recon_stride = recon.data_ptr() + fenc_off * es, fenc_stride
+    p.mode, p.levels, p.num_sig, p.dist, p.cost = mode.data_ptr(), levels.data_ptr(), num_sig.data_ptr(), dist.data_ptr(), _p(cost)
+    if chroma is not None:
+        o = chroma["org"] * es
+        p.qp_cb, p.qp_cr = chroma["qp"]
+        p.fenc_cb, p.fenc_cr, p.fenc_stride_c = chroma["fenc"][0].data_ptr() + o, chroma["fenc"][1].data_ptr() + o, chroma["stride"]
+        p.recon_cb, p.recon_cr, p.recon_stride_c = chroma["recon"][0].data_ptr() + o, chroma["recon"][1].data_ptr() + o, chroma["stride"]
+        p.levels_cb, p.levels_cr = (t.data_ptr() for t in chroma["levels"])
+        p.num_sig_cb, p.num_sig_cr = (t.data_ptr() for t in chroma["num_sig"])
+        p.dist_cb, p.dist_cr = (t.data_ptr() for t in chroma["dist"])
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_intra_picture
+    f.argtypes = [ctypes.POINTER(IntraPictureParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_intra_picture")
 
 
 def lowres_init(depth, src, src_stride, src_off, planes, stride, org, width, lines, margin_x, margin_y, stream=None):

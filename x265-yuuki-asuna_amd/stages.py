@@ -275,6 +275,21 @@ class Deblock:
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv0, num_sig, self.bs_ver, self.bs_hor, slice_b=True, mv1=mv1, ref0=ref0, ref1=ref1)
         hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp)
 
+    def prepare_intra(self):
+        """Allocates what run_intra passes beside num_sig (IFramePipeline calls it in its constructor, so that run() allocates nothing)."""
+        import torch
+        if getattr(self, "_intra_flags", None) is None:
+            nctu = (self.w64 // 64) * (self.h64 // 64)
+            self._intra_flags = torch.ones(nctu * (64 >> (2 * self.level)), dtype=torch.uint8, device=self.bs_ver.device)
+            self._intra_mv = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=self.bs_ver.device)
+
+    def run_intra(self, plane, pic: DevicePicture, num_sig):
+        """An I picture: every block is an intra CU, so every block edge gets Bs 2 (deblock.cpp:198-199) - all-ones intra flags; the
+        vector records are not looked at on such edges (zeros are passed)."""
+        self.prepare_intra()
+        hipabi.deblock_bs_inter(self.w64, self.h64, self.level, self._intra_mv, num_sig, self.bs_ver, self.bs_hor, intra=self._intra_flags)
+        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp)
+
 
 class Sao:
     """Sample adaptive offset of the deblocked luma picture: the two pixel passes on device (x265hip_sao_stats /
@@ -1346,24 +1361,174 @@ class BFramePipeline:
         return out
 
 
+class IntraPicture:
+    """One I picture on the TU stages' block grid (x265hip_intra_picture; reference Predict::initIntraNeighbors / fillReferenceSamples /
+    initAdiPattern, predict.cpp:600-876, Search::checkIntraInInter, search.cpp:1344-1446, and the coding contract of
+    x265hip_intra_recon_batch): per block the neighbours from the reconstruction, the 35-mode sa8d decision and the winner's transform
+    round trip, CTUs wave by wave (wave = cx + 2 cy, one launch each).  Owns mode uint8 [ctu][blocks], levels / num_sig / dist as
+    InterRecon lays them out, with chroma the Cb / Cr twins (levels_c / num_sig_c / dist_c, (N/2)^2 levels per block) and, with
+    want_cost, cost int32 [ctu][blocks][2] = {winning sad, winning cost}."""
+
+    def __init__(self, nctu, w64, h64, depth, level, qp, device, flags=hipabi.TU_INTRA_SLICE, chroma=False, qp_c=None, lambda8=1024,
+                 mode_bits=(2, 3, 6), strong_intra_smoothing=True, want_cost=False):
+        """lambda8: 256 x lambda (RDCost::m_lambda; 1024 at the pipeline's lambda 4).  mode_bits: bitsIntraModeMPM of preds[0], of
+        preds[1] / preds[2] and bitsIntraModeNonMPM at the host's context state - (2, 3, 6) prices both bin values at one bit."""
+        import torch
+        self.nctu, self.w64, self.h64, self.depth, self.level, self.qp, self.flags = nctu, w64, h64, depth, level, qp, flags
+        self.chroma, self.qp_c = chroma, (qp_c if qp_c is not None else (qp, qp))
+        self.lambda8, self.mode_bits, self.strong = int(lambda8), tuple(int(b) for b in mode_bits), bool(strong_intra_smoothing)
+        self.n = 8 << level
+        self.nblk = (64 // self.n) ** 2
+        self.waves = hipabi.intra_picture_waves(w64, h64)
+        nb = nctu * self.nblk
+
+        def outs(nn):
+            return (torch.zeros(nb * nn, dtype=torch.int16, device=device), torch.zeros(nb, dtype=torch.int32, device=device),
+                    torch.zeros(nb, dtype=torch.int64, device=device))
+        self.mode = torch.zeros(nb, dtype=torch.uint8, device=device)
+        self.levels, self.num_sig, self.dist = outs(self.n * self.n)
+        self.cost = torch.zeros(nb * 2, dtype=torch.int32, device=device) if want_cost else None
+        if chroma:
+            c = [outs(self.n * self.n // 4) for _ in range(2)]
+            self.levels_c, self.num_sig_c, self.dist_c = ([c[i][k] for i in range(2)] for k in range(3))
+
+    def run(self, cur: DevicePicture, recon_plane, recon_c=None, stream=None):
+        """recon_plane (and recon_c = [Cb, Cr] with chroma): planes of cur's geometry the reconstruction is written into - and read from,
+        block after block; their contents before the call do not matter."""
+        ch = None
+        if self.chroma:
+            ch = dict(fenc=cur.c, recon=recon_c, stride=cur.stride_c, org=cur.org_c, qp=self.qp_c, levels=self.levels_c, num_sig=self.num_sig_c,
+                      dist=self.dist_c)
+        hipabi.intra_picture(self.depth, self.w64, self.h64, self.level, self.qp, self.flags, self.lambda8, self.mode_bits, cur.t, cur.stride, cur.org,
+                             recon_plane, self.mode, self.levels, self.num_sig, self.dist, chroma=ch, cost=self.cost,
+                             strong_intra_smoothing=self.strong, stream=stream)
+
+    def checksum(self):
+        import torch
+        out = {"mode": int(self.mode.to(torch.int64).sum().item()), "levels": int(self.levels.to(torch.int64).sum().item()),
+               "num_sig": int(self.num_sig.sum().item()), "dist": int(self.dist.sum().item())}
+        if self.chroma:
+            for i in range(2):
+                out["levels_c%d" % i] = int(self.levels_c[i].to(torch.int64).sum().item())
+                out["num_sig_c%d" % i] = int(self.num_sig_c[i].sum().item())
+        return out
+
+
+class IFramePipeline:
+    """One I picture on the device: intra picture (IntraPicture: mode decision + coding, luma and 4:2:0 chroma) -> boundary strengths of
+    an all-intra picture + luma / chroma deblocking -> SAO (statistics, x265hip_sao_rdo or the distortion-only stand-in, application)
+    -> border extension.  The constructor switches mean what they mean in BFramePipeline; X265HIP_TU_INTRA_SLICE is always set.
+    final_planes() are the coded picture - the first reference of a GOP (MiniGop's i_step).  Every buffer is allocated in the constructor: run()
+    only launches, so it can be captured into a graph without a warm-up."""
+
+    def __init__(self, w64, h64, depth, device, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False, sign_hide=False,
+                 sao_rdo=None, lambda8=1024, mode_bits=(2, 3, 6), strong_intra_smoothing=True, want_cost=False):
+        import types
+        import torch
+        self.depth, self.qp, self.chroma = depth, qp, chroma
+        self.ms = types.SimpleNamespace(w64=w64, h64=h64, nctu=(w64 // 64) * (h64 // 64))     # geometry for the helpers shared with FramePipeline
+        self.tu_flags = hipabi.TU_INTRA_SLICE | (hipabi.TU_SIGN_HIDE if sign_hide else 0)
+        qpc = chroma_quant_qp(qp, depth)
+        self.ip = IntraPicture(self.ms.nctu, w64, h64, depth, level, qp, device, flags=self.tu_flags, chroma=chroma, qp_c=(qpc, qpc), lambda8=lambda8,
+                               mode_bits=mode_bits, strong_intra_smoothing=strong_intra_smoothing, want_cost=want_cost)
+        self.db = Deblock(w64, h64, depth, level, max(qp - 6 * (depth - 8), 0), device) if deblock else None
+        self.sao = Sao(w64, h64, depth, device) if sao else None
+        if self.db is not None:
+            self.db.prepare_intra()
+        if chroma:
+            self.sao_c = [Sao(w64 // 2, h64 // 2, depth, device, ctu=(32, 32), plane_offset=2) for _ in range(2)] if sao else None
+        self.sao_apply = bool(sao and sao_apply)
+        # the planes of the picture (PicYuv geometry of a DevicePicture), allocated here: run() allocates nothing and can be captured without a warm-up
+        from . import frames as F
+        _, _, stride, rows, _ = F.padded_dims(w64, h64)
+        dt = torch.uint8 if depth == 8 else torch.int16
+        nc = (h64 // 2 + 2 * F.CHROMA_MARGIN_Y) * (w64 // 2 + 2 * F.CHROMA_MARGIN_X)
+
+        def planes():
+            return torch.zeros((rows, stride), dtype=dt, device=device), ([torch.zeros(nc, dtype=dt, device=device) for _ in range(2)] if chroma else None)
+        self.recon, self.recon_c = planes()
+        self.out, self.out_c = planes() if self.sao_apply else (None, None)
+        self.sao_rdo = sao_rdo if (sao and sao_apply) else None
+        if self.sao_rdo is not None:
+            self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
+            self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
+
+    def run(self, cur: DevicePicture, mark=None):
+        """Returns the luma plane of the coded picture; mark(name), if given, is called after every stage."""
+        mark = mark or (lambda name: None)
+        assert cur.t.shape == self.recon.shape and cur.t.dtype == self.recon.dtype
+        self.ip.run(cur, self.recon, self.recon_c)
+        mark("intra")
+        if self.db is not None:
+            self.db.run_intra(self.recon, cur, self.ip.num_sig)
+            if self.chroma:
+                hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
+                                      self.db.bs_ver, self.db.bs_hor, self.db.qp)
+            mark("deblock")
+        final, final_c = self.recon, self.recon_c
+        if self.sao_rdo is not None:
+            planes = FramePipeline._sao_planes(self, cur)
+            hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes])
+            mark("sao_stats")
+            FramePipeline._sao_rdo(self)
+            mark("sao_rdo")
+            hipabi.sao_apply_planes(self.depth, planes)
+            final, final_c = self.out, self.out_c
+            mark("sao_apply")
+        elif self.sao is not None:
+            self.sao.stats(cur, self.recon, cur.stride, cur.org)
+            if self.chroma:
+                for i in range(2):
+                    self.sao_c[i].stats(None, self.recon_c[i], cur.stride_c, cur.org_c, src_plane=cur.c[i])
+            mark("sao_stats")
+            if self.sao_apply:
+                self.sao.decide()
+                self.sao.apply(self.recon, cur.stride, cur.org, self.out)
+                final = self.out
+                if self.chroma:
+                    for i in range(2):
+                        self.sao_c[i].decide()
+                        self.sao_c[i].apply(self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i])
+                    final_c = self.out_c
+                mark("sao_apply")
+        extend_border_picture([final] + (list(final_c) if self.chroma else []), cur)
+        mark("border")
+        self.final, self.final_c = final, final_c
+        return final
+
+    def final_planes(self):
+        """[Y, Cb, Cr] (or [Y]) of the picture run() coded last."""
+        return [self.final] + (list(self.final_c) if self.chroma else [])
+
+    def checksum(self):
+        import torch
+        out = self.ip.checksum()
+        out["recon"] = int(self.final.to(torch.int64).sum().item())
+        return out
+
+
 class MiniGop:
     """Display order in, coding order inside: anchor pictures 0, gop, 2 gop, ... form the P chain (each coded by p_step.run from the
     previous anchor's OUTPUT), and the pictures between two anchors are B pictures coded by b_step.run(cur, previous anchor, this
     anchor) once the later anchor is done.  B pictures are not referenced.  p_step: a FramePipeline, b_step: a BFramePipeline of the same
-    geometry and chroma setting."""
+    geometry and chroma setting; i_step: an IFramePipeline of that geometry that codes picture 0, or None."""
 
-    def __init__(self, p_step, b_step, gop):
+    def __init__(self, p_step, b_step, gop, i_step=None):
         assert gop >= 1
-        self.p, self.b, self.gop = p_step, b_step, int(gop)
+        self.p, self.b, self.gop, self.i = p_step, b_step, int(gop), i_step
 
     def run(self, pictures):
-        """pictures: DevicePictures in display order; picture 0 is the first anchor and is taken as it is (an intra picture is not this
-        pipeline's business).  Pictures behind the last anchor are left out.  Returns (coding order as display indices, {display index:
-        [Y, Cb, Cr] planes of the coded picture (clones)})."""
+        """pictures: DevicePictures in display order; picture 0 is the first anchor - coded by i_step where there is one (its output is
+        the first reference), otherwise taken as it is.  Pictures behind the last anchor are left out.  Returns (coding order as display
+        indices, {display index: [Y, Cb, Cr] planes of the coded picture (clones)})."""
         def keep(planes):
             return [p.clone() for p in planes]
         prev = pictures[0]
         out, order = {0: keep(prev.planes())}, [0]
+        if self.i is not None:
+            self.i.run(pictures[0])
+            out[0] = keep(self.i.final_planes())
+            prev = pictures[0].like(out[0])
         for a in range(self.gop, len(pictures), self.gop):
             self.p.run(pictures[a], prev)
             out[a] = keep(self.p.final_planes())

@@ -260,6 +260,11 @@ typedef struct x265hip_recon_params
     const void* mv;
     int16_t* levels; uint32_t* num_sig; uint64_t* dist;
     const x265hip_tu_tables* tables;            /* HOST pointer to the table record, or NULL */
+    /* Per-block quantiser QP (adaptive quantisation; x265hip_cu_qp_maps builds it): DEVICE int8 [height/8][width/8] over the LUMA grid, or
+     * NULL = `qp` for every block.  The block at luma sample (px, py) codes at qp_map[(py >> 3) * (width >> 3) + (px >> 3)], clamped to
+     * [0, 51 + 6 (depth - 8)]; a chroma record points at the Cb or Cr plane of tu_qp and its block position is doubled for the lookup.
+     * `qp` is then only range-checked.  Not together with `tables` (a scaling list's tables are selected per qp % 6 on the host). */
+    const int8_t* qp_map;
 } x265hip_recon_params;
 int x265hip_inter_recon(const x265hip_recon_params* p, void* stream);
 /* One chroma plane of the same stage for 4:2:0 pictures (Predict::predInterChromaPixel, predict.cpp:304-351, + the same residual
@@ -347,6 +352,30 @@ enum x265hip_tu_entry
  * min(nblocks, resident set / nplanes); the smaller ones launch one workgroup per block and get nblocks.  A diagnostic for tests and
  * tools: it launches nothing, but asks the current device.  Returns the grid, or X265HIP_EINVAL / X265HIP_ENODEV. */
 int x265hip_tu_launch_grid(int entry, int n, int depth, int tables, int nplanes, int nblocks);
+/* x265hip_cu_qp_maps - HOST function (host pointers, no device work, never X265HIP_ENODEV): the QP of every block of the TU stages' grid
+ *   from the lookahead's offsets - the non-hevcAq arm of Analysis::calculateQpforCuSize (analysis.cpp:3679-3713, without complexCheck,
+ *   analysis reuse and distortion refinement) followed by Quant::setQPforQuant / setChromaQP (quant.cpp:221-244, 4:2:0).  Per block of
+ *   (8 << level)^2 samples the offsets of its quantisation groups (qg_size = 8 or 16 = loopIncr) are summed in the reference's raster order
+ *   in double, divided by their count, added to base_qp, and (int)(qp + 0.5) is clipped to [qp_min, qp_max].
+ *   qp_offsets: double [ceil(height / qg_size)][ceil(width / qg_size)] - Lowres::qpAqOffset or qpCuTreeOffset, whichever the caller
+ *   selects (bCuTreeOffset); NULL = no offsets.  cb_qp_offset / cr_qp_offset: PPS + slice offsets added.
+ *   Outputs, int8 [height/8][width/8] each, every 8x8 cell of a block holding the block's value (one granularity for every level):
+ *     cu_qp : m_qp - the qp_map of x265hip_deblock_luma / x265hip_deblock_chroma
+ *     tu_qp : [3] planes, the quantiser QPs of Y, Cb, Cr - the qp_map of x265hip_recon_params: Y = m_qp + QP_BD_OFFSET; Cb / Cr clipped
+ *             to [-QP_BD_OFFSET, 57], through g_chromaScale from 30 up, + QP_BD_OFFSET
+ *   Either output may be NULL. */
+typedef struct x265hip_cu_qp_params
+{
+    int depth, width, height, level;                 /* width / height multiples of 64, level 0..2 */
+    int qg_size;
+    double base_qp;
+    const double* qp_offsets;
+    int qp_min, qp_max;                              /* rc.qpMin / rc.qpMax, within 0..51 (QP_MAX_SPEC) */
+    int cb_qp_offset, cr_qp_offset;                  /* each -24..24 */
+    int8_t* cu_qp;
+    int8_t* tu_qp;
+} x265hip_cu_qp_params;
+int x265hip_cu_qp_maps(const x265hip_cu_qp_params* p);
 
 /* Picture border extension (reference extendPicBorder, pixel.cpp:1027-1041 = extendRowBorder slot,
  * ipfilter.cpp:59-77, + top/bottom row replication): `pic` points at pixel (0,0) of a plane that has
@@ -1534,6 +1563,15 @@ typedef struct x265hip_intra_picture_params
     const x265hip_tu_tables* tables;                 /* must be NULL */
 } x265hip_intra_picture_params;
 int x265hip_intra_picture(const x265hip_intra_picture_params* p, void* stream);
+/* The same picture with per-block QPs (adaptive quantisation) - two DEVICE pointers beside the record, both optional (NULL, NULL is
+ * x265hip_intra_picture; the record itself keeps its layout):
+ *   qp_map        : the whole tu_qp of x265hip_cu_qp_maps - int8 [3][height/8][width/8], the quantiser QPs of Y, Cb, Cr one plane after
+ *                   another over the LUMA grid (a chroma block's position is doubled for the lookup); every entry is clamped to
+ *                   [0, 51 + 6 (depth - 8)].  The block's coding uses its own three QPs; the record's qp / qp_cb / qp_cr are only range-checked.
+ *   lambda8_by_qp : uint32 [52 + 6 (depth - 8)], indexed by a block's LUMA quantiser QP (the record's qp without a map): 256 x
+ *                   RDCost::m_lambda of a CU at that QP (rdcost.h:50-54, 93-97: the reference sets lambda per CU from the same QP); an
+ *                   entry above 2^24 counts as 2^24.  The block's mode decision is priced with its entry.  NULL = lambda8 for every block. */
+int x265hip_intra_picture_qp(const x265hip_intra_picture_params* p, const int8_t* qp_map, const uint32_t* lambda8_by_qp, void* stream);
 /* launches x265hip_intra_picture issues for a picture of this size: width / 64 + 2 * (height / 64 - 1).  Host arithmetic, needs no device. */
 int x265hip_intra_picture_waves(int width, int height);
 

@@ -39,6 +39,8 @@ struct IntraPicArgs
     uint8_t* mode;
     int16_t* levels[3]; uint32_t* numSig[3]; unsigned long long* dist[3];
     int2* cost;                                           // optional [ctu][blocks] {winning sad, winning cost}
+    const int8_t* qpMap;                                  // optional int8 [3][ctusH * 8][ctusW * 8]: the quantiser QPs of Y, Cb, Cr per 8x8 cell of the luma grid
+    const uint32_t* lambdaByQp;                           // optional, indexed by the block's luma quantiser QP
 };
 
 // z-order index of block (bx, by) of a CTU
@@ -142,6 +144,21 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(IntraPicArgs a, cons
         };
         const bool av[5] = { available(gbx - 1, gby + 1), available(gbx - 1, gby), available(gbx - 1, gby - 1), available(gbx, gby - 1),
                              available(gbx + 1, gby - 1) };
+        // the block's own three QPs and lambda (uniform: scalar loads, see tu_map_qp); without the pointers the record's values
+        int qpB[3] = { a.qp[0], a.qp[1], a.qp[2] };
+        if (a.qpMap)
+        {
+            const int cell = (gby * (N >> 3)) * (a.ctusW * 8) + gbx * (N >> 3), plane = (a.ctusH * 8) * (a.ctusW * 8);
+#pragma unroll
+            for (int c = 0; c < 3; c++) qpB[c] = tu_map_qp(a.qpMap + (size_t)c * plane, cell, a.depth);
+        }
+        int lambda8 = a.lambda8;
+        if (a.lambdaByQp)
+        {
+            typedef const uint32_t __attribute__((address_space(4))) * ConstWords;
+            const uint32_t l = ((ConstWords)reinterpret_cast<uintptr_t>(a.lambdaByQp))[__builtin_amdgcn_readfirstlane(qpB[0])];
+            lambda8 = (int)(l < (1u << 24) ? l : (1u << 24));
+        }
         // ---- luma: reference samples, filtered copy, source block -----------------------------------------------------------------
         ip_fill_neighbours<Px, N, 64>(nbU, tileY, planeY, strideY, bxz * N, byz * N, av, dcValue);
         {
@@ -226,7 +243,7 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(IntraPicArgs a, cons
 #pragma unroll
                 for (int u = 0; u < UNITS; u++) sad += sUnit[tid * UNITS + u];
                 const int bits = mode == p0 ? a.modeBits[0] : ((mode == p1 || mode == p2) ? a.modeBits[1] : a.modeBits[2]);
-                cost = (long long)sad + (((long long)bits * a.lambda8 + 128) >> 8);
+                cost = (long long)sad + (((long long)bits * lambda8 + 128) >> 8);
                 key = ((unsigned long long)cost << 6) | (unsigned)tid;
             }
             unsigned long long best = key;
@@ -244,7 +261,7 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(IntraPicArgs a, cons
         __syncthreads();
         const size_t blk = (size_t)ctu * NPU + z;
         const int scanLuma = N == 8 ? (mode >= 22 && mode <= 30 ? TU_SCAN_HOR : (mode >= 6 && mode <= 14 ? TU_SCAN_VER : TU_SCAN_DIAG)) : TU_SCAN_DIAG;
-        tu_chain<Px, N, false, false>(ops, pred, fe, A, B, red, sNumSig, a.depth, a.qp[0], a.flags, a.levels[0] + blk * NN, &a.numSig[0][blk], &a.dist[0][blk],
+        tu_chain<Px, N, false, false>(ops, pred, fe, A, B, red, sNumSig, a.depth, qpB[0], a.flags, a.levels[0] + blk * NN, &a.numSig[0][blk], &a.dist[0][blk],
                                       tileY + (byz * N) * 64 + bxz * N, 64, scanLuma);
         __syncthreads();
         {
@@ -287,7 +304,7 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(IntraPicArgs a, cons
                 for (int i = tid; i < NNC; i += nth)
                     pred[i] = (int16_t)intra_sample(nbU, NC, LOG2NC, mode, 0, dcC, maxVal, i & (NC - 1), i >> LOG2NC);
                 __syncthreads();
-                tu_chain<Px, NC, false, false>(opsC, pred, fe, A, B, red, sNumSig, a.depth, a.qp[1 + c], a.flags, a.levels[1 + c] + blk * NNC,
+                tu_chain<Px, NC, false, false>(opsC, pred, fe, A, B, red, sNumSig, a.depth, c ? qpB[2] : qpB[1], a.flags, a.levels[1 + c] + blk * NNC,
                                                &a.numSig[1 + c][blk], &a.dist[1 + c][blk], tileC[c] + (byz * NC) * 32 + bxz * NC, 32, scanC);
                 __syncthreads();
                 Px* r = reinterpret_cast<Px*>(a.recon[1 + c] + (long)(gby * NC) * a.reconStrideB[1 + c]) + gbx * NC;
@@ -307,7 +324,7 @@ extern "C" int x265hip_intra_picture_waves(int width, int height)
     return width / 64 + 2 * (height / 64 - 1);
 }
 
-extern "C" int x265hip_intra_picture(const x265hip_intra_picture_params* p, void* stream)
+extern "C" int x265hip_intra_picture_qp(const x265hip_intra_picture_params* p, const int8_t* qp_map, const uint32_t* lambda8_by_qp, void* stream)
 {
     using namespace x265hip;
     // argument checks first: they need no device
@@ -357,6 +374,7 @@ extern "C" int x265hip_intra_picture(const x265hip_intra_picture_params* p, void
     a.lambda8 = p->lambda8;
     for (int i = 0; i < 3; i++) a.modeBits[i] = p->mode_bits[i];
     a.mode = p->mode; a.cost = (int2*)p->cost;
+    a.qpMap = qp_map; a.lambdaByQp = lambda8_by_qp;
     hipStream_t s = (hipStream_t)stream;
     const int waves = a.ctusW + 2 * (a.ctusH - 1);
     for (int w = 0; w < waves; w++)
@@ -376,3 +394,5 @@ extern "C" int x265hip_intra_picture(const x265hip_intra_picture_params* p, void
     X265HIP_TRY(hipGetLastError());
     return 0;
 }
+
+extern "C" int x265hip_intra_picture(const x265hip_intra_picture_params* p, void* stream) { return x265hip_intra_picture_qp(p, nullptr, nullptr, stream); }

@@ -92,12 +92,30 @@ struct TuArgs
     int qp, intraSlice;          // intraSlice: the X265HIP_TU_* flag bits (+ TU_FLAG_RASTER_ORDER, set by the launcher alone)
     int16_t* levels; uint32_t* numSig; unsigned long long* dist;
     TuTables tab;
+    const int8_t* qpMap;         // per-block quantiser QP, int8 [height/8][ctusW * 8] over the luma grid, or NULL = qp everywhere
 };
 
 struct TuArgs2 { TuArgs p[2]; };
 
 __device__ __forceinline__ int tu_clip16(int v, int maxVal) { const int16_t s = (int16_t)v; return s < 0 ? 0 : (s > maxVal ? maxVal : s); }
 __device__ __forceinline__ int tu_sat16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+
+// One entry of a per-block QP map (int8 per 8x8 cell of the luma grid), clamped to the depth's range: no entry can push per / rem outside the
+// scale tables.  A block belongs to one workgroup, so the entry is uniform: the aligned dword that holds it is read through the constant
+// address space - a scalar load (the map is not written while the kernel runs) - and the QP stays in SGPRs like a record's qp.  The dword
+// holds bytes of the map and at most three bytes of the same allocation unit around it.
+__device__ __forceinline__ int tu_map_qp(const int8_t* map, const int cell, const int depth)
+{
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(map) + (uintptr_t)__builtin_amdgcn_readfirstlane(cell);
+    typedef const uint32_t __attribute__((address_space(4))) * ConstWords;
+    const uint32_t w = *(ConstWords)(addr & ~(uintptr_t)3);
+    return clip3(0, 51 + 6 * (depth - 8), (int)(int8_t)(w >> (8 * (int)(addr & 3))));
+}
+// The quantiser QP of the block whose first 8x8 cell of the luma grid is (cx8, cy8): the record's qp, or its map's entry
+__device__ __forceinline__ int tu_block_qp(const TuArgs& a, const int cx8, const int cy8)
+{
+    return a.qpMap ? tu_map_qp(a.qpMap, cy8 * (a.ctusW * 8) + cx8, a.depth) : a.qp;
+}
 
 // The transform-coding round trip of one N x N block whose prediction (pred) and source (fe) already sit in LDS:
 // residual -> forward transform -> quant -> dequant -> (DC shortcut | inverse transform) -> reconstruction -> SSE.
@@ -604,7 +622,7 @@ __global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>
     TuOpsFor<N, false> ops;
     ops.init(tid & 63);
     // geometry of block `blk` given its packed quarter-sample motion vector
-    struct Geo { int ctu, z, px, py, qx, qy, xf, yf; };
+    struct Geo { int ctu, z, px, py, qx, qy, xf, yf, qp; };
     auto geom = [&](const int blk, const int packed) -> Geo
     {
         Geo g;
@@ -613,6 +631,9 @@ __global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>
         g.px = (g.ctu % a.ctusW) * CTU + bxz * N; g.py = (g.ctu / a.ctusW) * CTU + byz * N;
         g.qx = (int16_t)(packed & 0xffff); g.qy = (int16_t)(packed >> 16);
         g.xf = g.qx & MVMASK; g.yf = g.qy & MVMASK;
+        // the block's own QP travels with its geometry: where the next block's operands are fetched ahead (16 points), its QP waits in gn
+        // and the chain below keeps reading g
+        g.qp = tu_block_qp(a, g.px >> (CHROMA ? 2 : 3), g.py >> (CHROMA ? 2 : 3));
         return g;
     };
     auto mv_of = [&](const int blk) -> int { const int ctu = blk / npu; return a.mv[(size_t)ctu * 85 + lbase + (blk - ctu * npu)].y; };
@@ -703,7 +724,7 @@ __global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>
     __syncthreads();
     between();
 
-    tu_chain<Px, N, false, TAB>(ops, pred, fe, A, B, red, sNumSig, a.depth, a.qp, a.intraSlice,
+    tu_chain<Px, N, false, TAB>(ops, pred, fe, A, B, red, sNumSig, a.depth, g.qp, a.intraSlice,
                            a.levels + ((size_t)ctu * npu + z) * NN, &a.numSig[(size_t)ctu * npu + z], &a.dist[(size_t)ctu * npu + z],
                            reinterpret_cast<Px*>(a.recon + (long)py * a.reconStrideB) + px, a.reconStrideB / BPP, TU_SCAN_DIAG,
                            TAB ? a.tab.at(((size_t)ctu * npu + z) * NN) : a.tab, (size_t)ctu * npu + z);
@@ -814,6 +835,7 @@ __global__ void __launch_bounds__(N >= 16 ? 64 : 256, TuWavesPerSimd<N>::value) 
         const int bxz = (z & 1) | ((z >> 1) & 2) | ((z >> 2) & 4), byz = ((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4);
         const int px = (ctu % a.ctusW) * CTU + bxz * N, py = (ctu / a.ctusW) * CTU + byz * N;
         const int d = b.dir ? b.dir[blk] : 3;
+        const int qp = tu_block_qp(a, px >> (CHROMA ? 2 : 3), py >> (CHROMA ? 2 : 3));
         {
             const Px* f = reinterpret_cast<const Px*>(a.fenc + (long)py * a.fencStrideB) + px;
             const long fst = a.fencStrideB / BPP;
@@ -907,7 +929,7 @@ __global__ void __launch_bounds__(N >= 16 ? 64 : 256, TuWavesPerSimd<N>::value) 
                 pred[i] = (int16_t)clip3(0, maxVal, ((b.w[l] * ((int)pred[i] + 8192) + round) >> shift) + b.wOff[l]);
             __syncthreads();
         }
-        tu_chain<Px, N, false, TAB>(ops, pred, fe, A, B, red, sNumSig, a.depth, a.qp, a.intraSlice,
+        tu_chain<Px, N, false, TAB>(ops, pred, fe, A, B, red, sNumSig, a.depth, qp, a.intraSlice,
                                a.levels + ((size_t)ctu * npu + z) * NN, &a.numSig[(size_t)ctu * npu + z], &a.dist[(size_t)ctu * npu + z],
                                reinterpret_cast<Px*>(a.recon + (long)py * a.reconStrideB) + px, a.reconStrideB / BPP, TU_SCAN_DIAG,
                                TAB ? a.tab.at(((size_t)ctu * npu + z) * NN) : a.tab, (size_t)ctu * npu + z);
@@ -1065,8 +1087,18 @@ extern "C" int x265hip_tu_launch_grid(int entry, int n, int depth, int tables, i
     return tu_launch_grid(entry, n, depth, tables != 0, nplanes, nblocks);
 }
 
+// A per-block QP and per-coefficient tables exclude each other: scaling-list tables are selected per qp % 6 on the host.  Checked before the
+// device is asked for, like the other argument checks that need none.
+static bool tu_map_with_tables(const x265hip_recon_params* p, const char* who)
+{
+    if (!p || !p->qp_map || !p->tables) return false;
+    set_error("%s: qp_map together with tables (scaling-list tables are selected per qp %% 6)", who);
+    return true;
+}
+
 extern "C" int x265hip_inter_recon(const x265hip_recon_params* p, void* stream)
 {
+    if (tu_map_with_tables(p, "inter_recon")) return X265HIP_EINVAL;
     int rc = ensure_device();
     if (rc) return rc;
     if (!p || !p->fenc || !p->fref || !p->recon || !p->mv || !p->levels || !p->num_sig || !p->dist)
@@ -1083,7 +1115,7 @@ extern "C" int x265hip_inter_recon(const x265hip_recon_params* p, void* stream)
     a.ctusW = p->width / 64; a.depth = p->depth; a.level = p->level;
     a.mv = (const int2*)p->mv; a.qp = p->qp; a.intraSlice = (p->intra_slice & ~TU_FLAG_RASTER_ORDER) | (tu_raster_order(false) ? TU_FLAG_RASTER_ORDER : 0);
     a.levels = p->levels; a.numSig = p->num_sig; a.dist = (unsigned long long*)p->dist;
-    a.tab = tu_tables_of(TABLES_OF(p));
+    a.tab = tu_tables_of(TABLES_OF(p)); a.qpMap = p->qp_map;
     TuArgs2 aa = {};
     aa.p[0] = a;
     const int nctu = a.ctusW * (p->height / 64);
@@ -1105,6 +1137,7 @@ extern "C" int x265hip_inter_recon(const x265hip_recon_params* p, void* stream)
 
 static int inter_recon_bi_impl(const x265hip_recon_bi_params* q, void* stream, const bool chroma)
 {
+    if (q && tu_map_with_tables(&q->base, "inter_recon_bi")) return X265HIP_EINVAL;
     int rc = ensure_device();
     if (rc) return rc;
     if (!q) { set_error("inter_recon_bi: NULL operand"); return X265HIP_EINVAL; }
@@ -1124,7 +1157,7 @@ static int inter_recon_bi_impl(const x265hip_recon_bi_params* q, void* stream, c
     a.ctusW = p->width / 64; a.depth = p->depth; a.level = p->level;
     a.mv = (const int2*)p->mv; a.qp = p->qp; a.intraSlice = p->intra_slice;
     a.levels = p->levels; a.numSig = p->num_sig; a.dist = (unsigned long long*)p->dist;
-    a.tab = tu_tables_of(TABLES_OF(p));
+    a.tab = tu_tables_of(TABLES_OF(p)); a.qpMap = p->qp_map;
     b.fref1 = (const uint8_t*)q->fref1; b.mv1 = (const int2*)q->mv1; b.dir = q->dir;
     {
         const x265hip_pred_weight* ws[2] = { q->weight0, q->weight1 };
@@ -1167,6 +1200,8 @@ extern "C" int x265hip_inter_recon_chroma_bi(const x265hip_recon_bi_params* q, v
 // One or both chroma planes of a picture: the same kernel, grid.y = plane.
 static int inter_recon_chroma_planes(const x265hip_recon_params* const* pp, int nplanes, void* stream)
 {
+    for (int i = 0; i < nplanes; i++)
+        if (tu_map_with_tables(pp[i], "inter_recon_chroma")) return X265HIP_EINVAL;
     int rc = ensure_device();
     if (rc) return rc;
     TuArgs2 aa = {};
@@ -1190,7 +1225,7 @@ static int inter_recon_chroma_planes(const x265hip_recon_params* const* pp, int 
         a.ctusW = q->width / 64; a.depth = q->depth; a.level = q->level;
         a.mv = (const int2*)q->mv; a.qp = q->qp; a.intraSlice = (q->intra_slice & ~TU_FLAG_RASTER_ORDER) | (tu_raster_order(true) ? TU_FLAG_RASTER_ORDER : 0);
         a.levels = q->levels; a.numSig = q->num_sig; a.dist = (unsigned long long*)q->dist;
-        a.tab = tu_tables_of(TABLES_OF(q));
+        a.tab = tu_tables_of(TABLES_OF(q)); a.qpMap = q->qp_map;
     }
     const int nctu = aa.p[0].ctusW * (p->height / 64);
     const int nblocks = nctu * (64 >> (2 * p->level));

@@ -285,10 +285,12 @@ def intra_picture_waves(width, height):
 
 
 def intra_picture(depth, width, height, level, qp, flags, lambda8, mode_bits, fenc, fenc_stride, fenc_off, recon, mode, levels, num_sig, dist,
-                  chroma=None, cost=None, strong_intra_smoothing=True, stream=None):
+                  chroma=None, cost=None, strong_intra_smoothing=True, stream=None, qp_map=None, lambda8_by_qp=None):
     """x265hip_intra_picture: one I picture (mode decision + coding of every block, wave by wave).  fenc / recon: luma tensors of one
     geometry (sample (0,0) at element fenc_off).  chroma: None or a dict - fenc (Cb, Cr), recon (Cb, Cr) tensors with `stride` samples per
-    row and sample (0,0) at element `org`, qp (Cb, Cr) and per plane levels / num_sig / dist tensors."""
+    row and sample (0,0) at element `org`, qp (Cb, Cr) and per plane levels / num_sig / dist tensors.  qp_map: device int8 tensor, the
+    whole tu_qp of cu_qp_maps (3 planes); lambda8_by_qp: device int32 tensor (uint32 bits) indexed by the luma quantiser QP - with either
+    the call goes to x265hip_intra_picture_qp."""
     es = 1 if depth == 8 else 2
     p = IntraPictureParams()
     p.depth, p.width, p.height, p.level, p.qp, p.flags = depth, width, height, level, qp, flags
@@ -306,6 +308,11 @@ def intra_picture(depth, width, height, level, qp, flags, lambda8, mode_bits, fe
         p.num_sig_cb, p.num_sig_cr = (t.data_ptr() for t in chroma["num_sig"])
         p.dist_cb, p.dist_cr = (t.data_ptr() for t in chroma["dist"])
     s = current_stream() if stream is None else stream
+    if qp_map is not None or lambda8_by_qp is not None:
+        f = lib().x265hip_intra_picture_qp
+        f.argtypes = [ctypes.POINTER(IntraPictureParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        check(f(ctypes.byref(p), _p(qp_map), _p(lambda8_by_qp), s), "x265hip_intra_picture_qp")
+        return
     f = lib().x265hip_intra_picture
     f.argtypes = [ctypes.POINTER(IntraPictureParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_intra_picture")
@@ -458,6 +465,36 @@ def aq_offsets(depth, qg_size, aq_mode, aq_strength, energy):
     f.argtypes = [ctypes.POINTER(AqOffsetsParams)]
     check(f(ctypes.byref(p)), "x265hip_aq_offsets")
     return qp, inv
+
+
+class CuQpParams(ctypes.Structure):
+    """x265hip_cu_qp_params (include/x265hip.h)."""
+    _fields_ = [("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int), ("qg_size", ctypes.c_int),
+                ("base_qp", ctypes.c_double), ("qp_offsets", ctypes.c_void_p), ("qp_min", ctypes.c_int), ("qp_max", ctypes.c_int),
+                ("cb_qp_offset", ctypes.c_int), ("cr_qp_offset", ctypes.c_int), ("cu_qp", ctypes.c_void_p), ("tu_qp", ctypes.c_void_p)]
+
+
+def cu_qp_maps(depth, width, height, level, qg_size, base_qp, qp_offsets=None, qp_min=0, qp_max=51, cb_qp_offset=0, cr_qp_offset=0):
+    """Host step between the lookahead's offsets and the coding stages (x265hip_cu_qp_maps; needs no device): qp_offsets = float64
+    [ceil(height / qg_size) * ceil(width / qg_size)] (qpAqOffset or qpCuTreeOffset) or None.  Returns (cu_qp int8 [height/8, width/8],
+    tu_qp int8 [3, height/8, width/8]) - the CUs' m_qp for the deblocking entries and the quantiser QPs of Y, Cb, Cr for the TU stages."""
+    import numpy as np
+    h8, w8 = max(height, 0) // 8, max(width, 0) // 8
+    cu, tu = np.zeros((h8, w8), np.int8), np.zeros((3, h8, w8), np.int8)
+    p = CuQpParams()
+    p.depth, p.width, p.height, p.level, p.qg_size, p.base_qp = depth, width, height, level, qg_size, float(base_qp)
+    p.qp_min, p.qp_max, p.cb_qp_offset, p.cr_qp_offset = qp_min, qp_max, cb_qp_offset, cr_qp_offset
+    offs = None
+    if qp_offsets is not None:
+        offs = np.ascontiguousarray(qp_offsets, dtype=np.float64).reshape(-1)
+        if qg_size in (8, 16) and len(offs) != -(-height // qg_size) * -(-width // qg_size):
+            raise X265HipError(f"cu_qp_maps: {len(offs)} offsets for a {width}x{height} picture in groups of {qg_size}")
+        p.qp_offsets = offs.ctypes.data
+    p.cu_qp, p.tu_qp = cu.ctypes.data, tu.ctypes.data
+    f = lib().x265hip_cu_qp_maps
+    f.argtypes = [ctypes.POINTER(CuQpParams)]
+    check(f(ctypes.byref(p)), "x265hip_cu_qp_maps")
+    return cu, tu
 
 
 class AqFrameHostParams(ctypes.Structure):

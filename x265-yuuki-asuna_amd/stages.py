@@ -22,7 +22,7 @@ class ReconParams(ctypes.Structure):
         ("fref", ctypes.c_void_p), ("fref_stride", ctypes.c_ssize_t),
         ("recon", ctypes.c_void_p), ("recon_stride", ctypes.c_ssize_t),
         ("mv", ctypes.c_void_p), ("levels", ctypes.c_void_p), ("num_sig", ctypes.c_void_p), ("dist", ctypes.c_void_p),
-        ("tables", ctypes.c_void_p),
+        ("tables", ctypes.c_void_p), ("qp_map", ctypes.c_void_p),
     ]
 
 
@@ -35,6 +35,8 @@ def _tu_part(stage, ctu_row0, ctu_rows):
     o.levels = stage.levels[c0 * nb * nn:(c0 + o.nctu) * nb * nn]
     o.num_sig = stage.num_sig[c0 * nb:(c0 + o.nctu) * nb]
     o.dist = stage.dist[c0 * nb:(c0 + o.nctu) * nb]
+    if stage.qp_map is not None:          # the part's blocks are looked up from the part's first row: 8 rows of width / 8 cells per CTU row
+        o.qp_map = stage.qp_map[ctu_row0 * 8 * (stage.w64 // 8):(ctu_row0 + ctu_rows) * 8 * (stage.w64 // 8)]
     return o
 
 
@@ -51,6 +53,7 @@ class InterRecon:
         self.num_sig = torch.zeros(nctu * self.nblk, dtype=torch.int32, device=device)
         self.dist = torch.zeros(nctu * self.nblk, dtype=torch.int64, device=device)
         self.tables = None          # hipabi.tu_tables(...): scaling-list coefficients / denoiser tables of this block size, or None
+        self.qp_map = None          # device int8 [h64 / 8 * w64 / 8]: the luma plane of CuQpMaps.tu_qp (per-block quantiser QP), or None = qp
 
     def part(self, ctu_row0, ctu_rows):
         """The stage for `ctu_rows` CTU rows from `ctu_row0` (outputs = the matching slices; see pipeline.MotionSearch.part)."""
@@ -70,6 +73,7 @@ class InterRecon:
         p.recon, p.recon_stride = recon_plane.data_ptr() + cur.org * es, cur.stride
         p.mv, p.levels, p.num_sig, p.dist = mv.data_ptr(), self.levels.data_ptr(), self.num_sig.data_ptr(), self.dist.data_ptr()
         p.tables = ctypes.addressof(self.tables) if self.tables is not None else None
+        p.qp_map = hipabi._p(self.qp_map)
         s = hipabi.current_stream() if stream is None else stream
         f = hipabi.lib().x265hip_inter_recon
         f.argtypes = [ctypes.POINTER(ReconParams), ctypes.c_void_p]
@@ -113,6 +117,7 @@ class InterReconBi(InterRecon):
         p.recon, p.recon_stride = recon_plane.data_ptr() + cur.org * es, cur.stride
         p.mv, p.levels, p.num_sig, p.dist = mv0.data_ptr(), self.levels.data_ptr(), self.num_sig.data_ptr(), self.dist.data_ptr()
         p.tables = ctypes.addressof(self.tables) if self.tables is not None else None
+        p.qp_map = hipabi._p(self.qp_map)
         q.fref1, q.mv1 = ref1.t.data_ptr() + ref1.org * es, mv1.data_ptr()
         q.dir = None if dir_flags is None else dir_flags.data_ptr()
         s = hipabi.current_stream() if stream is None else stream
@@ -135,6 +140,7 @@ class InterReconChroma:
         self.num_sig = torch.zeros(nctu * self.nblk, dtype=torch.int32, device=device)
         self.dist = torch.zeros(nctu * self.nblk, dtype=torch.int64, device=device)
         self.tables = None
+        self.qp_map = None          # device int8 [h64 / 8 * w64 / 8] over the LUMA grid: this plane's (Cb or Cr) part of CuQpMaps.tu_qp, or None = qp
 
     def part(self, ctu_row0, ctu_rows):
         return _tu_part(self, ctu_row0, ctu_rows)
@@ -148,6 +154,7 @@ class InterReconChroma:
         p.recon, p.recon_stride = recon.data_ptr() + org * es, stride
         p.mv, p.levels, p.num_sig, p.dist = mv.data_ptr(), self.levels.data_ptr(), self.num_sig.data_ptr(), self.dist.data_ptr()
         p.tables = ctypes.addressof(self.tables) if self.tables is not None else None
+        p.qp_map = hipabi._p(self.qp_map)
         return p
 
     def run(self, fenc, fref, recon, stride, org, mv, stream=None):
@@ -255,6 +262,65 @@ def chroma_quant_qp(qp, depth, offset=0):
     return q + bd
 
 
+class CuQpMaps:
+    """The step between the lookahead's QP offsets and the coding stages (x265hip_cu_qp_maps; reference Analysis::calculateQpforCuSize,
+    analysis.cpp:3679-3713, + Quant::setQPforQuant / setChromaQP, quant.cpp:221-244): offsets -> host maps -> device tensors.  After
+    run(): cu_qp int8 [h/8 * w/8] (the CUs' m_qp: what the deblocking entries take) and tu_qp int8 [3][h/8 * w/8] (the quantiser QPs of
+    Y, Cb, Cr: what the TU stages take), on the device; cu_qp_host / tu_qp_host the numpy arrays they were uploaded from."""
+
+    def __init__(self, w64, h64, depth, level, device, qg_size=16, qp_min=0, qp_max=51, cb_qp_offset=0, cr_qp_offset=0):
+        import torch
+        self.w64, self.h64, self.depth, self.level, self.qg_size = w64, h64, depth, level, qg_size
+        self.qp_min, self.qp_max, self.cb_qp_offset, self.cr_qp_offset = qp_min, qp_max, cb_qp_offset, cr_qp_offset
+        cells = (h64 // 8) * (w64 // 8)
+        self.cu_qp = torch.zeros(cells, dtype=torch.int8, device=device)
+        self.tu_qp = torch.zeros(3 * cells, dtype=torch.int8, device=device).view(3, cells)
+        self.cu_qp_host = self.tu_qp_host = None
+
+    def run(self, base_qp, qp_offsets=None):
+        """base_qp: the picture's QP as rate control hands it to the CTUs (a double; CU QP domain, without QP_BD_OFFSET); qp_offsets: the
+        picture's qpAqOffset or qpCuTreeOffset (AdaptiveQuant.qp_aq_offset / .qp_cutree_offset, a cuTree finish), or None."""
+        import torch
+        cu, tu = hipabi.cu_qp_maps(self.depth, self.w64, self.h64, self.level, self.qg_size, base_qp, qp_offsets, self.qp_min, self.qp_max,
+                                   self.cb_qp_offset, self.cr_qp_offset)
+        return self.load(cu, tu)
+
+    def load(self, cu, tu):
+        """Maps made elsewhere (numpy int8 [h/8, w/8] and [3, h/8, w/8], every 8x8 cell of a block holding the block's value)."""
+        import torch
+        self.cu_qp_host, self.tu_qp_host = np.ascontiguousarray(cu, dtype=np.int8), np.ascontiguousarray(tu, dtype=np.int8)
+        self.cu_qp.copy_(torch.from_numpy(self.cu_qp_host.reshape(-1)))
+        self.tu_qp.copy_(torch.from_numpy(self.tu_qp_host.reshape(3, -1)))
+        return self
+
+
+def _set_qp_maps(pipe, maps, tu_luma, tu_chroma):
+    """set_qp_maps of the frame pipelines: the maps' planes go to the TU stages (tu_qp) and to the deblocking stage (cu_qp), which
+    the pipeline's luma and chroma deblocking calls both read.  maps: a CuQpMaps of the pipeline's geometry, depth and level, or None."""
+    if maps is not None:
+        geo = (pipe.ms.w64, pipe.ms.h64, pipe.depth, tu_luma.level)
+        if (maps.w64, maps.h64, maps.depth, maps.level) != geo:
+            raise ValueError(f"set_qp_maps: maps of (w, h, depth, level) = {(maps.w64, maps.h64, maps.depth, maps.level)} for a pipeline of {geo}")
+    pipe.qp_maps = maps
+    tu_luma.qp_map = None if maps is None else maps.tu_qp[0]
+    for i, st in enumerate(tu_chroma):
+        st.qp_map = None if maps is None else maps.tu_qp[1 + i]
+    if pipe.db is not None:
+        pipe.db.qp_map = None if maps is None else maps.cu_qp
+
+
+def _qp_maps_run_check(pipe):
+    """run() of a pipeline whose maps are set, in a mode that would not honour them: raise instead of coding with other QPs than asked for."""
+    if getattr(pipe, "qp_maps", None) is None:
+        return
+    import torch
+    name = type(pipe).__name__
+    if getattr(pipe, "band_border", None) is not None:
+        raise ValueError(f"{name}: QP maps are set, but a band of a picture does not take its rows of them")
+    if torch.cuda.is_current_stream_capturing():
+        raise ValueError(f"{name}: QP maps are set, but a captured step would go on replaying the maps it was captured with")
+
+
 class Deblock:
     """In-loop deblocking of the luma reconstruction on device (x265hip_deblock_bs_inter + x265hip_deblock_luma; reference
     Deblock::getBoundaryStrength / edgeFilterLuma, deblock.cpp:191-215, 317-415) for the reconstruction stage's block grid."""
@@ -262,18 +328,19 @@ class Deblock:
     def __init__(self, w64, h64, depth, level, qp, device):
         import torch
         self.w64, self.h64, self.depth, self.level, self.qp = w64, h64, depth, level, qp
+        self.qp_map = None          # device int8 [h64 / 8 * w64 / 8]: CuQpMaps.cu_qp (the CUs' m_qp), or None = qp; the pipelines' chroma pass reads it too
         self.bs_ver = torch.zeros((h64 // 4) * (w64 // 8), dtype=torch.uint8, device=device)
         self.bs_hor = torch.zeros((h64 // 8) * (w64 // 4), dtype=torch.uint8, device=device)
 
     def run(self, plane, pic: DevicePicture, mv, num_sig):
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv, num_sig, self.bs_ver, self.bs_hor)
-        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp)
+        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
 
     def run_b(self, plane, pic: DevicePicture, mv0, mv1, ref0, ref1, num_sig):
         """A B picture: the boundary strengths compare (ref0, ref1) x (mv0, mv1) per block (deblock.cpp:217-247); ref0 / ref1 = int8 picture
         ids per block, -1 = list unused (what BidirDecide leaves)."""
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv0, num_sig, self.bs_ver, self.bs_hor, slice_b=True, mv1=mv1, ref0=ref0, ref1=ref1)
-        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp)
+        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
 
     def prepare_intra(self):
         """Allocates what run_intra passes beside num_sig (IFramePipeline calls it in its constructor, so that run() allocates nothing)."""
@@ -288,7 +355,7 @@ class Deblock:
         vector records are not looked at on such edges (zeros are passed)."""
         self.prepare_intra()
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, self._intra_mv, num_sig, self.bs_ver, self.bs_hor, intra=self._intra_flags)
-        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp)
+        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
 
 
 class Sao:
@@ -677,6 +744,13 @@ class FramePipeline:
         # band mode (BandedFramePipeline): (is_first_band, is_last_band) -> row-wise border extension instead of the whole-picture one
         self.band_border = None
 
+    def set_qp_maps(self, maps):
+        """Per-block QPs (adaptive quantisation) for the following run() calls: maps = a CuQpMaps of this geometry, depth and level, or None
+        = the picture-wide qp again.  Every run mode reads the maps from the stages; the parts of `split` are rebuilt with their rows of
+        the maps.  Not for bands (BandedFramePipeline), captured graphs or scaling-list tables: run() raises there."""
+        _set_qp_maps(self, maps, self.rc, self.rc_c if self.chroma else [])
+        self.parts = None
+
     def _sao_rdo(self):
         """x265hip_sao_rdo on the statistics of all planes -> every plane's Sao.params."""
         st = [self.sao] + (list(self.sao_c) if self.chroma else [])
@@ -693,6 +767,7 @@ class FramePipeline:
         the picture for the next frame's reference list (final_planes() has all three).  mark(name), if given, is called after every
         stage (bench.py records an event there)."""
         import torch
+        _qp_maps_run_check(self)
         par = self.parallel and mark is None and self.chroma and not self.lcb and self.ps is None and self.db is not None and self.sao is not None \
             and self.sao_apply
         if par:
@@ -741,7 +816,7 @@ class FramePipeline:
             self.db.run(self.recon, cur, mv, self.rc.num_sig)
             if self.chroma:                  # Bs 2 edges only (intra CUs): none in an all-inter picture, the pass still runs like the reference's
                 hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                      self.db.bs_ver, self.db.bs_hor, self.db.qp)
+                                      self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
             mark("deblock")
         final, final_c = self.recon, self.recon_c
         if self.sao_rdo is not None:
@@ -872,7 +947,7 @@ class FramePipeline:
         sCb.wait_event(ev_bs); sCb.wait_event(ev_rec[1])
         with torch.cuda.stream(sCb):
             hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                  self.db.bs_ver, self.db.bs_hor, self.db.qp)
+                                  self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
             ev_dbc = torch.cuda.Event(); ev_dbc.record(sCb)
         sCr.wait_event(ev_dbc)
         if self.sao_rdo is not None:
@@ -963,7 +1038,7 @@ class FramePipeline:
         sC.wait_event(ev_bs)
         with torch.cuda.stream(sC):
             hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                  self.db.bs_ver, self.db.bs_hor, self.db.qp)
+                                  self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
             hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes[1:3]])
             ev_cstats = torch.cuda.Event(); ev_cstats.record(sC)
             ms.reset_spare()                              # the sub-pel stage has long read this picture's minima: the other buffer may be cleared
@@ -1277,10 +1352,15 @@ class BFramePipeline:
             self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
             self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
 
+    def set_qp_maps(self, maps):
+        """Per-block QPs for the following run() calls (see FramePipeline.set_qp_maps); None = the picture-wide qp again."""
+        _set_qp_maps(self, maps, self.rc, self.rc_c if self.chroma else [])
+
     def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mark=None):
         """ref0 / ref1: the list-0 / list-1 reference pictures (extended borders; with chroma=True also their Cb / Cr planes).  Returns the
         luma plane of the coded picture; mark(name), if given, is called after every stage."""
         import torch
+        _qp_maps_run_check(self)
         mark = mark or (lambda name: None)
         if self.recon is None:
             self.recon = torch.zeros_like(cur.t)
@@ -1306,7 +1386,7 @@ class BFramePipeline:
             self.db.run_b(self.recon, cur, mv0, mv1, self.bd.ref0, self.bd.ref1, self.rc.num_sig)
             if self.chroma:
                 hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                      self.db.bs_ver, self.db.bs_hor, self.db.qp)
+                                      self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
             mark("deblock")
         final, final_c = self.recon, self.recon_c
         if self.sao is not None and self.sao_apply and self.out is None:
@@ -1391,6 +1471,9 @@ class IntraPicture:
         if chroma:
             c = [outs(self.n * self.n // 4) for _ in range(2)]
             self.levels_c, self.num_sig_c, self.dist_c = ([c[i][k] for i in range(2)] for k in range(3))
+        # per-block QPs: qp_map = the whole CuQpMaps.tu_qp (device int8 [3][h64 / 8 * w64 / 8]); lambda8_by_qp = device int32 [52 + 6 (depth - 8)],
+        # 256 x lambda of a CU at that luma quantiser QP (None = lambda8 for every block)
+        self.qp_map, self.lambda8_by_qp = None, None
 
     def run(self, cur: DevicePicture, recon_plane, recon_c=None, stream=None):
         """recon_plane (and recon_c = [Cb, Cr] with chroma): planes of cur's geometry the reconstruction is written into - and read from,
@@ -1401,7 +1484,7 @@ class IntraPicture:
                       dist=self.dist_c)
         hipabi.intra_picture(self.depth, self.w64, self.h64, self.level, self.qp, self.flags, self.lambda8, self.mode_bits, cur.t, cur.stride, cur.org,
                              recon_plane, self.mode, self.levels, self.num_sig, self.dist, chroma=ch, cost=self.cost,
-                             strong_intra_smoothing=self.strong, stream=stream)
+                             strong_intra_smoothing=self.strong, stream=stream, qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp)
 
     def checksum(self):
         import torch
@@ -1453,9 +1536,17 @@ class IFramePipeline:
             self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
             self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
 
+    def set_qp_maps(self, maps, lambda8_by_qp=None):
+        """Per-block QPs for the following run() calls (see FramePipeline.set_qp_maps); None = the picture-wide qp again.  lambda8_by_qp: device
+        int32 tensor [52 + 6 (depth - 8)] - 256 x lambda of a CU per luma quantiser QP - or None = the constructor's lambda8 for every block."""
+        _set_qp_maps(self, maps, self.ip, [])
+        self.ip.qp_map = None if maps is None else maps.tu_qp
+        self.ip.lambda8_by_qp = None if maps is None else lambda8_by_qp
+
     def run(self, cur: DevicePicture, mark=None):
         """Returns the luma plane of the coded picture; mark(name), if given, is called after every stage."""
         mark = mark or (lambda name: None)
+        _qp_maps_run_check(self)
         assert cur.t.shape == self.recon.shape and cur.t.dtype == self.recon.dtype
         self.ip.run(cur, self.recon, self.recon_c)
         mark("intra")
@@ -1463,7 +1554,7 @@ class IFramePipeline:
             self.db.run_intra(self.recon, cur, self.ip.num_sig)
             if self.chroma:
                 hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                      self.db.bs_ver, self.db.bs_hor, self.db.qp)
+                                      self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
             mark("deblock")
         final, final_c = self.recon, self.recon_c
         if self.sao_rdo is not None:

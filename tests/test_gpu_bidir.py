@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import bidir_expect as BE
+import bipred_cases as BC
 
 pytestmark = pytest.mark.gpu
 
@@ -133,3 +134,16 @@ def test_bidir_decide_3840x2160(depth):
     for use_planes in (False, True):
         got = _run_kernel(depth, level, cur, refs, stride, org, w64, h64, recs, cq, qoff, BE.DIR_COST, use_planes)
         _assert_equal(got, e, level, nctu, f"4K depth {depth} planes {use_planes}")
+
+
+@pytest.mark.parametrize("case,level,use_planes", BC.BIDIR_CASES, ids=lambda v: v.id if isinstance(v, BC.BiCase) else str(v))
+def test_bidir_decide_on_clipping_content(case, level, use_planes):
+    """Two `edges` references and a current picture planted for every outcome (tests/bipred_cases.py): both clips of the kernel's own
+    interpolation, phase-plane reads at vectors up to 57 samples from the block, records with a zero cost key under non-zero vectors and
+    full-amplitude differences at 12 bits.  tests/test_bipred_cases_cpu.py asserts that every outcome occurs on at least 3 % of the blocks."""
+    c = BC.build_bi(*case.build)
+    e = BC.decided(case, level)
+    cq, qoff = F.qpel_cost_table(c.R)
+    got = _run_kernel(c.depth, level, c.cur, c.refs, c.stride, c.org, c.w64, c.h64, BC.refined_bi(case), cq, qoff, BE.DIR_COST, use_planes)
+    _assert_equal(got, e, level, c.nctu, f"{case.id} level {level} planes {use_planes}")
+    assert all(e["masks"][k].any() for k in BE.OUTCOMES)

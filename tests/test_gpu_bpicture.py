@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import bidir_expect as BE
+import bipred_cases as BC
 
 pytestmark = pytest.mark.gpu
 
@@ -29,12 +30,13 @@ def _b_step(w64, h64, depth, dev, rng, subme, level, qp, subpel_planes=False):
                             sign_hide=True, subpel_planes=subpel_planes, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_B), want_cost=True)
 
 
-def _check_b_step(depth, width, height, rng, subme, level, seed, subpel_planes, min_values):
+def _check_b_step(depth, width, height, rng, subme, level, seed, subpel_planes, min_values, clip=None):
     import torch
     B = importlib.import_module("bench")
     dev = torch.device("cuda:0")
     qp = 30 + 12 * (depth == 10)
-    clip = BE.occluded_clip(width, height, 3, depth, seed)
+    if clip is None:
+        clip = BE.occluded_clip(width, height, 3, depth, seed)
     cur, r0, r1 = (P.DevicePicture(clip[i][0], dev, clip[i][1], clip[i][2]) for i in (1, 0, 2))
     pipe = _b_step(cur.w64, cur.h64, depth, dev, rng, subme, level, qp, subpel_planes)
     marks = []
@@ -66,6 +68,16 @@ def test_b_step_3840x2160_with_the_bench_settings():
     """The B twin of test_whole_4k_frame_every_stage_equals_oracle_chain: one 3840x2160 8-bit B picture with the bench's settings (range 57,
     subme 3, 32x32 blocks, sub-pel candidates from phase planes) against the chain, all CTUs."""
     _check_b_step(8, 3840, 2160, 57, 3, 2, 265, True, 25_000_000)
+
+
+@pytest.mark.parametrize("case,level,subpel_planes", BC.B_STEP_CASES, ids=lambda v: v.id if isinstance(v, BC.BiCase) else str(v))
+def test_b_step_on_clipping_content(case, level, subpel_planes):
+    """The whole B step on the three Y / Cb / Cr pictures of a tests/bipred_cases.py input, 256x128 at the bench's range 57 and subme 3: the
+    device's own searches find the planted far vectors in two `edges` references, and every later stage works on predictions that clip."""
+    c = BC.build_bi(*case.build)
+    cpu_out = _check_b_step(c.depth, case.width, case.height, c.R, 3, level, case.seed, subpel_planes, 100_000, clip=c.yuv)
+    inner = cpu_out["recon"][F.MARGIN_Y:F.MARGIN_Y + c.h64, F.MARGIN_X:F.MARGIN_X + c.w64]
+    assert (inner == 0).any() and (inner == (1 << c.depth) - 1).any()
 
 
 @pytest.mark.parametrize("depth", [8, 10])

@@ -7,6 +7,7 @@ import sys
 import numpy as np
 import pytest
 
+import bipred_cases as BC
 import subpel_cases as SC
 
 pytestmark = pytest.mark.gpu
@@ -254,6 +255,101 @@ def test_inter_recon_chroma_bi_matches_oracle(depth, level, qp, w0, w1):
             n = 4 << level
             only0 = torch.from_numpy(np.repeat(dirs == 1, n * n)).to(dev)
             assert torch.equal(uni.levels[only0], st.levels[only0])
+
+
+def _bi_inputs(case, level, dev):
+    """A tests/bipred_cases.py input on the device: the three luma + chroma pictures, both lists' refined records, the decision's directions."""
+    import torch
+    c = BC.build_bi(*case.build)
+    r0, cur, r1 = (P.DevicePicture(y, dev, u, v) for (y, u, v) in c.yuv)
+    mvs = BC.refined_bi(case)
+    dirs = BC.dir_flags(case, level)
+    d_mv = [torch.from_numpy(m.reshape(-1).copy()).to(dev) for m in mvs]
+    return c, cur, r0, r1, mvs, dirs, d_mv, torch.from_numpy(dirs.copy()).to(dev)
+
+
+def _assert_stage(st, recon, dt, want, what=""):
+    erec, elev, ens, edist = want
+    assert np.array_equal(st.num_sig.cpu().numpy().view(np.uint32), ens), f"{what}numSig differs"
+    assert np.array_equal(st.levels.cpu().numpy(), elev), f"{what}levels differ"
+    grec = recon.cpu().numpy().view(dt).reshape(-1)
+    assert np.array_equal(grec, erec.reshape(-1)), f"{what}reconstruction differs at {np.count_nonzero(grec != erec.reshape(-1))} samples"
+    assert np.array_equal(st.dist.cpu().numpy().view(np.uint64), edist), f"{what}SSE differs"
+
+
+@pytest.mark.parametrize("case,level,qp,flags", BC.RECON_BI_CASES, ids=lambda v: v.id if isinstance(v, BC.BiCase) else str(v))
+def test_inter_recon_bi_clipping_content_matches_oracle(case, level, qp, flags):
+    """addAvg's clip and the 14-bit short predictions feeding it: two `edges` references (tests/bipred_cases.py) predicted with the oracle's
+    refined vectors of both lists, anywhere in a +-57 window, under the bidirectional decision's own directions.  tests/test_bipred_cases_cpu.py
+    asserts that the unclipped average leaves [0, max] at each end on at least 1 % of the samples (the one-list prediction on 5 %) and that the
+    oracle codes at least 30 % of the blocks and reconstructs to 0 and to max where the source is neither."""
+    import torch
+    dev = torch.device("cuda:0")
+    c, cur, r0, r1, mvs, dirs, d_mv, d_dir = _bi_inputs(case, level, dev)
+    st = S.InterReconBi(c.nctu, c.w64, c.h64, c.depth, level, qp, dev, intra_slice=flags)
+    recon = torch.zeros_like(cur.t)
+    st.run(cur, r0, r1, recon, d_mv[0], d_mv[1], dir_flags=d_dir)
+    torch.cuda.synchronize()
+    want = _oracle().inter_recon_bi(c.depth, c.cur.reshape(-1), c.stride, c.org, c.refs[0].reshape(-1), c.refs[1].reshape(-1), c.w64, c.h64, level, mvs[0], mvs[1], qp,
+                                    dir_flags=dirs, intra_slice=flags)
+    _assert_stage(st, recon, c.cur.dtype, want)
+    assert all((dirs == k).any() for k in (1, 2, 3))
+
+
+@pytest.mark.parametrize("case,level,qp,wname", BC.RECON_BI_WEIGHT_CASES, ids=lambda v: v.id if isinstance(v, BC.BiCase) else str(v))
+def test_inter_recon_bi_weights_on_clipping_content(case, level, qp, wname):
+    """The clips of addWeightBi and addWeightUni on the same inputs: weight tables with gain above 1 and negative offsets, wtPresent on both lists
+    or on one (tests/bipred_cases.WEIGHTS); at least 0.5 % of the samples of each weighted path leave [0, max] at each end before the clip."""
+    import torch
+    dev = torch.device("cuda:0")
+    w = BC.WEIGHTS[wname]
+    c, cur, r0, r1, mvs, dirs, d_mv, d_dir = _bi_inputs(case, level, dev)
+    st = S.InterReconBi(c.nctu, c.w64, c.h64, c.depth, level, qp, dev, intra_slice=2)
+    plain = S.InterReconBi(c.nctu, c.w64, c.h64, c.depth, level, qp, dev, intra_slice=2)
+    recon, recon_plain = torch.zeros_like(cur.t), torch.zeros_like(cur.t)
+    st.run(cur, r0, r1, recon, d_mv[0], d_mv[1], dir_flags=d_dir, weights=w)
+    plain.run(cur, r0, r1, recon_plain, d_mv[0], d_mv[1], dir_flags=d_dir)
+    torch.cuda.synchronize()
+    want = _oracle().inter_recon_bi(c.depth, c.cur.reshape(-1), c.stride, c.org, c.refs[0].reshape(-1), c.refs[1].reshape(-1), c.w64, c.h64, level, mvs[0], mvs[1], qp,
+                                    dir_flags=dirs, intra_slice=2, weights=w)
+    _assert_stage(st, recon, c.cur.dtype, want)
+    assert not torch.equal(st.levels, plain.levels), "the weights changed nothing"
+
+
+@pytest.mark.parametrize("case,level,qp,wname", BC.RECON_CHROMA_CASES, ids=lambda v: v.id if isinstance(v, BC.BiCase) else str(v))
+def test_inter_recon_chroma_bi_clipping_content_matches_oracle(case, level, qp, wname):
+    """Both chroma planes of the same inputs (4-tap filters at eighth-sample vectors up to 29.5 chroma samples long, every plane an `edges`
+    picture of its own), with and without the weight tables."""
+    import torch
+    dev = torch.device("cuda:0")
+    w = BC.WEIGHTS[wname] if wname else None
+    c, cur, r0, r1, mvs, dirs, d_mv, d_dir = _bi_inputs(case, level, dev)
+    assert (cur.stride_c, cur.org_c) == (c.stride_c, c.org_c)
+    for p in range(2):
+        st = S.InterReconChromaBi(c.nctu, c.w64, c.h64, c.depth, level, qp - p, dev, intra_slice=2)
+        recon = torch.zeros_like(cur.c[p])
+        st.run(cur.c[p], r0.c[p], r1.c[p], recon, cur.stride_c, cur.org_c, d_mv[0], d_mv[1], dir_flags=d_dir, weights=w)
+        torch.cuda.synchronize()
+        want = _oracle().inter_recon_chroma_bi(c.depth, c.cur_c[p].reshape(-1), c.refs_c[0][p].reshape(-1), c.refs_c[1][p].reshape(-1), c.stride_c, c.org_c,
+                                               c.w64, c.h64, level, mvs[0], mvs[1], qp - p, dir_flags=dirs, intra_slice=2, weights=w)
+        _assert_stage(st, recon, c.cur.dtype, want, f"plane {p}: ")
+
+
+@pytest.mark.parametrize("case,level,qp,flags", BC.RECON_CHROMA_UNI_CASES, ids=lambda v: v.id if isinstance(v, BC.BiCase) else str(v))
+def test_inter_recon_chroma_clipping_content_matches_oracle(case, level, qp, flags):
+    """The uni-directional chroma stage on list 0 of the same inputs: the 4-tap prediction leaves [0, max] at each end on at least 5 % of the
+    samples before its clip."""
+    import torch
+    dev = torch.device("cuda:0")
+    c, cur, r0, r1, mvs, dirs, d_mv, d_dir = _bi_inputs(case, level, dev)
+    for p in range(2):
+        st = S.InterReconChroma(c.nctu, c.w64, c.h64, c.depth, level, qp - p, dev, intra_slice=flags)
+        recon = torch.zeros_like(cur.c[p])
+        st.run(cur.c[p], r0.c[p], recon, cur.stride_c, cur.org_c, d_mv[0])
+        torch.cuda.synchronize()
+        want = _oracle().inter_recon_chroma(c.depth, c.cur_c[p].reshape(-1), c.refs_c[0][p].reshape(-1), c.stride_c, c.org_c, c.w64, c.h64, level, mvs[0], qp - p,
+                                            intra_slice=flags)
+        _assert_stage(st, recon, c.cur.dtype, want, f"plane {p}: ")
 
 
 def test_inter_recon_bi_rejects_bad_weights():

@@ -193,6 +193,25 @@ typedef struct x265hip_subpel_params
 } x265hip_subpel_params;
 int x265hip_subpel_refine(const x265hip_subpel_params* p, void* stream);
 
+/* The same refinement with the chroma SATD the reference adds at subme >= 3 (MotionEstimate::setSourcePU, motion.cpp:212: bChromaSATD =
+ * subpelRefine > 2 && chromaSatd && csp != I400 && bChroma; subpelCompare :1601-1661).  4:2:0 only.  Every comparison of a PU of size N
+ * at luma (px, py) with quarter-sample vector q costs what x265hip_subpel_refine charges plus satd(Cb) + satd(Cr)
+ * (chroma[I420].pu[part].satd) between the (N/2) x (N/2) source block at (px/2, py/2) and the reference block at the same position
+ * displaced by (q.x >> 3, q.y >> 3) (arithmetic shifts), interpolated at eighth-sample phase (q.x & 7, q.y & 7): nothing for (0,0),
+ * filter_hpp / filter_vpp for one axis, filter_hps with row extension + filter_vsp for both (ipfilter.cpp, 4 taps).  The zero-residual
+ * shortcut on the integer stage's key, the vector cost, the strict '<', the direction order, the workload rows and the record layout
+ * are those of x265hip_subpel_refine; phase_planes stays legal and serves luma only - chroma is interpolated in the kernel.
+ *   c == NULL  : exactly x265hip_subpel_refine (same kernels, same launches).
+ *   subme <= 2 : c is ignored and the result is the luma-only one, as bChromaSATD is off there (a non-NULL c is still validated).
+ * The planes of c point at sample (0,0), strides in samples; NULL planes and strides <= 0 are X265HIP_EINVAL, checked before the device
+ * is asked for.  The reference's chroma planes need >= range / 2 + 8 valid samples of margin (half the luma drift, the 4-tap apron, whole dwords read). */
+typedef struct x265hip_subpel_chroma
+{
+    const void* fenc_cb; const void* fenc_cr; intptr_t fenc_stride_c;
+    const void* fref_cb; const void* fref_cr; intptr_t fref_stride_c;
+} x265hip_subpel_chroma;
+int x265hip_subpel_refine_chroma(const x265hip_subpel_params* p, const x265hip_subpel_chroma* c, void* stream);
+
 /* Fused inter prediction + residual coding round trip of every NxN block (N = 8 << level, level 0..2), the
  * caller sequence of SURVEY section 8(f) item 2: Predict::predInterLumaPixel (predict.cpp:245-265),
  * calcresidual, Quant::transformNxN without RDOQ (quant.cpp:397-480, flat scaling lists; sign-bit hiding optional),
@@ -337,6 +356,27 @@ typedef struct x265hip_bidir_params
     int32_t* cost_out;                               /* optional [ctu][blocks][4] = { c0, c1, bidir at the refined vectors, cz or -1 if not tried } */
 } x265hip_bidir_params;
 int x265hip_bidir_decide(const x265hip_bidir_params* p, void* stream);
+
+/* The decision with chroma, for records that come from x265hip_subpel_refine_chroma (the reference at subme >= 3 with chroma SATD:
+ * Search::predInterSearch measures the motion-compensated prediction of all three planes, search.cpp:2487-2497, 2533-2543).  4:2:0 only.
+ *   c0, c1 : the records' costs + dir_cost, as in x265hip_bidir_decide.
+ *   cbi    : satd(Y) + satd_c(Cb) + satd_c(Cr) + mvc(mv0) + mvc(mv1) + dir_cost[2], the three predictions being those of
+ *            Predict::motionCompensation's bi arm without weights: predInterLumaShort / predInterChromaShort of both lists combined by
+ *            addAvg - the 14-bit intermediates x265hip_inter_recon_bi / x265hip_inter_recon_chroma_bi form with dir = 3, NOT pixelavg_pp
+ *            of rounded pixels: the luma term differs from x265hip_bidir_decide's too.
+ *   zero candidate : the same motion compensation at zero vectors on all three planes (for luma that equals (a + b + 1) >> 1).
+ * Selection, tie rules, outputs and cost_out are those of x265hip_bidir_decide.
+ *   c == NULL : exactly x265hip_bidir_decide (same kernels, same launches).
+ * The planes of c point at sample (0,0), strides in samples, margins as x265hip_subpel_chroma wants them.  NULL planes, strides <= 0 and
+ * phase_planes0 / phase_planes1 != NULL together with c (the luma phase planes hold rounded pixels and cannot serve this flavour) are
+ * X265HIP_EINVAL, checked before the device is asked for. */
+typedef struct x265hip_bidir_chroma
+{
+    const void* fenc_cb;  const void* fenc_cr;  intptr_t fenc_stride_c;
+    const void* fref0_cb; const void* fref0_cr;
+    const void* fref1_cb; const void* fref1_cr; intptr_t fref_stride_c;
+} x265hip_bidir_chroma;
+int x265hip_bidir_decide_chroma(const x265hip_bidir_params* p, const x265hip_bidir_chroma* c, void* stream);
 /* The TU-stage entries, as x265hip_tu_launch_grid names them. */
 enum x265hip_tu_entry
 {

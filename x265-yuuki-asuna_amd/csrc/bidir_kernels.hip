@@ -44,6 +44,27 @@ template <int LEVEL> struct BdGeom
     static constexpr int LBASE = LEVEL == 0 ? 0 : (LEVEL == 1 ? 64 : 80);
 };
 
+// The decision of one block from the summed SATDs of the bidirectional candidate (sBi) and of the zero candidate (sZ): one lane per block.
+__device__ __forceinline__ void bd_decide(const BidirArgs& a, size_t blk, size_t rec, int2 r0, int2 r1, int sBi, int sZ)
+{
+    auto mvc = [&](const int w) { return (int)a.costQ[a.qoff + (int16_t)(w & 0xffff)] + (int)a.costQ[a.qoff + (w >> 16)]; };
+    const int c0 = r0.x + a.dirCost[0], c1 = r1.x + a.dirCost[1];
+    const int cRef = sBi + mvc(r0.y) + mvc(r1.y) + a.dirCost[2];
+    int cbi = cRef, cz = -1, m0 = r0.y, m1 = r1.y;
+    if (m0 != 0 || m1 != 0)                                      // bTryZero
+    {
+        cz = sZ + 4 * (int)a.costQ[a.qoff] + a.dirCost[2];
+        if (cz < cbi) { cbi = cz; m0 = 0; m1 = 0; }
+    }
+    const int dir = (cbi < c0 && cbi < c1) ? 3 : (c0 <= c1 ? 1 : 2);
+    a.dir[blk] = (uint8_t)dir;
+    if (a.ref[0]) a.ref[0][blk] = (int8_t)((dir & 1) ? a.refId[0] : -1);
+    if (a.ref[1]) a.ref[1][blk] = (int8_t)((dir & 2) ? a.refId[1] : -1);
+    a.mvOut[0][rec] = dir == 3 ? make_int2(cbi, m0) : make_int2(c0, dir == 1 ? m0 : 0);
+    a.mvOut[1][rec] = dir == 3 ? make_int2(cbi, m1) : make_int2(c1, dir == 2 ? m1 : 0);
+    if (a.costOut) { int* co = a.costOut + blk * 4; co[0] = c0; co[1] = c1; co[2] = cRef; co[3] = cz; }
+}
+
 template <typename Px, int LEVEL, bool PL>
 __global__ void __launch_bounds__(256) bidir_decide_kernel(BidirArgs a)
 {
@@ -101,25 +122,97 @@ __global__ void __launch_bounds__(256) bidir_decide_kernel(BidirArgs a)
     if (G::NTILES >= 16) { sBi = row_sum_of_quads(sBi); sZ = row_sum_of_quads(sZ); }
     if (G::NTILES >= 64) { sBi = wave_sum_of_rows(sBi); sZ = wave_sum_of_rows(sZ); }
 
-    if (tile == 0)
+    if (tile == 0) bd_decide(a, (size_t)ctu * G::NPU + pu, rec, r0, r1, sBi, sZ);
+}
+
+// The chroma flavour (x265hip_bidir_decide_chroma): the records come from the chroma refinement, and the bidirectional candidate is
+// measured on the motion-compensated prediction of all three planes - Predict::motionCompensation's bi arm without weights:
+// predInterLumaShort / predInterChromaShort of both lists (14-bit intermediates) combined by addAvg (search.cpp:2487-2497, 2533-2543) -
+// with satd(Y) + satd_c(Cb) + satd_c(Cr).  Same mapping; a block's NTILES / 4 chroma tiles per plane go to its lanes [0, NTILES / 4)
+// (Cb) and [NTILES / 4, NTILES / 2) (Cr) after the luma tile, and the partial SATDs are added in front of the same DPP sums.
+struct BidirChromaArgs
+{
+    const uint8_t* fencCb; const uint8_t* fencCr; long fencStrideCB;
+    const uint8_t* fref0Cb; const uint8_t* fref0Cr;
+    const uint8_t* fref1Cb; const uint8_t* fref1Cr; long frefStrideCB;
+};
+
+// SATD of one 4x4 tile against addAvg of both lists' intermediates, at the records' vectors (sBi) and at zero vectors (sZ).  z0 / z1 =
+// byte address of the tile's sample (0,0) in each list's plane; CHROMA: eighth-sample vectors and the 4-tap filters.
+template <int BPP, bool CHROMA>
+__device__ __forceinline__ void bd_tile_costs(const uint8_t* fe, long fencStrideB, const uint8_t* z0, const uint8_t* z1, long frefStrideB,
+                                              int w0, int w1, int depth, int& sBi, int& sZ)
+{
+    constexpr int SH = CHROMA ? 3 : 2, MASK = CHROMA ? 7 : 3;
+    int src[4][4];
+    tile_predict<BPP>(fe, fencStrideB, 0, 0, depth, src);
+    int sumP[4][4] = {}, sumZ[4][4] = {};
+#pragma unroll 1
+    for (int l = 0; l < 2; l++)
     {
-        auto mvc = [&](const int w) { return (int)a.costQ[a.qoff + (int16_t)(w & 0xffff)] + (int)a.costQ[a.qoff + (w >> 16)]; };
-        const int c0 = r0.x + a.dirCost[0], c1 = r1.x + a.dirCost[1];
-        const int cRef = sBi + mvc(r0.y) + mvc(r1.y) + a.dirCost[2];
-        int cbi = cRef, cz = -1, m0 = r0.y, m1 = r1.y;
-        if (m0 != 0 || m1 != 0)                                      // bTryZero
-        {
-            cz = sZ + 4 * (int)a.costQ[a.qoff] + a.dirCost[2];
-            if (cz < cbi) { cbi = cz; m0 = 0; m1 = 0; }
-        }
-        const int dir = (cbi < c0 && cbi < c1) ? 3 : (c0 <= c1 ? 1 : 2);
-        const size_t blk = (size_t)ctu * G::NPU + pu;
-        a.dir[blk] = (uint8_t)dir;
-        if (a.ref[0]) a.ref[0][blk] = (int8_t)((dir & 1) ? a.refId[0] : -1);
-        if (a.ref[1]) a.ref[1][blk] = (int8_t)((dir & 2) ? a.refId[1] : -1);
-        a.mvOut[0][rec] = dir == 3 ? make_int2(cbi, m0) : make_int2(c0, dir == 1 ? m0 : 0);
-        a.mvOut[1][rec] = dir == 3 ? make_int2(cbi, m1) : make_int2(c1, dir == 2 ? m1 : 0);
-        if (a.costOut) { int* co = a.costOut + blk * 4; co[0] = c0; co[1] = c1; co[2] = cRef; co[3] = cz; }
+        const int w = l ? w1 : w0;
+        const int qx = (int16_t)(w & 0xffff), qy = w >> 16;
+        const uint8_t* z = l ? z1 : z0;
+        const uint8_t* org = z + (long)(qy >> SH) * frefStrideB + (long)(qx >> SH) * BPP;
+        int d[4][4], e[4][4];
+        if (CHROMA) tile_predict_chroma<BPP, true>(org, frefStrideB, qx & MASK, qy & MASK, depth, d);
+        else tile_predict<BPP, true>(org, frefStrideB, qx & MASK, qy & MASK, depth, d);
+        tile_predict<BPP, true>(z, frefStrideB, 0, 0, depth, e);
+#pragma unroll
+        for (int y = 0; y < 4; y++)
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+            {
+                sumP[y][x] = l ? src[y][x] - tile_add_avg(sumP[y][x], d[y][x], depth) : d[y][x];
+                sumZ[y][x] = l ? src[y][x] - tile_add_avg(sumZ[y][x], e[y][x], depth) : e[y][x];
+            }
+    }
+    sBi += tile_satd4(sumP); sZ += tile_satd4(sumZ);
+}
+
+template <typename Px, int LEVEL>
+__global__ void __launch_bounds__(256) bidir_decide_chroma_kernel(BidirArgs a, BidirChromaArgs c)
+{
+    typedef BdGeom<LEVEL> G;
+    constexpr int BPP = sizeof(Px), N = G::N, CTILES = G::NTILES / 4;
+    const int ctu = xcd_swizzle(blockIdx.x, gridDim.x);
+    const int cx = (ctu % a.ctusW) * 64, cy = (ctu / a.ctusW) * 64;
+    const int tid = threadIdx.x;
+    const int pu = tid >> G::TSHIFT, tile = tid & (G::NTILES - 1);
+    const int bxz = (pu & 1) | ((pu >> 1) & 2) | ((pu >> 2) & 4), byz = ((pu >> 1) & 1) | ((pu >> 2) & 2) | ((pu >> 3) & 4);
+    const int ty = tile / G::TPR, tx = tile % G::TPR;
+    const int px = cx + bxz * N + tx * 4, py = cy + byz * N + ty * 4;
+
+    const size_t rec = (size_t)ctu * 85 + G::LBASE + pu;
+    const int2 r0 = a.mv[0][rec], r1 = a.mv[1][rec];
+    const long tileOff = (long)py * a.frefStrideB + (long)px * BPP;
+
+    int sBi = 0, sZ = 0;
+    bd_tile_costs<BPP, false>(a.fenc + (long)py * a.fencStrideB + (long)px * BPP, a.fencStrideB, a.fref[0] + tileOff, a.fref[1] + tileOff, a.frefStrideB,
+                              r0.y, r1.y, a.depth, sBi, sZ);
+    if (tile < 2 * CTILES)
+    {
+        const int cpl = tile >= CTILES, ct = tile - cpl * CTILES;
+        const int ccx = cx / 2 + bxz * (N / 2) + (ct % (G::TPR / 2)) * 4, ccy = cy / 2 + byz * (N / 2) + (ct / (G::TPR / 2)) * 4;
+        const long cOff = (long)ccy * c.frefStrideCB + (long)ccx * BPP;
+        bd_tile_costs<BPP, true>((cpl ? c.fencCr : c.fencCb) + (long)ccy * c.fencStrideCB + (long)ccx * BPP, c.fencStrideCB,
+                                 (cpl ? c.fref0Cr : c.fref0Cb) + cOff, (cpl ? c.fref1Cr : c.fref1Cb) + cOff, c.frefStrideCB, r0.y, r1.y, a.depth, sBi, sZ);
+    }
+    sBi = quad_sum(sBi); sZ = quad_sum(sZ);
+    if (G::NTILES >= 16) { sBi = row_sum_of_quads(sBi); sZ = row_sum_of_quads(sZ); }
+    if (G::NTILES >= 64) { sBi = wave_sum_of_rows(sBi); sZ = wave_sum_of_rows(sZ); }
+
+    if (tile == 0) bd_decide(a, (size_t)ctu * G::NPU + pu, rec, r0, r1, sBi, sZ);
+}
+
+template <typename Px>
+static void bidir_chroma_launch(int level, int nctu, hipStream_t s, const BidirArgs& a, const BidirChromaArgs& c)
+{
+    switch (level)
+    {
+    case 0: hipLaunchKernelGGL((bidir_decide_chroma_kernel<Px, 0>), dim3(nctu), dim3(256), 0, s, a, c); break;
+    case 1: hipLaunchKernelGGL((bidir_decide_chroma_kernel<Px, 1>), dim3(nctu), dim3(256), 0, s, a, c); break;
+    default: hipLaunchKernelGGL((bidir_decide_chroma_kernel<Px, 2>), dim3(nctu), dim3(256), 0, s, a, c); break;
     }
 }
 
@@ -140,6 +233,11 @@ using namespace x265hip;
 
 extern "C" int x265hip_bidir_decide(const x265hip_bidir_params* p, void* stream)
 {
+    return x265hip_bidir_decide_chroma(p, nullptr, stream);
+}
+
+extern "C" int x265hip_bidir_decide_chroma(const x265hip_bidir_params* p, const x265hip_bidir_chroma* c, void* stream)
+{
     // argument checks first: they need no device
     if (!p || !p->fenc || !p->fref0 || !p->fref1 || !p->mv0 || !p->mv1 || !p->cost_q || !p->dir || !p->mv0_out || !p->mv1_out)
     { set_error("bidir_decide: NULL operand"); return X265HIP_EINVAL; }
@@ -159,6 +257,13 @@ extern "C" int x265hip_bidir_decide(const x265hip_bidir_params* p, void* stream)
     const bool planes = p->phase_planes0 || p->phase_planes1;
     if (planes && (!p->phase_planes0 || !p->phase_planes1 || p->phase_plane_samples <= 0))
     { set_error("bidir_decide: phase planes of both lists and phase_plane_samples are needed together"); return X265HIP_EINVAL; }
+    if (c)
+    {
+        if (!c->fenc_cb || !c->fenc_cr || !c->fref0_cb || !c->fref0_cr || !c->fref1_cb || !c->fref1_cr)
+        { set_error("bidir_decide_chroma: NULL chroma plane"); return X265HIP_EINVAL; }
+        if (c->fenc_stride_c <= 0 || c->fref_stride_c <= 0) { set_error("bidir_decide_chroma: chroma strides must be positive"); return X265HIP_EINVAL; }
+        if (planes) { set_error("bidir_decide_chroma: the luma phase planes hold rounded pixels and cannot serve the chroma flavour"); return X265HIP_EINVAL; }
+    }
     int rc = ensure_device();
     if (rc) return rc;
 
@@ -177,7 +282,15 @@ extern "C" int x265hip_bidir_decide(const x265hip_bidir_params* p, void* stream)
     a.mvOut[0] = (int2*)p->mv0_out; a.mvOut[1] = (int2*)p->mv1_out;
     a.costOut = p->cost_out;
     hipStream_t s = (hipStream_t)stream;
-    if (planes) { if (bpp == 1) bidir_launch<uint8_t, true>(p->level, nctu, s, a); else bidir_launch<uint16_t, true>(p->level, nctu, s, a); }
+    if (c)
+    {
+        BidirChromaArgs ca;
+        ca.fencCb = (const uint8_t*)c->fenc_cb; ca.fencCr = (const uint8_t*)c->fenc_cr; ca.fencStrideCB = (long)c->fenc_stride_c * bpp;
+        ca.fref0Cb = (const uint8_t*)c->fref0_cb; ca.fref0Cr = (const uint8_t*)c->fref0_cr;
+        ca.fref1Cb = (const uint8_t*)c->fref1_cb; ca.fref1Cr = (const uint8_t*)c->fref1_cr; ca.frefStrideCB = (long)c->fref_stride_c * bpp;
+        if (bpp == 1) bidir_chroma_launch<uint8_t>(p->level, nctu, s, a, ca); else bidir_chroma_launch<uint16_t>(p->level, nctu, s, a, ca);
+    }
+    else if (planes) { if (bpp == 1) bidir_launch<uint8_t, true>(p->level, nctu, s, a); else bidir_launch<uint16_t, true>(p->level, nctu, s, a); }
     else { if (bpp == 1) bidir_launch<uint8_t, false>(p->level, nctu, s, a); else bidir_launch<uint16_t, false>(p->level, nctu, s, a); }
     X265HIP_TRY(hipGetLastError());
     return 0;

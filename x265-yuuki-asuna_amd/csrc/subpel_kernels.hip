@@ -15,6 +15,7 @@
 // serial decision loop of the reference then runs in one thread per PU on the reduced costs, so no
 // host round trip sits between the candidates - this is SURVEY section 8(f) item 1 for the sub-pel part.
 #include "common.h"
+#include "tile_interp.h"
 
 namespace x265hip {
 
@@ -28,6 +29,14 @@ struct SubpelArgs
     int hpelIters, hpelDirs, qpelIters, qpelDirs, hpelSatd;
     int2* out;                       // {cost, qx | qy << 16} per PU, [ctu][85]
     const uint8_t* planes; long planeBytes;      // phase planes of fref (x265hip_phase_planes), sample (0,0) of phase 1; NULL = interpolate
+};
+
+// The chroma operands of the chroma flavour (x265hip_subpel_refine_chroma): 4:2:0 Cb / Cr planes of the source and the reference picture,
+// sample (0,0) each.  The luma-only kernels take an empty one and never look at it.
+struct SubpelChromaArgs
+{
+    const uint8_t* fencC[2]; long fencStrideCB;
+    const uint8_t* frefC[2]; long frefStrideCB;
 };
 
 __constant__ int16_t kSpLumaTaps[4][8] = {
@@ -67,8 +76,12 @@ template <typename Px, int LEVEL> struct SpGeom
 // PL: the candidates' samples are READ from the reference picture's phase planes (x265hip_phase_planes: the same luma_hpp / luma_vpp /
 // luma_hvpp samples, computed once per picture) instead of being interpolated per candidate tile: no LDS patches, four dword loads
 // per candidate tile.
-template <typename Px, int LEVEL, bool PL>
-__device__ __forceinline__ void subpel_level(const SubpelArgs& a, uint8_t* smemRaw, SpShared& sh)
+// CH: every SATD comparison adds the SATD of the PU's Cb and Cr blocks (subpelCompare with bChromaSATD, motion.cpp:1601-1661): the PU's
+// NTILES / 4 chroma tiles per plane go to its lanes [0, NTILES / 4) (Cb) and [NTILES / 4, NTILES / 2) (Cr), source tile in registers, the
+// reference tile interpolated from global memory with the 4-tap filters at phase (q & 7) (tile_predict_chroma); the tile's SATD joins the
+// lane's luma partial in front of the reduction.
+template <typename Px, int LEVEL, bool PL, bool CH = false>
+__device__ __forceinline__ void subpel_level(const SubpelArgs& a, uint8_t* smemRaw, SpShared& sh, const SubpelChromaArgs& ca = SubpelChromaArgs())
 {
     typedef SpGeom<Px, LEVEL> G;
     constexpr int BPP = G::BPP, N = G::N, NPU = G::NPU, PW = G::PW, PITCH = G::PITCH;
@@ -120,6 +133,25 @@ __device__ __forceinline__ void subpel_level(const SubpelArgs& a, uint8_t* smemR
     {
         srcP[y] = BPP == 1 ? pk(src[y][0], src[y][2]) : pk(src[y][0], src[y][1]);
         srcQ[y] = BPP == 1 ? pk(src[y][1], src[y][3]) : pk(src[y][2], src[y][3]);
+    }
+    // CH: the lane's chroma tile - plane, source rows as packed pairs, byte offset of its sample (0,0) in the reference plane
+    constexpr int CTILES = G::NTILES / 4;
+    const bool chLane = CH && tile < 2 * CTILES;
+    sp_v2s csrcP[4], csrcQ[4];
+    const uint8_t* crefTile = nullptr;
+    if (CH && chLane)
+    {
+        const int cpl = tile >= CTILES, ct = tile - cpl * CTILES, cty = ct / (G::TPR / 2), ctx = ct % (G::TPR / 2);
+        const int ccx = cx / 2 + bxz * (N / 2) + ctx * 4, ccy = cy / 2 + byz * (N / 2) + cty * 4;
+        const uint8_t* fe = ca.fencC[cpl] + (long)ccy * ca.fencStrideCB + (long)ccx * BPP;
+        crefTile = ca.frefC[cpl] + (long)ccy * ca.frefStrideCB + (long)ccx * BPP;
+#pragma unroll
+        for (int y = 0; y < 4; y++)
+        {
+            const uint8_t* rp = fe + y * ca.fencStrideCB;
+            if (BPP == 1) { const uint32_t w = ld_u32(rp); csrcP[y] = __builtin_bit_cast(sp_v2s, w & 0x00ff00ffu); csrcQ[y] = __builtin_bit_cast(sp_v2s, (w >> 8) & 0x00ff00ffu); }
+            else { csrcP[y] = __builtin_bit_cast(sp_v2s, ld_u32(rp)); csrcQ[y] = __builtin_bit_cast(sp_v2s, ld_u32(rp + 4)); }
+        }
     }
     __syncthreads();
     if (!PL)
@@ -321,6 +353,30 @@ __device__ __forceinline__ void subpel_level(const SubpelArgs& a, uint8_t* smemR
         return acc;
     };
 
+    // CH: SATD of the lane's chroma tile at quarter-sample luma vector (qx, qy) = eighth-sample chroma vector: displacement q >> 3, phase q & 7
+    auto chroma_cost = [&](const int qx, const int qy) -> int
+    {
+        int d[4][4];
+        tile_predict_chroma<BPP>(crefTile + (long)(qy >> 3) * ca.frefStrideCB + (long)(qx >> 3) * BPP, ca.frefStrideCB, qx & 7, qy & 7, a.depth, d);
+        sp_v2s dP[4], dQ[4];
+#pragma unroll
+        for (int y = 0; y < 4; y++)
+        {
+            dP[y] = csrcP[y] - (BPP == 1 ? pk(d[y][0], d[y][2]) : pk(d[y][0], d[y][1]));
+            dQ[y] = csrcQ[y] - (BPP == 1 ? pk(d[y][1], d[y][3]) : pk(d[y][2], d[y][3]));
+        }
+        auto pabs = [](const sp_v2s v) -> sp_v2s { return __builtin_elementwise_max(v, (sp_v2s)(-v)); };
+        auto lo_max_hi = [](const sp_v2s v) -> int { const uint32_t u = __builtin_bit_cast(uint32_t, v); const uint32_t l = u & 0xffffu, h = u >> 16; return (int)(l > h ? l : h); };
+        const sp_v2s a0 = dP[0] + dP[1], b0 = dP[0] - dP[1], c0 = dP[2] + dP[3], e0 = dP[2] - dP[3];
+        const sp_v2s a1 = dQ[0] + dQ[1], b1 = dQ[0] - dQ[1], c1 = dQ[2] + dQ[3], e1 = dQ[2] - dQ[3];
+        const sp_v2s pv[4] = { a0 + c0, b0 + e0, a0 - c0, b0 - e0 }, qv[4] = { a1 + c1, b1 + e1, a1 - c1, b1 - e1 };
+        int acc = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            acc += lo_max_hi(pabs(pv[k] + qv[k])) + lo_max_hi(pabs(pv[k] - qv[k]));
+        return acc;
+    };
+
     auto mvcost = [&](const int qx, const int qy) { return (int)a.costQ[qx + a.qoff] + (int)a.costQ[qy + a.qoff]; };
 
     // PU state: 0 = zero residual at the integer mv, refinement skipped; 1 = searching; 2 = the current phase
@@ -349,6 +405,7 @@ __device__ __forceinline__ void subpel_level(const SubpelArgs& a, uint8_t* smemR
             for (int c = first; c <= last; c++)
             {
                 int v = on ? tile_cost(qx0 + kSpSquare1[c][0] * step, qy0 + kSpSquare1[c][1] * step, useSatd) : 0;
+                if (CH) { if (on && chLane) v += chroma_cost(qx0 + kSpSquare1[c][0] * step, qy0 + kSpSquare1[c][1] * step); }
                 // sum over the PU's NTILES consecutive threads (all lanes take part)
                 v = quad_sum(v);
                 if (G::NTILES >= 16) v = row_sum_of_quads(v);
@@ -402,18 +459,45 @@ __global__ void __launch_bounds__(256) subpel_refine_kernel(SubpelArgs a)
     }
 }
 
+// The chroma flavour: the same search with CH = true, launched only where every comparison is a SATD (subme >= 3).
+template <typename Px, bool PL>
+__global__ void __launch_bounds__(256) subpel_refine_chroma_kernel(SubpelArgs a, SubpelChromaArgs ca)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smemRaw[];
+    __shared__ SpShared sh;
+    switch (blockIdx.y)
+    {
+    case 0: subpel_level<Px, 0, PL, true>(a, smemRaw, sh, ca); break;
+    case 1: subpel_level<Px, 1, PL, true>(a, smemRaw, sh, ca); break;
+    case 2: subpel_level<Px, 2, PL, true>(a, smemRaw, sh, ca); break;
+    default: subpel_level<Px, 3, PL, true>(a, smemRaw, sh, ca); break;
+    }
+}
+
 } // namespace x265hip
 
 using namespace x265hip;
 
 extern "C" int x265hip_subpel_refine(const x265hip_subpel_params* p, void* stream)
 {
-    int rc = ensure_device();
-    if (rc) return rc;
+    return x265hip_subpel_refine_chroma(p, nullptr, stream);
+}
+
+extern "C" int x265hip_subpel_refine_chroma(const x265hip_subpel_params* p, const x265hip_subpel_chroma* c, void* stream)
+{
+    // every argument check runs before the device is asked for
     if (!p || !p->fenc || !p->fref || !p->best_in || !p->cost_q || !p->out) { set_error("subpel_refine: NULL operand"); return X265HIP_EINVAL; }
     if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("subpel_refine: width/height must be multiples of 64"); return X265HIP_EINVAL; }
     if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("subpel_refine: depth %d", p->depth); return X265HIP_EINVAL; }
     if (p->subme < 0 || p->subme > 7) { set_error("subpel_refine: subme %d out of [0,7]", p->subme); return X265HIP_EINVAL; }
+    if (p->phase_planes && p->phase_plane_samples <= 0) { set_error("subpel_refine: phase_plane_samples"); return X265HIP_EINVAL; }
+    if (c)                               // validated at every subme, also where it is then ignored (subme <= 2)
+    {
+        if (!c->fenc_cb || !c->fenc_cr || !c->fref_cb || !c->fref_cr) { set_error("subpel_refine_chroma: NULL chroma plane"); return X265HIP_EINVAL; }
+        if (c->fenc_stride_c <= 0 || c->fref_stride_c <= 0) { set_error("subpel_refine_chroma: chroma strides must be positive"); return X265HIP_EINVAL; }
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
     static const int wl[8][5] = { { 1, 4, 0, 4, 0 }, { 1, 4, 1, 4, 0 }, { 1, 4, 1, 4, 1 }, { 2, 4, 1, 4, 1 },
                                   { 2, 4, 2, 4, 1 }, { 1, 8, 1, 8, 1 }, { 2, 8, 1, 8, 1 }, { 2, 8, 2, 8, 1 } };   // motion.cpp:48-58
     const int bpp = p->depth == 8 ? 1 : 2;
@@ -425,7 +509,6 @@ extern "C" int x265hip_subpel_refine(const x265hip_subpel_params* p, void* strea
     a.hpelIters = wl[p->subme][0]; a.hpelDirs = wl[p->subme][1]; a.qpelIters = wl[p->subme][2]; a.qpelDirs = wl[p->subme][3]; a.hpelSatd = wl[p->subme][4];
     a.out = (int2*)p->out;
     a.planes = (const uint8_t*)p->phase_planes; a.planeBytes = (long)p->phase_plane_samples * bpp;
-    if (a.planes && p->phase_plane_samples <= 0) { set_error("subpel_refine: phase_plane_samples"); return X265HIP_EINVAL; }
     const int nctu = a.ctusW * (p->height / 64);
     hipStream_t s = (hipStream_t)stream;
     // one launch: grid.y = PU level; LDS sized for level 0 (64 patches of 23 rows), the largest
@@ -434,7 +517,26 @@ extern "C" int x265hip_subpel_refine(const x265hip_subpel_params* p, void* strea
                   && SpGeom<uint8_t, 0>::PSZ * 64 >= SpGeom<uint8_t, 3>::PSZ, "level 0 is the largest");
     static_assert(SpGeom<uint16_t, 0>::PSZ * 64 >= SpGeom<uint16_t, 1>::PSZ * 16 && SpGeom<uint16_t, 0>::PSZ * 64 >= SpGeom<uint16_t, 2>::PSZ * 4
                   && SpGeom<uint16_t, 0>::PSZ * 64 >= SpGeom<uint16_t, 3>::PSZ, "level 0 is the largest");
-    if (a.planes)
+    if (c && p->subme >= 3)              // subme <= 2: bChromaSATD is off (motion.cpp:212), the luma-only launch below
+    {
+        SubpelChromaArgs ca;
+        ca.fencC[0] = (const uint8_t*)c->fenc_cb; ca.fencC[1] = (const uint8_t*)c->fenc_cr; ca.fencStrideCB = (long)c->fenc_stride_c * bpp;
+        ca.frefC[0] = (const uint8_t*)c->fref_cb; ca.frefC[1] = (const uint8_t*)c->fref_cr; ca.frefStrideCB = (long)c->fref_stride_c * bpp;
+        if (a.planes)
+        {
+            if (p->depth == 8) hipLaunchKernelGGL((subpel_refine_chroma_kernel<uint8_t, true>), dim3(nctu, 4), dim3(256), 0, s, a, ca);
+            else hipLaunchKernelGGL((subpel_refine_chroma_kernel<uint16_t, true>), dim3(nctu, 4), dim3(256), 0, s, a, ca);
+        }
+        else if (p->depth == 8)
+            hipLaunchKernelGGL((subpel_refine_chroma_kernel<uint8_t, false>), dim3(nctu, 4), dim3(256), lds, s, a, ca);
+        else
+        {
+            static bool attrC = false;
+            if (!attrC) { X265HIP_TRY(hipFuncSetAttribute((const void*)subpel_refine_chroma_kernel<uint16_t, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attrC = true; }
+            hipLaunchKernelGGL((subpel_refine_chroma_kernel<uint16_t, false>), dim3(nctu, 4), dim3(256), lds, s, a, ca);
+        }
+    }
+    else if (a.planes)
     {
         if (p->depth == 8) hipLaunchKernelGGL((subpel_refine_kernel<uint8_t, true>), dim3(nctu, 4), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((subpel_refine_kernel<uint16_t, true>), dim3(nctu, 4), dim3(256), 0, s, a);

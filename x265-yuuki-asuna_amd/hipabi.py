@@ -51,6 +51,14 @@ class SubpelParams(ctypes.Structure):
     ]
 
 
+class SubpelChroma(ctypes.Structure):
+    """x265hip_subpel_chroma (include/x265hip.h)."""
+    _fields_ = [
+        ("fenc_cb", ctypes.c_void_p), ("fenc_cr", ctypes.c_void_p), ("fenc_stride_c", ctypes.c_ssize_t),
+        ("fref_cb", ctypes.c_void_p), ("fref_cr", ctypes.c_void_p), ("fref_stride_c", ctypes.c_ssize_t),
+    ]
+
+
 class BidirParams(ctypes.Structure):
     """x265hip_bidir_params (include/x265hip.h)."""
     _fields_ = [
@@ -64,6 +72,15 @@ class BidirParams(ctypes.Structure):
         ("phase_planes0", ctypes.c_void_p), ("phase_planes1", ctypes.c_void_p), ("phase_plane_samples", ctypes.c_ssize_t),
         ("dir", ctypes.c_void_p), ("ref0", ctypes.c_void_p), ("ref1", ctypes.c_void_p),
         ("mv0_out", ctypes.c_void_p), ("mv1_out", ctypes.c_void_p), ("cost_out", ctypes.c_void_p),
+    ]
+
+
+class BidirChroma(ctypes.Structure):
+    """x265hip_bidir_chroma (include/x265hip.h)."""
+    _fields_ = [
+        ("fenc_cb", ctypes.c_void_p), ("fenc_cr", ctypes.c_void_p), ("fenc_stride_c", ctypes.c_ssize_t),
+        ("fref0_cb", ctypes.c_void_p), ("fref0_cr", ctypes.c_void_p),
+        ("fref1_cb", ctypes.c_void_p), ("fref1_cr", ctypes.c_void_p), ("fref_stride_c", ctypes.c_ssize_t),
     ]
 
 
@@ -238,8 +255,10 @@ def me_fullsearch(depth, width, height, rng, fenc, fenc_stride, fref, fref_strid
 
 
 def subpel_refine(depth, width, height, rng, subme, fenc, fenc_stride, fref, fref_stride, best_in, cost_q, qoff, out,
-                  fenc_off=0, fref_off=0, stream=None, phase_planes=None):
-    """phase_planes: byte tensor with the 15 luma phase planes of the fref buffer (x265hip_phase_planes, same geometry as fref's tensor)."""
+                  fenc_off=0, fref_off=0, stream=None, phase_planes=None, chroma=None):
+    """phase_planes: byte tensor with the 15 luma phase planes of the fref buffer (x265hip_phase_planes, same geometry as fref's tensor).
+    chroma: None or a dict - fenc (Cb, Cr) and fref (Cb, Cr) tensors, fenc_stride / fref_stride in samples, fenc_org / fref_org = element
+    of sample (0,0); the call then goes to x265hip_subpel_refine_chroma (chroma SATD in every comparison at subme >= 3)."""
     es = 1 if depth == 8 else 2
     p = SubpelParams()
     p.depth, p.width, p.height, p.range, p.subme = depth, width, height, rng, subme
@@ -249,15 +268,26 @@ def subpel_refine(depth, width, height, rng, subme, fenc, fenc_stride, fref, fre
     if phase_planes is not None:
         p.phase_planes, p.phase_plane_samples = phase_planes.data_ptr() + fref_off * es, fref.numel() * fref.element_size() // es
     s = current_stream() if stream is None else stream
+    if chroma is not None:
+        c = SubpelChroma()
+        c.fenc_cb, c.fenc_cr = (t.data_ptr() + chroma["fenc_org"] * es for t in chroma["fenc"])
+        c.fref_cb, c.fref_cr = (t.data_ptr() + chroma["fref_org"] * es for t in chroma["fref"])
+        c.fenc_stride_c, c.fref_stride_c = chroma["fenc_stride"], chroma["fref_stride"]
+        f = lib().x265hip_subpel_refine_chroma
+        f.argtypes = [ctypes.POINTER(SubpelParams), ctypes.POINTER(SubpelChroma), ctypes.c_void_p]
+        check(f(ctypes.byref(p), ctypes.byref(c), s), "x265hip_subpel_refine_chroma")
+        return
     f = lib().x265hip_subpel_refine
     f.argtypes = [ctypes.POINTER(SubpelParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_subpel_refine")
 
 
 def bidir_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, mv0, mv1, cost_q, qoff, dir_cost, dir_out, mv0_out, mv1_out,
-                 ref0=None, ref1=None, cost_out=None, ref_ids=(0, 1), fenc_off=0, fref_off=0, phase_planes=None, stream=None):
+                 ref0=None, ref1=None, cost_out=None, ref_ids=(0, 1), fenc_off=0, fref_off=0, phase_planes=None, stream=None, chroma=None):
     """x265hip_bidir_decide: list 0 / list 1 / both for every block of a B picture from the two refinements' records.  fref0 / fref1:
-    tensors of one geometry (sample (0,0) at element fref_off); phase_planes: (list 0, list 1) byte tensors of x265hip_phase_planes."""
+    tensors of one geometry (sample (0,0) at element fref_off); phase_planes: (list 0, list 1) byte tensors of x265hip_phase_planes.
+    chroma: None or a dict - fenc, fref0, fref1 (Cb, Cr) tensors, fenc_stride / fref_stride in samples, fenc_org / fref_org = element of
+    sample (0,0); the call then goes to x265hip_bidir_decide_chroma (motion compensation of all three planes; no phase planes)."""
     es = 1 if depth == 8 else 2
     p = BidirParams()
     p.depth, p.width, p.height, p.level = depth, width, height, level
@@ -272,6 +302,16 @@ def bidir_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, f
     p.dir, p.ref0, p.ref1 = dir_out.data_ptr(), _p(ref0), _p(ref1)
     p.mv0_out, p.mv1_out, p.cost_out = mv0_out.data_ptr(), mv1_out.data_ptr(), _p(cost_out)
     s = current_stream() if stream is None else stream
+    if chroma is not None:
+        c = BidirChroma()
+        c.fenc_cb, c.fenc_cr = (t.data_ptr() + chroma["fenc_org"] * es for t in chroma["fenc"])
+        c.fref0_cb, c.fref0_cr = (t.data_ptr() + chroma["fref_org"] * es for t in chroma["fref0"])
+        c.fref1_cb, c.fref1_cr = (t.data_ptr() + chroma["fref_org"] * es for t in chroma["fref1"])
+        c.fenc_stride_c, c.fref_stride_c = chroma["fenc_stride"], chroma["fref_stride"]
+        f = lib().x265hip_bidir_decide_chroma
+        f.argtypes = [ctypes.POINTER(BidirParams), ctypes.POINTER(BidirChroma), ctypes.c_void_p]
+        check(f(ctypes.byref(p), ctypes.byref(c), s), "x265hip_bidir_decide_chroma")
+        return
     f = lib().x265hip_bidir_decide
     f.argtypes = [ctypes.POINTER(BidirParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_bidir_decide")

@@ -209,11 +209,14 @@ class SubpelRefine:
     (x265hip_subpel_refine; reference caller motion.cpp:1448-1664).  Output int32 [ctu*85][2] =
     {cost, qmvx | qmvy << 16}."""
 
-    def __init__(self, ms: MotionSearch, subme: int, device, lam=4.0, phase_planes=False):
+    def __init__(self, ms: MotionSearch, subme: int, device, lam=4.0, phase_planes=False, chroma_satd=False):
         """phase_planes=True: the reference picture's 15 fractional-phase planes are computed first (x265hip_phase_planes, one launch)
-        and every candidate is READ from them instead of being interpolated per candidate tile - same samples, same result."""
+        and every candidate is READ from them instead of being interpolated per candidate tile - same samples, same result.
+        chroma_satd=True: every comparison adds the SATD of the PU's Cb and Cr blocks, as the reference does at subme >= 3
+        (x265hip_subpel_refine_chroma; the pictures given to run() must carry chroma planes).  The phase planes serve luma either way."""
         import torch
         self.ms, self.subme = ms, subme
+        self.chroma_satd = bool(chroma_satd)
         self.use_planes, self.planes = bool(phase_planes), None
         cq, self.qoff = F.qpel_cost_table(ms.range, lam)
         self.cost_q_host = cq
@@ -245,8 +248,16 @@ class SubpelRefine:
         if not prepared:
             self.prepare(ref)
         planes = getattr(self, "parent", self).planes if self.use_planes else None
+        chroma = None
+        if self.chroma_satd:
+            if cur.c is None or ref.c is None:
+                raise ValueError("SubpelRefine(chroma_satd=True) needs pictures with chroma planes")
+            # the chroma tiles are read up to (4 R + 6) >> 3 samples away plus the 4-tap apron and whole dwords: inside the chroma margin?
+            if (4 * ms.range + 6 + 7) // 8 + 6 > min(F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_Y):
+                raise ValueError(f"SubpelRefine(chroma_satd=True): range {ms.range} reaches past the {F.CHROMA_MARGIN_Y}-row chroma margin")
+            chroma = dict(fenc=cur.c, fenc_stride=cur.stride_c, fenc_org=cur.org_c, fref=ref.c, fref_stride=ref.stride_c, fref_org=ref.org_c)
         hipabi.subpel_refine(ms.depth, ms.w64, ms.h64, ms.range, self.subme, cur.t, cur.stride, ref.t, ref.stride,
-                             ms.best, self.cost_q, self.qoff, self.out, fenc_off=cur.org, fref_off=ref.org, phase_planes=planes)
+                             ms.best, self.cost_q, self.qoff, self.out, fenc_off=cur.org, fref_off=ref.org, phase_planes=planes, chroma=chroma)
 
     def checksum(self):
         return {"subpel": int(self.out.to(dtype=__import__("torch").int64).sum().item())}

@@ -665,8 +665,10 @@ class FramePipeline:
 
     def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, want_surf=True, packed=False, lookahead=None,
                  search="full", deblock=False, sao=False, lookahead_cost_batch=0, chroma=False, sao_apply=False, sign_hide=False,
-                 subpel_planes=False, parallel_planes=False, split=1, sao_rdo=None):
-        """split (with parallel_planes): the picture goes through search -> sub-pel refinement -> reconstruction in `split` parts of whole
+                 subpel_planes=False, parallel_planes=False, split=1, sao_rdo=None, chroma_satd=False):
+        """chroma_satd (with chroma): the sub-pel refinement adds the SATD of Cb and Cr to every comparison, as the reference does at
+        subme >= 3 (x265hip_subpel_refine_chroma); every run mode honours it.  Exhaustive search only: x265hip_me_search is luma only.
+        split (with parallel_planes): the picture goes through search -> sub-pel refinement -> reconstruction in `split` parts of whole
         CTU rows; while the search of part k + 1 runs on the caller's stream, part k is refined and reconstructed on a side stream.  No
         CTU's result depends on another CTU before the loop filters, which still run on the whole picture: same outputs, and only the last
         part's refinement + reconstruction stay behind the search on the critical path.  Measured at 4K 8-bit (profiles/r02_split.txt):
@@ -693,7 +695,11 @@ class FramePipeline:
         self.prep_next_to_search = os.environ.get("X265HIP_PREP_OVERLAP", "0") == "1"
         self.ms = MotionSearch(w64, h64, rng, depth, device, want_surf=want_surf and search == "full", want_best=True, packed=packed)
         # subpel_planes: sub-pel candidates read from the reference picture's phase planes (one x265hip_phase_planes launch per frame)
-        self.sp = SubpelRefine(self.ms, subme, device, phase_planes=subpel_planes)
+        if chroma_satd and search != "full":
+            raise ValueError("FramePipeline: chroma_satd needs search='full' (the pattern-search step is luma only)")
+        if chroma_satd and not chroma:
+            raise ValueError("FramePipeline: chroma_satd needs chroma=True")
+        self.sp = SubpelRefine(self.ms, subme, device, phase_planes=subpel_planes, chroma_satd=chroma_satd)
         # search != "full": the pattern-search drivers replace the exhaustive search + sub-pel pair
         self.ps = None
         if search != "full":
@@ -1184,6 +1190,8 @@ class BandedFramePipeline:
         for opt in ("subpel_planes", "split"):
             if kw.get(opt):
                 raise ValueError(f"BandedFramePipeline: {opt} is a whole-picture option and cannot be forwarded to the band pipelines")
+        if kw.get("chroma_satd"):
+            raise ValueError("BandedFramePipeline: chroma_satd is not supported in band mode")
         # streams > 1: band b runs on HIP stream b % streams with its own set of stage buffers.  The bands of one picture do not depend on
         # each other (each is a slice), so the exhaustive search of band b + 1 - the one launch that fills the chip - overlaps the
         # reconstruction / deblocking / SAO launches of band b, which at band size are a few dozen workgroups each and bound by their own
@@ -1295,9 +1303,12 @@ class BidirDecide:
     takes), ref0 / ref1 int8 [ctu][blocks] (what Deblock.run_b takes), mv0_out / mv1_out int32 [ctu*85][2] (the level's entries) and,
     with want_cost, cost_out int32 [ctu][blocks][4]."""
 
-    def __init__(self, nctu, w64, h64, depth, level, device, dir_cost=(12, 12, 20), ref_ids=(0, 1), want_cost=False):
-        """dir_cost: lambda x the list-selection bits of a B slice's 2Nx2N (3, 3, 5; search.cpp:2649-2656) - (12, 12, 20) at the pipeline's lambda 4."""
+    def __init__(self, nctu, w64, h64, depth, level, device, dir_cost=(12, 12, 20), ref_ids=(0, 1), want_cost=False, chroma_satd=False):
+        """dir_cost: lambda x the list-selection bits of a B slice's 2Nx2N (3, 3, 5; search.cpp:2649-2656) - (12, 12, 20) at the pipeline's lambda 4.
+        chroma_satd: the records come from the chroma refinement and the bidirectional candidate is the motion compensation of all three
+        planes (x265hip_bidir_decide_chroma); the pictures must carry chroma planes and no phase planes are passed."""
         import torch
+        self.chroma_satd = bool(chroma_satd)
         self.nctu, self.w64, self.h64, self.depth, self.level = nctu, w64, h64, depth, level
         self.nblk = (64 // (8 << level)) ** 2
         self.dir_cost, self.ref_ids = tuple(int(c) for c in dir_cost), tuple(ref_ids)
@@ -1311,9 +1322,16 @@ class BidirDecide:
     def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mv0, mv1, cost_q, qoff, phase_planes=None, stream=None):
         """mv0 / mv1: the two SubpelRefine outputs; phase_planes: (list 0, list 1) planes of x265hip_phase_planes or None (interpolate)."""
         assert ref0.stride == ref1.stride and ref0.org == ref1.org
+        chroma = None
+        if self.chroma_satd:
+            if cur.c is None or ref0.c is None or ref1.c is None:
+                raise ValueError("BidirDecide(chroma_satd=True) needs pictures with chroma planes")
+            assert ref0.stride_c == ref1.stride_c and ref0.org_c == ref1.org_c
+            chroma = dict(fenc=cur.c, fenc_stride=cur.stride_c, fenc_org=cur.org_c, fref0=ref0.c, fref1=ref1.c, fref_stride=ref0.stride_c, fref_org=ref0.org_c)
+            phase_planes = None              # rounded pixels: they cannot serve the 14-bit motion compensation
         hipabi.bidir_decide(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, ref0.t, ref1.t, ref0.stride, mv0, mv1, cost_q, qoff,
                             self.dir_cost, self.dir, self.mv0_out, self.mv1_out, ref0=self.ref0, ref1=self.ref1, cost_out=self.cost_out,
-                            ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org, phase_planes=phase_planes, stream=stream)
+                            ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org, phase_planes=phase_planes, stream=stream, chroma=chroma)
 
     def checksum(self):
         import torch
@@ -1329,14 +1347,19 @@ class BFramePipeline:
     The constructor switches mean what they mean in FramePipeline.  A B picture is not referenced here; final_planes() are its output."""
 
     def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
-                 sign_hide=False, subpel_planes=False, sao_rdo=None, dir_cost=(12, 12, 20), want_cost=False):
+                 sign_hide=False, subpel_planes=False, sao_rdo=None, dir_cost=(12, 12, 20), want_cost=False, chroma_satd=False):
+        """chroma_satd (with chroma): both refinements and the decision measure chroma as the reference does at subme >= 3
+        (x265hip_subpel_refine_chroma, x265hip_bidir_decide_chroma)."""
         import torch
         from .pipeline import MotionSearch, SubpelRefine
+        if chroma_satd and not chroma:
+            raise ValueError("BFramePipeline: chroma_satd needs chroma=True")
         self.depth, self.qp, self.chroma = depth, qp, chroma
         self.msl = [MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True) for _ in range(2)]
-        self.spl = [SubpelRefine(m, subme, device, phase_planes=subpel_planes) for m in self.msl]
+        self.spl = [SubpelRefine(m, subme, device, phase_planes=subpel_planes, chroma_satd=chroma_satd) for m in self.msl]
         self.ms = self.msl[0]                # geometry (nctu, w64, h64) for the helpers shared with FramePipeline
-        self.bd = BidirDecide(self.ms.nctu, w64, h64, depth, level, device, dir_cost=dir_cost, want_cost=want_cost)
+        self.bd = BidirDecide(self.ms.nctu, w64, h64, depth, level, device, dir_cost=dir_cost, want_cost=want_cost,
+                              chroma_satd=chroma_satd and subme >= 3)      # bChromaSATD is off at subme <= 2 (motion.cpp:212): luma-only decision there
         self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
         self.rc = InterReconBi(self.ms.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
         self.db = Deblock(w64, h64, depth, level, max(qp - 6 * (depth - 8), 0), device) if deblock else None

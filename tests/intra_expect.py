@@ -240,13 +240,14 @@ def expect(depth, planes, w64, h64, level, qp, qp_c=None, flags=H.TU_INTRA_SLICE
     nc = n // 2
     qp_c = qp_c if qp_c is not None else (qp, qp)
     tot = nctu * nblk
+    max_val = (1 << depth) - 1
     mode_out = np.zeros(tot, np.uint8)
     cost_out = np.zeros((tot, 2), np.int32)
     lev = [np.zeros(tot * n * n, np.int16)] + [np.zeros(tot * nc * nc, np.int16) for _ in range(2)]
     ns = [np.zeros(tot, np.uint32) for _ in range(3)]
     dist = [np.zeros(tot, np.uint64) for _ in range(3)]
     names = ("dc", "planar", "angular_lt18", "angular_ge18", "mpm_priced", "non_mpm", "left_above_differ", "num_sig_0", "num_sig_gt1", "strong_taken",
-             "strong_refused", "bits_flip")
+             "strong_refused", "bits_flip", "edge_clip", "edge_clip_lo", "edge_clip_hi", "cost_tie", "tie_not_p0", "level_sat", "recon_at_limit", "chroma_coded")
     masks = {k: np.zeros(tot, bool) for k in names}
     job = np.zeros(1, dtype=H.job_dtype())
     for ctu in range(nctu):
@@ -266,12 +267,14 @@ def expect(depth, planes, w64, h64, level, qp, qp_c=None, flags=H.TU_INTRA_SLICE
             fp = src[0].ctypes.data + off * es
             best = None                     # (cost, sad, mode, bits)
             best_sad = None
+            costs = {}
             for mode in SCAN_ORDER:
                 buf = ref_buf if mode == 1 else (flt_buf if FILTER_FLAGS[mode] & n else ref_buf)        # search.cpp:1358, :1365-1369, :1394
                 p = slots.predict(mode, buf, 1 if (n <= 16 and mode != 0) else 0)
                 sad = slots.cost(fp, stride, p)
                 bits = mode_bits[0] if mode == preds[0] else (mode_bits[1] if mode in preds[1:] else mode_bits[2])
                 cost = sad + ((bits * lambda8 + 128) >> 8)                                              # rdcost.h:148-153
+                costs[mode] = cost
                 if best is None or cost < best[0]:                                                      # COPY4_IF_LT: strict, in scan order
                     best = (cost, sad, mode, bits, p)
                 if best_sad is None or sad < best_sad[0]:
@@ -310,6 +313,20 @@ def expect(depth, planes, w64, h64, level, qp, qp_c=None, flags=H.TU_INTRA_SLICE
             masks["num_sig_0"][b], masks["num_sig_gt1"][b] = ns[0][b] == 0, ns[0][b] > 1
             masks["strong_taken"][b], masks["strong_refused"][b] = took_strong, (n == 32 and strong and not took_strong)
             masks["bits_flip"][b] = best_sad[1] != mode
+            if mode in (10, 26) and n <= 16:
+                # the edge filter of the pure directions before its clip (intrapred.cpp:137-142): main = the arm the mode copies, side = the other
+                main0, side0 = (1, 2 * n + 1) if mode == 26 else (2 * n + 1, 1)
+                edge = int(ref_buf[main0]) + ((ref_buf[side0:side0 + n].astype(np.int64) - int(ref_buf[0])) >> 1)
+                masks["edge_clip_lo"][b], masks["edge_clip_hi"][b] = (edge < 0).any(), (edge > max_val).any()
+                masks["edge_clip"][b] = masks["edge_clip_lo"][b] or masks["edge_clip_hi"][b]
+            tied = [m for m in SCAN_ORDER if costs[m] == cost]
+            masks["cost_tie"][b] = len(tied) > 1
+            masks["tie_not_p0"][b] = len(tied) > 1 and preds[0] in tied and preds[0] != mode
+            lb = lev[0][b * n * n:(b + 1) * n * n]
+            masks["level_sat"][b] = ((lb == -32768) | (lb == 32767)).any()
+            yb = rec[0].reshape(rows, stride)[F.MARGIN_Y + gy:F.MARGIN_Y + gy + n, F.MARGIN_X + gx:F.MARGIN_X + gx + n]
+            masks["recon_at_limit"][b] = ((yb == 0) | (yb == max_val)).any()
+            masks["chroma_coded"][b] = chroma and (ns[1][b] > 0 or ns[2][b] > 0)
     out = dict(mode=mode_out, cost=cost_out, levels=lev[0], num_sig=ns[0], dist=dist[0], recon=rec[0], masks=masks, tables=slots.tables)
     if chroma:
         for c in range(2):

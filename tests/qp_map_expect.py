@@ -202,7 +202,7 @@ def walk(depth, planes, w64, h64, level, tu_qp, lambda8_by_qp=None, lambda8=1024
             gx, gy = cx + bx * n, cy + by * n
             b = ctu * nblk + z
             qps = [min(max(int(tu_qp[c, gy // 8, gx // 8]), 0), qmax) for c in range(3)]
-            lam = lambda8 if lambda8_by_qp is None else int(lambda8_by_qp[qps[0]])
+            lam = lambda8 if lambda8_by_qp is None else min(int(lambda8_by_qp[qps[0]]), 1 << 24)       # the stage prices an entry above 2^24 like 2^24
             lam_used[b] = lam
             flg = IE.neighbour_flags(gx, gy, n, w64, h64)
             off = org + gy * stride + gx

@@ -1,13 +1,15 @@
 """GPU parity of the I-picture stage (x265hip_intra_picture, stages.IntraPicture), of the I step (stages.IFramePipeline) and of the
 mini-GOP driver with an i_step against the coding-order walk of tests/intra_expect.py and the oracle chain behind it: the walk ->
-deblock_bs_inter(intra = all ones) -> deblock_luma / deblock_chroma -> sao_stats / sao_rdo / sao_apply -> border extension.  Equal means
-equal."""
+deblock_bs_inter(intra = all ones) -> deblock_luma / deblock_chroma -> sao_stats / sao_rdo / sao_apply -> border extension.  The stage
+alone also runs on the hostile pictures and operating points of tests/intra_cases.py: the edge filter's clip, ties, a rate term of 2^36,
+both ends of the QP range, no chroma planes.  Equal means equal."""
 import importlib
 
 import numpy as np
 import pytest
 
 import bidir_expect as BE
+import intra_cases as IC
 import intra_expect as IE
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +24,8 @@ _cache = {}
 
 
 def _case(depth, w, h, level, flags, strong):
-    """The walk's expectation, computed once per case and shared (nothing modifies it)."""
+    """The walk's expectation on intra_expect.test_picture at the mid operating point, computed once per case and shared (nothing modifies
+    it): the dict intra_cases.expectation returns for its cases."""
     key = (depth, w, h, level, flags, strong)
     if key not in _cache:
         yuv = IE.test_picture(depth, w, h)
@@ -31,43 +34,61 @@ def _case(depth, w, h, level, flags, strong):
         qpc = S.chroma_quant_qp(qp, depth)
         init = IE.garbage_planes(depth, [np.asarray(p).reshape(-1).shape for p in pl])
         e = IE.expect(depth, pl, w64, h64, level, qp, qp_c=(qpc, qpc), flags=flags, strong=strong, recon_init=init, with_reference=False)
-        _cache[key] = (yuv, w64, h64, qp, qpc, init, e)
+        _cache[key] = dict(yuv=yuv, w64=w64, h64=h64, qp=qp, qp_c=(qpc, qpc), lambda8=IE.LAMBDA8, mode_bits=IE.MODE_BITS, init=init, e=e)
     return _cache[key]
 
 
-def _run_kernel(depth, w, h, level, flags, strong):
+def _run(x, depth, level, flags, strong, chroma=True):
+    """x: a picture, an operating point, the recon planes' contents before the run and the walk's expectation (_case /
+    intra_cases.expectation).  Two runs into recon planes pre-filled with garbage; every output and the whole planes against the walk."""
     import torch
     dev = torch.device("cuda:0")
-    yuv, w64, h64, qp, qpc, init, e = _case(depth, w, h, level, flags, strong)
+    yuv, w64, h64, init, e = x["yuv"], x["w64"], x["h64"], x["init"], x["e"]
     cur = P.DevicePicture(yuv[0], dev, yuv[1], yuv[2])
     dt = cur.host.dtype
 
     def up(a):
         return torch.from_numpy(a if a.dtype == np.uint8 else a.view(np.int16)).to(dev)
-    ip = S.IntraPicture((w64 // 64) * (h64 // 64), w64, h64, depth, level, qp, dev, flags=flags, chroma=True, qp_c=(qpc, qpc), lambda8=IE.LAMBDA8,
-                        mode_bits=IE.MODE_BITS, strong_intra_smoothing=strong, want_cost=True)
+    ip = S.IntraPicture((w64 // 64) * (h64 // 64), w64, h64, depth, level, x["qp"], dev, flags=flags, chroma=chroma, qp_c=x["qp_c"], lambda8=x["lambda8"],
+                        mode_bits=x["mode_bits"], strong_intra_smoothing=strong, want_cost=True)
     assert ip.waves == IE.waves(w64, h64)
     runs = []
     for _ in range(2):                                   # the second run goes into the buffers the first one left
         if not runs:
             rec = [up(p.copy()) for p in init]           # recon planes pre-filled with garbage
-        ip.run(cur, rec[0], rec[1:])
+        ip.run(cur, rec[0], rec[1:] if chroma else None)
         torch.cuda.synchronize()
         got = {"mode": ip.mode.cpu().numpy(), "cost": ip.cost.cpu().numpy().reshape(-1, 2), "levels": ip.levels.cpu().numpy(),
                "num_sig": ip.num_sig.cpu().numpy(), "dist": ip.dist.cpu().numpy(), "recon": rec[0].cpu().numpy().view(dt)}
-        for c in range(2):
+        for c in range(2 if chroma else 0):
             got.update({"levels_c%d" % c: ip.levels_c[c].cpu().numpy(), "num_sig_c%d" % c: ip.num_sig_c[c].cpu().numpy(),
                         "dist_c%d" % c: ip.dist_c[c].cpu().numpy(), "recon_c%d" % c: rec[1 + c].cpu().numpy().view(dt)})
         runs.append(got)
     want = {k: v for k, v in e.items() if k not in ("masks", "tables")}
+    assert set(want) == set(runs[0])
     # whole planes are compared: the margins of the recon planes stay as they were pre-filled
     bad = BE.compare(runs[0], want)
     assert not bad, bad
     # a second run over a finished reconstruction changes nothing
     again = BE.compare(runs[1], want)
     assert not again, again
-    assert set(ip.checksum()) >= {"mode", "levels", "num_sig", "dist", "levels_c0", "levels_c1"}
+    assert set(ip.checksum()) >= ({"mode", "levels", "num_sig", "dist", "levels_c0", "levels_c1"} if chroma else {"mode", "levels", "num_sig", "dist"})
     return e
+
+
+def _run_kernel(depth, w, h, level, flags, strong):
+    return _run(_case(depth, w, h, level, flags, strong), depth, level, flags, strong)
+
+
+def _run_case(c):
+    """One case of tests/intra_cases.py (what each is listed for is asserted, with the walk alone, by tests/test_intra_cases_cpu.py)."""
+    x = IC.expectation(c)
+    assert x["qp_c"][0] == S.chroma_quant_qp(x["qp"], c.depth)
+    return _run(x, c.depth, c.level, c.flags, c.strong, c.chroma)
+
+
+def _ids(cases):
+    return dict(argvalues=cases, ids=[c.id for c in cases])
 
 
 @pytest.mark.parametrize("depth,level,sign_hide,strong", [(8, 0, True, True), (8, 0, False, True), (8, 1, True, True), (8, 1, False, True), (8, 2, True, True),
@@ -90,6 +111,53 @@ def test_intra_picture_equals_the_walk(depth, level, sign_hide, strong):
 def test_intra_picture_degenerate_grids(w, h, depth, level):
     """One CTU, one CTU column (every odd wave is empty), one CTU row."""
     _run_kernel(depth, w, h, level, H.TU_INTRA_SLICE | H.TU_SIGN_HIDE, True)
+
+
+@pytest.mark.parametrize("c", **_ids(IC.CLIPPING_CASES))
+def test_intra_picture_on_clipping_content(c):
+    """192x128 (3x2 CTUs).  edge_clip pictures at two operating points, all depths, levels 0 and 1: the winners are modes 10 / 26 whose edge
+    filter leaves the sample range at both bounds; edges at 8 / 10 bits, levels 0 - 2, sign hiding on and off, strong smoothing off; noise at
+    12 bits, levels 0 and 2: reconstructions at 0 and max that the next blocks predict from, chroma coded everywhere."""
+    m = _run_case(c)["masks"]
+    if c.kind == "edge_clip":
+        assert m["edge_clip_lo"].any() and m["edge_clip_hi"].any()
+    else:
+        assert m["recon_at_limit"].any() and m["chroma_coded"].any()
+
+
+@pytest.mark.parametrize("c", **_ids(IC.QP_END_CASES))
+def test_intra_picture_at_the_ends_of_the_qp_range(c):
+    """The largest QP (51 / 63 / 75, lambda8 0) on edges, flat_hi and flat_lo at every depth and level: next to nothing is coded, the picture
+    is neighbour substitution carried from block to block with ties everywhere.  QP 0 on edges and noise: the largest levels, at 12 bits
+    (levels 1 and 2) both int16 limits."""
+    e = _run_case(c)
+    if c.point == "qp-max":
+        assert e["masks"]["cost_tie"].any() or c.kind == "edges"
+    elif c.depth == 12:
+        assert e["masks"]["level_sat"].any()
+
+
+@pytest.mark.parametrize("c", **_ids(IC.TIE_CASES))
+def test_intra_picture_ties_follow_the_scan_order(c):
+    """halves with mode bits (3, 3, 6) and (6, 3, 2) at 8 / 10 bits, levels 0 - 2, and flat_hi with lambda8 0: most blocks are exact ties,
+    and the winner is the first of the tied modes in the order DC, planar, 2 .. 34 - not the most probable one."""
+    assert _run_case(c)["masks"]["cost_tie"].any()
+
+
+@pytest.mark.parametrize("c", **_ids(IC.COST_CASES))
+def test_intra_picture_cost_near_its_int32_bound(c):
+    """lambda8 2^24 with mode_bits 4096 (bits * lambda8 = 2^36, every reported cost 2^28 + sad) at 8 / 12 bits, levels 0 and 2, and with
+    (1, 4095, 4096) - the losers' costs near 2^28, the winner's small - at 10 bits, level 1."""
+    e = _run_case(c)
+    assert (e["cost"][:, 1] >= 1 << 28).all() or c.point == "big-cost-mpm"
+
+
+@pytest.mark.parametrize("c", **_ids(IC.LUMA_ONLY_CASES))
+def test_intra_picture_without_chroma(c):
+    """IntraPicture(chroma=False): luma mode, cost, levels, num_sig, dist and the Y plane equal the walk without chroma (which
+    test_intra_cases_cpu.test_luma_does_not_read_chroma shows equal to the luma outputs of the walk with it)."""
+    e = _run_case(c)
+    assert "recon_c0" not in e and int(e["num_sig"].sum()) > 0
 
 
 def _sao_rdo_inputs(depth, qp, slice_type):

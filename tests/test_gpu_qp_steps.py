@@ -1,7 +1,7 @@
 """GPU parity of the I-picture stage and of the three frame steps under per-block QP maps.
 
   * x265hip_intra_picture with qp_map + lambda8_by_qp against the coding-order walk with the block's own QPs and lambda
-    (qp_map_expect.walk, built from the pieces of tests/intra_expect.py).
+    (qp_map_expect.walk, built from the pieces of tests/intra_expect.py), also with a map and a lambda table at and beyond the ends of their ranges.
   * Closed loop at 256x192 for FramePipeline, BFramePipeline and IFramePipeline: AdaptiveQuant offsets -> CuQpMaps -> set_qp_maps -> one
     step, stage by stage against the oracle chain (qp_map_expect.p_chain / b_chain / i_chain: the TU stages composed from one oracle run
     per QP, deblock_luma / deblock_chroma with qp_map = cu_qp); set_qp_maps(None) afterwards reproduces the uniform step's checksum.
@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import bidir_expect as BE
+import intra_cases as IC
 import intra_expect as IE
 import qp_map_expect as QE
 
@@ -82,6 +83,42 @@ def test_intra_picture_with_maps_equals_the_walk(depth, level, sign_hide):
     # the table matters: blocks are priced with different lambdas, and some decisions differ from those at the record's lambda8
     assert len(np.unique(e["lambda8"])) >= 6 and not np.array_equal(e["cost"], e0["cost"])
     assert not np.array_equal(e["mode"], e0["mode"]), "no block's decision depends on its lambda: the case does not test the table"
+
+
+@pytest.mark.parametrize("depth", [8, 10])
+def test_intra_picture_with_maps_at_the_range_ends(depth):
+    """intra_cases' edges picture (192x128) at level 1 under a map whose entries are 0, 1, max - 1, max, two values between and int8 values
+    outside the range (-128, -1, 127: they code like 0 and like max), chroma planes with maps of their own, and a lambda table with an entry
+    above 2^24 (priced like 2^24) and a 0 - against qp_map_expect.walk, which clamps both the same way (test_intra_cases_cpu shows the map to
+    be what this says)."""
+    import torch
+    dev = torch.device("cuda:0")
+    level, flags = 1, H.TU_INTRA_SLICE | H.TU_SIGN_HIDE
+    key = ("range ends", depth)
+    if key not in _walks:
+        yuv = IC.build(depth, "edges")
+        pl, w64, h64 = IC.planes(depth, "edges", level)
+        tu, lam, _ = IC.range_end_map(depth, level)
+        init = IE.garbage_planes(depth, [np.asarray(p).reshape(-1).shape for p in pl])
+        _walks[key] = (yuv, w64, h64, tu, lam, init, QE.walk(depth, pl, w64, h64, level, tu, lambda8_by_qp=lam, flags=flags, recon_init=init))
+    yuv, w64, h64, tu, lam, init, e = _walks[key]
+    cur = P.DevicePicture(yuv[0], dev, yuv[1], yuv[2])
+    dt = cur.host.dtype
+    qp = 30 + 6 * (depth - 8)
+    ip = S.IntraPicture((w64 // 64) * (h64 // 64), w64, h64, depth, level, qp, dev, flags=flags, chroma=True, qp_c=(qp, qp), lambda8=IE.LAMBDA8,
+                        mode_bits=IE.MODE_BITS, want_cost=True)
+    ip.qp_map, ip.lambda8_by_qp = _up(tu.reshape(-1), dev), _up(lam.view(np.int32), dev)
+    rec = [_up(p.copy(), dev) for p in init]
+    ip.run(cur, rec[0], rec[1:])
+    torch.cuda.synchronize()
+    got = {"mode": ip.mode.cpu().numpy(), "cost": ip.cost.cpu().numpy().reshape(-1, 2), "levels": ip.levels.cpu().numpy(),
+           "num_sig": ip.num_sig.cpu().numpy(), "dist": ip.dist.cpu().numpy(), "recon": rec[0].cpu().numpy().view(dt)}
+    for c in range(2):
+        got.update({"levels_c%d" % c: ip.levels_c[c].cpu().numpy(), "num_sig_c%d" % c: ip.num_sig_c[c].cpu().numpy(),
+                    "dist_c%d" % c: ip.dist_c[c].cpu().numpy(), "recon_c%d" % c: rec[1 + c].cpu().numpy().view(dt)})
+    bad = BE.compare(got, {k: v for k, v in e.items() if k != "lambda8"})
+    assert not bad, bad
+    assert (e["lambda8"] == 1 << 24).any() and (tu < 0).any() and (tu > 51 + 6 * (depth - 8)).any()
 
 
 def _aq_maps(pic, depth, level, dev, base_qp):

@@ -377,6 +377,46 @@ typedef struct x265hip_bidir_chroma
     const void* fref1_cb; const void* fref1_cr; intptr_t fref_stride_c;
 } x265hip_bidir_chroma;
 int x265hip_bidir_decide_chroma(const x265hip_bidir_params* p, const x265hip_bidir_chroma* c, void* stream);
+/* The reference of every block of a P picture with several references: the uni-directional loop of Search::predInterSearch
+ * (search.cpp:2386-2471) for a P slice's 2Nx2N, on the block grid of the TU stages (N = 8 << level).  With rec_r = the block's record
+ * of the x265hip_subpel_refine pass against reference r (entry base(level) + z of [ctu][85]), r = 0 .. nrefs - 1 in list order:
+ *     cost_r = rec_r.cost + ref_cost[r]
+ *     best   = the smallest cost_r; strict '<' in list order, the lowest r wins a tie (search.cpp:2457)
+ * ref_cost[r] = lambda x (m_listSelBits[0] + MVP_IDX_BITS + getTUBits(r, nrefs)) = lambda x (1 + 1 + r + (r < nrefs - 1))
+ * (search.cpp:2403-2404, search.h:246-249, getBlkBits :2653): (8) for one reference and (12, 16, 20, 20) for four at lambda 4.
+ * Every reference is searched around one predictor, (0,0), so checkBestMVP has nothing to choose; refMasks / limitReferences are not
+ * modelled.  One lane per block, no LDS, no atomics.
+ *   mv_out  : the level's entries get { winning cost_r, the winner's vector }; no other entry is written.  It must not alias or overlap
+ *             any mv[r].
+ * Argument checks (depth, level, sizes, nrefs, NULL pointers, aliasing) return X265HIP_EINVAL before the device is asked for. */
+#define X265HIP_MAX_REFS 8
+typedef struct x265hip_ref_select_params
+{
+    int depth, width, height, level;                 /* width / height multiples of 64, level 0..2 */
+    int nrefs;                                       /* 1 .. X265HIP_MAX_REFS */
+    const int32_t* mv[X265HIP_MAX_REFS];             /* [ctu*85][2] records of the nrefs refinements, list order */
+    int32_t ref_cost[X265HIP_MAX_REFS];
+    int ref_ids[X265HIP_MAX_REFS];                   /* picture ids written into ref_id (what x265hip_deblock_bs_inter compares) */
+    int8_t* ref_idx;                                 /* [ctu][blocks]: the list index, the `ref_idx` of x265hip_recon_refs_params */
+    int8_t* ref_id;                                  /* optional [ctu][blocks]: ref_ids[ref_idx] - the `ref0` of x265hip_deblock_bs_inter */
+    int32_t* mv_out;                                 /* [ctu*85][2] */
+    int32_t* cost_out;                               /* optional [ctu][blocks][nrefs]: every cost_r */
+} x265hip_ref_select_params;
+int x265hip_ref_select(const x265hip_ref_select_params* p, void* stream);
+/* The inter TU stage of a P picture with several references: block blk is predicted from fref[ref_idx[blk]] with base.mv - everything
+ * else is the contract of x265hip_inter_recon / _chroma / _chroma_pair (qp_map included).  base.fref is ignored; the nrefs planes
+ * (sample (0,0); for the chroma entries the planes of Cb or Cr) share base.fref_stride.  ref_idx: DEVICE int8 [ctu][blocks]; an index
+ * outside [0, nrefs) is clamped into it.  base.tables is refused (X265HIP_EINVAL): scaling lists / the denoiser are not supported here. */
+typedef struct x265hip_recon_refs_params
+{
+    x265hip_recon_params base;
+    int nrefs;                                       /* 1 .. X265HIP_MAX_REFS */
+    const void* fref[X265HIP_MAX_REFS];
+    const int8_t* ref_idx;
+} x265hip_recon_refs_params;
+int x265hip_inter_recon_refs(const x265hip_recon_refs_params* p, void* stream);
+int x265hip_inter_recon_chroma_refs(const x265hip_recon_refs_params* p, void* stream);
+int x265hip_inter_recon_chroma_pair_refs(const x265hip_recon_refs_params* cb, const x265hip_recon_refs_params* cr, void* stream);
 /* The TU-stage entries, as x265hip_tu_launch_grid names them. */
 enum x265hip_tu_entry
 {
@@ -385,6 +425,13 @@ enum x265hip_tu_entry
     X265HIP_TU_ENTRY_INTER_CHROMA,       /* x265hip_inter_recon_chroma (nplanes 1) / _chroma_pair (nplanes 2) */
     X265HIP_TU_ENTRY_INTER_CHROMA_BI,    /* x265hip_inter_recon_chroma_bi */
     X265HIP_TU_ENTRY_INTRA               /* x265hip_intra_recon_batch (nblocks = njobs) */
+};
+/* The entries of the P step with several references, as x265hip_tu_launch_grid names them: enumerators of their own behind the values of
+ * x265hip_tu_entry, whose list and range stay what hosts were built with. */
+enum x265hip_tu_entry_refs
+{
+    X265HIP_TU_ENTRY_INTER_REFS = 8,     /* x265hip_inter_recon_refs */
+    X265HIP_TU_ENTRY_INTER_CHROMA_REFS   /* x265hip_inter_recon_chroma_refs (nplanes 1) / _chroma_pair_refs (nplanes 2) */
 };
 /* grid.x of the launch `entry` makes for `nblocks` blocks (or jobs) of n x n transforms (n = the transform size: 8 << level for luma,
  * 4 << level for chroma, intra n) at `depth`, with (tables != 0) or without a x265hip_tu_tables record, over `nplanes` planes.  The 16- and

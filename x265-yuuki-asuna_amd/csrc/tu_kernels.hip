@@ -139,6 +139,15 @@ template <int N> struct TuOps<N, true>
     }
 };
 template <int N, bool DST> using TuOpsFor = TuOps<N, (N >= 16 && !DST)>;
+// The operands built again (inter_recon_refs_kernel at 32 points, two bytes per sample: per block).  Functors of its own: the instances of
+// DctOperand::init the other kernels share keep their callers, and with them their code.
+template <int N> __device__ __forceinline__ void tu_ops_rebuild(TuOps<N, true>& o, int lane)
+{
+    auto matrix = [](int r, int c) { return (int)kTu.m[r][c]; };
+    auto colsum = [](int c) { return N == 16 ? kTuColSum.s16[c] : kTuColSum.s32[c]; };
+    o.fw.init(lane, matrix, colsum);
+    o.iv.init(lane, matrix, colsum);
+}
 
 // ---- sign-bit hiding (Quant::signBitHidingHDQ, quant.cpp:247-395; on by default in x265: pps.bSignHideEnabled) -------------------
 // Coefficient scans of the standard (6.5.3-6.5.5) over 4x4 coefficient groups: up-right diagonal everywhere, horizontal / vertical
@@ -796,6 +805,238 @@ __global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>
     }
 }
 
+// P pictures with several references (x265hip_inter_recon_refs and the chroma entries): block blk is predicted from the plane
+// fref[refIdx[blk]] of the launch's table of nrefs reference planes - refIdx = int8 [ctu][blocks], x265hip_ref_select's ref_idx.  Per
+// plane of grid.y its own table and indices.  No scaling-list / denoiser tables.
+struct TuRefsArgs
+{
+    TuArgs2 aa;
+    const uint8_t* fref[2][X265HIP_MAX_REFS];
+    const int8_t* refIdx[2];
+    int nrefs;
+};
+
+// inter_recon_kernel with the reference patch pointer of load_regs and of the 8-point load taken from the table.  A COPY of that kernel's
+// body, not a shared template: with the body moved into a __device__ __forceinline__ template the existing instances compiled to other
+// register counts, and those are tuned and pinned (tests/test_kernel_regs.py).  What differs: Geo::ref - the block's
+// list index travels with its geometry, so a patch fetched ahead is fetched from the plane of the block it belongs to -, ref_of, plane_of.
+template <typename Px, int N, bool CHROMA>
+__global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>::value) inter_recon_refs_kernel(TuRefsArgs ra, int nblocks)
+{
+    const TuArgs& a = ra.aa.p[blockIdx.y];          // grid.y = plane
+    const uint8_t* const* planes = ra.fref[blockIdx.y];
+    const int8_t* refIdx = ra.refIdx[blockIdx.y];
+    const int nrefs = ra.nrefs;
+    constexpr bool TAB = false;
+    constexpr int NN = N * N, LOG2N = N == 4 ? 2 : (N == 8 ? 3 : (N == 16 ? 4 : 5));
+    constexpr int TAPS = CHROMA ? 4 : 8, APRON = TAPS / 2 - 1, PW = N + TAPS - 1, PP = PW + 1;
+    constexpr int NL = CHROMA ? 2 * N : N, CTU = CHROMA ? 32 : 64, MVSH = CHROMA ? 3 : 2, MVMASK = CHROMA ? 7 : 3;
+    constexpr int BPP = sizeof(Px);
+    __shared__ __attribute__((aligned(16))) int16_t patch[PW * PP];
+    __shared__ int16_t immed[PW * N];
+    __shared__ __attribute__((aligned(16))) int16_t pred[NN], fe[NN], A[NN], B[NN];
+    __shared__ unsigned long long red[4];
+    __shared__ int sNumSig;
+
+    const int npu = (64 / NL) * (64 / NL);
+    const int lbase = NL == 8 ? 0 : (NL == 16 ? 64 : 80);
+    const int tid = threadIdx.x, nth = blockDim.x;
+    const int maxVal = (1 << a.depth) - 1, headRoom = 14 - a.depth;
+    auto tap = [](int f, int t) { return CHROMA ? (int)kTuChromaTaps[f][t] : (int)kTuTaps[f][t]; };
+    // 16 / 32: a persistent single-wavefront workgroup walks blocks blockIdx.x, + gridDim.x, ... with the MFMA operands of the
+    // transforms built once (its barriers are wave-local); 8: one block per workgroup
+    TuOpsFor<N, false> ops;
+    ops.init(tid & 63);
+    // geometry of block `blk` given its packed quarter-sample motion vector
+    struct Geo { int ctu, z, px, py, qx, qy, xf, yf, qp, ref; };
+    auto geom = [&](const int blk, const int packed, const int ref) -> Geo
+    {
+        Geo g;
+        g.ctu = blk / npu; g.z = blk - g.ctu * npu;
+        const int bxz = (g.z & 1) | ((g.z >> 1) & 2) | ((g.z >> 2) & 4), byz = ((g.z >> 1) & 1) | ((g.z >> 2) & 2) | ((g.z >> 3) & 4);
+        g.px = (g.ctu % a.ctusW) * CTU + bxz * N; g.py = (g.ctu / a.ctusW) * CTU + byz * N;
+        g.qx = (int16_t)(packed & 0xffff); g.qy = (int16_t)(packed >> 16);
+        g.xf = g.qx & MVMASK; g.yf = g.qy & MVMASK;
+        // the block's own QP travels with its geometry: where the next block's operands are fetched ahead (16 points), its QP waits in gn
+        // and the chain below keeps reading g
+        g.qp = tu_block_qp(a, g.px >> (CHROMA ? 2 : 3), g.py >> (CHROMA ? 2 : 3));
+        // the block's list index, uniform over the workgroup (one block), clamped to the table: no entry is dereferenced out of range
+        g.ref = clip3(0, nrefs - 1, __builtin_amdgcn_readfirstlane(ref));
+        return g;
+    };
+    auto mv_of = [&](const int blk) -> int { const int ctu = blk / npu; return a.mv[(size_t)ctu * 85 + lbase + (blk - ctu * npu)].y; };
+    auto ref_of = [&](const int blk) -> int { return (int)refIdx[blk]; };
+    // sample (0,0) of the plane block g is predicted from: the table sits in the kernel arguments and g.ref is uniform - a scalar load
+    auto plane_of = [&](const Geo& g) -> const uint8_t* { return planes[g.ref]; };
+    // 16 / 32: dword loads (4 / 2 samples) of the source block and the reference patch into REGISTERS, all issued before the first one is
+    // waited for; they go into LDS (widened to int16 pairs) at the top of the block's turn.  A patch row is read to the next dword boundary
+    // (one sample beyond the 2 * apron + N needed: still inside the padded plane, and inside the row's LDS pitch).
+    constexpr int NT = InterReconThreads<N>::value, SPD = 4 / BPP, FD = N / SPD, PWD = (PW + SPD - 1) / SPD;
+    constexpr int FI = N >= 16 ? (N * FD) / NT : 1, PI = N >= 16 ? (PW * PWD + NT - 1) / NT : 1;
+    static_assert(N < 16 || (PWD * SPD <= PP && (N * FD) % NT == 0), "patch pitch / source block size");
+    auto load_regs = [&](const Geo& g, uint32_t (&fv)[FI], uint32_t (&pv)[PI])
+    {
+        const Px* f = reinterpret_cast<const Px*>(a.fenc + (long)g.py * a.fencStrideB) + g.px;
+        const long fst = a.fencStrideB / BPP;
+        const Px* r = reinterpret_cast<const Px*>(plane_of(g) + (long)(g.py + (g.qy >> MVSH) - APRON) * a.frefStrideB) + (g.px + (g.qx >> MVSH) - APRON);
+        const long rst = a.frefStrideB / BPP;
+#pragma unroll
+        for (int k = 0; k < FI; k++) { const int i = tid + k * NT, y = i / FD, c = i - y * FD; fv[k] = ld_u32(reinterpret_cast<const uint8_t*>(f + y * fst) + 4 * c); }
+#pragma unroll
+        for (int k = 0; k < PI; k++)
+        {
+            const int i = tid + k * NT, y = i / PWD, c = i - y * PWD;
+            pv[k] = i < PW * PWD ? ld_u32(reinterpret_cast<const uint8_t*>(r + y * rst) + 4 * c) : 0u;
+        }
+    };
+    auto store_regs = [&](const uint32_t (&fv)[FI], const uint32_t (&pv)[PI])
+    {
+        auto put = [&](int16_t* dst, const uint32_t w)
+        {
+            if (BPP == 1)
+            {
+                uint2 v;
+                v.x = (w & 0xffu) | ((w & 0xff00u) << 8); v.y = ((w >> 16) & 0xffu) | ((w >> 8) & 0xff0000u);
+                *reinterpret_cast<uint2*>(dst) = v;
+            }
+            else *reinterpret_cast<uint32_t*>(dst) = w;
+        };
+#pragma unroll
+        for (int k = 0; k < FI; k++) { const int i = tid + k * NT; put(fe + i * SPD, fv[k]); }
+#pragma unroll
+        for (int k = 0; k < PI; k++) { const int i = tid + k * NT, y = i / PWD, c = i - y * PWD; if (i < PW * PWD) put(patch + y * PP + c * SPD, pv[k]); }
+    };
+    // everything behind the staging: prediction from the patch in LDS; `between` runs after the prediction (the next block's loads are issued
+    // there: its motion vector has arrived by then and the loads have the whole transform chain to complete); then the transform chain
+    auto do_rest = [&](const Geo& g, auto&& between)
+    {
+    const int ctu = g.ctu, z = g.z, px = g.px, py = g.py, xf = g.xf, yf = g.yf;
+    // ---- predInterLumaPixel ----------------------------------------------------------------------------
+    if (xf && yf)
+    {
+        const int shiftPS = 6 - headRoom, offPS = -(8192 << shiftPS);
+        for (int i = tid; i < PW * N; i += nth)
+        {
+            const int y = i >> LOG2N, x = i & (N - 1);
+            int s = 0;
+#pragma unroll
+            for (int t = 0; t < TAPS; t++) s += (int)patch[y * PP + x + t] * tap(xf, t);
+            immed[i] = (int16_t)((s + offPS) >> shiftPS);
+        }
+        __syncthreads();
+        const int shiftSP = 6 + headRoom, offSP = (1 << (shiftSP - 1)) + (8192 << 6);
+        for (int i = tid; i < NN; i += nth)
+        {
+            const int y = i >> LOG2N, x = i & (N - 1);
+            int s = 0;
+#pragma unroll
+            for (int t = 0; t < TAPS; t++) s += (int)immed[(y + t) * N + x] * tap(yf, t);
+            pred[i] = (int16_t)tu_clip16((s + offSP) >> shiftSP, maxVal);
+        }
+    }
+    else
+    {
+        for (int i = tid; i < NN; i += nth)
+        {
+            const int y = i >> LOG2N, x = i & (N - 1);
+            int v;
+            if (!(xf | yf)) v = patch[(y + APRON) * PP + x + APRON];
+            else
+            {
+                int s = 0;
+#pragma unroll
+                for (int t = 0; t < TAPS; t++)
+                    s += (int)(xf ? patch[(y + APRON) * PP + x + t] : patch[(y + t) * PP + x + APRON]) * tap(xf ? xf : yf, t);
+                v = tu_clip16((s + 32) >> 6, maxVal);
+            }
+            pred[i] = (int16_t)v;
+        }
+    }
+    __syncthreads();
+    between();
+
+    tu_chain<Px, N, false, TAB>(ops, pred, fe, A, B, red, sNumSig, a.depth, g.qp, a.intraSlice,
+                           a.levels + ((size_t)ctu * npu + z) * NN, &a.numSig[(size_t)ctu * npu + z], &a.dist[(size_t)ctu * npu + z],
+                           reinterpret_cast<Px*>(a.recon + (long)py * a.reconStrideB) + px, a.reconStrideB / BPP, TU_SCAN_DIAG,
+                           TAB ? a.tab.at(((size_t)ctu * npu + z) * NN) : a.tab, (size_t)ctu * npu + z);
+    __syncthreads();
+    };
+    if constexpr (N >= 16)
+    {
+        // A persistent wavefront walks blocks blockIdx.x, + gridDim.x, ...  Per block it used to pay two dependent trips to memory before any
+        // work - the motion vector, then the source block / reference patch the vector points at - ~3 us of a 10 us (16x16) / 17 us (32x32)
+        // block at one instruction per ~28 cycles (profiles/r03_inst_counters.txt).  Now the NEXT block's vector is requested at the top of a
+        // block and its samples right after the prediction, into registers; they wait there until the block's turn.
+        // (32x32: only the vector travels ahead - the 11 sample registers on top of its 252 made the compiler spill 261)
+        constexpr bool AHEAD = N == 16;
+        uint32_t fvC[FI], pvC[PI], fvN[AHEAD ? FI : 1], pvN[AHEAD ? PI : 1];
+        // XCD-aware order (round 6): wavefront w sits on XCD w % 8 (observed placement, for speed only) and walks virtual indices w, w + gridDim.x, ...; the virtual index
+        // -> block map hands every XCD a contiguous eighth of the picture's blocks, so the TUs of a CTU and the CTUs of a row - whose 32-byte source rows and straddling
+        // reference rows share 64-byte lines - meet in ONE L2 instead of being fetched by up to four (inter_recon<32> fetched 2.3 - 4.6 x its planes, profiles/stage_traffic.json)
+        int v = blockIdx.x;
+        const bool xcdOrder = !(a.intraSlice & TU_FLAG_RASTER_ORDER);
+        auto order = [&](const int i) { return xcdOrder ? xcd_swizzle(i, nblocks) : i; };
+        if (v < nblocks)
+        {
+            int blk = order(v);
+            Geo g = geom(blk, mv_of(blk), ref_of(blk));
+            if constexpr (AHEAD) load_regs(g, fvC, pvC);
+            for (; v < nblocks; v += gridDim.x)
+            {
+                const bool has = v + (int)gridDim.x < nblocks;
+                const int nb = has ? order(v + (int)gridDim.x) : 0;
+                int packedN = 0, refN = 0;
+                if (has) { packedN = mv_of(nb); refN = ref_of(nb); }
+                if constexpr (N == 32 && BPP == 2)
+                {
+                    // 32 points at two bytes per sample: with the operands kept over the whole walk the chain does not fit 256 registers (30 spilled,
+                    // 124 bytes of scratch - as the single-reference twin).  Built per block - ~70 loads from constant memory
+                    // beside a block's thousands of instructions - each operand lives from its build to its last product: 253 registers, nothing
+                    // spilled.  The lane index goes through an empty asm so that the build is not hoisted out of the walk again.
+                    int lane = tid & 63;
+                    asm volatile("" : "+v"(lane));
+                    tu_ops_rebuild(ops, lane);
+                }
+                if constexpr (!AHEAD) load_regs(g, fvC, pvC);
+                store_regs(fvC, pvC);
+                if (tid == 0) sNumSig = 0;
+                __syncthreads();
+                Geo gn = g;
+                if constexpr (AHEAD)
+                {
+                    do_rest(g, [&]() { if (has) { gn = geom(nb, packedN, refN); load_regs(gn, fvN, pvN); } });
+#pragma unroll
+                    for (int k = 0; k < FI; k++) fvC[k] = fvN[k];
+#pragma unroll
+                    for (int k = 0; k < PI; k++) pvC[k] = pvN[k];
+                }
+                else
+                {
+                    do_rest(g, []() {});
+                    if (has) gn = geom(nb, packedN, refN);
+                }
+                g = gn;
+            }
+        }
+    }
+    else
+    {
+        const int blk = blockIdx.x;
+        const Geo g = geom(blk, mv_of(blk), ref_of(blk));
+        {
+            const Px* f = reinterpret_cast<const Px*>(a.fenc + (long)g.py * a.fencStrideB) + g.px;
+            const long fst = a.fencStrideB / BPP;
+            const Px* r = reinterpret_cast<const Px*>(plane_of(g) + (long)(g.py + (g.qy >> MVSH) - APRON) * a.frefStrideB) + (g.px + (g.qx >> MVSH) - APRON);
+            const long rst = a.frefStrideB / BPP;
+            for (int i = tid; i < NN; i += nth) { const int y = i >> LOG2N, x = i & (N - 1); fe[i] = (int16_t)f[y * fst + x]; }
+            for (int i = tid; i < PW * PW; i += nth) { const int y = i / PW, x = i - y * PW; patch[y * PP + x] = (int16_t)r[y * rst + x]; }
+            if (tid == 0) sNumSig = 0;
+        }
+        __syncthreads();
+        do_rest(g, []() {});
+    }
+}
+
 // Bi-predictive flavour of the inter stage (B pictures; Predict::motionCompensation, predict.cpp:168-243 without weighted prediction):
 // dir 1 / 2 = one list as above, dir 3 = predInterLumaShort of both lists (convert_p2s / luma_hps / luma_vps / luma_hps + luma_vss at
 // 14-bit intermediate precision, :267-304) combined by addAvg.
@@ -1051,6 +1292,10 @@ template <typename Px, bool TB> static const void* tu_persistent_kernel(const in
         return n == 16 ? (const void*)inter_recon_kernel<Px, 16, true, TB> : nullptr;
     case X265HIP_TU_ENTRY_INTER_CHROMA_BI:
         return n == 16 ? (const void*)inter_recon_bi_kernel<Px, 16, true, TB> : nullptr;
+    case X265HIP_TU_ENTRY_INTER_REFS:             // no table flavour: the entry refuses tables
+        return n == 16 ? (const void*)inter_recon_refs_kernel<Px, 16, false> : (n == 32 ? (const void*)inter_recon_refs_kernel<Px, 32, false> : nullptr);
+    case X265HIP_TU_ENTRY_INTER_CHROMA_REFS:
+        return n == 16 ? (const void*)inter_recon_refs_kernel<Px, 16, true> : nullptr;
     default:
         return n == 16 ? (const void*)intra_recon_kernel<Px, 16, false, TB> : (n == 32 ? (const void*)intra_recon_kernel<Px, 32, false, TB> : nullptr);
     }
@@ -1074,13 +1319,15 @@ static int tu_launch_grid(const int entry, const int n, const int depth, const b
 
 extern "C" int x265hip_tu_launch_grid(int entry, int n, int depth, int tables, int nplanes, int nblocks)
 {
-    const bool chroma = entry == X265HIP_TU_ENTRY_INTER_CHROMA || entry == X265HIP_TU_ENTRY_INTER_CHROMA_BI;
-    if (entry < X265HIP_TU_ENTRY_INTER || entry > X265HIP_TU_ENTRY_INTRA) { set_error("tu_launch_grid: entry %d", entry); return X265HIP_EINVAL; }
+    const bool chroma = entry == X265HIP_TU_ENTRY_INTER_CHROMA || entry == X265HIP_TU_ENTRY_INTER_CHROMA_BI || entry == X265HIP_TU_ENTRY_INTER_CHROMA_REFS;
+    const bool refs = entry == X265HIP_TU_ENTRY_INTER_REFS || entry == X265HIP_TU_ENTRY_INTER_CHROMA_REFS;
+    if ((entry < X265HIP_TU_ENTRY_INTER || entry > X265HIP_TU_ENTRY_INTRA) && !refs) { set_error("tu_launch_grid: entry %d", entry); return X265HIP_EINVAL; }
     const bool sizeOk = entry == X265HIP_TU_ENTRY_INTRA ? (n == 4 || n == 8 || n == 16 || n == 32)
                                                         : (chroma ? (n == 4 || n == 8 || n == 16) : (n == 8 || n == 16 || n == 32));
     if (!sizeOk) { set_error("tu_launch_grid: transform size %d for entry %d", n, entry); return X265HIP_EINVAL; }
     if (depth != 8 && depth != 10 && depth != 12) { set_error("tu_launch_grid: depth %d", depth); return X265HIP_EINVAL; }
-    if (nplanes != 1 && !(nplanes == 2 && entry == X265HIP_TU_ENTRY_INTER_CHROMA)) { set_error("tu_launch_grid: %d planes for entry %d", nplanes, entry); return X265HIP_EINVAL; }
+    if (refs && tables) { set_error("tu_launch_grid: entry %d takes no tables", entry); return X265HIP_EINVAL; }
+    if (nplanes != 1 && !(nplanes == 2 && (entry == X265HIP_TU_ENTRY_INTER_CHROMA || entry == X265HIP_TU_ENTRY_INTER_CHROMA_REFS))) { set_error("tu_launch_grid: %d planes for entry %d", nplanes, entry); return X265HIP_EINVAL; }
     if (nblocks < 1) { set_error("tu_launch_grid: nblocks %d", nblocks); return X265HIP_EINVAL; }
     int rc = ensure_device();
     if (rc) return rc;
@@ -1255,6 +1502,73 @@ extern "C" int x265hip_inter_recon_chroma_pair(const x265hip_recon_params* cb, c
     if (!cb || !cr) { set_error("inter_recon_chroma_pair: NULL operand"); return X265HIP_EINVAL; }
     const x265hip_recon_params* pp[2] = { cb, cr };
     return inter_recon_chroma_planes(pp, 2, stream);
+}
+
+// P pictures with several references: one or two planes (luma; Cb and / or Cr) through inter_recon_refs_kernel, grid.y = plane.
+static int inter_recon_refs_planes(const x265hip_recon_refs_params* const* pp, const int nplanes, const bool chroma, void* stream)
+{
+    const char* who = chroma ? "inter_recon_chroma_refs" : "inter_recon_refs";
+    // argument checks first: they need no device
+    const x265hip_recon_params* p = pp[0] ? &pp[0]->base : nullptr;
+    TuRefsArgs ra = {};
+    for (int i = 0; i < nplanes; i++)
+    {
+        const x265hip_recon_refs_params* r = pp[i];
+        if (!r) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
+        const x265hip_recon_params* q = &r->base;
+        if (q->tables) { set_error("%s: tables (scaling lists / the denoiser) are not supported by this stage", who); return X265HIP_EINVAL; }
+        if (!q->fenc || !q->recon || !q->mv || !q->levels || !q->num_sig || !q->dist || !r->ref_idx) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
+        if (r->nrefs < 1 || r->nrefs > X265HIP_MAX_REFS) { set_error("%s: nrefs %d out of [1,%d]", who, r->nrefs, X265HIP_MAX_REFS); return X265HIP_EINVAL; }
+        for (int k = 0; k < r->nrefs; k++)
+            if (!r->fref[k]) { set_error("%s: NULL plane of reference %d", who, k); return X265HIP_EINVAL; }
+        if ((q->width & 63) || (q->height & 63) || q->width <= 0 || q->height <= 0) { set_error("%s: width/height (luma) must be multiples of 64", who); return X265HIP_EINVAL; }
+        if (q->depth != 8 && q->depth != 10 && q->depth != 12) { set_error("%s: depth %d", who, q->depth); return X265HIP_EINVAL; }
+        if (q->level < 0 || q->level > 2) { set_error("%s: level %d (0..2 = 8x8, 16x16, 32x32 luma blocks)", who, q->level); return X265HIP_EINVAL; }
+        if (q->qp < 0 || q->qp > 51 + 6 * (q->depth - 8)) { set_error("%s: qp %d out of range", who, q->qp); return X265HIP_EINVAL; }
+        if (q->width != p->width || q->height != p->height || q->depth != p->depth || q->level != p->level || r->nrefs != pp[0]->nrefs)
+        { set_error("%s: the two planes differ in geometry / depth / level / nrefs", who); return X265HIP_EINVAL; }
+        const int bpp = q->depth == 8 ? 1 : 2;
+        TuArgs& a = ra.aa.p[i];
+        a.fenc = (const uint8_t*)q->fenc; a.fencStrideB = (long)q->fenc_stride * bpp;
+        a.fref = (const uint8_t*)r->fref[0]; a.frefStrideB = (long)q->fref_stride * bpp;
+        a.recon = (uint8_t*)q->recon; a.reconStrideB = (long)q->recon_stride * bpp;
+        a.ctusW = q->width / 64; a.depth = q->depth; a.level = q->level;
+        a.mv = (const int2*)q->mv; a.qp = q->qp; a.intraSlice = (q->intra_slice & ~TU_FLAG_RASTER_ORDER) | (tu_raster_order(chroma) ? TU_FLAG_RASTER_ORDER : 0);
+        a.levels = q->levels; a.numSig = q->num_sig; a.dist = (unsigned long long*)q->dist;
+        a.tab = tu_tables_of(nullptr); a.qpMap = q->qp_map;
+        // entries behind nrefs repeat the last plane: the kernel clamps the index, and no entry of the table is left dangling
+        for (int k = 0; k < X265HIP_MAX_REFS; k++) ra.fref[i][k] = (const uint8_t*)r->fref[k < r->nrefs ? k : r->nrefs - 1];
+        ra.refIdx[i] = r->ref_idx;
+    }
+    ra.nrefs = pp[0]->nrefs;
+    int rc = ensure_device();
+    if (rc) return rc;
+    const int nblocks = (p->width / 64) * (p->height / 64) * (64 >> (2 * p->level));
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = tu_launch_grid(chroma ? X265HIP_TU_ENTRY_INTER_CHROMA_REFS : X265HIP_TU_ENTRY_INTER_REFS, (chroma ? 4 : 8) << p->level, p->depth, false, nplanes, nblocks);
+#define GOR(PX) do { \
+        if (chroma) { \
+            if (p->level == 0) hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 4, true>), dim3(grid, nplanes), dim3(64), 0, s, ra, nblocks); \
+            else if (p->level == 1) hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 8, true>), dim3(grid, nplanes), dim3(64), 0, s, ra, nblocks); \
+            else hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 16, true>), dim3(grid, nplanes), dim3(64), 0, s, ra, nblocks); } \
+        else { \
+            if (p->level == 0) hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 8, false>), dim3(grid), dim3(64), 0, s, ra, nblocks); \
+            else if (p->level == 1) hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 16, false>), dim3(grid), dim3(64), 0, s, ra, nblocks); \
+            else hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 32, false>), dim3(grid), dim3(64), 0, s, ra, nblocks); } } while (0)
+    if (p->depth == 8) GOR(uint8_t); else GOR(uint16_t);
+#undef GOR
+    X265HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int x265hip_inter_recon_refs(const x265hip_recon_refs_params* p, void* stream) { return inter_recon_refs_planes(&p, 1, false, stream); }
+/* one chroma plane of a 4:2:0 picture (the conventions of x265hip_inter_recon_chroma) */
+extern "C" int x265hip_inter_recon_chroma_refs(const x265hip_recon_refs_params* p, void* stream) { return inter_recon_refs_planes(&p, 1, true, stream); }
+/* Cb and Cr of one picture in ONE launch: results are those of two x265hip_inter_recon_chroma_refs calls */
+extern "C" int x265hip_inter_recon_chroma_pair_refs(const x265hip_recon_refs_params* cb, const x265hip_recon_refs_params* cr, void* stream)
+{
+    const x265hip_recon_refs_params* pp[2] = { cb, cr };
+    return inter_recon_refs_planes(pp, 2, true, stream);
 }
 
 extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, void* stream)

@@ -36,6 +36,8 @@ class MEParams(ctypes.Structure):
 
 TU_INTRA_SLICE, TU_SIGN_HIDE = 1, 2        # X265HIP_TU_* flag bits of the TU stages' intra_slice field
 TU_ENTRY_INTER, TU_ENTRY_INTER_BI, TU_ENTRY_INTER_CHROMA, TU_ENTRY_INTER_CHROMA_BI, TU_ENTRY_INTRA = range(5)     # enum x265hip_tu_entry
+TU_ENTRY_INTER_REFS, TU_ENTRY_INTER_CHROMA_REFS = 8, 9                                                              # enum x265hip_tu_entry_refs
+MAX_REFS = 8                               # X265HIP_MAX_REFS
 SURF_I32, SURF_PACKED, SURF_PACKED_T, SURF_PACKED_B = 0, 1, 2, 3
 SURF_GROUP_BYTES_I32, SURF_GROUP_BYTES_PACKED = 1360, 720
 
@@ -82,6 +84,37 @@ class BidirChroma(ctypes.Structure):
         ("fref0_cb", ctypes.c_void_p), ("fref0_cr", ctypes.c_void_p),
         ("fref1_cb", ctypes.c_void_p), ("fref1_cr", ctypes.c_void_p), ("fref_stride_c", ctypes.c_ssize_t),
     ]
+
+
+class RefSelectParams(ctypes.Structure):
+    """x265hip_ref_select_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("nrefs", ctypes.c_int),
+        ("mv", ctypes.c_void_p * MAX_REFS),
+        ("ref_cost", ctypes.c_int32 * MAX_REFS),
+        ("ref_ids", ctypes.c_int * MAX_REFS),
+        ("ref_idx", ctypes.c_void_p), ("ref_id", ctypes.c_void_p),
+        ("mv_out", ctypes.c_void_p), ("cost_out", ctypes.c_void_p),
+    ]
+
+
+class ReconParams(ctypes.Structure):
+    """x265hip_recon_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("qp", ctypes.c_int), ("intra_slice", ctypes.c_int),
+        ("fenc", ctypes.c_void_p), ("fenc_stride", ctypes.c_ssize_t),
+        ("fref", ctypes.c_void_p), ("fref_stride", ctypes.c_ssize_t),
+        ("recon", ctypes.c_void_p), ("recon_stride", ctypes.c_ssize_t),
+        ("mv", ctypes.c_void_p), ("levels", ctypes.c_void_p), ("num_sig", ctypes.c_void_p), ("dist", ctypes.c_void_p),
+        ("tables", ctypes.c_void_p), ("qp_map", ctypes.c_void_p),
+    ]
+
+
+class ReconRefsParams(ctypes.Structure):
+    """x265hip_recon_refs_params (include/x265hip.h)."""
+    _fields_ = [("base", ReconParams), ("nrefs", ctypes.c_int), ("fref", ctypes.c_void_p * MAX_REFS), ("ref_idx", ctypes.c_void_p)]
 
 
 class IntraPictureParams(ctypes.Structure):
@@ -315,6 +348,62 @@ def bidir_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, f
     f = lib().x265hip_bidir_decide
     f.argtypes = [ctypes.POINTER(BidirParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_bidir_decide")
+
+
+def ref_cost_bits(nrefs, lam=4):
+    """lambda x (m_listSelBits[0] + MVP_IDX_BITS + getTUBits(r, nrefs)) of a P slice's 2Nx2N for r = 0 .. nrefs - 1 (search.cpp:2403-2404,
+    search.h:246-249): (8) for one reference, (12, 16, 20, 20) for four at lambda 4."""
+    return tuple(int(lam) * (1 + 1 + r + (1 if r < nrefs - 1 else 0)) for r in range(nrefs))
+
+
+def ref_select(depth, width, height, level, mvs, ref_cost, ref_idx, mv_out, ref_id=None, cost_out=None, ref_ids=None, stream=None):
+    """x265hip_ref_select: the reference of every block of a P picture from the records of the per-reference refinements.  mvs: the
+    nrefs record tensors in list order; ref_cost: nrefs ints; ref_ids: the picture ids ref_id gets (default 0 .. nrefs - 1)."""
+    p = RefSelectParams()
+    p.depth, p.width, p.height, p.level, p.nrefs = depth, width, height, level, len(mvs)
+    ids = range(len(mvs)) if ref_ids is None else ref_ids
+    for r, (m, c, i) in enumerate(zip(mvs[:MAX_REFS], ref_cost, ids)):
+        p.mv[r], p.ref_cost[r], p.ref_ids[r] = m.data_ptr(), int(c), int(i)
+    p.ref_idx, p.ref_id, p.mv_out, p.cost_out = ref_idx.data_ptr(), _p(ref_id), mv_out.data_ptr(), _p(cost_out)
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_ref_select
+    f.argtypes = [ctypes.POINTER(RefSelectParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_ref_select")
+
+
+def recon_refs_params(base, frefs, ref_idx):
+    """A ReconRefsParams from a filled ReconParams (its fref is ignored), the nrefs plane ADDRESSES of sample (0,0) and the ref_idx tensor."""
+    q = ReconRefsParams()
+    q.base = base                      # copied into the record
+    q.nrefs = len(frefs)
+    for r, a in enumerate(frefs[:MAX_REFS]):
+        q.fref[r] = a
+    q.ref_idx = ref_idx.data_ptr()
+    return q
+
+
+def inter_recon_refs(q, stream=None):
+    """x265hip_inter_recon_refs on a ReconRefsParams record."""
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_inter_recon_refs
+    f.argtypes = [ctypes.POINTER(ReconRefsParams), ctypes.c_void_p]
+    check(f(ctypes.byref(q), s), "x265hip_inter_recon_refs")
+
+
+def inter_recon_chroma_refs(q, stream=None):
+    """x265hip_inter_recon_chroma_refs: one chroma plane of a 4:2:0 picture."""
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_inter_recon_chroma_refs
+    f.argtypes = [ctypes.POINTER(ReconRefsParams), ctypes.c_void_p]
+    check(f(ctypes.byref(q), s), "x265hip_inter_recon_chroma_refs")
+
+
+def inter_recon_chroma_pair_refs(cb, cr, stream=None):
+    """x265hip_inter_recon_chroma_pair_refs: Cb and Cr in one launch."""
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_inter_recon_chroma_pair_refs
+    f.argtypes = [ctypes.POINTER(ReconRefsParams), ctypes.POINTER(ReconRefsParams), ctypes.c_void_p]
+    check(f(ctypes.byref(cb), ctypes.byref(cr), s), "x265hip_inter_recon_chroma_pair_refs")
 
 
 def intra_picture_waves(width, height):

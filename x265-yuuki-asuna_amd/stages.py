@@ -14,16 +14,7 @@ from . import hipabi
 from .pipeline import PUS_PER_CTU, DevicePicture
 
 
-class ReconParams(ctypes.Structure):
-    _fields_ = [
-        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
-        ("qp", ctypes.c_int), ("intra_slice", ctypes.c_int),
-        ("fenc", ctypes.c_void_p), ("fenc_stride", ctypes.c_ssize_t),
-        ("fref", ctypes.c_void_p), ("fref_stride", ctypes.c_ssize_t),
-        ("recon", ctypes.c_void_p), ("recon_stride", ctypes.c_ssize_t),
-        ("mv", ctypes.c_void_p), ("levels", ctypes.c_void_p), ("num_sig", ctypes.c_void_p), ("dist", ctypes.c_void_p),
-        ("tables", ctypes.c_void_p), ("qp_map", ctypes.c_void_p),
-    ]
+ReconParams = hipabi.ReconParams          # x265hip_recon_params: the record lives beside ReconRefsParams, which embeds it
 
 
 def _tu_part(stage, ctu_row0, ctu_rows):
@@ -172,6 +163,45 @@ class InterReconChroma:
         f = hipabi.lib().x265hip_inter_recon_chroma_pair
         f.argtypes = [ctypes.POINTER(ReconParams), ctypes.POINTER(ReconParams), ctypes.c_void_p]
         hipabi.check(f(ctypes.byref(ps[0]), ctypes.byref(ps[1]), s), "x265hip_inter_recon_chroma_pair")
+
+
+class InterReconRefs(InterRecon):
+    """The inter TU stage of a P picture with several references (x265hip_inter_recon_refs): block blk is predicted from
+    refs[ref_idx[blk]]; everything else is InterRecon's contract.  No scaling-list / denoiser tables."""
+
+    def run(self, cur: DevicePicture, refs, recon_plane, mv, ref_idx, stream=None):
+        """refs: the reference pictures in list order (one geometry); ref_idx: int8 [ctu][blocks] (RefSelect.ref_idx)."""
+        es = 1 if self.depth == 8 else 2
+        assert all(r.stride == refs[0].stride and r.org == refs[0].org for r in refs)
+        p = ReconParams()
+        p.depth, p.width, p.height, p.level, p.qp, p.intra_slice = self.depth, self.w64, self.h64, self.level, self.qp, self.intra
+        p.fenc, p.fenc_stride = cur.t.data_ptr() + cur.org * es, cur.stride
+        p.fref, p.fref_stride = None, refs[0].stride
+        p.recon, p.recon_stride = recon_plane.data_ptr() + cur.org * es, cur.stride
+        p.mv, p.levels, p.num_sig, p.dist = mv.data_ptr(), self.levels.data_ptr(), self.num_sig.data_ptr(), self.dist.data_ptr()
+        p.tables = ctypes.addressof(self.tables) if self.tables is not None else None          # refused by the entry
+        p.qp_map = hipabi._p(self.qp_map)
+        hipabi.inter_recon_refs(hipabi.recon_refs_params(p, [r.t.data_ptr() + r.org * es for r in refs], ref_idx), stream)
+
+
+class InterReconChromaRefs(InterReconChroma):
+    """One chroma plane of a P picture with several references (x265hip_inter_recon_chroma_refs), run_pair: Cb and Cr in one launch."""
+
+    def params_refs(self, fenc, frefs, recon, stride, org, mv, ref_idx):
+        es = 1 if self.depth == 8 else 2
+        p = self.params(fenc, frefs[0], recon, stride, org, mv)
+        p.fref = None
+        return hipabi.recon_refs_params(p, [f.data_ptr() + org * es for f in frefs], ref_idx)
+
+    def run(self, fenc, frefs, recon, stride, org, mv, ref_idx, stream=None):
+        """frefs: this plane (Cb or Cr) of every reference picture, list order."""
+        hipabi.inter_recon_chroma_refs(self.params_refs(fenc, frefs, recon, stride, org, mv, ref_idx), stream)
+
+    @staticmethod
+    def run_pair(stages, fencs, frefs, recons, stride, org, mv, ref_idx, stream=None):
+        """stages = the two planes' objects; frefs = ([Cb of every reference], [Cr of every reference])."""
+        qs = [st.params_refs(fenc, fr, recon, stride, org, mv, ref_idx) for st, fenc, fr, recon in zip(stages, fencs, frefs, recons)]
+        hipabi.inter_recon_chroma_pair_refs(qs[0], qs[1], stream)
 
 
 class InterReconChromaBi(InterReconChroma):
@@ -340,6 +370,12 @@ class Deblock:
         """A B picture: the boundary strengths compare (ref0, ref1) x (mv0, mv1) per block (deblock.cpp:217-247); ref0 / ref1 = int8 picture
         ids per block, -1 = list unused (what BidirDecide leaves)."""
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv0, num_sig, self.bs_ver, self.bs_hor, slice_b=True, mv1=mv1, ref0=ref0, ref1=ref1)
+        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
+
+    def run_refs(self, plane, pic: DevicePicture, mv, ref_id, num_sig):
+        """A P picture with several references: two blocks predicted from different pictures get Bs 1 whatever their vectors
+        (deblock.cpp:217-247 in a P slice); ref_id = int8 picture ids per block (what RefSelect leaves)."""
+        hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv, num_sig, self.bs_ver, self.bs_hor, slice_b=False, ref0=ref_id)
         hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
 
     def prepare_intra(self):
@@ -1464,6 +1500,169 @@ class BFramePipeline:
         return out
 
 
+class RefSelect:
+    """The reference of every block of a P picture with several references (x265hip_ref_select; reference Search::predInterSearch's
+    uni-directional loop, search.cpp:2386-2471): from the records of the per-reference refinements, per block of the TU stages' grid,
+    the list index with the smallest cost + ref_cost, the lowest index on a tie.  Owns ref_idx int8 [ctu][blocks] (what InterReconRefs
+    takes), ref_id int8 [ctu][blocks] (what Deblock.run_refs takes), mv_out int32 [ctu*85][2] (the level's entries) and, with want_cost,
+    cost_out int32 [ctu][blocks][max_refs] (the first nrefs * blocks entries hold [ctu][blocks][nrefs] of a run with nrefs references)."""
+
+    def __init__(self, nctu, w64, h64, depth, level, device, max_refs=4, want_cost=False):
+        import torch
+        if not 1 <= max_refs <= hipabi.MAX_REFS:
+            raise ValueError(f"RefSelect: max_refs {max_refs} out of [1, {hipabi.MAX_REFS}]")
+        self.nctu, self.w64, self.h64, self.depth, self.level, self.max_refs = nctu, w64, h64, depth, level, max_refs
+        self.nblk = (64 // (8 << level)) ** 2
+        self.ref_idx = torch.zeros(nctu * self.nblk, dtype=torch.int8, device=device)
+        self.ref_id = torch.zeros(nctu * self.nblk, dtype=torch.int8, device=device)
+        self.mv_out = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device)
+        self.cost_out = torch.zeros(nctu * self.nblk * max_refs, dtype=torch.int32, device=device) if want_cost else None
+
+    def run(self, mvs, ref_cost=None, ref_ids=None, stream=None):
+        """mvs: the SubpelRefine outputs, list order (1 .. max_refs of them); ref_cost: one int per reference, None = lambda 4 x the bits of
+        the index (hipabi.ref_cost_bits); ref_ids: the picture ids ref_id gets, None = the list indices."""
+        n = len(mvs)
+        if not 1 <= n <= self.max_refs:
+            raise ValueError(f"RefSelect: {n} references for max_refs {self.max_refs}")
+        cost = hipabi.ref_cost_bits(n) if ref_cost is None else tuple(int(c) for c in ref_cost)
+        if len(cost) != n or (ref_ids is not None and len(ref_ids) != n):
+            raise ValueError("RefSelect: ref_cost / ref_ids need one entry per reference")
+        hipabi.ref_select(self.depth, self.w64, self.h64, self.level, mvs, cost, self.ref_idx, self.mv_out, ref_id=self.ref_id,
+                          cost_out=self.cost_out, ref_ids=ref_ids, stream=stream)
+
+    def checksum(self):
+        import torch
+        return {"ref_idx": int(self.ref_idx.to(torch.int64).sum().item()), "mv_out": int(self.mv_out.to(torch.int64).sum().item())}
+
+
+class MultiRefFramePipeline:
+    """One P picture with several references on the device, the stages of FramePipeline.run with a reference list:
+        per reference: exhaustive search (best mv) -> sub-pel refinement;  reference selection (RefSelect);  luma + 4:2:0 chroma
+        reconstruction of every block from its chosen picture;  boundary strengths that compare the blocks' pictures + luma / chroma
+        deblocking;  SAO (statistics, x265hip_sao_rdo or the distortion-only stand-in, application);  border extension.
+    The constructor switches mean what they mean in BFramePipeline.  Everything runs serially on the caller's stream."""
+
+    def __init__(self, w64, h64, depth, device, max_refs=4, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False,
+                 sao_apply=False, sign_hide=False, subpel_planes=False, sao_rdo=None, chroma_satd=False, ref_cost=None, want_cost=False):
+        """ref_cost: one int per reference of every run() (lambda x the bits of the reference index), None = hipabi.ref_cost_bits of the
+        number of references a run() is given."""
+        import torch
+        from .pipeline import MotionSearch, SubpelRefine
+        if chroma_satd and not chroma:
+            raise ValueError("MultiRefFramePipeline: chroma_satd needs chroma=True")
+        self.depth, self.qp, self.chroma, self.max_refs = depth, qp, chroma, max_refs
+        self.ref_cost = None if ref_cost is None else tuple(int(c) for c in ref_cost)
+        self.msl = [MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True) for _ in range(max_refs)]
+        self.spl = [SubpelRefine(m, subme, device, phase_planes=subpel_planes, chroma_satd=chroma_satd) for m in self.msl]
+        self.ms = self.msl[0]                # geometry (nctu, w64, h64) for the helpers shared with FramePipeline
+        self.rs = RefSelect(self.ms.nctu, w64, h64, depth, level, device, max_refs=max_refs, want_cost=want_cost)
+        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
+        self.rc = InterReconRefs(self.ms.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        self.db = Deblock(w64, h64, depth, level, max(qp - 6 * (depth - 8), 0), device) if deblock else None
+        self.sao = Sao(w64, h64, depth, device) if sao else None
+        self.recon, self.recon_c, self.out, self.out_c = None, None, None, None
+        if chroma:
+            qpc = chroma_quant_qp(qp, depth)
+            self.rc_c = [InterReconChromaRefs(self.ms.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
+            self.sao_c = [Sao(w64 // 2, h64 // 2, depth, device, ctu=(32, 32), plane_offset=2) for _ in range(2)] if sao else None
+        self.sao_apply = bool(sao and sao_apply)
+        self.sao_rdo = sao_rdo if (sao and sao_apply) else None
+        if self.sao_rdo is not None:
+            self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
+            self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
+
+    def set_qp_maps(self, maps):
+        """Per-block QPs for the following run() calls (see FramePipeline.set_qp_maps); None = the picture-wide qp again."""
+        _set_qp_maps(self, maps, self.rc, self.rc_c if self.chroma else [])
+
+    def run(self, cur: DevicePicture, refs, mark=None):
+        """refs: 1 .. max_refs reference pictures, nearest first = list order (extended borders; with chroma=True also their Cb / Cr
+        planes).  Returns the luma plane of the coded picture; mark(name), if given, is called after every stage."""
+        import torch
+        _qp_maps_run_check(self)
+        mark = mark or (lambda name: None)
+        refs = list(refs)
+        if not 1 <= len(refs) <= self.max_refs:
+            raise ValueError(f"MultiRefFramePipeline: {len(refs)} references for max_refs {self.max_refs}")
+        if self.ref_cost is not None and len(self.ref_cost) != len(refs):
+            raise ValueError(f"MultiRefFramePipeline: ref_cost has {len(self.ref_cost)} entries for {len(refs)} references")
+        if self.recon is None:
+            self.recon = torch.zeros_like(cur.t)
+        for r, ref in enumerate(refs):
+            self.msl[r].reset()
+            self.msl[r].search(cur, ref)
+            mark("me%d" % r)
+            self.spl[r].run(cur, ref)
+            mark("subpel%d" % r)
+        self.rs.run([self.spl[r].out for r in range(len(refs))], ref_cost=self.ref_cost)
+        mark("ref_select")
+        mv, idx = self.rs.mv_out, self.rs.ref_idx
+        self.rc.run(cur, refs, self.recon, mv, idx)
+        mark("recon")
+        if self.chroma:
+            if self.recon_c is None:
+                self.recon_c = [torch.zeros_like(p) for p in cur.c]
+            InterReconChromaRefs.run_pair(self.rc_c, cur.c, [[ref.c[i] for ref in refs] for i in range(2)], self.recon_c, cur.stride_c, cur.org_c, mv, idx)
+            mark("recon_chroma")
+        if self.db is not None:
+            self.db.run_refs(self.recon, cur, mv, self.rs.ref_id, self.rc.num_sig)
+            if self.chroma:
+                hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
+                                      self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
+            mark("deblock")
+        final, final_c = self.recon, self.recon_c
+        if self.sao is not None and self.sao_apply and self.out is None:
+            self.out = torch.zeros_like(cur.t)
+            self.out_c = [torch.zeros_like(p) for p in cur.c] if self.chroma else None
+        if self.sao_rdo is not None:
+            planes = FramePipeline._sao_planes(self, cur)
+            hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes])
+            mark("sao_stats")
+            FramePipeline._sao_rdo(self)
+            mark("sao_rdo")
+            hipabi.sao_apply_planes(self.depth, planes)
+            final, final_c = self.out, self.out_c
+            mark("sao_apply")
+        elif self.sao is not None:
+            self.sao.stats(cur, self.recon, cur.stride, cur.org)
+            if self.chroma:
+                for i in range(2):
+                    self.sao_c[i].stats(None, self.recon_c[i], cur.stride_c, cur.org_c, src_plane=cur.c[i])
+            mark("sao_stats")
+            if self.sao_apply:
+                self.sao.decide()
+                self.sao.apply(self.recon, cur.stride, cur.org, self.out)
+                final = self.out
+                if self.chroma:
+                    for i in range(2):
+                        self.sao_c[i].decide()
+                        self.sao_c[i].apply(self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i])
+                    final_c = self.out_c
+                mark("sao_apply")
+        extend_border_picture([final] + (list(final_c) if self.chroma else []), cur)
+        mark("border")
+        self.final, self.final_c = final, final_c
+        return final
+
+    def final_planes(self):
+        """[Y, Cb, Cr] (or [Y]) of the picture run() coded last."""
+        return [self.final] + (list(self.final_c) if self.chroma else [])
+
+    def checksum(self):
+        import torch
+        out = {}
+        for r in range(self.max_refs):
+            out.update({"%s%d" % (k, r): v for k, v in self.msl[r].checksum().items()})
+            out.update({"%s%d" % (k, r): v for k, v in self.spl[r].checksum().items()})
+        out.update(self.rs.checksum())
+        out.update(self.rc.checksum())
+        if self.chroma:
+            for i in range(2):
+                out.update({"%s_c%d" % (k, i): v for k, v in InterRecon.checksum(self.rc_c[i]).items()})
+        out["recon"] = int(self.final.to(torch.int64).sum().item())
+        return out
+
+
 class IntraPicture:
     """One I picture on the TU stages' block grid (x265hip_intra_picture; reference Predict::initIntraNeighbors / fillReferenceSamples /
     initAdiPattern, predict.cpp:600-876, Search::checkIntraInInter, search.cpp:1344-1446, and the coding contract of
@@ -1625,11 +1824,13 @@ class MiniGop:
     """Display order in, coding order inside: anchor pictures 0, gop, 2 gop, ... form the P chain (each coded by p_step.run from the
     previous anchor's OUTPUT), and the pictures between two anchors are B pictures coded by b_step.run(cur, previous anchor, this
     anchor) once the later anchor is done.  B pictures are not referenced.  p_step: a FramePipeline, b_step: a BFramePipeline of the same
-    geometry and chroma setting; i_step: an IFramePipeline of that geometry that codes picture 0, or None."""
+    geometry and chroma setting; i_step: an IFramePipeline of that geometry that codes picture 0, or None.
+    p_refs > 1: p_step is a MultiRefFramePipeline and every anchor is coded by p_step.run(cur, [up to p_refs previous coded anchors,
+    newest first]); B pictures keep using the two anchors around them."""
 
-    def __init__(self, p_step, b_step, gop, i_step=None):
-        assert gop >= 1
-        self.p, self.b, self.gop, self.i = p_step, b_step, int(gop), i_step
+    def __init__(self, p_step, b_step, gop, i_step=None, p_refs=1):
+        assert gop >= 1 and p_refs >= 1
+        self.p, self.b, self.gop, self.i, self.p_refs = p_step, b_step, int(gop), i_step, int(p_refs)
 
     def run(self, pictures):
         """pictures: DevicePictures in display order; picture 0 is the first anchor - coded by i_step where there is one (its output is
@@ -1643,8 +1844,12 @@ class MiniGop:
             self.i.run(pictures[0])
             out[0] = keep(self.i.final_planes())
             prev = pictures[0].like(out[0])
+        anchors = [prev]                 # coded anchors, newest first (p_refs > 1)
         for a in range(self.gop, len(pictures), self.gop):
-            self.p.run(pictures[a], prev)
+            if self.p_refs > 1:
+                self.p.run(pictures[a], anchors[:self.p_refs])
+            else:
+                self.p.run(pictures[a], prev)
             out[a] = keep(self.p.final_planes())
             order.append(a)
             anchor = pictures[a].like(out[a])
@@ -1653,4 +1858,5 @@ class MiniGop:
                 out[k] = keep(self.b.final_planes())
                 order.append(k)
             prev = anchor
+            anchors.insert(0, anchor)
         return order, out

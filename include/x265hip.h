@@ -212,6 +212,15 @@ typedef struct x265hip_subpel_chroma
 } x265hip_subpel_chroma;
 int x265hip_subpel_refine_chroma(const x265hip_subpel_params* p, const x265hip_subpel_chroma* c, void* stream);
 
+/* The same refinement for a subset of the PU sizes: bit L of level_mask set = the PUs of size 8 << L are refined (bit 0: the 64 8x8 PUs of
+ * a CTU, bit 3: its 64x64 PU).  Exactly the `out` records of the selected levels are written, in the layout above (ctu * 85 + base(L) + pu,
+ * base = 0 / 64 / 80 / 84); every other record of `out` is left as it is, so launches with disjoint masks into one buffer add up to the
+ * result of x265hip_subpel_refine_chroma(p, c, stream), which IS this call with level_mask 15.  c may be NULL (luma only).  A caller that
+ * waits for one level only (the reconstruction reads the level it codes) launches that level first and the rest wherever the device has
+ * room.  One bit set: a kernel compiled for that level alone, grid (ctus, 1); several bits: one launch, grid (ctus, bits set).
+ * level_mask == 0 or > 15 is X265HIP_EINVAL, checked with the other arguments before the device is asked for. */
+int x265hip_subpel_refine_levels(const x265hip_subpel_params* p, const x265hip_subpel_chroma* c, unsigned level_mask, void* stream);
+
 /* Fused inter prediction + residual coding round trip of every NxN block (N = 8 << level, level 0..2), the
  * caller sequence of SURVEY section 8(f) item 2: Predict::predInterLumaPixel (predict.cpp:245-265),
  * calcresidual, Quant::transformNxN without RDOQ (quant.cpp:397-480, flat scaling lists; sign-bit hiding optional),

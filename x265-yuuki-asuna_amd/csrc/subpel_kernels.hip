@@ -29,6 +29,7 @@ struct SubpelArgs
     int hpelIters, hpelDirs, qpelIters, qpelDirs, hpelSatd;
     int2* out;                       // {cost, qx | qy << 16} per PU, [ctu][85]
     const uint8_t* planes; long planeBytes;      // phase planes of fref (x265hip_phase_planes), sample (0,0) of phase 1; NULL = interpolate
+    unsigned levelTab;               // multi-level launches: the PU level of grid row y in bits [2y, 2y + 2) (0xe4 = all four, in order)
 };
 
 // The chroma operands of the chroma flavour (x265hip_subpel_refine_chroma): 4:2:0 Cb / Cr planes of the source and the reference picture,
@@ -445,12 +446,14 @@ __device__ __forceinline__ void subpel_level(const SubpelArgs& a, uint8_t* smemR
     }
 }
 
+// Several PU levels in ONE launch (x265hip_subpel_refine_levels with more than one bit set; all four = x265hip_subpel_refine): grid row y
+// refines the level the table in the arguments names for it, so a launch of three levels has three rows and no idle workgroups.
 template <typename Px, bool PL = false>
 __global__ void __launch_bounds__(256) subpel_refine_kernel(SubpelArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smemRaw[];
     __shared__ SpShared sh;
-    switch (blockIdx.y)                                   // all four PU levels of a CTU run concurrently
+    switch ((a.levelTab >> (2 * blockIdx.y)) & 3)         // the selected PU levels of a CTU run concurrently
     {
     case 0: subpel_level<Px, 0, PL>(a, smemRaw, sh); break;
     case 1: subpel_level<Px, 1, PL>(a, smemRaw, sh); break;
@@ -465,13 +468,114 @@ __global__ void __launch_bounds__(256) subpel_refine_chroma_kernel(SubpelArgs a,
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smemRaw[];
     __shared__ SpShared sh;
-    switch (blockIdx.y)
+    switch ((a.levelTab >> (2 * blockIdx.y)) & 3)
     {
     case 0: subpel_level<Px, 0, PL, true>(a, smemRaw, sh, ca); break;
     case 1: subpel_level<Px, 1, PL, true>(a, smemRaw, sh, ca); break;
     case 2: subpel_level<Px, 2, PL, true>(a, smemRaw, sh, ca); break;
     default: subpel_level<Px, 3, PL, true>(a, smemRaw, sh, ca); break;
     }
+}
+
+// ONE PU level per launch (a single bit in the mask of x265hip_subpel_refine_levels), grid (nctu, 1): the switch-free body as a kernel of
+// its own, so the level a caller waits for is compiled to its own register count instead of the maximum over the four levels.
+template <typename Px, int LEVEL, bool PL>
+__global__ void __launch_bounds__(256) subpel_refine_level_kernel(SubpelArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smemRaw[];
+    __shared__ SpShared sh;
+    subpel_level<Px, LEVEL, PL>(a, smemRaw, sh);
+}
+
+template <typename Px, int LEVEL, bool PL>
+__global__ void __launch_bounds__(256) subpel_refine_chroma_level_kernel(SubpelArgs a, SubpelChromaArgs ca)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smemRaw[];
+    __shared__ SpShared sh;
+    subpel_level<Px, LEVEL, PL, true>(a, smemRaw, sh, ca);
+}
+
+// Bytes of dynamic LDS the patches of the selected levels need (the flavours that interpolate; the phase-plane flavours stage nothing)
+template <typename Px>
+static size_t sp_patch_bytes(const unsigned mask)
+{
+    const size_t per[4] = { (size_t)SpGeom<Px, 0>::PSZ * 64, (size_t)SpGeom<Px, 1>::PSZ * 16, (size_t)SpGeom<Px, 2>::PSZ * 4, (size_t)SpGeom<Px, 3>::PSZ };
+    size_t n = 0;
+    for (int l = 0; l < 4; l++)
+        if (((mask >> l) & 1) && per[l] > n) n = per[l];
+    return n * sizeof(Px);
+}
+
+constexpr size_t SP_LDS_DEFAULT_MAX = 65536;             // dynamic LDS past this needs hipFuncAttributeMaxDynamicSharedMemorySize (16-bit level-0 patches)
+
+template <typename Px, int LEVEL, bool PL, bool CH>
+static hipError_t sp_launch_level(const SubpelArgs& a, const SubpelChromaArgs& ca, const int nctu, const size_t lds, hipStream_t s)
+{
+    static bool attr = false;
+    if constexpr (CH)
+    {
+        if (lds > SP_LDS_DEFAULT_MAX && !attr)
+        {
+            const hipError_t e = hipFuncSetAttribute((const void*)subpel_refine_chroma_level_kernel<Px, LEVEL, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            attr = true;
+        }
+        hipLaunchKernelGGL((subpel_refine_chroma_level_kernel<Px, LEVEL, PL>), dim3(nctu, 1), dim3(256), lds, s, a, ca);
+    }
+    else
+    {
+        if (lds > SP_LDS_DEFAULT_MAX && !attr)
+        {
+            const hipError_t e = hipFuncSetAttribute((const void*)subpel_refine_level_kernel<Px, LEVEL, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            attr = true;
+        }
+        hipLaunchKernelGGL((subpel_refine_level_kernel<Px, LEVEL, PL>), dim3(nctu, 1), dim3(256), lds, s, a);
+    }
+    return hipSuccess;
+}
+
+// The launch of one flavour (sample type, phase planes, chroma SATD) for the levels of `mask`
+template <typename Px, bool PL, bool CH>
+static hipError_t sp_launch(SubpelArgs a, const SubpelChromaArgs& ca, const unsigned mask, const int nctu, hipStream_t s)
+{
+    const size_t lds = PL ? 0 : sp_patch_bytes<Px>(mask);
+    if (!(mask & (mask - 1)))                             // one level: its own instantiation
+    {
+        switch (mask)
+        {
+        case 1: return sp_launch_level<Px, 0, PL, CH>(a, ca, nctu, lds, s);
+        case 2: return sp_launch_level<Px, 1, PL, CH>(a, ca, nctu, lds, s);
+        case 4: return sp_launch_level<Px, 2, PL, CH>(a, ca, nctu, lds, s);
+        default: return sp_launch_level<Px, 3, PL, CH>(a, ca, nctu, lds, s);
+        }
+    }
+    int rows = 0;
+    a.levelTab = 0;
+    for (unsigned l = 0; l < 4; l++)
+        if ((mask >> l) & 1) a.levelTab |= l << (2 * rows++);
+    static bool attr = false;                             // the attribute only ever grows: level 0 is the largest and the only one past the default
+    if constexpr (CH)
+    {
+        if (lds > SP_LDS_DEFAULT_MAX && !attr)
+        {
+            const hipError_t e = hipFuncSetAttribute((const void*)subpel_refine_chroma_kernel<Px, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            attr = true;
+        }
+        hipLaunchKernelGGL((subpel_refine_chroma_kernel<Px, PL>), dim3(nctu, rows), dim3(256), lds, s, a, ca);
+    }
+    else
+    {
+        if (lds > SP_LDS_DEFAULT_MAX && !attr)
+        {
+            const hipError_t e = hipFuncSetAttribute((const void*)subpel_refine_kernel<Px, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            attr = true;
+        }
+        hipLaunchKernelGGL((subpel_refine_kernel<Px, PL>), dim3(nctu, rows), dim3(256), lds, s, a);
+    }
+    return hipSuccess;
 }
 
 } // namespace x265hip
@@ -485,12 +589,18 @@ extern "C" int x265hip_subpel_refine(const x265hip_subpel_params* p, void* strea
 
 extern "C" int x265hip_subpel_refine_chroma(const x265hip_subpel_params* p, const x265hip_subpel_chroma* c, void* stream)
 {
+    return x265hip_subpel_refine_levels(p, c, 15, stream);
+}
+
+extern "C" int x265hip_subpel_refine_levels(const x265hip_subpel_params* p, const x265hip_subpel_chroma* c, unsigned level_mask, void* stream)
+{
     // every argument check runs before the device is asked for
     if (!p || !p->fenc || !p->fref || !p->best_in || !p->cost_q || !p->out) { set_error("subpel_refine: NULL operand"); return X265HIP_EINVAL; }
     if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("subpel_refine: width/height must be multiples of 64"); return X265HIP_EINVAL; }
     if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("subpel_refine: depth %d", p->depth); return X265HIP_EINVAL; }
     if (p->subme < 0 || p->subme > 7) { set_error("subpel_refine: subme %d out of [0,7]", p->subme); return X265HIP_EINVAL; }
     if (p->phase_planes && p->phase_plane_samples <= 0) { set_error("subpel_refine: phase_plane_samples"); return X265HIP_EINVAL; }
+    if (level_mask == 0 || level_mask > 15) { set_error("subpel_refine_levels: level_mask %u out of [1,15]", level_mask); return X265HIP_EINVAL; }
     if (c)                               // validated at every subme, also where it is then ignored (subme <= 2)
     {
         if (!c->fenc_cb || !c->fenc_cr || !c->fref_cb || !c->fref_cr) { set_error("subpel_refine_chroma: NULL chroma plane"); return X265HIP_EINVAL; }
@@ -509,46 +619,26 @@ extern "C" int x265hip_subpel_refine_chroma(const x265hip_subpel_params* p, cons
     a.hpelIters = wl[p->subme][0]; a.hpelDirs = wl[p->subme][1]; a.qpelIters = wl[p->subme][2]; a.qpelDirs = wl[p->subme][3]; a.hpelSatd = wl[p->subme][4];
     a.out = (int2*)p->out;
     a.planes = (const uint8_t*)p->phase_planes; a.planeBytes = (long)p->phase_plane_samples * bpp;
+    a.levelTab = 0xe4;
     const int nctu = a.ctusW * (p->height / 64);
     hipStream_t s = (hipStream_t)stream;
-    // one launch: grid.y = PU level; LDS sized for level 0 (64 patches of 23 rows), the largest
-    const size_t lds = (size_t)(bpp == 1 ? SpGeom<uint8_t, 0>::PSZ : SpGeom<uint16_t, 0>::PSZ) * 64 * bpp;
-    static_assert(SpGeom<uint8_t, 0>::PSZ * 64 >= SpGeom<uint8_t, 1>::PSZ * 16 && SpGeom<uint8_t, 0>::PSZ * 64 >= SpGeom<uint8_t, 2>::PSZ * 4
-                  && SpGeom<uint8_t, 0>::PSZ * 64 >= SpGeom<uint8_t, 3>::PSZ, "level 0 is the largest");
-    static_assert(SpGeom<uint16_t, 0>::PSZ * 64 >= SpGeom<uint16_t, 1>::PSZ * 16 && SpGeom<uint16_t, 0>::PSZ * 64 >= SpGeom<uint16_t, 2>::PSZ * 4
-                  && SpGeom<uint16_t, 0>::PSZ * 64 >= SpGeom<uint16_t, 3>::PSZ, "level 0 is the largest");
-    if (c && p->subme >= 3)              // subme <= 2: bChromaSATD is off (motion.cpp:212), the luma-only launch below
+    // one launch: grid.y = the selected PU levels (one level: its own kernel); dynamic LDS for the patches of the largest of them
+    SubpelChromaArgs ca = SubpelChromaArgs();
+    const bool ch = c && p->subme >= 3;  // subme <= 2: bChromaSATD is off (motion.cpp:212), the luma-only launch
+    if (ch)
     {
-        SubpelChromaArgs ca;
         ca.fencC[0] = (const uint8_t*)c->fenc_cb; ca.fencC[1] = (const uint8_t*)c->fenc_cr; ca.fencStrideCB = (long)c->fenc_stride_c * bpp;
         ca.frefC[0] = (const uint8_t*)c->fref_cb; ca.frefC[1] = (const uint8_t*)c->fref_cr; ca.frefStrideCB = (long)c->fref_stride_c * bpp;
-        if (a.planes)
-        {
-            if (p->depth == 8) hipLaunchKernelGGL((subpel_refine_chroma_kernel<uint8_t, true>), dim3(nctu, 4), dim3(256), 0, s, a, ca);
-            else hipLaunchKernelGGL((subpel_refine_chroma_kernel<uint16_t, true>), dim3(nctu, 4), dim3(256), 0, s, a, ca);
-        }
-        else if (p->depth == 8)
-            hipLaunchKernelGGL((subpel_refine_chroma_kernel<uint8_t, false>), dim3(nctu, 4), dim3(256), lds, s, a, ca);
-        else
-        {
-            static bool attrC = false;
-            if (!attrC) { X265HIP_TRY(hipFuncSetAttribute((const void*)subpel_refine_chroma_kernel<uint16_t, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attrC = true; }
-            hipLaunchKernelGGL((subpel_refine_chroma_kernel<uint16_t, false>), dim3(nctu, 4), dim3(256), lds, s, a, ca);
-        }
     }
-    else if (a.planes)
-    {
-        if (p->depth == 8) hipLaunchKernelGGL((subpel_refine_kernel<uint8_t, true>), dim3(nctu, 4), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((subpel_refine_kernel<uint16_t, true>), dim3(nctu, 4), dim3(256), 0, s, a);
-    }
-    else if (p->depth == 8)
-        hipLaunchKernelGGL(subpel_refine_kernel<uint8_t>, dim3(nctu, 4), dim3(256), lds, s, a);
+    const bool pl = a.planes != nullptr;
+    hipError_t e;
+    if (bpp == 1)
+        e = ch ? (pl ? sp_launch<uint8_t, true, true>(a, ca, level_mask, nctu, s) : sp_launch<uint8_t, false, true>(a, ca, level_mask, nctu, s))
+               : (pl ? sp_launch<uint8_t, true, false>(a, ca, level_mask, nctu, s) : sp_launch<uint8_t, false, false>(a, ca, level_mask, nctu, s));
     else
-    {
-        static bool attr = false;
-        if (!attr) { X265HIP_TRY(hipFuncSetAttribute((const void*)subpel_refine_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = true; }
-        hipLaunchKernelGGL(subpel_refine_kernel<uint16_t>, dim3(nctu, 4), dim3(256), lds, s, a);
-    }
+        e = ch ? (pl ? sp_launch<uint16_t, true, true>(a, ca, level_mask, nctu, s) : sp_launch<uint16_t, false, true>(a, ca, level_mask, nctu, s))
+               : (pl ? sp_launch<uint16_t, true, false>(a, ca, level_mask, nctu, s) : sp_launch<uint16_t, false, false>(a, ca, level_mask, nctu, s));
+    X265HIP_TRY(e);
     X265HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -287,11 +287,28 @@ def me_fullsearch(depth, width, height, rng, fenc, fenc_stride, fref, fref_strid
     check(lib().x265hip_me_fullsearch(ctypes.byref(p), s), "x265hip_me_fullsearch")
 
 
+def subpel_level_mask(levels):
+    """The level_mask of x265hip_subpel_refine_levels from a mask (int) or an iterable of PU levels 0..3."""
+    if isinstance(levels, int):
+        mask = levels
+    else:
+        mask = 0
+        for l in levels:
+            if not 0 <= int(l) <= 3:
+                raise ValueError(f"subpel level {l} out of [0,3]")
+            mask |= 1 << int(l)
+    if not 1 <= mask <= 15:
+        raise ValueError(f"subpel level mask {mask} out of [1,15]")
+    return mask
+
+
 def subpel_refine(depth, width, height, rng, subme, fenc, fenc_stride, fref, fref_stride, best_in, cost_q, qoff, out,
-                  fenc_off=0, fref_off=0, stream=None, phase_planes=None, chroma=None):
+                  fenc_off=0, fref_off=0, stream=None, phase_planes=None, chroma=None, levels=None):
     """phase_planes: byte tensor with the 15 luma phase planes of the fref buffer (x265hip_phase_planes, same geometry as fref's tensor).
     chroma: None or a dict - fenc (Cb, Cr) and fref (Cb, Cr) tensors, fenc_stride / fref_stride in samples, fenc_org / fref_org = element
-    of sample (0,0); the call then goes to x265hip_subpel_refine_chroma (chroma SATD in every comparison at subme >= 3)."""
+    of sample (0,0); the call then goes to x265hip_subpel_refine_chroma (chroma SATD in every comparison at subme >= 3).
+    levels: None = every PU level in one launch; a mask (bit L = the PUs of size 8 << L) or an iterable of levels = only those, through
+    x265hip_subpel_refine_levels - the other levels' records of `out` stay as they are."""
     es = 1 if depth == 8 else 2
     p = SubpelParams()
     p.depth, p.width, p.height, p.range, p.subme = depth, width, height, rng, subme
@@ -301,11 +318,18 @@ def subpel_refine(depth, width, height, rng, subme, fenc, fenc_stride, fref, fre
     if phase_planes is not None:
         p.phase_planes, p.phase_plane_samples = phase_planes.data_ptr() + fref_off * es, fref.numel() * fref.element_size() // es
     s = current_stream() if stream is None else stream
+    c = None
     if chroma is not None:
         c = SubpelChroma()
         c.fenc_cb, c.fenc_cr = (t.data_ptr() + chroma["fenc_org"] * es for t in chroma["fenc"])
         c.fref_cb, c.fref_cr = (t.data_ptr() + chroma["fref_org"] * es for t in chroma["fref"])
         c.fenc_stride_c, c.fref_stride_c = chroma["fenc_stride"], chroma["fref_stride"]
+    if levels is not None:
+        f = lib().x265hip_subpel_refine_levels
+        f.argtypes = [ctypes.POINTER(SubpelParams), ctypes.POINTER(SubpelChroma), ctypes.c_uint, ctypes.c_void_p]
+        check(f(ctypes.byref(p), None if c is None else ctypes.byref(c), subpel_level_mask(levels), s), "x265hip_subpel_refine_levels")
+        return
+    if c is not None:
         f = lib().x265hip_subpel_refine_chroma
         f.argtypes = [ctypes.POINTER(SubpelParams), ctypes.POINTER(SubpelChroma), ctypes.c_void_p]
         check(f(ctypes.byref(p), ctypes.byref(c), s), "x265hip_subpel_refine_chroma")

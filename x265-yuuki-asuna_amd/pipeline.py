@@ -243,7 +243,9 @@ class SubpelRefine:
             self.planes = torch.empty(15 * nb, dtype=torch.uint8, device=ref.t.device)
         hipabi.phase_planes(self.ms.depth, ref.t, 0, self.planes, ref.stride, nb // (ref.stride * (1 if self.ms.depth == 8 else 2)))
 
-    def run(self, cur: DevicePicture, ref: DevicePicture, prepared=False):
+    def run(self, cur: DevicePicture, ref: DevicePicture, prepared=False, levels=None):
+        """levels: None = all four PU levels in one launch; a mask or an iterable of levels = those records of `out` only
+        (x265hip_subpel_refine_levels), e.g. the level the reconstruction codes first and the others on another stream."""
         ms = self.ms
         if not prepared:
             self.prepare(ref)
@@ -257,7 +259,7 @@ class SubpelRefine:
                 raise ValueError(f"SubpelRefine(chroma_satd=True): range {ms.range} reaches past the {F.CHROMA_MARGIN_Y}-row chroma margin")
             chroma = dict(fenc=cur.c, fenc_stride=cur.stride_c, fenc_org=cur.org_c, fref=ref.c, fref_stride=ref.stride_c, fref_org=ref.org_c)
         hipabi.subpel_refine(ms.depth, ms.w64, ms.h64, ms.range, self.subme, cur.t, cur.stride, ref.t, ref.stride,
-                             ms.best, self.cost_q, self.qoff, self.out, fenc_off=cur.org, fref_off=ref.org, phase_planes=planes, chroma=chroma)
+                             ms.best, self.cost_q, self.qoff, self.out, fenc_off=cur.org, fref_off=ref.org, phase_planes=planes, chroma=chroma, levels=levels)
 
     def checksum(self):
         return {"subpel": int(self.out.to(dtype=__import__("torch").int64).sum().item())}

@@ -279,6 +279,8 @@ def extend_border_picture(planes, pic: DevicePicture, stream=None, top=True, bot
     hipabi.check(f(arr, len(planes), pic.depth, s), "x265hip_extend_border_planes")
 
 
+SUBPEL_DEFER_DEFAULT = "after"       # FramePipeline._run_parallel2: where the PU levels the reconstruction does not read are refined
+
 # g_chromaScale (constants.cpp:346-350) as Quant::setChromaQP applies it to 4:2:0 pictures (quant.cpp:233-244)
 _CHROMA_SCALE = list(range(30)) + [29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37] + list(range(38, 52)) + [51] * 12
 
@@ -729,6 +731,14 @@ class FramePipeline:
         # experiment switches of the parallel-planes launch structure (read once): where the lookahead and the phase planes run
         self.la_after_search = os.environ.get("X265HIP_LA_AFTER_ME", "1") == "1"
         self.prep_next_to_search = os.environ.get("X265HIP_PREP_OVERLAP", "0") == "1"
+        # the default parallel schedule refines only the PU level the reconstruction codes in front of it and the other three levels on the
+        # side stream, next to the SAO decision (x265hip_subpel_refine_levels).  0: one launch of all four levels (A/B runs);
+        # "before" / "after" / "mv": where the three levels go - in front of the lookahead, behind it, or on a stream of their own right
+        # behind the first launch (1 = the default placement)
+        defer = os.environ.get("X265HIP_SUBPEL_DEFER", "1")
+        if defer not in ("0", "1", "before", "after", "mv"):
+            raise ValueError(f"X265HIP_SUBPEL_DEFER={defer}: 0, 1, before, after or mv")
+        self.subpel_defer = {"0": None, "1": SUBPEL_DEFER_DEFAULT}.get(defer, defer)
         self.ms = MotionSearch(w64, h64, rng, depth, device, want_surf=want_surf and search == "full", want_best=True, packed=packed)
         # subpel_planes: sub-pel candidates read from the reference picture's phase planes (one x265hip_phase_planes launch per frame)
         if chroma_satd and search != "full":
@@ -1050,6 +1060,9 @@ class FramePipeline:
           * the lookahead of the source picture runs on that stream BEHIND the chroma statistics, i.e. next to the SAO decision - a serial
             pass on ONE compute unit (115 us with the other 255 idle) - instead of next to the phase planes / sub-pel refinement, which it
             slowed; the minima of the NEXT picture's search are cleared there too (MotionSearch.reset_spare);
+          * the sub-pel launch in front of the reconstruction refines the PU level the reconstruction codes and nothing else (25 instead of
+            96 us at 4K); the other three levels' records are refined on the side stream behind the lookahead, next to the SAO decision
+            (profiles/subpel_levels_kernel_trace.txt; X265HIP_SUBPEL_DEFER=0: all four in the one launch again);
           * ONE side stream: every cross-stream dependency costs the waiting stream ~8 us on this runtime, and a step on three side streams
             had eight of them on the caller's stream - now three records and two waits."""
         import torch
@@ -1067,9 +1080,20 @@ class FramePipeline:
         ms.search(cur, ref)
         if self.prep_next_to_search:
             main.wait_event(ev_pl)
-        self.sp.run(cur, ref, prepared=self.prep_next_to_search)
+        # only the level the reconstruction codes is refined in front of it; the records of the other three are products of the step that
+        # nothing in it reads: they are refined next to the SAO decision (below), or all four here in one launch (X265HIP_SUBPEL_DEFER=0)
+        defer = self.subpel_defer
+        rest = [l for l in range(4) if l != self.rc.level]
+        self.sp.run(cur, ref, prepared=self.prep_next_to_search, levels=(self.rc.level,) if defer else None)
         mv = self.sp.out
         ev_mv = torch.cuda.Event(); ev_mv.record(main)
+        ev_rest = None
+        if defer == "mv":                                 # a stream of their own: the chroma chain on sC is on the critical path
+            sD = self.pstreams[1]
+            sD.wait_event(ev_mv)
+            with torch.cuda.stream(sD):
+                self.sp.run(cur, ref, prepared=True, levels=rest)
+                ev_rest = torch.cuda.Event(); ev_rest.record(sD)
         self.rc.run(cur, ref, self.recon, mv)
         sC.wait_event(ev_mv)
         with torch.cuda.stream(sC):
@@ -1085,8 +1109,14 @@ class FramePipeline:
             ev_cstats = torch.cuda.Event(); ev_cstats.record(sC)
             ms.reset_spare()                              # the sub-pel stage has long read this picture's minima: the other buffer may be cleared
             self._spare_ready = True
+            # behind the record the caller's stream waits for, in front of the one the step ends with: every record of sp.out is written
+            # when run() returns, and the next step's phase planes are not rewritten while these launches read them
+            if defer == "before":
+                self.sp.run(cur, ref, prepared=True, levels=rest)
             if self.la is not None:
                 self.la.run(cur)
+            if defer == "after":
+                self.sp.run(cur, ref, prepared=True, levels=rest)
             ev_side = torch.cuda.Event(); ev_side.record(sC)
         hipabi.sao_planes(self.depth, [dict(planes[0], out=None)])
         main.wait_event(ev_cstats)
@@ -1099,6 +1129,8 @@ class FramePipeline:
         else:
             extend_border_picture([self.out] + list(self.out_c), cur)
         main.wait_event(ev_side)                          # the lookahead and the cleared minima (long done: next to the SAO decision)
+        if ev_rest is not None:
+            main.wait_event(ev_rest)
         self.final, self.final_c = self.out, self.out_c
         return self.final
 

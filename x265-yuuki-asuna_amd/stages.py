@@ -326,33 +326,6 @@ class CuQpMaps:
         return self
 
 
-def _set_qp_maps(pipe, maps, tu_luma, tu_chroma):
-    """set_qp_maps of the frame pipelines: the maps' planes go to the TU stages (tu_qp) and to the deblocking stage (cu_qp), which
-    the pipeline's luma and chroma deblocking calls both read.  maps: a CuQpMaps of the pipeline's geometry, depth and level, or None."""
-    if maps is not None:
-        geo = (pipe.ms.w64, pipe.ms.h64, pipe.depth, tu_luma.level)
-        if (maps.w64, maps.h64, maps.depth, maps.level) != geo:
-            raise ValueError(f"set_qp_maps: maps of (w, h, depth, level) = {(maps.w64, maps.h64, maps.depth, maps.level)} for a pipeline of {geo}")
-    pipe.qp_maps = maps
-    tu_luma.qp_map = None if maps is None else maps.tu_qp[0]
-    for i, st in enumerate(tu_chroma):
-        st.qp_map = None if maps is None else maps.tu_qp[1 + i]
-    if pipe.db is not None:
-        pipe.db.qp_map = None if maps is None else maps.cu_qp
-
-
-def _qp_maps_run_check(pipe):
-    """run() of a pipeline whose maps are set, in a mode that would not honour them: raise instead of coding with other QPs than asked for."""
-    if getattr(pipe, "qp_maps", None) is None:
-        return
-    import torch
-    name = type(pipe).__name__
-    if getattr(pipe, "band_border", None) is not None:
-        raise ValueError(f"{name}: QP maps are set, but a band of a picture does not take its rows of them")
-    if torch.cuda.is_current_stream_capturing():
-        raise ValueError(f"{name}: QP maps are set, but a captured step would go on replaying the maps it was captured with")
-
-
 class Deblock:
     """In-loop deblocking of the luma reconstruction on device (x265hip_deblock_bs_inter + x265hip_deblock_luma; reference
     Deblock::getBoundaryStrength / edgeFilterLuma, deblock.cpp:191-215, 317-415) for the reconstruction stage's block grid."""
@@ -364,21 +337,25 @@ class Deblock:
         self.bs_ver = torch.zeros((h64 // 4) * (w64 // 8), dtype=torch.uint8, device=device)
         self.bs_hor = torch.zeros((h64 // 8) * (w64 // 4), dtype=torch.uint8, device=device)
 
+    def _luma(self, plane, pic: DevicePicture):
+        """The luma edge filter with the boundary strengths a run* method has just left."""
+        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
+
     def run(self, plane, pic: DevicePicture, mv, num_sig):
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv, num_sig, self.bs_ver, self.bs_hor)
-        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
+        self._luma(plane, pic)
 
     def run_b(self, plane, pic: DevicePicture, mv0, mv1, ref0, ref1, num_sig):
         """A B picture: the boundary strengths compare (ref0, ref1) x (mv0, mv1) per block (deblock.cpp:217-247); ref0 / ref1 = int8 picture
         ids per block, -1 = list unused (what BidirDecide leaves)."""
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv0, num_sig, self.bs_ver, self.bs_hor, slice_b=True, mv1=mv1, ref0=ref0, ref1=ref1)
-        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
+        self._luma(plane, pic)
 
     def run_refs(self, plane, pic: DevicePicture, mv, ref_id, num_sig):
         """A P picture with several references: two blocks predicted from different pictures get Bs 1 whatever their vectors
         (deblock.cpp:217-247 in a P slice); ref_id = int8 picture ids per block (what RefSelect leaves)."""
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv, num_sig, self.bs_ver, self.bs_hor, slice_b=False, ref0=ref_id)
-        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
+        self._luma(plane, pic)
 
     def prepare_intra(self):
         """Allocates what run_intra passes beside num_sig (IFramePipeline calls it in its constructor, so that run() allocates nothing)."""
@@ -393,7 +370,7 @@ class Deblock:
         vector records are not looked at on such edges (zeros are passed)."""
         self.prepare_intra()
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, self._intra_mv, num_sig, self.bs_ver, self.bs_hor, intra=self._intra_flags)
-        hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
+        self._luma(plane, pic)
 
 
 class Sao:
@@ -693,13 +670,195 @@ class PatternSearch:
         return {"subpel": int(self.out.to(dtype=torch.int64).sum().item())}
 
 
-class FramePipeline:
+class _PictureStep:
+    """What the whole-picture steps (FramePipeline, BFramePipeline, MultiRefFramePipeline, IFramePipeline) share: the picture's geometry,
+    the loop-filter stages, the planes they work on and everything behind the luma deblocking - chroma deblocking, SAO (statistics,
+    x265hip_sao_rdo or the distortion-only stand-in, application), border extension."""
+
+    fuse_sao = False            # FramePipeline: the stand-in SAO of Y, Cb, Cr as ONE launch per step (X265HIP_FUSE_SAO)
+    band_border = None          # FramePipeline as a band of a picture: (is_first_band, is_last_band) -> row-wise border extension
+    border_switch = None        # FramePipeline: the environment switch whose "0" means one border launch per plane instead of one per picture
+
+    def __init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo):
+        import torch
+        self.w64, self.h64, self.nctu, self.depth, self.qp, self.chroma = w64, h64, (w64 // 64) * (h64 // 64), depth, qp, chroma
+        # `qp` is the quantiser's QP (qp + QP_BD_OFFSET, what transformNxN works with); the deblocking tables are indexed with the
+        # CU's own QP (m_qp, 0..51)
+        self.db = Deblock(w64, h64, depth, level, max(qp - 6 * (depth - 8), 0), device) if deblock else None
+        # SAO statistics of the deblocked reconstruction (what rdoSaoUnitCu reads), 4:2:0 chroma on 32x32 footprints
+        self.sao = Sao(w64, h64, depth, device) if sao else None
+        self.sao_c = [Sao(w64 // 2, h64 // 2, depth, device, ctu=(32, 32), plane_offset=2) for _ in range(2)] if (sao and chroma) else None
+        # SAO applied in the loop: the picture handed on is deblocked AND offset like a decoder's.  sao_rdo: dict(lambdas=(luma, chroma),
+        # ctx_merge, ctx_type, entropy_bits) - the parameters come from x265hip_sao_rdo, the reference's own rate-distortion decision
+        # (SAO::rdoSaoUnitCu) on all planes' statistics; None - from x265hip_sao_decide (initial offsets + distortion-only choice)
+        self.sao_apply = bool(sao and sao_apply)
+        self.sao_rdo = sao_rdo if (sao and sao_apply) else None
+        if self.sao_rdo is not None:
+            self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
+            self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
+        self.recon, self.recon_c, self.out, self.out_c = None, None, None, None          # _alloc_planes, or whoever owns the step
+        self.qp_maps = None
+
+    def _alloc_planes(self, cur):
+        """The reconstruction and, where SAO is applied, the planes it is applied into: on first use, with cur's geometry."""
+        import torch
+        if self.recon is None:
+            self.recon = torch.zeros_like(cur.t)
+        if self.chroma and self.recon_c is None:
+            self.recon_c = [torch.zeros_like(p) for p in cur.c]
+        if self.sao_apply and self.out is None:
+            self.out = torch.zeros_like(cur.t)
+            self.out_c = [torch.zeros_like(p) for p in cur.c] if self.chroma else None
+
+    def _set_qp_maps(self, maps, tu_luma, tu_chroma):
+        """The maps' planes go to the TU stages (tu_qp) and to the deblocking stage (cu_qp), which the luma and chroma deblocking calls
+        both read.  maps: a CuQpMaps of the step's geometry, depth and level, or None."""
+        if maps is not None:
+            geo = (self.w64, self.h64, self.depth, tu_luma.level)
+            if (maps.w64, maps.h64, maps.depth, maps.level) != geo:
+                raise ValueError(f"set_qp_maps: maps of (w, h, depth, level) = {(maps.w64, maps.h64, maps.depth, maps.level)} for a pipeline of {geo}")
+        self.qp_maps = maps
+        tu_luma.qp_map = None if maps is None else maps.tu_qp[0]
+        for i, st in enumerate(tu_chroma):
+            st.qp_map = None if maps is None else maps.tu_qp[1 + i]
+        if self.db is not None:
+            self.db.qp_map = None if maps is None else maps.cu_qp
+
+    def set_qp_maps(self, maps):
+        """Per-block QPs (adaptive quantisation) for the following run() calls: maps = a CuQpMaps of this geometry, depth and level, or None
+        = the picture-wide qp again.  Not for bands (BandedFramePipeline), captured graphs or scaling-list tables: run() raises there."""
+        self._set_qp_maps(maps, self.rc, self.rc_c if self.chroma else [])
+
+    def _qp_maps_run_check(self):
+        """run() with maps set, in a mode that would not honour them: raise instead of coding with other QPs than asked for."""
+        if self.qp_maps is None:
+            return
+        import torch
+        name = type(self).__name__
+        if self.band_border is not None:
+            raise ValueError(f"{name}: QP maps are set, but a band of a picture does not take its rows of them")
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError(f"{name}: QP maps are set, but a captured step would go on replaying the maps it was captured with")
+
+    def _deblock_chroma(self, cur):
+        """Both chroma planes with the boundary strengths of the luma pass (in an all-inter picture no edge has Bs 2: the pass still runs
+        like the reference's)."""
+        hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
+                              self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
+
+    def _sao_planes(self, cur):
+        """The planes' records for hipabi.sao_planes / sao_apply_planes: [Y, Cb, Cr] or [Y]."""
+        return [self.sao.plane(cur.t, cur.stride, cur.org, self.recon, cur.stride, cur.org, self.out)] + \
+               ([self.sao_c[i].plane(cur.c[i], cur.stride_c, cur.org_c, self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i]) for i in range(2)] if self.chroma else [])
+
+    def _sao_rdo(self):
+        """x265hip_sao_rdo on the statistics of all planes -> every plane's Sao.params."""
+        st = [self.sao] + (list(self.sao_c) if self.chroma else [])
+        q = self.sao_rdo
+        hipabi.sao_rdo(self.depth, [x.count for x in st], [x.offset_org for x in st], self.w64 // 64, self.h64 // 64, q["lambdas"], q["ctx_merge"], q["ctx_type"],
+                       q["entropy_bits"], [x.params for x in st], self.sao_scratch, sao_flag=(1, 1 if self.chroma else 0), num_no_sao=self.sao_no)
+
+    def _extend_border(self, plane, cur, chroma=False):
+        """One plane: the whole picture's margins, or a band's (side margins, top / bottom margin only at the picture's edge)."""
+        if self.band_border is not None:
+            extend_border_rows(plane, cur, self.band_border[0], self.band_border[1], chroma=chroma)
+        else:
+            extend_border(plane, cur, chroma=chroma)
+
+    def _extend_borders(self, cur, planes):
+        """planes = [Y, Cb, Cr] or [Y] in one launch, or plane by plane where the step's switch asks for it."""
+        if self.border_switch is None or os.environ.get(self.border_switch, "1") != "0":
+            top, bottom = self.band_border or (True, True)
+            extend_border_picture(planes, cur, top=top, bottom=bottom)
+        else:
+            for i, plane in enumerate(planes):
+                self._extend_border(plane, cur, chroma=i > 0)
+
+    def _filter_tail(self, cur, mark):
+        """Everything behind the luma deblocking, serially on the caller's stream; sets final / final_c and returns final."""
+        if self.db is not None:
+            if self.chroma:
+                self._deblock_chroma(cur)
+            mark("deblock")
+        final, final_c = (self.out, self.out_c) if self.sao_apply else (self.recon, self.recon_c)
+        if self.sao_rdo is not None:
+            # statistics of all planes (one launch) -> the reference's rate-distortion decision (x265hip_sao_rdo: it needs every plane's
+            # statistics, Cb / Cr share a type) -> application of all planes (one launch)
+            planes = self._sao_planes(cur)
+            hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes])
+            mark("sao_stats")
+            self._sao_rdo()
+            mark("sao_rdo")
+            hipabi.sao_apply_planes(self.depth, planes)
+            mark("sao_apply")
+        elif self.sao_apply and self.chroma and self.fuse_sao:
+            hipabi.sao_planes(self.depth, self._sao_planes(cur))
+            mark("sao")                      # statistics + parameters + application of the three planes: three launches
+        elif self.sao is not None:
+            self.sao.stats(cur, self.recon, cur.stride, cur.org)
+            if self.chroma:
+                for i in range(2):
+                    self.sao_c[i].stats(None, self.recon_c[i], cur.stride_c, cur.org_c, src_plane=cur.c[i])
+            mark("sao_stats")
+            if self.sao_apply:
+                self.sao.decide()
+                self.sao.apply(self.recon, cur.stride, cur.org, self.out)
+                if self.chroma:
+                    for i in range(2):
+                        self.sao_c[i].decide()
+                        self.sao_c[i].apply(self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i])
+                mark("sao_apply")
+        self._extend_borders(cur, [final] + (list(final_c) if self.chroma else []))
+        mark("border")
+        self.final, self.final_c = final, final_c
+        return final
+
+    def final_planes(self):
+        """[Y, Cb, Cr] (or [Y]) of the picture the last run() produced."""
+        return [self.final] + (list(self.final_c) if self.chroma else [])
+
+
+class _RefListStep(_PictureStep):
+    """The part BFramePipeline and MultiRefFramePipeline share: one exhaustive search + sub-pel refinement per reference picture."""
+
+    def _build_lists(self, n, w64, h64, depth, device, rng, subme, subpel_planes, chroma_satd):
+        from .pipeline import MotionSearch, SubpelRefine
+        self.msl = [MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True) for _ in range(n)]
+        self.spl = [SubpelRefine(m, subme, device, phase_planes=subpel_planes, chroma_satd=chroma_satd) for m in self.msl]
+
+    def _search_lists(self, cur, refs, mark):
+        for l, ref in enumerate(refs):
+            self.msl[l].reset()
+            self.msl[l].search(cur, ref)
+            mark("me%d" % l)
+            self.spl[l].run(cur, ref)
+            mark("subpel%d" % l)
+
+    def _checksum(self, choice):
+        """choice: the stage that chose between the lists (BidirDecide / RefSelect)."""
+        import torch
+        out = {}
+        for l in range(len(self.msl)):
+            out.update({"%s%d" % (k, l): v for k, v in self.msl[l].checksum().items()})
+            out.update({"%s%d" % (k, l): v for k, v in self.spl[l].checksum().items()})
+        out.update(choice.checksum())
+        out.update(self.rc.checksum())
+        if self.chroma:
+            for i in range(2):
+                out.update({"%s_c%d" % (k, i): v for k, v in InterRecon.checksum(self.rc_c[i]).items()})
+        out["recon"] = int(self.final.to(torch.int64).sum().item())
+        return out
+
+
+class FramePipeline(_PictureStep):
     """Closed-loop frame pipeline: every frame is searched in, predicted from and reconstructed against the
     RECONSTRUCTION of the previous frame (like the reference's P-frame chain), all on device:
         ME (exhaustive, SAD surfaces and/or best mv) -> sub-pel refinement -> prediction + residual round trip
         (NxN blocks) -> border extension -> the reconstruction becomes the next reference.
     With lookahead=(width, height) the source picture also goes through the lookahead stage (half-resolution planes + intra
     cost estimate per 8x8 block), which only depends on the source."""
+
+    border_switch = "X265HIP_BORDER_PLANES"          # 0 (A/B runs): the picture's (band's) planes in three border launches instead of one
 
     def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, want_surf=True, packed=False, lookahead=None,
                  search="full", deblock=False, sao=False, lookahead_cost_batch=0, chroma=False, sao_apply=False, sign_hide=False,
@@ -714,7 +873,7 @@ class FramePipeline:
         its workgroup slots, and workgroups of other kernels resident next to it cost it more than the overlap hides.  Off by default."""
         import torch
         from .pipeline import MotionSearch, SubpelRefine
-        self.depth = depth
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
         # parallel_planes: after the sub-pel stage the three planes are independent chains (reconstruction -> deblocking -> SAO ->
         # border) of small, latency-bound launches: Cb and Cr run on their own HIP streams next to Y, the lookahead (source picture
         # only) next to the search; everything joins the caller's stream before run() returns
@@ -753,7 +912,7 @@ class FramePipeline:
             self.ps = PatternSearch(w64, h64, depth, method, subme, rng, device)
         # sign_hide: Quant::signBitHidingHDQ after the quantiser (pps.bSignHideEnabled, the x265 default)
         self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
-        self.rc = InterRecon(self.ms.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        self.rc = InterRecon(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
         self.la = Lookahead(lookahead[0], lookahead[1], depth, device) if lookahead else None
         # The lookahead's P-frame cost estimate runs AHEAD of the encode like the reference's lookahead thread: every
         # `lookahead_cost_batch` frames one launch on a side stream scores that many (picture, previous picture) pairs.  The
@@ -770,63 +929,30 @@ class FramePipeline:
             for j in range(nring):
                 self._table(tuple(((j * self.lcb + 1 + i) % nring, (j * self.lcb + i) % nring) for i in range(self.lcb)))
             torch.cuda.synchronize()
-        # `qp` is the quantiser's QP (qp + QP_BD_OFFSET, what transformNxN works with); the deblocking tables are indexed with the
-        # CU's own QP (m_qp, 0..51)
-        self.db = Deblock(w64, h64, depth, level, max(qp - 6 * (depth - 8), 0), device) if deblock else None
-        # SAO statistics of the deblocked reconstruction (what rdoSaoUnitCu reads); the offsets themselves are the host's decision
-        self.sao = Sao(w64, h64, depth, device) if sao else None
-        self.recon = None
-        # 4:2:0 chroma through the same closed loop (predInterChromaPixel + residual round trip, edgeFilterChroma, SAO on 32x32 footprints)
-        self.chroma = chroma
-        self.qp = qp
-        self.recon_c, self.out, self.out_c = None, None, None
+        # 4:2:0 chroma through the same closed loop (predInterChromaPixel + residual round trip, edgeFilterChroma)
         if chroma:
             qpc = chroma_quant_qp(qp, depth)
-            self.rc_c = [InterReconChroma(self.ms.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
-            self.sao_c = [Sao(w64 // 2, h64 // 2, depth, device, ctu=(32, 32), plane_offset=2) for _ in range(2)] if sao else None
-        # SAO applied in the loop: the parameters come from x265hip_sao_decide (initial offsets + distortion-only choice), so the
-        # picture handed to the next frame is deblocked AND offset like a decoder's
-        self.sao_apply = bool(sao and sao_apply)
-        # sao_rdo: dict(lambdas=(luma, chroma), ctx_merge, ctx_type, entropy_bits) - the parameters come from x265hip_sao_rdo, the
-        # reference's own rate-distortion decision (SAO::rdoSaoUnitCu) on all planes' statistics, instead of the distortion-only stand-in
-        self.sao_rdo = sao_rdo if (sao and sao_apply) else None
-        if self.sao_rdo is not None:
-            self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
-            self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
-        # band mode (BandedFramePipeline): (is_first_band, is_last_band) -> row-wise border extension instead of the whole-picture one
-        self.band_border = None
+            self.rc_c = [InterReconChroma(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
 
     def set_qp_maps(self, maps):
         """Per-block QPs (adaptive quantisation) for the following run() calls: maps = a CuQpMaps of this geometry, depth and level, or None
         = the picture-wide qp again.  Every run mode reads the maps from the stages; the parts of `split` are rebuilt with their rows of
         the maps.  Not for bands (BandedFramePipeline), captured graphs or scaling-list tables: run() raises there."""
-        _set_qp_maps(self, maps, self.rc, self.rc_c if self.chroma else [])
+        _PictureStep.set_qp_maps(self, maps)
         self.parts = None
-
-    def _sao_rdo(self):
-        """x265hip_sao_rdo on the statistics of all planes -> every plane's Sao.params."""
-        st = [self.sao] + (list(self.sao_c) if self.chroma else [])
-        q = self.sao_rdo
-        hipabi.sao_rdo(self.depth, [x.count for x in st], [x.offset_org for x in st], self.ms.w64 // 64, self.ms.h64 // 64, q["lambdas"], q["ctx_merge"], q["ctx_type"],
-                       q["entropy_bits"], [x.params for x in st], self.sao_scratch, sao_flag=(1, 1 if self.chroma else 0), num_no_sao=self.sao_no)
-
-    def _sao_planes(self, cur):
-        return [self.sao.plane(cur.t, cur.stride, cur.org, self.recon, cur.stride, cur.org, self.out)] + \
-               ([self.sao_c[i].plane(cur.c[i], cur.stride_c, cur.org_c, self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i]) for i in range(2)] if self.chroma else [])
 
     def run(self, cur: DevicePicture, ref: DevicePicture, mark=None):
         """ref: the current reference picture (extended borders; with chroma=True also its Cb / Cr planes); returns the luma plane of
         the picture for the next frame's reference list (final_planes() has all three).  mark(name), if given, is called after every
         stage (bench.py records an event there)."""
         import torch
-        _qp_maps_run_check(self)
+        self._qp_maps_run_check()
+        self._alloc_planes(cur)
         par = self.parallel and mark is None and self.chroma and not self.lcb and self.ps is None and self.db is not None and self.sao is not None \
             and self.sao_apply
         if par:
             return self._run_parallel(cur, ref)
         mark = mark or (lambda name: None)
-        if self.recon is None:
-            self.recon = torch.zeros_like(cur.t)
         if self.lcb:
             slot = self.frame_no % len(self.ring)
             if slot in self.read_done:                       # the cost launches that read this slot must be through
@@ -856,8 +982,6 @@ class FramePipeline:
         self.rc.run(cur, ref, self.recon, mv)
         mark("recon")
         if self.chroma:
-            if self.recon_c is None:
-                self.recon_c = [torch.zeros_like(p) for p in cur.c]
             if self.rc_c[0].tables is None and self.rc_c[1].tables is None:
                 InterReconChroma.run_pair(self.rc_c, cur.c, ref.c, self.recon_c, cur.stride_c, cur.org_c, mv)      # Cb + Cr: one launch
             else:
@@ -866,73 +990,7 @@ class FramePipeline:
             mark("recon_chroma")
         if self.db is not None:
             self.db.run(self.recon, cur, mv, self.rc.num_sig)
-            if self.chroma:                  # Bs 2 edges only (intra CUs): none in an all-inter picture, the pass still runs like the reference's
-                hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                      self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
-            mark("deblock")
-        final, final_c = self.recon, self.recon_c
-        if self.sao_rdo is not None:
-            # statistics of all planes (one launch) -> the reference's rate-distortion decision (x265hip_sao_rdo: it needs every plane's
-            # statistics, Cb / Cr share a type) -> application of all planes (one launch)
-            if self.out is None:
-                self.out = torch.zeros_like(cur.t)
-                self.out_c = [torch.zeros_like(p) for p in cur.c] if self.chroma else None
-            planes = self._sao_planes(cur)
-            hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes])
-            mark("sao_stats")
-            self._sao_rdo()
-            mark("sao_rdo")
-            hipabi.sao_apply_planes(self.depth, planes)
-            final, final_c = self.out, self.out_c
-            mark("sao_apply")
-        elif self.sao is not None and self.sao_apply and self.chroma and self.fuse_sao:
-            # Y, Cb, Cr through statistics -> parameters -> application with ONE launch per step (x265hip_sao_planes)
-            if self.out is None:
-                self.out = torch.zeros_like(cur.t)
-                self.out_c = [torch.zeros_like(p) for p in cur.c]
-            hipabi.sao_planes(self.depth, [self.sao.plane(cur.t, cur.stride, cur.org, self.recon, cur.stride, cur.org, self.out)] +
-                              [self.sao_c[i].plane(cur.c[i], cur.stride_c, cur.org_c, self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i]) for i in range(2)])
-            final, final_c = self.out, self.out_c
-            mark("sao")                      # statistics + parameters + application of the three planes: three launches
-        elif self.sao is not None:
-            self.sao.stats(cur, self.recon, cur.stride, cur.org)
-            if self.chroma:
-                for i in range(2):
-                    self.sao_c[i].stats(None, self.recon_c[i], cur.stride_c, cur.org_c, src_plane=cur.c[i])
-            mark("sao_stats")
-            if self.sao_apply:
-                if self.out is None:
-                    self.out = torch.zeros_like(cur.t)
-                    self.out_c = [torch.zeros_like(p) for p in cur.c] if self.chroma else None
-                self.sao.decide()
-                self.sao.apply(self.recon, cur.stride, cur.org, self.out)
-                final = self.out
-                if self.chroma:
-                    for i in range(2):
-                        self.sao_c[i].decide()
-                        self.sao_c[i].apply(self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i])
-                    final_c = self.out_c
-                mark("sao_apply")
-        one_launch = os.environ.get("X265HIP_BORDER_PLANES", "1") != "0"          # round 6: the picture's (band's) planes in one launch
-        if self.band_border is not None:
-            top, bottom = self.band_border
-            if one_launch:
-                extend_border_picture([final] + (list(final_c) if self.chroma else []), cur, top=top, bottom=bottom)
-            else:
-                extend_border_rows(final, cur, top, bottom)
-                if self.chroma:
-                    for i in range(2):
-                        extend_border_rows(final_c[i], cur, top, bottom, chroma=True)
-        elif one_launch:
-            extend_border_picture([final] + (list(final_c) if self.chroma else []), cur)
-        else:
-            extend_border(final, cur)
-            if self.chroma:
-                for i in range(2):
-                    extend_border(final_c[i], cur, chroma=True)
-        mark("border")
-        self.final, self.final_c = final, final_c
-        return final
+        return self._filter_tail(cur, mark)
 
     def _run_parallel(self, cur: DevicePicture, ref: DevicePicture):
         """The same launches as run(), Y on the caller's stream, Cb / Cr on two side streams from the reconstruction on, the lookahead on
@@ -944,13 +1002,6 @@ class FramePipeline:
             # against 2.163 without, profiles/r03_step_timeline.txt)
             self.pstreams = [torch.cuda.Stream() for _ in range(4)]
         sCb, sCr, sLa = self.pstreams[:3]
-        if self.recon is None:
-            self.recon = torch.zeros_like(cur.t)
-        if self.recon_c is None:
-            self.recon_c = [torch.zeros_like(p) for p in cur.c]
-        if self.out is None:
-            self.out = torch.zeros_like(cur.t)
-            self.out_c = [torch.zeros_like(p) for p in cur.c]
         if self.sao_rdo is not None and self.split == 1 and self.la_after_search and self.schedule2 and self.band_border is None:
             return self._run_parallel2(cur, ref, main, sCb)
         start = torch.cuda.Event(); start.record(main)
@@ -998,8 +1049,7 @@ class FramePipeline:
         ev_bs = torch.cuda.Event(); ev_bs.record(main)
         sCb.wait_event(ev_bs); sCb.wait_event(ev_rec[1])
         with torch.cuda.stream(sCb):
-            hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                  self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
+            self._deblock_chroma(cur)
             ev_dbc = torch.cuda.Event(); ev_dbc.record(sCb)
         sCr.wait_event(ev_dbc)
         if self.sao_rdo is not None:
@@ -1019,21 +1069,14 @@ class FramePipeline:
         elif self.fuse_sao_parallel:
             # SAO of the three planes: one launch per step on the caller's stream; only the border extensions go back to the side streams
             main.wait_event(ev_dbc)
-            hipabi.sao_planes(self.depth, [self.sao.plane(cur.t, cur.stride, cur.org, self.recon, cur.stride, cur.org, self.out)] +
-                              [self.sao_c[i].plane(cur.c[i], cur.stride_c, cur.org_c, self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i]) for i in range(2)])
+            hipabi.sao_planes(self.depth, self._sao_planes(cur))
             ev_sao = torch.cuda.Event(); ev_sao.record(main)
         else:
             # SAO + border extension per plane
             self.sao.stats(cur, self.recon, cur.stride, cur.org)
             self.sao.decide()
             self.sao.apply(self.recon, cur.stride, cur.org, self.out)
-
-        def border(plane, chroma):
-            if self.band_border is not None:              # a band of a picture: side margins, top / bottom margin only at the picture's edge
-                extend_border_rows(plane, cur, self.band_border[0], self.band_border[1], chroma=chroma)
-            else:
-                extend_border(plane, cur, chroma=chroma)
-        border(self.out, False)
+        self._extend_border(self.out, cur)
         done = []
         for i, st in enumerate((sCb, sCr)):
             if self.fuse_sao_parallel or self.sao_rdo is not None:
@@ -1043,7 +1086,7 @@ class FramePipeline:
                     self.sao_c[i].stats(None, self.recon_c[i], cur.stride_c, cur.org_c, src_plane=cur.c[i])
                     self.sao_c[i].decide()
                     self.sao_c[i].apply(self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i])
-                border(self.out_c[i], True)
+                self._extend_border(self.out_c[i], cur, chroma=True)
                 e = torch.cuda.Event(); e.record(st); done.append(e)
         if self.la is not None:
             e = torch.cuda.Event(); e.record(sLa); done.append(e)
@@ -1103,8 +1146,7 @@ class FramePipeline:
         planes = self._sao_planes(cur)
         sC.wait_event(ev_bs)
         with torch.cuda.stream(sC):
-            hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                  self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
+            self._deblock_chroma(cur)
             hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes[1:3]])
             ev_cstats = torch.cuda.Event(); ev_cstats.record(sC)
             ms.reset_spare()                              # the sub-pel stage has long read this picture's minima: the other buffer may be cleared
@@ -1122,12 +1164,7 @@ class FramePipeline:
         main.wait_event(ev_cstats)
         self._sao_rdo()
         hipabi.sao_apply_planes(self.depth, planes)
-        if os.environ.get("X265HIP_BORDER_PLANES", "1") == "0":       # A/B: three launches back to back (15 us) instead of one
-            extend_border(self.out, cur)
-            for i in range(2):
-                extend_border(self.out_c[i], cur, chroma=True)
-        else:
-            extend_border_picture([self.out] + list(self.out_c), cur)
+        self._extend_borders(cur, [self.out] + list(self.out_c))          # one launch; three back to back (15 us) with the switch at 0
         main.wait_event(ev_side)                          # the lookahead and the cleared minima (long done: next to the SAO decision)
         if ev_rest is not None:
             main.wait_event(ev_rest)
@@ -1152,7 +1189,7 @@ class FramePipeline:
         there anyway).  Returns the events after which Cb / Cr are reconstructed; `main` has waited for every luma part."""
         import torch
         if self.parts is None:
-            rows = self.ms.h64 // 64
+            rows = self.h64 // 64
             cuts = [rows * k // self.split for k in range(self.split + 1)]
             self.parts = []
             for r0, r1 in zip(cuts[:-1], cuts[1:]):
@@ -1184,10 +1221,6 @@ class FramePipeline:
         for sc in (sCb, sCr):
             e = torch.cuda.Event(); e.record(sc); ev_rec.append(e)
         return ev_rec
-
-    def final_planes(self):
-        """[luma, cb, cr] of the picture the last run() produced for the next frame's reference list."""
-        return [self.final] + (list(self.final_c) if self.chroma else [])
 
     def _table(self, key):
         if key not in self.tables:
@@ -1407,7 +1440,7 @@ class BidirDecide:
                 "mv1_out": int(self.mv1_out.to(torch.int64).sum().item())}
 
 
-class BFramePipeline:
+class BFramePipeline(_RefListStep):
     """One B picture on the device, the stages of FramePipeline.run with two reference lists:
         per list: exhaustive search (best mv) -> sub-pel refinement;  bidirectional decision (BidirDecide);  bi-predictive luma + 4:2:0
         chroma reconstruction with the decided dir / vectors;  B-picture boundary strengths + luma / chroma deblocking;  SAO (statistics,
@@ -1418,49 +1451,25 @@ class BFramePipeline:
                  sign_hide=False, subpel_planes=False, sao_rdo=None, dir_cost=(12, 12, 20), want_cost=False, chroma_satd=False):
         """chroma_satd (with chroma): both refinements and the decision measure chroma as the reference does at subme >= 3
         (x265hip_subpel_refine_chroma, x265hip_bidir_decide_chroma)."""
-        import torch
-        from .pipeline import MotionSearch, SubpelRefine
         if chroma_satd and not chroma:
             raise ValueError("BFramePipeline: chroma_satd needs chroma=True")
-        self.depth, self.qp, self.chroma = depth, qp, chroma
-        self.msl = [MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True) for _ in range(2)]
-        self.spl = [SubpelRefine(m, subme, device, phase_planes=subpel_planes, chroma_satd=chroma_satd) for m in self.msl]
-        self.ms = self.msl[0]                # geometry (nctu, w64, h64) for the helpers shared with FramePipeline
-        self.bd = BidirDecide(self.ms.nctu, w64, h64, depth, level, device, dir_cost=dir_cost, want_cost=want_cost,
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
+        self._build_lists(2, w64, h64, depth, device, rng, subme, subpel_planes, chroma_satd)
+        self.bd = BidirDecide(self.nctu, w64, h64, depth, level, device, dir_cost=dir_cost, want_cost=want_cost,
                               chroma_satd=chroma_satd and subme >= 3)      # bChromaSATD is off at subme <= 2 (motion.cpp:212): luma-only decision there
         self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
-        self.rc = InterReconBi(self.ms.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
-        self.db = Deblock(w64, h64, depth, level, max(qp - 6 * (depth - 8), 0), device) if deblock else None
-        self.sao = Sao(w64, h64, depth, device) if sao else None
-        self.recon, self.recon_c, self.out, self.out_c = None, None, None, None
+        self.rc = InterReconBi(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
         if chroma:
             qpc = chroma_quant_qp(qp, depth)
-            self.rc_c = [InterReconChromaBi(self.ms.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
-            self.sao_c = [Sao(w64 // 2, h64 // 2, depth, device, ctu=(32, 32), plane_offset=2) for _ in range(2)] if sao else None
-        self.sao_apply = bool(sao and sao_apply)
-        self.sao_rdo = sao_rdo if (sao and sao_apply) else None
-        if self.sao_rdo is not None:
-            self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
-            self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
-
-    def set_qp_maps(self, maps):
-        """Per-block QPs for the following run() calls (see FramePipeline.set_qp_maps); None = the picture-wide qp again."""
-        _set_qp_maps(self, maps, self.rc, self.rc_c if self.chroma else [])
+            self.rc_c = [InterReconChromaBi(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
 
     def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mark=None):
         """ref0 / ref1: the list-0 / list-1 reference pictures (extended borders; with chroma=True also their Cb / Cr planes).  Returns the
         luma plane of the coded picture; mark(name), if given, is called after every stage."""
-        import torch
-        _qp_maps_run_check(self)
+        self._qp_maps_run_check()
         mark = mark or (lambda name: None)
-        if self.recon is None:
-            self.recon = torch.zeros_like(cur.t)
-        for l, ref in enumerate((ref0, ref1)):
-            self.msl[l].reset()
-            self.msl[l].search(cur, ref)
-            mark("me%d" % l)
-            self.spl[l].run(cur, ref)
-            mark("subpel%d" % l)
+        self._alloc_planes(cur)
+        self._search_lists(cur, (ref0, ref1), mark)
         phases = (self.spl[0].planes, self.spl[1].planes) if self.spl[0].use_planes else None      # what the two refinements just prepared
         self.bd.run(cur, ref0, ref1, self.spl[0].out, self.spl[1].out, self.spl[0].cost_q, self.spl[0].qoff, phase_planes=phases)
         mark("bidir")
@@ -1468,68 +1477,15 @@ class BFramePipeline:
         self.rc.run(cur, ref0, ref1, self.recon, mv0, mv1, dir_flags=dirs)
         mark("recon")
         if self.chroma:
-            if self.recon_c is None:
-                self.recon_c = [torch.zeros_like(p) for p in cur.c]
             for i in range(2):
                 self.rc_c[i].run(cur.c[i], ref0.c[i], ref1.c[i], self.recon_c[i], cur.stride_c, cur.org_c, mv0, mv1, dir_flags=dirs)
             mark("recon_chroma")
         if self.db is not None:
             self.db.run_b(self.recon, cur, mv0, mv1, self.bd.ref0, self.bd.ref1, self.rc.num_sig)
-            if self.chroma:
-                hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                      self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
-            mark("deblock")
-        final, final_c = self.recon, self.recon_c
-        if self.sao is not None and self.sao_apply and self.out is None:
-            self.out = torch.zeros_like(cur.t)
-            self.out_c = [torch.zeros_like(p) for p in cur.c] if self.chroma else None
-        if self.sao_rdo is not None:
-            planes = FramePipeline._sao_planes(self, cur)
-            hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes])
-            mark("sao_stats")
-            FramePipeline._sao_rdo(self)
-            mark("sao_rdo")
-            hipabi.sao_apply_planes(self.depth, planes)
-            final, final_c = self.out, self.out_c
-            mark("sao_apply")
-        elif self.sao is not None:
-            self.sao.stats(cur, self.recon, cur.stride, cur.org)
-            if self.chroma:
-                for i in range(2):
-                    self.sao_c[i].stats(None, self.recon_c[i], cur.stride_c, cur.org_c, src_plane=cur.c[i])
-            mark("sao_stats")
-            if self.sao_apply:
-                self.sao.decide()
-                self.sao.apply(self.recon, cur.stride, cur.org, self.out)
-                final = self.out
-                if self.chroma:
-                    for i in range(2):
-                        self.sao_c[i].decide()
-                        self.sao_c[i].apply(self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i])
-                    final_c = self.out_c
-                mark("sao_apply")
-        extend_border_picture([final] + (list(final_c) if self.chroma else []), cur)
-        mark("border")
-        self.final, self.final_c = final, final_c
-        return final
-
-    def final_planes(self):
-        """[Y, Cb, Cr] (or [Y]) of the picture run() coded last."""
-        return [self.final] + (list(self.final_c) if self.chroma else [])
+        return self._filter_tail(cur, mark)
 
     def checksum(self):
-        import torch
-        out = {}
-        for l in range(2):
-            out.update({"%s%d" % (k, l): v for k, v in self.msl[l].checksum().items()})
-            out.update({"%s%d" % (k, l): v for k, v in self.spl[l].checksum().items()})
-        out.update(self.bd.checksum())
-        out.update(self.rc.checksum())
-        if self.chroma:
-            for i in range(2):
-                out.update({"%s_c%d" % (k, i): v for k, v in InterRecon.checksum(self.rc_c[i]).items()})
-        out["recon"] = int(self.final.to(torch.int64).sum().item())
-        return out
+        return self._checksum(self.bd)
 
 
 class RefSelect:
@@ -1567,7 +1523,7 @@ class RefSelect:
         return {"ref_idx": int(self.ref_idx.to(torch.int64).sum().item()), "mv_out": int(self.mv_out.to(torch.int64).sum().item())}
 
 
-class MultiRefFramePipeline:
+class MultiRefFramePipeline(_RefListStep):
     """One P picture with several references on the device, the stages of FramePipeline.run with a reference list:
         per reference: exhaustive search (best mv) -> sub-pel refinement;  reference selection (RefSelect);  luma + 4:2:0 chroma
         reconstruction of every block from its chosen picture;  boundary strengths that compare the blocks' pictures + luma / chroma
@@ -1578,121 +1534,45 @@ class MultiRefFramePipeline:
                  sao_apply=False, sign_hide=False, subpel_planes=False, sao_rdo=None, chroma_satd=False, ref_cost=None, want_cost=False):
         """ref_cost: one int per reference of every run() (lambda x the bits of the reference index), None = hipabi.ref_cost_bits of the
         number of references a run() is given."""
-        import torch
-        from .pipeline import MotionSearch, SubpelRefine
         if chroma_satd and not chroma:
             raise ValueError("MultiRefFramePipeline: chroma_satd needs chroma=True")
-        self.depth, self.qp, self.chroma, self.max_refs = depth, qp, chroma, max_refs
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
+        self.max_refs = max_refs
         self.ref_cost = None if ref_cost is None else tuple(int(c) for c in ref_cost)
-        self.msl = [MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True) for _ in range(max_refs)]
-        self.spl = [SubpelRefine(m, subme, device, phase_planes=subpel_planes, chroma_satd=chroma_satd) for m in self.msl]
-        self.ms = self.msl[0]                # geometry (nctu, w64, h64) for the helpers shared with FramePipeline
-        self.rs = RefSelect(self.ms.nctu, w64, h64, depth, level, device, max_refs=max_refs, want_cost=want_cost)
+        self._build_lists(max_refs, w64, h64, depth, device, rng, subme, subpel_planes, chroma_satd)
+        self.rs = RefSelect(self.nctu, w64, h64, depth, level, device, max_refs=max_refs, want_cost=want_cost)
         self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
-        self.rc = InterReconRefs(self.ms.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
-        self.db = Deblock(w64, h64, depth, level, max(qp - 6 * (depth - 8), 0), device) if deblock else None
-        self.sao = Sao(w64, h64, depth, device) if sao else None
-        self.recon, self.recon_c, self.out, self.out_c = None, None, None, None
+        self.rc = InterReconRefs(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
         if chroma:
             qpc = chroma_quant_qp(qp, depth)
-            self.rc_c = [InterReconChromaRefs(self.ms.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
-            self.sao_c = [Sao(w64 // 2, h64 // 2, depth, device, ctu=(32, 32), plane_offset=2) for _ in range(2)] if sao else None
-        self.sao_apply = bool(sao and sao_apply)
-        self.sao_rdo = sao_rdo if (sao and sao_apply) else None
-        if self.sao_rdo is not None:
-            self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
-            self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
-
-    def set_qp_maps(self, maps):
-        """Per-block QPs for the following run() calls (see FramePipeline.set_qp_maps); None = the picture-wide qp again."""
-        _set_qp_maps(self, maps, self.rc, self.rc_c if self.chroma else [])
+            self.rc_c = [InterReconChromaRefs(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
 
     def run(self, cur: DevicePicture, refs, mark=None):
         """refs: 1 .. max_refs reference pictures, nearest first = list order (extended borders; with chroma=True also their Cb / Cr
         planes).  Returns the luma plane of the coded picture; mark(name), if given, is called after every stage."""
-        import torch
-        _qp_maps_run_check(self)
+        self._qp_maps_run_check()
         mark = mark or (lambda name: None)
         refs = list(refs)
         if not 1 <= len(refs) <= self.max_refs:
             raise ValueError(f"MultiRefFramePipeline: {len(refs)} references for max_refs {self.max_refs}")
         if self.ref_cost is not None and len(self.ref_cost) != len(refs):
             raise ValueError(f"MultiRefFramePipeline: ref_cost has {len(self.ref_cost)} entries for {len(refs)} references")
-        if self.recon is None:
-            self.recon = torch.zeros_like(cur.t)
-        for r, ref in enumerate(refs):
-            self.msl[r].reset()
-            self.msl[r].search(cur, ref)
-            mark("me%d" % r)
-            self.spl[r].run(cur, ref)
-            mark("subpel%d" % r)
+        self._alloc_planes(cur)
+        self._search_lists(cur, refs, mark)
         self.rs.run([self.spl[r].out for r in range(len(refs))], ref_cost=self.ref_cost)
         mark("ref_select")
         mv, idx = self.rs.mv_out, self.rs.ref_idx
         self.rc.run(cur, refs, self.recon, mv, idx)
         mark("recon")
         if self.chroma:
-            if self.recon_c is None:
-                self.recon_c = [torch.zeros_like(p) for p in cur.c]
             InterReconChromaRefs.run_pair(self.rc_c, cur.c, [[ref.c[i] for ref in refs] for i in range(2)], self.recon_c, cur.stride_c, cur.org_c, mv, idx)
             mark("recon_chroma")
         if self.db is not None:
             self.db.run_refs(self.recon, cur, mv, self.rs.ref_id, self.rc.num_sig)
-            if self.chroma:
-                hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                      self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
-            mark("deblock")
-        final, final_c = self.recon, self.recon_c
-        if self.sao is not None and self.sao_apply and self.out is None:
-            self.out = torch.zeros_like(cur.t)
-            self.out_c = [torch.zeros_like(p) for p in cur.c] if self.chroma else None
-        if self.sao_rdo is not None:
-            planes = FramePipeline._sao_planes(self, cur)
-            hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes])
-            mark("sao_stats")
-            FramePipeline._sao_rdo(self)
-            mark("sao_rdo")
-            hipabi.sao_apply_planes(self.depth, planes)
-            final, final_c = self.out, self.out_c
-            mark("sao_apply")
-        elif self.sao is not None:
-            self.sao.stats(cur, self.recon, cur.stride, cur.org)
-            if self.chroma:
-                for i in range(2):
-                    self.sao_c[i].stats(None, self.recon_c[i], cur.stride_c, cur.org_c, src_plane=cur.c[i])
-            mark("sao_stats")
-            if self.sao_apply:
-                self.sao.decide()
-                self.sao.apply(self.recon, cur.stride, cur.org, self.out)
-                final = self.out
-                if self.chroma:
-                    for i in range(2):
-                        self.sao_c[i].decide()
-                        self.sao_c[i].apply(self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i])
-                    final_c = self.out_c
-                mark("sao_apply")
-        extend_border_picture([final] + (list(final_c) if self.chroma else []), cur)
-        mark("border")
-        self.final, self.final_c = final, final_c
-        return final
-
-    def final_planes(self):
-        """[Y, Cb, Cr] (or [Y]) of the picture run() coded last."""
-        return [self.final] + (list(self.final_c) if self.chroma else [])
+        return self._filter_tail(cur, mark)
 
     def checksum(self):
-        import torch
-        out = {}
-        for r in range(self.max_refs):
-            out.update({"%s%d" % (k, r): v for k, v in self.msl[r].checksum().items()})
-            out.update({"%s%d" % (k, r): v for k, v in self.spl[r].checksum().items()})
-        out.update(self.rs.checksum())
-        out.update(self.rc.checksum())
-        if self.chroma:
-            for i in range(2):
-                out.update({"%s_c%d" % (k, i): v for k, v in InterRecon.checksum(self.rc_c[i]).items()})
-        out["recon"] = int(self.final.to(torch.int64).sum().item())
-        return out
+        return self._checksum(self.rs)
 
 
 class IntraPicture:
@@ -1751,7 +1631,7 @@ class IntraPicture:
         return out
 
 
-class IFramePipeline:
+class IFramePipeline(_PictureStep):
     """One I picture on the device: intra picture (IntraPicture: mode decision + coding, luma and 4:2:0 chroma) -> boundary strengths of
     an all-intra picture + luma / chroma deblocking -> SAO (statistics, x265hip_sao_rdo or the distortion-only stand-in, application)
     -> border extension.  The constructor switches mean what they mean in BFramePipeline; X265HIP_TU_INTRA_SLICE is always set.
@@ -1760,21 +1640,14 @@ class IFramePipeline:
 
     def __init__(self, w64, h64, depth, device, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False, sign_hide=False,
                  sao_rdo=None, lambda8=1024, mode_bits=(2, 3, 6), strong_intra_smoothing=True, want_cost=False):
-        import types
         import torch
-        self.depth, self.qp, self.chroma = depth, qp, chroma
-        self.ms = types.SimpleNamespace(w64=w64, h64=h64, nctu=(w64 // 64) * (h64 // 64))     # geometry for the helpers shared with FramePipeline
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
         self.tu_flags = hipabi.TU_INTRA_SLICE | (hipabi.TU_SIGN_HIDE if sign_hide else 0)
         qpc = chroma_quant_qp(qp, depth)
-        self.ip = IntraPicture(self.ms.nctu, w64, h64, depth, level, qp, device, flags=self.tu_flags, chroma=chroma, qp_c=(qpc, qpc), lambda8=lambda8,
+        self.ip = IntraPicture(self.nctu, w64, h64, depth, level, qp, device, flags=self.tu_flags, chroma=chroma, qp_c=(qpc, qpc), lambda8=lambda8,
                                mode_bits=mode_bits, strong_intra_smoothing=strong_intra_smoothing, want_cost=want_cost)
-        self.db = Deblock(w64, h64, depth, level, max(qp - 6 * (depth - 8), 0), device) if deblock else None
-        self.sao = Sao(w64, h64, depth, device) if sao else None
         if self.db is not None:
             self.db.prepare_intra()
-        if chroma:
-            self.sao_c = [Sao(w64 // 2, h64 // 2, depth, device, ctu=(32, 32), plane_offset=2) for _ in range(2)] if sao else None
-        self.sao_apply = bool(sao and sao_apply)
         # the planes of the picture (PicYuv geometry of a DevicePicture), allocated here: run() allocates nothing and can be captured without a warm-up
         from . import frames as F
         _, _, stride, rows, _ = F.padded_dims(w64, h64)
@@ -1785,65 +1658,24 @@ class IFramePipeline:
             return torch.zeros((rows, stride), dtype=dt, device=device), ([torch.zeros(nc, dtype=dt, device=device) for _ in range(2)] if chroma else None)
         self.recon, self.recon_c = planes()
         self.out, self.out_c = planes() if self.sao_apply else (None, None)
-        self.sao_rdo = sao_rdo if (sao and sao_apply) else None
-        if self.sao_rdo is not None:
-            self.sao_scratch = torch.zeros(hipabi.sao_rdo_scratch_bytes(w64 // 64, h64 // 64), dtype=torch.uint8, device=device)
-            self.sao_no = torch.zeros(2, dtype=torch.int32, device=device)
 
     def set_qp_maps(self, maps, lambda8_by_qp=None):
         """Per-block QPs for the following run() calls (see FramePipeline.set_qp_maps); None = the picture-wide qp again.  lambda8_by_qp: device
         int32 tensor [52 + 6 (depth - 8)] - 256 x lambda of a CU per luma quantiser QP - or None = the constructor's lambda8 for every block."""
-        _set_qp_maps(self, maps, self.ip, [])
+        self._set_qp_maps(maps, self.ip, [])
         self.ip.qp_map = None if maps is None else maps.tu_qp
         self.ip.lambda8_by_qp = None if maps is None else lambda8_by_qp
 
     def run(self, cur: DevicePicture, mark=None):
         """Returns the luma plane of the coded picture; mark(name), if given, is called after every stage."""
         mark = mark or (lambda name: None)
-        _qp_maps_run_check(self)
+        self._qp_maps_run_check()
         assert cur.t.shape == self.recon.shape and cur.t.dtype == self.recon.dtype
         self.ip.run(cur, self.recon, self.recon_c)
         mark("intra")
         if self.db is not None:
             self.db.run_intra(self.recon, cur, self.ip.num_sig)
-            if self.chroma:
-                hipabi.deblock_chroma(self.depth, self.recon_c[0], self.recon_c[1], cur.stride_c, cur.org_c, cur.w64, cur.h64,
-                                      self.db.bs_ver, self.db.bs_hor, self.db.qp, qp_map=self.db.qp_map)
-            mark("deblock")
-        final, final_c = self.recon, self.recon_c
-        if self.sao_rdo is not None:
-            planes = FramePipeline._sao_planes(self, cur)
-            hipabi.sao_planes(self.depth, [dict(q, out=None) for q in planes])
-            mark("sao_stats")
-            FramePipeline._sao_rdo(self)
-            mark("sao_rdo")
-            hipabi.sao_apply_planes(self.depth, planes)
-            final, final_c = self.out, self.out_c
-            mark("sao_apply")
-        elif self.sao is not None:
-            self.sao.stats(cur, self.recon, cur.stride, cur.org)
-            if self.chroma:
-                for i in range(2):
-                    self.sao_c[i].stats(None, self.recon_c[i], cur.stride_c, cur.org_c, src_plane=cur.c[i])
-            mark("sao_stats")
-            if self.sao_apply:
-                self.sao.decide()
-                self.sao.apply(self.recon, cur.stride, cur.org, self.out)
-                final = self.out
-                if self.chroma:
-                    for i in range(2):
-                        self.sao_c[i].decide()
-                        self.sao_c[i].apply(self.recon_c[i], cur.stride_c, cur.org_c, self.out_c[i])
-                    final_c = self.out_c
-                mark("sao_apply")
-        extend_border_picture([final] + (list(final_c) if self.chroma else []), cur)
-        mark("border")
-        self.final, self.final_c = final, final_c
-        return final
-
-    def final_planes(self):
-        """[Y, Cb, Cr] (or [Y]) of the picture run() coded last."""
-        return [self.final] + (list(self.final_c) if self.chroma else [])
+        return self._filter_tail(cur, mark)
 
     def checksum(self):
         import torch

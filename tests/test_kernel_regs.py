@@ -43,7 +43,7 @@ def test_hot_kernels_keep_the_occupancy_they_were_tuned_for():
     k = _kernels()
     waves = lambda name: min(8, 512 // k[name]["vgpr"])
     # the uni-predictive 16 / 32 point TU stages of the default step: two wavefronts per SIMD, nothing spilled (profiles/r03_tail_kernels.txt)
-    for name in ("inter_recon_kernel<unsigned char, 32, false, false>", "inter_recon_kernel<unsigned char, 16, true, false>"):
+    for name in ("inter_recon_kernel<unsigned char, 32, false, false, TuArgs2>", "inter_recon_kernel<unsigned char, 16, true, false, TuArgs2>"):
         assert waves(name) >= 2 and k[name]["vspill"] == 0 and k[name]["scratch"] == 0, (name, k[name])
     # the exhaustive search the bench times: two workgroups of four wavefronts per CU by design (194 registers), no spills
     for me in ("me_ctu_c_kernel<true, true, 3, 3>", "me_ctu_c_kernel<true, true, 2, 3>"):          # block-major (the default) / chunk-major records

@@ -212,7 +212,7 @@ def _kernels():
     return read()
 
 
-REFS_INSTANCES = [f"inter_recon_refs_kernel<{px}, {n}, {c}>" for px in ("unsigned char", "unsigned short") for n, c in ((16, "false"), (32, "false"), (16, "true"))]
+REFS_INSTANCES = [f"inter_recon_kernel<{px}, {n}, {c}, false, TuRefsArgs>" for px in ("unsigned char", "unsigned short") for n, c in ((16, "false"), (32, "false"), (16, "true"))]
 
 
 @pytest.mark.parametrize("name", REFS_INSTANCES)

@@ -139,8 +139,8 @@ template <int N> struct TuOps<N, true>
     }
 };
 template <int N, bool DST> using TuOpsFor = TuOps<N, (N >= 16 && !DST)>;
-// The operands built again (inter_recon_refs_kernel at 32 points, two bytes per sample: per block).  Functors of its own: the instances of
-// DctOperand::init the other kernels share keep their callers, and with them their code.
+// The operands built again (the multi-reference instance of inter_recon_kernel at 32 points, two bytes per sample: per block).  Functors of
+// its own: the instances of DctOperand::init the other kernels share keep their callers, and with them their code.
 template <int N> __device__ __forceinline__ void tu_ops_rebuild(TuOps<N, true>& o, int lane)
 {
     auto matrix = [](int r, int c) { return (int)kTu.m[r][c]; };
@@ -607,204 +607,6 @@ template <int N> struct InterReconThreads { static constexpr int value = N >= 16
 // (spills) made the chroma pair slower, 81 -> 93 / 85 us (profiles/r03_tail_kernels.txt).
 template <int N> struct TuWavesPerSimd { static constexpr int value = N == 32 ? 2 : (N == 16 ? 2 : 1); };
 
-template <typename Px, int N, bool CHROMA, bool TAB = false>
-__global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>::value) inter_recon_kernel(TuArgs2 aa, int nblocks)
-{
-    const TuArgs& a = aa.p[blockIdx.y];          // grid.y = plane: Cb and Cr of a picture (or of a band of it) share one launch
-    constexpr int NN = N * N, LOG2N = N == 4 ? 2 : (N == 8 ? 3 : (N == 16 ? 4 : 5));
-    constexpr int TAPS = CHROMA ? 4 : 8, APRON = TAPS / 2 - 1, PW = N + TAPS - 1, PP = PW + 1;
-    constexpr int NL = CHROMA ? 2 * N : N, CTU = CHROMA ? 32 : 64, MVSH = CHROMA ? 3 : 2, MVMASK = CHROMA ? 7 : 3;
-    constexpr int BPP = sizeof(Px);
-    __shared__ __attribute__((aligned(16))) int16_t patch[PW * PP];
-    __shared__ int16_t immed[PW * N];
-    __shared__ __attribute__((aligned(16))) int16_t pred[NN], fe[NN], A[NN], B[NN];
-    __shared__ unsigned long long red[4];
-    __shared__ int sNumSig;
-
-    const int npu = (64 / NL) * (64 / NL);
-    const int lbase = NL == 8 ? 0 : (NL == 16 ? 64 : 80);
-    const int tid = threadIdx.x, nth = blockDim.x;
-    const int maxVal = (1 << a.depth) - 1, headRoom = 14 - a.depth;
-    auto tap = [](int f, int t) { return CHROMA ? (int)kTuChromaTaps[f][t] : (int)kTuTaps[f][t]; };
-    // 16 / 32: a persistent single-wavefront workgroup walks blocks blockIdx.x, + gridDim.x, ... with the MFMA operands of the
-    // transforms built once (its barriers are wave-local); 8: one block per workgroup
-    TuOpsFor<N, false> ops;
-    ops.init(tid & 63);
-    // geometry of block `blk` given its packed quarter-sample motion vector
-    struct Geo { int ctu, z, px, py, qx, qy, xf, yf, qp; };
-    auto geom = [&](const int blk, const int packed) -> Geo
-    {
-        Geo g;
-        g.ctu = blk / npu; g.z = blk - g.ctu * npu;
-        const int bxz = (g.z & 1) | ((g.z >> 1) & 2) | ((g.z >> 2) & 4), byz = ((g.z >> 1) & 1) | ((g.z >> 2) & 2) | ((g.z >> 3) & 4);
-        g.px = (g.ctu % a.ctusW) * CTU + bxz * N; g.py = (g.ctu / a.ctusW) * CTU + byz * N;
-        g.qx = (int16_t)(packed & 0xffff); g.qy = (int16_t)(packed >> 16);
-        g.xf = g.qx & MVMASK; g.yf = g.qy & MVMASK;
-        // the block's own QP travels with its geometry: where the next block's operands are fetched ahead (16 points), its QP waits in gn
-        // and the chain below keeps reading g
-        g.qp = tu_block_qp(a, g.px >> (CHROMA ? 2 : 3), g.py >> (CHROMA ? 2 : 3));
-        return g;
-    };
-    auto mv_of = [&](const int blk) -> int { const int ctu = blk / npu; return a.mv[(size_t)ctu * 85 + lbase + (blk - ctu * npu)].y; };
-    // 16 / 32: dword loads (4 / 2 samples) of the source block and the reference patch into REGISTERS, all issued before the first one is
-    // waited for; they go into LDS (widened to int16 pairs) at the top of the block's turn.  A patch row is read to the next dword boundary
-    // (one sample beyond the 2 * apron + N needed: still inside the padded plane, and inside the row's LDS pitch).
-    constexpr int NT = InterReconThreads<N>::value, SPD = 4 / BPP, FD = N / SPD, PWD = (PW + SPD - 1) / SPD;
-    constexpr int FI = N >= 16 ? (N * FD) / NT : 1, PI = N >= 16 ? (PW * PWD + NT - 1) / NT : 1;
-    static_assert(N < 16 || (PWD * SPD <= PP && (N * FD) % NT == 0), "patch pitch / source block size");
-    auto load_regs = [&](const Geo& g, uint32_t (&fv)[FI], uint32_t (&pv)[PI])
-    {
-        const Px* f = reinterpret_cast<const Px*>(a.fenc + (long)g.py * a.fencStrideB) + g.px;
-        const long fst = a.fencStrideB / BPP;
-        const Px* r = reinterpret_cast<const Px*>(a.fref + (long)(g.py + (g.qy >> MVSH) - APRON) * a.frefStrideB) + (g.px + (g.qx >> MVSH) - APRON);
-        const long rst = a.frefStrideB / BPP;
-#pragma unroll
-        for (int k = 0; k < FI; k++) { const int i = tid + k * NT, y = i / FD, c = i - y * FD; fv[k] = ld_u32(reinterpret_cast<const uint8_t*>(f + y * fst) + 4 * c); }
-#pragma unroll
-        for (int k = 0; k < PI; k++)
-        {
-            const int i = tid + k * NT, y = i / PWD, c = i - y * PWD;
-            pv[k] = i < PW * PWD ? ld_u32(reinterpret_cast<const uint8_t*>(r + y * rst) + 4 * c) : 0u;
-        }
-    };
-    auto store_regs = [&](const uint32_t (&fv)[FI], const uint32_t (&pv)[PI])
-    {
-        auto put = [&](int16_t* dst, const uint32_t w)
-        {
-            if (BPP == 1)
-            {
-                uint2 v;
-                v.x = (w & 0xffu) | ((w & 0xff00u) << 8); v.y = ((w >> 16) & 0xffu) | ((w >> 8) & 0xff0000u);
-                *reinterpret_cast<uint2*>(dst) = v;
-            }
-            else *reinterpret_cast<uint32_t*>(dst) = w;
-        };
-#pragma unroll
-        for (int k = 0; k < FI; k++) { const int i = tid + k * NT; put(fe + i * SPD, fv[k]); }
-#pragma unroll
-        for (int k = 0; k < PI; k++) { const int i = tid + k * NT, y = i / PWD, c = i - y * PWD; if (i < PW * PWD) put(patch + y * PP + c * SPD, pv[k]); }
-    };
-    // everything behind the staging: prediction from the patch in LDS; `between` runs after the prediction (the next block's loads are issued
-    // there: its motion vector has arrived by then and the loads have the whole transform chain to complete); then the transform chain
-    auto do_rest = [&](const Geo& g, auto&& between)
-    {
-    const int ctu = g.ctu, z = g.z, px = g.px, py = g.py, xf = g.xf, yf = g.yf;
-    // ---- predInterLumaPixel ----------------------------------------------------------------------------
-    if (xf && yf)
-    {
-        const int shiftPS = 6 - headRoom, offPS = -(8192 << shiftPS);
-        for (int i = tid; i < PW * N; i += nth)
-        {
-            const int y = i >> LOG2N, x = i & (N - 1);
-            int s = 0;
-#pragma unroll
-            for (int t = 0; t < TAPS; t++) s += (int)patch[y * PP + x + t] * tap(xf, t);
-            immed[i] = (int16_t)((s + offPS) >> shiftPS);
-        }
-        __syncthreads();
-        const int shiftSP = 6 + headRoom, offSP = (1 << (shiftSP - 1)) + (8192 << 6);
-        for (int i = tid; i < NN; i += nth)
-        {
-            const int y = i >> LOG2N, x = i & (N - 1);
-            int s = 0;
-#pragma unroll
-            for (int t = 0; t < TAPS; t++) s += (int)immed[(y + t) * N + x] * tap(yf, t);
-            pred[i] = (int16_t)tu_clip16((s + offSP) >> shiftSP, maxVal);
-        }
-    }
-    else
-    {
-        for (int i = tid; i < NN; i += nth)
-        {
-            const int y = i >> LOG2N, x = i & (N - 1);
-            int v;
-            if (!(xf | yf)) v = patch[(y + APRON) * PP + x + APRON];
-            else
-            {
-                int s = 0;
-#pragma unroll
-                for (int t = 0; t < TAPS; t++)
-                    s += (int)(xf ? patch[(y + APRON) * PP + x + t] : patch[(y + t) * PP + x + APRON]) * tap(xf ? xf : yf, t);
-                v = tu_clip16((s + 32) >> 6, maxVal);
-            }
-            pred[i] = (int16_t)v;
-        }
-    }
-    __syncthreads();
-    between();
-
-    tu_chain<Px, N, false, TAB>(ops, pred, fe, A, B, red, sNumSig, a.depth, g.qp, a.intraSlice,
-                           a.levels + ((size_t)ctu * npu + z) * NN, &a.numSig[(size_t)ctu * npu + z], &a.dist[(size_t)ctu * npu + z],
-                           reinterpret_cast<Px*>(a.recon + (long)py * a.reconStrideB) + px, a.reconStrideB / BPP, TU_SCAN_DIAG,
-                           TAB ? a.tab.at(((size_t)ctu * npu + z) * NN) : a.tab, (size_t)ctu * npu + z);
-    __syncthreads();
-    };
-    if constexpr (N >= 16)
-    {
-        // A persistent wavefront walks blocks blockIdx.x, + gridDim.x, ...  Per block it used to pay two dependent trips to memory before any
-        // work - the motion vector, then the source block / reference patch the vector points at - ~3 us of a 10 us (16x16) / 17 us (32x32)
-        // block at one instruction per ~28 cycles (profiles/r03_inst_counters.txt).  Now the NEXT block's vector is requested at the top of a
-        // block and its samples right after the prediction, into registers; they wait there until the block's turn.
-        // (32x32: only the vector travels ahead - the 11 sample registers on top of its 252 made the compiler spill 261)
-        constexpr bool AHEAD = N == 16;
-        uint32_t fvC[FI], pvC[PI], fvN[AHEAD ? FI : 1], pvN[AHEAD ? PI : 1];
-        // XCD-aware order (round 6): wavefront w sits on XCD w % 8 (observed placement, for speed only) and walks virtual indices w, w + gridDim.x, ...; the virtual index
-        // -> block map hands every XCD a contiguous eighth of the picture's blocks, so the TUs of a CTU and the CTUs of a row - whose 32-byte source rows and straddling
-        // reference rows share 64-byte lines - meet in ONE L2 instead of being fetched by up to four (inter_recon<32> fetched 2.3 - 4.6 x its planes, profiles/stage_traffic.json)
-        int v = blockIdx.x;
-        const bool xcdOrder = !(a.intraSlice & TU_FLAG_RASTER_ORDER);
-        auto order = [&](const int i) { return xcdOrder ? xcd_swizzle(i, nblocks) : i; };
-        if (v < nblocks)
-        {
-            int blk = order(v);
-            Geo g = geom(blk, mv_of(blk));
-            if constexpr (AHEAD) load_regs(g, fvC, pvC);
-            for (; v < nblocks; v += gridDim.x)
-            {
-                const bool has = v + (int)gridDim.x < nblocks;
-                const int nb = has ? order(v + (int)gridDim.x) : 0;
-                int packedN = 0;
-                if (has) packedN = mv_of(nb);
-                if constexpr (!AHEAD) load_regs(g, fvC, pvC);
-                store_regs(fvC, pvC);
-                if (tid == 0) sNumSig = 0;
-                __syncthreads();
-                Geo gn = g;
-                if constexpr (AHEAD)
-                {
-                    do_rest(g, [&]() { if (has) { gn = geom(nb, packedN); load_regs(gn, fvN, pvN); } });
-#pragma unroll
-                    for (int k = 0; k < FI; k++) fvC[k] = fvN[k];
-#pragma unroll
-                    for (int k = 0; k < PI; k++) pvC[k] = pvN[k];
-                }
-                else
-                {
-                    do_rest(g, []() {});
-                    if (has) gn = geom(nb, packedN);
-                }
-                g = gn;
-            }
-        }
-    }
-    else
-    {
-        const int blk = blockIdx.x;
-        const Geo g = geom(blk, mv_of(blk));
-        {
-            const Px* f = reinterpret_cast<const Px*>(a.fenc + (long)g.py * a.fencStrideB) + g.px;
-            const long fst = a.fencStrideB / BPP;
-            const Px* r = reinterpret_cast<const Px*>(a.fref + (long)(g.py + (g.qy >> MVSH) - APRON) * a.frefStrideB) + (g.px + (g.qx >> MVSH) - APRON);
-            const long rst = a.frefStrideB / BPP;
-            for (int i = tid; i < NN; i += nth) { const int y = i >> LOG2N, x = i & (N - 1); fe[i] = (int16_t)f[y * fst + x]; }
-            for (int i = tid; i < PW * PW; i += nth) { const int y = i / PW, x = i - y * PW; patch[y * PP + x] = (int16_t)r[y * rst + x]; }
-            if (tid == 0) sNumSig = 0;
-        }
-        __syncthreads();
-        do_rest(g, []() {});
-    }
-}
-
 // P pictures with several references (x265hip_inter_recon_refs and the chroma entries): block blk is predicted from the plane
 // fref[refIdx[blk]] of the launch's table of nrefs reference planes - refIdx = int8 [ctu][blocks], x265hip_ref_select's ref_idx.  Per
 // plane of grid.y its own table and indices.  No scaling-list / denoiser tables.
@@ -815,19 +617,25 @@ struct TuRefsArgs
     const int8_t* refIdx[2];
     int nrefs;
 };
+// the record of plane `plane` (grid.y; unsigned like blockIdx.y: a signed index changes the scalar address arithmetic of the tuned instances)
+__device__ __forceinline__ const TuArgs& tu_plane_args(const TuArgs2& aa, const unsigned plane) { return aa.p[plane]; }
+__device__ __forceinline__ const TuArgs& tu_plane_args(const TuRefsArgs& ra, const unsigned plane) { return ra.aa.p[plane]; }
 
-// inter_recon_kernel with the reference patch pointer of load_regs and of the 8-point load taken from the table.  A COPY of that kernel's
-// body, not a shared template: with the body moved into a __device__ __forceinline__ template the existing instances compiled to other
-// register counts, and those are tuned and pinned (tests/test_kernel_regs.py).  What differs: Geo::ref - the block's
-// list index travels with its geometry, so a patch fetched ahead is fetched from the plane of the block it belongs to -, ref_of, plane_of.
-template <typename Px, int N, bool CHROMA>
-__global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>::value) inter_recon_refs_kernel(TuRefsArgs ra, int nblocks)
+// Args = TuArgs2: every block is predicted from a.fref.  Args = TuRefsArgs (REFS): from the plane of the launch's table its list index
+// selects; the index travels with the block's geometry (Geo::ref), so a patch fetched ahead is fetched from the plane of the block it
+// belongs to.  REFS is a parameter of the kernel, not of a function the kernel calls: each instance is compiled from one body with the
+// other flavour's statements discarded, and the tuned, pinned single-reference instances (tests/test_kernel_regs.py) keep their code
+// instruction for instruction.
+template <typename Px, int N, bool CHROMA, bool TAB = false, class Args = TuArgs2>
+__global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>::value) inter_recon_kernel(Args ra, int nblocks)
 {
-    const TuArgs& a = ra.aa.p[blockIdx.y];          // grid.y = plane
-    const uint8_t* const* planes = ra.fref[blockIdx.y];
-    const int8_t* refIdx = ra.refIdx[blockIdx.y];
-    const int nrefs = ra.nrefs;
-    constexpr bool TAB = false;
+    constexpr bool REFS = std::is_same<Args, TuRefsArgs>::value;
+    static_assert(!(REFS && TAB), "the multi-reference entries take no tables");
+    const TuArgs& a = tu_plane_args(ra, blockIdx.y);          // grid.y = plane: Cb and Cr of a picture (or of a band of it) share one launch
+    const uint8_t* const* planes = nullptr;
+    const int8_t* refIdx = nullptr;
+    int nrefs = 1;
+    if constexpr (REFS) { planes = ra.fref[blockIdx.y]; refIdx = ra.refIdx[blockIdx.y]; nrefs = ra.nrefs; }
     constexpr int NN = N * N, LOG2N = N == 4 ? 2 : (N == 8 ? 3 : (N == 16 ? 4 : 5));
     constexpr int TAPS = CHROMA ? 4 : 8, APRON = TAPS / 2 - 1, PW = N + TAPS - 1, PP = PW + 1;
     constexpr int NL = CHROMA ? 2 * N : N, CTU = CHROMA ? 32 : 64, MVSH = CHROMA ? 3 : 2, MVMASK = CHROMA ? 7 : 3;
@@ -860,14 +668,15 @@ __global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>
         // the block's own QP travels with its geometry: where the next block's operands are fetched ahead (16 points), its QP waits in gn
         // and the chain below keeps reading g
         g.qp = tu_block_qp(a, g.px >> (CHROMA ? 2 : 3), g.py >> (CHROMA ? 2 : 3));
-        // the block's list index, uniform over the workgroup (one block), clamped to the table: no entry is dereferenced out of range
-        g.ref = clip3(0, nrefs - 1, __builtin_amdgcn_readfirstlane(ref));
+        // REFS: the block's list index, uniform over the workgroup (one block), clamped to the table: no entry is dereferenced out of range
+        if constexpr (REFS) g.ref = clip3(0, nrefs - 1, __builtin_amdgcn_readfirstlane(ref));
+        else g.ref = 0;
         return g;
     };
     auto mv_of = [&](const int blk) -> int { const int ctu = blk / npu; return a.mv[(size_t)ctu * 85 + lbase + (blk - ctu * npu)].y; };
-    auto ref_of = [&](const int blk) -> int { return (int)refIdx[blk]; };
-    // sample (0,0) of the plane block g is predicted from: the table sits in the kernel arguments and g.ref is uniform - a scalar load
-    auto plane_of = [&](const Geo& g) -> const uint8_t* { return planes[g.ref]; };
+    auto ref_of = [&](const int blk) -> int { if constexpr (REFS) return (int)refIdx[blk]; else return 0; };
+    // sample (0,0) of the plane block g is predicted from.  REFS: the table sits in the kernel arguments and g.ref is uniform - a scalar load
+    auto plane_of = [&](const Geo& g) -> const uint8_t* { if constexpr (REFS) return planes[g.ref]; else return a.fref; };
     // 16 / 32: dword loads (4 / 2 samples) of the source block and the reference patch into REGISTERS, all issued before the first one is
     // waited for; they go into LDS (widened to int16 pairs) at the top of the block's turn.  A patch row is read to the next dword boundary
     // (one sample beyond the 2 * apron + N needed: still inside the padded plane, and inside the row's LDS pitch).
@@ -987,10 +796,10 @@ __global__ void __launch_bounds__(InterReconThreads<N>::value, TuWavesPerSimd<N>
                 const int nb = has ? order(v + (int)gridDim.x) : 0;
                 int packedN = 0, refN = 0;
                 if (has) { packedN = mv_of(nb); refN = ref_of(nb); }
-                if constexpr (N == 32 && BPP == 2)
+                if constexpr (REFS && N == 32 && BPP == 2)
                 {
-                    // 32 points at two bytes per sample: with the operands kept over the whole walk the chain does not fit 256 registers (30 spilled,
-                    // 124 bytes of scratch - as the single-reference twin).  Built per block - ~70 loads from constant memory
+                    // Several references, 32 points at two bytes per sample: with the operands kept over the whole walk the chain does not fit
+                    // 256 registers (30 spilled, 124 bytes of scratch - DESIGN.md section 14).  Built per block - ~70 loads from constant memory
                     // beside a block's thousands of instructions - each operand lives from its build to its last product: 253 registers, nothing
                     // spilled.  The lane index goes through an empty asm so that the build is not hoisted out of the walk again.
                     int lane = tid & 63;
@@ -1279,35 +1088,47 @@ static bool tu_raster_order(const bool chroma)
     return e[0] == '1' || (chroma ? e[0] == 'c' : e[0] == 'l');
 }
 
-// The persistent kernel (16 / 32 points) `entry` launches for n x n transforms, or NULL where it launches one workgroup per block
-template <typename Px, bool TB> static const void* tu_persistent_kernel(const int entry, const int n)
+// The one table of the TU-stage kernels: what `entry` (X265HIP_TU_ENTRY_*) launches for n x n transforms of Px samples, at every size its
+// launcher takes - 8 / 16 / 32 for luma, 4 / 8 / 16 for chroma, 4 (dst: the DST-VII of intra luma) / 8 / 16 / 32 for the intra batch - or
+// NULL.  The multi-reference entries have no table flavour: they refuse tables.
+template <typename Px, bool TB> static const void* tu_kernel_of(const int entry, const int n, const bool dst)
 {
+    typedef const void* K;
     switch (entry)
     {
     case X265HIP_TU_ENTRY_INTER:
-        return n == 16 ? (const void*)inter_recon_kernel<Px, 16, false, TB> : (n == 32 ? (const void*)inter_recon_kernel<Px, 32, false, TB> : nullptr);
-    case X265HIP_TU_ENTRY_INTER_BI:
-        return n == 16 ? (const void*)inter_recon_bi_kernel<Px, 16, false, TB> : (n == 32 ? (const void*)inter_recon_bi_kernel<Px, 32, false, TB> : nullptr);
+        return n == 8 ? (K)inter_recon_kernel<Px, 8, false, TB> : n == 16 ? (K)inter_recon_kernel<Px, 16, false, TB> : n == 32 ? (K)inter_recon_kernel<Px, 32, false, TB> : nullptr;
     case X265HIP_TU_ENTRY_INTER_CHROMA:
-        return n == 16 ? (const void*)inter_recon_kernel<Px, 16, true, TB> : nullptr;
+        return n == 4 ? (K)inter_recon_kernel<Px, 4, true, TB> : n == 8 ? (K)inter_recon_kernel<Px, 8, true, TB> : n == 16 ? (K)inter_recon_kernel<Px, 16, true, TB> : nullptr;
+    case X265HIP_TU_ENTRY_INTER_BI:
+        return n == 8 ? (K)inter_recon_bi_kernel<Px, 8, false, TB> : n == 16 ? (K)inter_recon_bi_kernel<Px, 16, false, TB> : n == 32 ? (K)inter_recon_bi_kernel<Px, 32, false, TB> : nullptr;
     case X265HIP_TU_ENTRY_INTER_CHROMA_BI:
-        return n == 16 ? (const void*)inter_recon_bi_kernel<Px, 16, true, TB> : nullptr;
-    case X265HIP_TU_ENTRY_INTER_REFS:             // no table flavour: the entry refuses tables
-        return n == 16 ? (const void*)inter_recon_refs_kernel<Px, 16, false> : (n == 32 ? (const void*)inter_recon_refs_kernel<Px, 32, false> : nullptr);
+        return n == 4 ? (K)inter_recon_bi_kernel<Px, 4, true, TB> : n == 8 ? (K)inter_recon_bi_kernel<Px, 8, true, TB> : n == 16 ? (K)inter_recon_bi_kernel<Px, 16, true, TB> : nullptr;
+    case X265HIP_TU_ENTRY_INTER_REFS:
+        return n == 8 ? (K)inter_recon_kernel<Px, 8, false, false, TuRefsArgs> : n == 16 ? (K)inter_recon_kernel<Px, 16, false, false, TuRefsArgs>
+             : n == 32 ? (K)inter_recon_kernel<Px, 32, false, false, TuRefsArgs> : nullptr;
     case X265HIP_TU_ENTRY_INTER_CHROMA_REFS:
-        return n == 16 ? (const void*)inter_recon_refs_kernel<Px, 16, true> : nullptr;
+        return n == 4 ? (K)inter_recon_kernel<Px, 4, true, false, TuRefsArgs> : n == 8 ? (K)inter_recon_kernel<Px, 8, true, false, TuRefsArgs>
+             : n == 16 ? (K)inter_recon_kernel<Px, 16, true, false, TuRefsArgs> : nullptr;
+    case X265HIP_TU_ENTRY_INTRA:
+        return n == 4 ? (dst ? (K)intra_recon_kernel<Px, 4, true, TB> : (K)intra_recon_kernel<Px, 4, false, TB>) : n == 8 ? (K)intra_recon_kernel<Px, 8, false, TB>
+             : n == 16 ? (K)intra_recon_kernel<Px, 16, false, TB> : n == 32 ? (K)intra_recon_kernel<Px, 32, false, TB> : nullptr;
     default:
-        return n == 16 ? (const void*)intra_recon_kernel<Px, 16, false, TB> : (n == 32 ? (const void*)intra_recon_kernel<Px, 32, false, TB> : nullptr);
+        return nullptr;
     }
 }
+static const void* tu_kernel(const int entry, const int n, const int depth, const bool tables, const bool dst = false)
+{
+    return depth == 8 ? (tables ? tu_kernel_of<uint8_t, true>(entry, n, dst) : tu_kernel_of<uint8_t, false>(entry, n, dst))
+                      : (tables ? tu_kernel_of<uint16_t, true>(entry, n, dst) : tu_kernel_of<uint16_t, false>(entry, n, dst));
+}
 
-// grid.x of every TU-stage launch (x265hip_tu_launch_grid): the persistent kernels get exactly one resident set of single-wavefront
-// workgroups (a second partial round would double the time), split over `nplanes` rows of grid.y, never more workgroups than blocks;
-// the others one workgroup per block
+// grid.x of every TU-stage launch (x265hip_tu_launch_grid): the persistent kernels (16 / 32 points) get exactly one resident set of
+// single-wavefront workgroups (a second partial round would double the time), split over `nplanes` rows of grid.y, never more workgroups
+// than blocks; the others one workgroup per block
 static int tu_launch_grid(const int entry, const int n, const int depth, const bool tables, const int nplanes, const int nblocks)
 {
-    const void* fn = depth == 8 ? (tables ? tu_persistent_kernel<uint8_t, true>(entry, n) : tu_persistent_kernel<uint8_t, false>(entry, n))
-                                : (tables ? tu_persistent_kernel<uint16_t, true>(entry, n) : tu_persistent_kernel<uint16_t, false>(entry, n));
+    const void* fn = n >= 16 ? tu_kernel(entry, n, depth, tables) : nullptr;
     if (!fn) return nblocks;
     int dev = 0, cus = 256, per = 8;
     (void)hipGetDevice(&dev);
@@ -1343,43 +1164,71 @@ static bool tu_map_with_tables(const x265hip_recon_params* p, const char* who)
     return true;
 }
 
+// The checks of one base record, in the order and the words every inter entry has always had.  lumaWords: the entries that take a chroma
+// plane say that sizes and levels count luma samples.  refs: the record of a multi-reference entry - base.fref is ignored, the planes come
+// from its table, whose checks sit between those of the operands and those of the geometry.
+static bool tu_record_ok(const x265hip_recon_params* q, const char* who, const bool lumaWords, const x265hip_recon_refs_params* refs = nullptr)
+{
+    if (!q || !q->fenc || (!refs && !q->fref) || !q->recon || !q->mv || !q->levels || !q->num_sig || !q->dist || (refs && !refs->ref_idx))
+    { set_error("%s: NULL operand", who); return false; }
+    if (refs)
+    {
+        if (refs->nrefs < 1 || refs->nrefs > X265HIP_MAX_REFS) { set_error("%s: nrefs %d out of [1,%d]", who, refs->nrefs, X265HIP_MAX_REFS); return false; }
+        for (int k = 0; k < refs->nrefs; k++)
+            if (!refs->fref[k]) { set_error("%s: NULL plane of reference %d", who, k); return false; }
+    }
+    if ((q->width & 63) || (q->height & 63) || q->width <= 0 || q->height <= 0) { set_error("%s: width/height%s must be multiples of 64", who, lumaWords ? " (luma)" : ""); return false; }
+    if (q->depth != 8 && q->depth != 10 && q->depth != 12) { set_error("%s: depth %d", who, q->depth); return false; }
+    if (q->level < 0 || q->level > 2) { set_error("%s: level %d (0..2 = 8x8, 16x16, 32x32%s)", who, q->level, lumaWords ? " luma blocks" : ""); return false; }
+    if (q->qp < 0 || q->qp > 51 + 6 * (q->depth - 8)) { set_error("%s: qp %d out of range", who, q->qp); return false; }
+    return true;
+}
+
+// The kernel's record of a checked base record predicted from `fref`.  The flag bits are the record's: the entries that walk the blocks
+// in the XCD-aware order put their switch on top (tu_walk_order)
+static TuArgs tu_args_of(const x265hip_recon_params* q, const void* fref)
+{
+    const int bpp = q->depth == 8 ? 1 : 2;
+    TuArgs a;
+    a.fenc = (const uint8_t*)q->fenc; a.fencStrideB = (long)q->fenc_stride * bpp;
+    a.fref = (const uint8_t*)fref; a.frefStrideB = (long)q->fref_stride * bpp;
+    a.recon = (uint8_t*)q->recon; a.reconStrideB = (long)q->recon_stride * bpp;
+    a.ctusW = q->width / 64; a.depth = q->depth; a.level = q->level;
+    a.mv = (const int2*)q->mv; a.qp = q->qp; a.intraSlice = q->intra_slice;
+    a.levels = q->levels; a.numSig = q->num_sig; a.dist = (unsigned long long*)q->dist;
+    a.tab = tu_tables_of(TABLES_OF(q)); a.qpMap = q->qp_map;
+    return a;
+}
+static void tu_walk_order(TuArgs& a, const bool chroma) { a.intraSlice = (a.intraSlice & ~TU_FLAG_RASTER_ORDER) | (tu_raster_order(chroma) ? TU_FLAG_RASTER_ORDER : 0); }
+static int tu_blocks(const x265hip_recon_params* p) { return (p->width / 64) * (p->height / 64) * (64 >> (2 * p->level)); }
+
+// One launch of a kernel of the table: 64 threads per workgroup, args = the addresses of the kernel's arguments
+static int tu_launch(const void* fn, const dim3 grid, void* stream, void** args)
+{
+    (void)hipLaunchKernel(fn, grid, dim3(64), args, 0, (hipStream_t)stream);
+    X265HIP_TRY(hipGetLastError());
+    return 0;
+}
+// The launch of an inter entry: its kernel for the records' block size, one resident set (or one workgroup per block) per plane of grid.y
+static int tu_launch_inter(const int entry, const x265hip_recon_params* p, const bool chroma, const int nplanes, void* stream, void* record)
+{
+    const int n = (chroma ? 4 : 8) << p->level;
+    int nblocks = tu_blocks(p);
+    const int grid = tu_launch_grid(entry, n, p->depth, p->tables != nullptr, nplanes, nblocks);
+    void* args[] = { record, &nblocks };
+    return tu_launch(tu_kernel(entry, n, p->depth, p->tables != nullptr), dim3(grid, nplanes), stream, args);
+}
+
 extern "C" int x265hip_inter_recon(const x265hip_recon_params* p, void* stream)
 {
     if (tu_map_with_tables(p, "inter_recon")) return X265HIP_EINVAL;
     int rc = ensure_device();
     if (rc) return rc;
-    if (!p || !p->fenc || !p->fref || !p->recon || !p->mv || !p->levels || !p->num_sig || !p->dist)
-    { set_error("inter_recon: NULL operand"); return X265HIP_EINVAL; }
-    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("inter_recon: width/height must be multiples of 64"); return X265HIP_EINVAL; }
-    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("inter_recon: depth %d", p->depth); return X265HIP_EINVAL; }
-    if (p->level < 0 || p->level > 2) { set_error("inter_recon: level %d (0..2 = 8x8, 16x16, 32x32)", p->level); return X265HIP_EINVAL; }
-    if (p->qp < 0 || p->qp > 51 + 6 * (p->depth - 8)) { set_error("inter_recon: qp %d out of range", p->qp); return X265HIP_EINVAL; }
-    const int bpp = p->depth == 8 ? 1 : 2;
-    TuArgs a;
-    a.fenc = (const uint8_t*)p->fenc; a.fencStrideB = (long)p->fenc_stride * bpp;
-    a.fref = (const uint8_t*)p->fref; a.frefStrideB = (long)p->fref_stride * bpp;
-    a.recon = (uint8_t*)p->recon; a.reconStrideB = (long)p->recon_stride * bpp;
-    a.ctusW = p->width / 64; a.depth = p->depth; a.level = p->level;
-    a.mv = (const int2*)p->mv; a.qp = p->qp; a.intraSlice = (p->intra_slice & ~TU_FLAG_RASTER_ORDER) | (tu_raster_order(false) ? TU_FLAG_RASTER_ORDER : 0);
-    a.levels = p->levels; a.numSig = p->num_sig; a.dist = (unsigned long long*)p->dist;
-    a.tab = tu_tables_of(TABLES_OF(p)); a.qpMap = p->qp_map;
+    if (!tu_record_ok(p, "inter_recon", false)) return X265HIP_EINVAL;
     TuArgs2 aa = {};
-    aa.p[0] = a;
-    const int nctu = a.ctusW * (p->height / 64);
-    const int npu = 64 >> (2 * p->level);
-    hipStream_t s = (hipStream_t)stream;
-    const int nblocks = nctu * npu;
-    const int grid = tu_launch_grid(X265HIP_TU_ENTRY_INTER, 8 << p->level, p->depth, p->tables != nullptr, 1, nblocks);
-#define GO_T(PX, TB) do { \
-        if (p->level == 0) hipLaunchKernelGGL((inter_recon_kernel<PX, 8, false, TB>), dim3(grid), dim3(64), 0, s, aa, nblocks); \
-        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_kernel<PX, 16, false, TB>), dim3(grid), dim3(64), 0, s, aa, nblocks); \
-        else hipLaunchKernelGGL((inter_recon_kernel<PX, 32, false, TB>), dim3(grid), dim3(64), 0, s, aa, nblocks); } while (0)
-#define GO(PX) do { if (p->tables) GO_T(PX, true); else GO_T(PX, false); } while (0)
-    if (p->depth == 8) GO(uint8_t); else GO(uint16_t);
-#undef GO_T
-#undef GO
-    X265HIP_TRY(hipGetLastError());
-    return 0;
+    aa.p[0] = tu_args_of(p, p->fref);
+    tu_walk_order(aa.p[0], false);
+    return tu_launch_inter(X265HIP_TU_ENTRY_INTER, p, false, 1, stream, &aa);
 }
 
 static int inter_recon_bi_impl(const x265hip_recon_bi_params* q, void* stream, const bool chroma)
@@ -1387,24 +1236,11 @@ static int inter_recon_bi_impl(const x265hip_recon_bi_params* q, void* stream, c
     if (q && tu_map_with_tables(&q->base, "inter_recon_bi")) return X265HIP_EINVAL;
     int rc = ensure_device();
     if (rc) return rc;
-    if (!q) { set_error("inter_recon_bi: NULL operand"); return X265HIP_EINVAL; }
+    if (!q || !q->fref1 || !q->mv1) { set_error("inter_recon_bi: NULL operand"); return X265HIP_EINVAL; }
     const x265hip_recon_params* p = &q->base;
-    if (!p->fenc || !p->fref || !q->fref1 || !p->recon || !p->mv || !q->mv1 || !p->levels || !p->num_sig || !p->dist)
-    { set_error("inter_recon_bi: NULL operand"); return X265HIP_EINVAL; }
-    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("inter_recon_bi: width/height must be multiples of 64"); return X265HIP_EINVAL; }
-    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("inter_recon_bi: depth %d", p->depth); return X265HIP_EINVAL; }
-    if (p->level < 0 || p->level > 2) { set_error("inter_recon_bi: level %d (0..2 = 8x8, 16x16, 32x32)", p->level); return X265HIP_EINVAL; }
-    if (p->qp < 0 || p->qp > 51 + 6 * (p->depth - 8)) { set_error("inter_recon_bi: qp %d out of range", p->qp); return X265HIP_EINVAL; }
-    const int bpp = p->depth == 8 ? 1 : 2;
+    if (!tu_record_ok(p, "inter_recon_bi", false)) return X265HIP_EINVAL;
     TuBiArgs b;
-    TuArgs& a = b.t;
-    a.fenc = (const uint8_t*)p->fenc; a.fencStrideB = (long)p->fenc_stride * bpp;
-    a.fref = (const uint8_t*)p->fref; a.frefStrideB = (long)p->fref_stride * bpp;
-    a.recon = (uint8_t*)p->recon; a.reconStrideB = (long)p->recon_stride * bpp;
-    a.ctusW = p->width / 64; a.depth = p->depth; a.level = p->level;
-    a.mv = (const int2*)p->mv; a.qp = p->qp; a.intraSlice = p->intra_slice;
-    a.levels = p->levels; a.numSig = p->num_sig; a.dist = (unsigned long long*)p->dist;
-    a.tab = tu_tables_of(TABLES_OF(p)); a.qpMap = p->qp_map;
+    b.t = tu_args_of(p, p->fref);          // its kernel walks the blocks in raster order: no switch on top of the record's flags
     b.fref1 = (const uint8_t*)q->fref1; b.mv1 = (const int2*)q->mv1; b.dir = q->dir;
     {
         const x265hip_pred_weight* ws[2] = { q->weight0, q->weight1 };
@@ -1418,25 +1254,7 @@ static int inter_recon_bi_impl(const x265hip_recon_bi_params* q, void* stream, c
         }
         b.wDenom = b.wDenomUni[0];
     }
-    const int nblocks = a.ctusW * (p->height / 64) * (64 >> (2 * p->level));
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = tu_launch_grid(chroma ? X265HIP_TU_ENTRY_INTER_CHROMA_BI : X265HIP_TU_ENTRY_INTER_BI, (chroma ? 4 : 8) << p->level, p->depth,
-                                    p->tables != nullptr, 1, nblocks);
-#define GOB_T(PX, TB) do { \
-        if (p->level == 0) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 8, false, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); \
-        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 16, false, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); \
-        else hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 32, false, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); } while (0)
-#define GOBC_T(PX, TB) do { \
-        if (p->level == 0) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 4, true, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); \
-        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 8, true, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); \
-        else hipLaunchKernelGGL((inter_recon_bi_kernel<PX, 16, true, TB>), dim3(grid), dim3(64), 0, s, b, nblocks); } while (0)
-#define GOB(PX) do { if (chroma) { if (p->tables) GOBC_T(PX, true); else GOBC_T(PX, false); } else { if (p->tables) GOB_T(PX, true); else GOB_T(PX, false); } } while (0)
-    if (p->depth == 8) GOB(uint8_t); else GOB(uint16_t);
-#undef GOB_T
-#undef GOBC_T
-#undef GOB
-    X265HIP_TRY(hipGetLastError());
-    return 0;
+    return tu_launch_inter(chroma ? X265HIP_TU_ENTRY_INTER_CHROMA_BI : X265HIP_TU_ENTRY_INTER_BI, p, chroma, 1, stream, &b);
 }
 
 extern "C" int x265hip_inter_recon_bi(const x265hip_recon_bi_params* q, void* stream) { return inter_recon_bi_impl(q, stream, false); }
@@ -1456,38 +1274,13 @@ static int inter_recon_chroma_planes(const x265hip_recon_params* const* pp, int 
     for (int i = 0; i < nplanes; i++)
     {
         const x265hip_recon_params* q = pp[i];
-        if (!q || !q->fenc || !q->fref || !q->recon || !q->mv || !q->levels || !q->num_sig || !q->dist)
-        { set_error("inter_recon_chroma: NULL operand"); return X265HIP_EINVAL; }
-        if ((q->width & 63) || (q->height & 63) || q->width <= 0 || q->height <= 0) { set_error("inter_recon_chroma: width/height (luma) must be multiples of 64"); return X265HIP_EINVAL; }
-        if (q->depth != 8 && q->depth != 10 && q->depth != 12) { set_error("inter_recon_chroma: depth %d", q->depth); return X265HIP_EINVAL; }
-        if (q->level < 0 || q->level > 2) { set_error("inter_recon_chroma: level %d (0..2 = 8x8, 16x16, 32x32 luma blocks)", q->level); return X265HIP_EINVAL; }
-        if (q->qp < 0 || q->qp > 51 + 6 * (q->depth - 8)) { set_error("inter_recon_chroma: qp %d out of range", q->qp); return X265HIP_EINVAL; }
+        if (!tu_record_ok(q, "inter_recon_chroma", true)) return X265HIP_EINVAL;
         if (q->width != p->width || q->height != p->height || q->depth != p->depth || q->level != p->level || !q->tables != !p->tables)
         { set_error("inter_recon_chroma: the two planes differ in geometry / depth / level / use of tables"); return X265HIP_EINVAL; }
-        const int bpp = q->depth == 8 ? 1 : 2;
-        TuArgs& a = aa.p[i];
-        a.fenc = (const uint8_t*)q->fenc; a.fencStrideB = (long)q->fenc_stride * bpp;
-        a.fref = (const uint8_t*)q->fref; a.frefStrideB = (long)q->fref_stride * bpp;
-        a.recon = (uint8_t*)q->recon; a.reconStrideB = (long)q->recon_stride * bpp;
-        a.ctusW = q->width / 64; a.depth = q->depth; a.level = q->level;
-        a.mv = (const int2*)q->mv; a.qp = q->qp; a.intraSlice = (q->intra_slice & ~TU_FLAG_RASTER_ORDER) | (tu_raster_order(true) ? TU_FLAG_RASTER_ORDER : 0);
-        a.levels = q->levels; a.numSig = q->num_sig; a.dist = (unsigned long long*)q->dist;
-        a.tab = tu_tables_of(TABLES_OF(q)); a.qpMap = q->qp_map;
+        aa.p[i] = tu_args_of(q, q->fref);
+        tu_walk_order(aa.p[i], true);
     }
-    const int nctu = aa.p[0].ctusW * (p->height / 64);
-    const int nblocks = nctu * (64 >> (2 * p->level));
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = tu_launch_grid(X265HIP_TU_ENTRY_INTER_CHROMA, 4 << p->level, p->depth, p->tables != nullptr, nplanes, nblocks);
-#define GOC_T(PX, TB) do { \
-        if (p->level == 0) hipLaunchKernelGGL((inter_recon_kernel<PX, 4, true, TB>), dim3(grid, nplanes), dim3(64), 0, s, aa, nblocks); \
-        else if (p->level == 1) hipLaunchKernelGGL((inter_recon_kernel<PX, 8, true, TB>), dim3(grid, nplanes), dim3(64), 0, s, aa, nblocks); \
-        else hipLaunchKernelGGL((inter_recon_kernel<PX, 16, true, TB>), dim3(grid, nplanes), dim3(64), 0, s, aa, nblocks); } while (0)
-#define GOC(PX) do { if (p->tables) GOC_T(PX, true); else GOC_T(PX, false); } while (0)
-    if (p->depth == 8) GOC(uint8_t); else GOC(uint16_t);
-#undef GOC_T
-#undef GOC
-    X265HIP_TRY(hipGetLastError());
-    return 0;
+    return tu_launch_inter(X265HIP_TU_ENTRY_INTER_CHROMA, p, true, nplanes, stream, &aa);
 }
 
 extern "C" int x265hip_inter_recon_chroma(const x265hip_recon_params* p, void* stream)
@@ -1504,7 +1297,7 @@ extern "C" int x265hip_inter_recon_chroma_pair(const x265hip_recon_params* cb, c
     return inter_recon_chroma_planes(pp, 2, stream);
 }
 
-// P pictures with several references: one or two planes (luma; Cb and / or Cr) through inter_recon_refs_kernel, grid.y = plane.
+// P pictures with several references: one or two planes (luma; Cb and / or Cr) through the multi-reference instances of inter_recon_kernel, grid.y = plane.
 static int inter_recon_refs_planes(const x265hip_recon_refs_params* const* pp, const int nplanes, const bool chroma, void* stream)
 {
     const char* who = chroma ? "inter_recon_chroma_refs" : "inter_recon_refs";
@@ -1517,25 +1310,11 @@ static int inter_recon_refs_planes(const x265hip_recon_refs_params* const* pp, c
         if (!r) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
         const x265hip_recon_params* q = &r->base;
         if (q->tables) { set_error("%s: tables (scaling lists / the denoiser) are not supported by this stage", who); return X265HIP_EINVAL; }
-        if (!q->fenc || !q->recon || !q->mv || !q->levels || !q->num_sig || !q->dist || !r->ref_idx) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
-        if (r->nrefs < 1 || r->nrefs > X265HIP_MAX_REFS) { set_error("%s: nrefs %d out of [1,%d]", who, r->nrefs, X265HIP_MAX_REFS); return X265HIP_EINVAL; }
-        for (int k = 0; k < r->nrefs; k++)
-            if (!r->fref[k]) { set_error("%s: NULL plane of reference %d", who, k); return X265HIP_EINVAL; }
-        if ((q->width & 63) || (q->height & 63) || q->width <= 0 || q->height <= 0) { set_error("%s: width/height (luma) must be multiples of 64", who); return X265HIP_EINVAL; }
-        if (q->depth != 8 && q->depth != 10 && q->depth != 12) { set_error("%s: depth %d", who, q->depth); return X265HIP_EINVAL; }
-        if (q->level < 0 || q->level > 2) { set_error("%s: level %d (0..2 = 8x8, 16x16, 32x32 luma blocks)", who, q->level); return X265HIP_EINVAL; }
-        if (q->qp < 0 || q->qp > 51 + 6 * (q->depth - 8)) { set_error("%s: qp %d out of range", who, q->qp); return X265HIP_EINVAL; }
+        if (!tu_record_ok(q, who, true, r)) return X265HIP_EINVAL;
         if (q->width != p->width || q->height != p->height || q->depth != p->depth || q->level != p->level || r->nrefs != pp[0]->nrefs)
         { set_error("%s: the two planes differ in geometry / depth / level / nrefs", who); return X265HIP_EINVAL; }
-        const int bpp = q->depth == 8 ? 1 : 2;
-        TuArgs& a = ra.aa.p[i];
-        a.fenc = (const uint8_t*)q->fenc; a.fencStrideB = (long)q->fenc_stride * bpp;
-        a.fref = (const uint8_t*)r->fref[0]; a.frefStrideB = (long)q->fref_stride * bpp;
-        a.recon = (uint8_t*)q->recon; a.reconStrideB = (long)q->recon_stride * bpp;
-        a.ctusW = q->width / 64; a.depth = q->depth; a.level = q->level;
-        a.mv = (const int2*)q->mv; a.qp = q->qp; a.intraSlice = (q->intra_slice & ~TU_FLAG_RASTER_ORDER) | (tu_raster_order(chroma) ? TU_FLAG_RASTER_ORDER : 0);
-        a.levels = q->levels; a.numSig = q->num_sig; a.dist = (unsigned long long*)q->dist;
-        a.tab = tu_tables_of(nullptr); a.qpMap = q->qp_map;
+        ra.aa.p[i] = tu_args_of(q, r->fref[0]);          // q->tables is NULL here
+        tu_walk_order(ra.aa.p[i], chroma);
         // entries behind nrefs repeat the last plane: the kernel clamps the index, and no entry of the table is left dangling
         for (int k = 0; k < X265HIP_MAX_REFS; k++) ra.fref[i][k] = (const uint8_t*)r->fref[k < r->nrefs ? k : r->nrefs - 1];
         ra.refIdx[i] = r->ref_idx;
@@ -1543,22 +1322,7 @@ static int inter_recon_refs_planes(const x265hip_recon_refs_params* const* pp, c
     ra.nrefs = pp[0]->nrefs;
     int rc = ensure_device();
     if (rc) return rc;
-    const int nblocks = (p->width / 64) * (p->height / 64) * (64 >> (2 * p->level));
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = tu_launch_grid(chroma ? X265HIP_TU_ENTRY_INTER_CHROMA_REFS : X265HIP_TU_ENTRY_INTER_REFS, (chroma ? 4 : 8) << p->level, p->depth, false, nplanes, nblocks);
-#define GOR(PX) do { \
-        if (chroma) { \
-            if (p->level == 0) hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 4, true>), dim3(grid, nplanes), dim3(64), 0, s, ra, nblocks); \
-            else if (p->level == 1) hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 8, true>), dim3(grid, nplanes), dim3(64), 0, s, ra, nblocks); \
-            else hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 16, true>), dim3(grid, nplanes), dim3(64), 0, s, ra, nblocks); } \
-        else { \
-            if (p->level == 0) hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 8, false>), dim3(grid), dim3(64), 0, s, ra, nblocks); \
-            else if (p->level == 1) hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 16, false>), dim3(grid), dim3(64), 0, s, ra, nblocks); \
-            else hipLaunchKernelGGL((inter_recon_refs_kernel<PX, 32, false>), dim3(grid), dim3(64), 0, s, ra, nblocks); } } while (0)
-    if (p->depth == 8) GOR(uint8_t); else GOR(uint16_t);
-#undef GOR
-    X265HIP_TRY(hipGetLastError());
-    return 0;
+    return tu_launch_inter(chroma ? X265HIP_TU_ENTRY_INTER_CHROMA_REFS : X265HIP_TU_ENTRY_INTER_REFS, p, chroma, nplanes, stream, &ra);
 }
 
 extern "C" int x265hip_inter_recon_refs(const x265hip_recon_refs_params* p, void* stream) { return inter_recon_refs_planes(&p, 1, false, stream); }
@@ -1589,21 +1353,10 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
     a.jobs = p->jobs; a.njobs = p->njobs; a.depth = p->depth; a.qp = p->qp; a.intraSlice = p->intra_slice; a.chroma = p->chroma != 0;
     a.levels = p->levels; a.numSig = p->num_sig; a.dist = (unsigned long long*)p->dist;
     a.tab = tu_tables_of(TABLES_OF(p));
-    hipStream_t s = (hipStream_t)stream;
     // 16 / 32: persistent single-wavefront workgroups, exactly one resident set; 4 / 8: nothing to amortise, one workgroup per job
     const int grid = tu_launch_grid(X265HIP_TU_ENTRY_INTRA, p->n, p->depth, p->tables != nullptr, 1, p->njobs);
-#define GOI_T(PX, TB) do { \
-        if (p->n == 4 && !p->chroma) hipLaunchKernelGGL((intra_recon_kernel<PX, 4, true, TB>), dim3(grid), dim3(64), 0, s, a); \
-        else if (p->n == 4) hipLaunchKernelGGL((intra_recon_kernel<PX, 4, false, TB>), dim3(grid), dim3(64), 0, s, a); \
-        else if (p->n == 8) hipLaunchKernelGGL((intra_recon_kernel<PX, 8, false, TB>), dim3(grid), dim3(64), 0, s, a); \
-        else if (p->n == 16) hipLaunchKernelGGL((intra_recon_kernel<PX, 16, false, TB>), dim3(grid), dim3(64), 0, s, a); \
-        else hipLaunchKernelGGL((intra_recon_kernel<PX, 32, false, TB>), dim3(grid), dim3(64), 0, s, a); } while (0)
-#define GOI(PX) do { if (p->tables) GOI_T(PX, true); else GOI_T(PX, false); } while (0)
-    if (p->depth == 8) GOI(uint8_t); else GOI(uint16_t);
-#undef GOI_T
-#undef GOI
-    X265HIP_TRY(hipGetLastError());
-    return 0;
+    void* args[] = { &a };
+    return tu_launch(tu_kernel(X265HIP_TU_ENTRY_INTRA, p->n, p->depth, p->tables != nullptr, !p->chroma), dim3(grid), stream, args);
 }
 
 // the I-picture stage (x265hip_intra_picture): its kernel codes blocks with tu_chain / TuOpsFor above

@@ -426,6 +426,61 @@ typedef struct x265hip_recon_refs_params
 int x265hip_inter_recon_refs(const x265hip_recon_refs_params* p, void* stream);
 int x265hip_inter_recon_chroma_refs(const x265hip_recon_refs_params* p, void* stream);
 int x265hip_inter_recon_chroma_pair_refs(const x265hip_recon_refs_params* cb, const x265hip_recon_refs_params* cr, void* stream);
+/* The bidirectional decision of a B picture with several references per list: Search::predInterSearch (search.cpp:2386-2640) for a B
+ * slice's 2Nx2N on the block grid of the TU stages, without the merge arm, luma only.  The per-list loop (:2391-2470) is x265hip_ref_select
+ * run once per list with ref_cost_l[r] = lambda x (MVP_IDX_BITS + getTUBits(r, nrefs_l)) = lambda x (1 + r + (r < nrefs_l - 1)) - the
+ * list-selection bits are not in it, dir_cost adds them; its mv_out = { cost incl. ref_cost_l, vector } (rec_l below) and ref_idx (i_l)
+ * are inputs here.  The bidirectional part (:2473-2640) keeps the reference bits of both lists in the candidate - bidirBits =
+ * bestME[0].bits + bestME[1].bits + listSel[2] - listSel[0] - listSel[1] - and in the zero candidate (:2554-2558).  With F_l = fref_l[i_l]:
+ *     c0  = rec0.cost + dir_cost[0]          c1 = rec1.cost + dir_cost[1]
+ *     rb  = ref_cost0[i0] + ref_cost1[i1]
+ *     cbi = satd(fenc, (P(F0, mv0) + P(F1, mv1) + 1) >> 1) + mvc(mv0) + mvc(mv1) + dir_cost[2] + rb
+ *     if (mv0 != 0 || mv1 != 0) { cz = satd(fenc, (F0[block] + F1[block] + 1) >> 1) + 4 * cost_q[qoff] + dir_cost[2] + rb;
+ *                                 if (cz < cbi) cbi = cz, mv0 = mv1 = 0; }
+ *     dir = (cbi < c0 && cbi < c1) ? 3 : (c0 <= c1 ? 1 : 2)
+ * P, mvc, the SATD tiling and the meaning of the outputs are those of x265hip_bidir_decide: a used list gets { winning cost, vector }, an
+ * unused list { its own c_l, 0 }; only the level's entries are written.  With one reference per list and both ref_cost tables zero this
+ * IS x265hip_bidir_decide.  Every reference is searched around one predictor, (0,0).
+ *   fref0 / fref1     : sample (0,0) of each list's pictures, one shared fref_stride; entries behind nrefs_l are not looked at
+ *   ref_idx0 / ref_idx1 : DEVICE int8 [ctu][blocks], the two x265hip_ref_select outputs; an index outside its list is clamped into it
+ *   ref_ids0 / ref_ids1 : picture ids; ref0 / ref1 get ref_ids_l[i_l], or -1 for an unused list (what x265hip_deblock_bs_inter compares)
+ *   phase_planes0 / 1 : optional, as x265hip_bidir_params takes them - of EVERY listed reference or of none
+ *   cost_out          : optional [ctu][blocks][4] = { c0, c1, cbi at the refined vectors, cz or -1 if not tried }
+ * Argument checks (those of x265hip_bidir_decide, the range of nrefs0 / nrefs1, NULL table entries below nrefs_l, NULL ref_idx, aliasing
+ * among mv0 / mv1 / mv0_out / mv1_out) return X265HIP_EINVAL before the device is asked for. */
+typedef struct x265hip_bidir_refs_params
+{
+    int depth, width, height, level;                 /* width / height multiples of 64, level 0..2 */
+    const void* fenc;  intptr_t fenc_stride;
+    const uint16_t* cost_q; int qoff;
+    int32_t dir_cost[3];
+    int nrefs0, nrefs1;                              /* 1 .. X265HIP_MAX_REFS each */
+    const void* fref0[X265HIP_MAX_REFS]; const void* fref1[X265HIP_MAX_REFS]; intptr_t fref_stride;
+    int32_t ref_cost0[X265HIP_MAX_REFS]; int32_t ref_cost1[X265HIP_MAX_REFS];
+    int ref_ids0[X265HIP_MAX_REFS]; int ref_ids1[X265HIP_MAX_REFS];
+    const int8_t* ref_idx0; const int8_t* ref_idx1;
+    const int32_t* mv0; const int32_t* mv1;          /* [ctu*85][2]: the mv_out of the two x265hip_ref_select passes */
+    const void* phase_planes0[X265HIP_MAX_REFS]; const void* phase_planes1[X265HIP_MAX_REFS]; intptr_t phase_plane_samples;
+    uint8_t* dir;                                    /* [ctu][blocks]: 1 / 2 / 3 */
+    int8_t* ref0; int8_t* ref1;                      /* optional [ctu][blocks] */
+    int32_t* mv0_out; int32_t* mv1_out;              /* [ctu*85][2]; must not alias mv0 / mv1 or each other */
+    int32_t* cost_out;
+} x265hip_bidir_refs_params;
+int x265hip_bidir_decide_refs(const x265hip_bidir_refs_params* p, void* stream);
+/* The bi-predictive TU stage of a B picture with several references per list: block blk with dir d is predicted from
+ * fref0[ref_idx0[blk]] and / or fref1[ref_idx1[blk]]; the index of a list the block does not use is not read.  Everything else is the
+ * contract of x265hip_inter_recon_bi / _chroma_bi (qp_map included).  base.base.fref and base.fref1 are ignored; the planes (sample (0,0);
+ * for the chroma entry the planes of Cb or Cr) share base.base.fref_stride.  ref_idx0 / ref_idx1: DEVICE int8 [ctu][blocks]; an index
+ * outside its list is clamped into it.  base.base.tables, base.weight0 and base.weight1 are refused (X265HIP_EINVAL). */
+typedef struct x265hip_recon_bi_refs_params
+{
+    x265hip_recon_bi_params base;
+    int nrefs0, nrefs1;                              /* 1 .. X265HIP_MAX_REFS each */
+    const void* fref0[X265HIP_MAX_REFS]; const void* fref1[X265HIP_MAX_REFS];
+    const int8_t* ref_idx0; const int8_t* ref_idx1;
+} x265hip_recon_bi_refs_params;
+int x265hip_inter_recon_bi_refs(const x265hip_recon_bi_refs_params* p, void* stream);
+int x265hip_inter_recon_chroma_bi_refs(const x265hip_recon_bi_refs_params* p, void* stream);
 /* The TU-stage entries, as x265hip_tu_launch_grid names them. */
 enum x265hip_tu_entry
 {
@@ -441,6 +496,12 @@ enum x265hip_tu_entry_refs
 {
     X265HIP_TU_ENTRY_INTER_REFS = 8,     /* x265hip_inter_recon_refs */
     X265HIP_TU_ENTRY_INTER_CHROMA_REFS   /* x265hip_inter_recon_chroma_refs (nplanes 1) / _chroma_pair_refs (nplanes 2) */
+};
+/* The entries of the B step with several references per list: again enumerators of their own; the values in between (10, 11) name nothing. */
+enum x265hip_tu_entry_bi_refs
+{
+    X265HIP_TU_ENTRY_INTER_BI_REFS = 12, /* x265hip_inter_recon_bi_refs */
+    X265HIP_TU_ENTRY_INTER_CHROMA_BI_REFS /* x265hip_inter_recon_chroma_bi_refs */
 };
 /* grid.x of the launch `entry` makes for `nblocks` blocks (or jobs) of n x n transforms (n = the transform size: 8 << level for luma,
  * 4 << level for chroma, intra n) at `depth`, with (tables != 0) or without a x265hip_tu_tables record, over `nplanes` planes.  The 16- and

@@ -48,7 +48,7 @@ def kernels_of_elf(path):
         m = re.match(r"[0-9a-f]+ <(\S+)>:", line)
         if m:
             cur = code.setdefault(m[1], [])
-        elif cur is not None and line.startswith("\t"):
+        elif cur is not None and line.startswith("\t") and line.strip() != "...":          # "...": zero padding behind a kernel, elided by objdump
             cur.append(re.sub(r"\s*//.*", "", line).strip())
     syms = sorted(res)
     return {d: (res[s], code[s]) for s, d in zip(syms, demangle(syms))}

@@ -2,6 +2,7 @@
 """Summarise rocprofv3 (ROCm 7.2) rocpd SQLite outputs into the small text files kept under profiles/.
 
   python tools/rocprof_summary.py kernel-trace gpurun_out/prof/kt/me_results.db   > profiles/rNN_kernel_stats.txt
+  python tools/rocprof_summary.py spread DIR/me_results.db bidir_decide inter_recon_bi     # min / avg / max per kernel
   python tools/rocprof_summary.py pmc gpurun_out/prof/pmc_fetch/me_results.db ...  > profiles/rNN_pmc.txt
 """
 import sqlite3
@@ -31,6 +32,24 @@ def pmc(paths):
         print(f"{'kernel':92s} {'counter':>12s} {'n':>4s} {'avg':>16s} {'min':>16s} {'max':>16s} {'avg_dur_ns':>12s}")
         for k, c, n, a, mn, mx, d in rows:
             print(f"{short(k):92s} {c:>12s} {n:4d} {a:16.2f} {mn:16.2f} {mx:16.2f} {d:12.0f}")
+
+
+def spread(path, patterns):
+    """Per kernel whose name contains one of `patterns` (all kernels without patterns): launches, min / average / max duration in us and
+    max - min - the margin a kernel's own launches leave for a comparison inside ONE trace."""
+    c = sqlite3.connect(path)
+    tabs = [r[0] for r in c.execute("select name from sqlite_master where type='table'")]
+    kd = [t for t in tabs if t.startswith("rocpd_kernel_dispatch")][0]
+    ks = [t for t in tabs if t.startswith("rocpd_info_kernel_symbol")][0]
+    rows = c.execute(f"select s.kernel_name, count(*), min(d.end - d.start), avg(d.end - d.start), max(d.end - d.start) from {kd} d join {ks} s "
+                     f"on d.kernel_id = s.id group by s.kernel_name order by s.kernel_name").fetchall()
+    print(f"# per-kernel spread of {path}")
+    print(f"{'kernel':100s} {'calls':>6s} {'min_us':>9s} {'avg_us':>9s} {'max_us':>9s} {'max-min':>9s}")
+    for name, n, lo, avg, hi in rows:
+        name = name.split("(")[0].replace("void ", "").replace("x265hip::", "")
+        if patterns and not any(p in name for p in patterns):
+            continue
+        print(f"{short(name, 100):100s} {n:6d} {lo / 1e3:9.2f} {avg / 1e3:9.2f} {hi / 1e3:9.2f} {(hi - lo) / 1e3:9.2f}")
 
 
 def timeline(path, anchor="me_ctu"):
@@ -64,5 +83,7 @@ if __name__ == "__main__":
         kernel_trace(sys.argv[2])
     elif sys.argv[1] == "timeline":
         timeline(*sys.argv[2:4])
+    elif sys.argv[1] == "spread":
+        spread(sys.argv[2], sys.argv[3:])
     else:
         pmc(sys.argv[2:])

@@ -15,7 +15,7 @@
 // (the geometry of the sub-pel stage), the tile's source samples in registers.  Each thread forms its tile of both lists' predictions
 // (tile_predict: the exact interpolation; with phase planes four dword loads per list instead), takes the SATD of the averaged
 // prediction and of the zero candidate, and the two partial costs are summed over the block's lanes with DPP moves - a block never
-// straddles a wavefront, so there is no LDS and no barrier.  One lane per block decides and writes.  No atomics.
+// straddles a wavefront, so the sums need no LDS and no barrier.  One lane per block decides and writes.  No atomics.
 #include "common.h"
 #include "tile_interp.h"
 
@@ -37,6 +37,30 @@ struct BidirArgs
     int* costOut;                        // [ctu][blocks][4]
 };
 
+// Several references per list (x265hip_bidir_decide_refs): every block is measured against the two pictures IT chose - list index
+// refIdx[l][blk] (x265hip_ref_select's ref_idx) into the launch's tables of reference planes, phase planes, reference bits and picture
+// ids, per list.  At level 2 a wavefront holds one block: its list index is uniform and the tables are read where they arrive, in the
+// kernel arguments, with a scalar index.  At levels 0 and 1 a wavefront holds 16 or 4 blocks, the index varies from lane to lane, and a
+// table in the kernel arguments indexed by a vector register would be copied to scratch memory: there every wavefront stages a quarter
+// of the tables in LDS once per workgroup with scalar indices (its lane 0 writes) and a lane reads its block's entries - the one use of
+// LDS and the one barrier of this file.
+struct BdRefTables
+{
+    const uint8_t* fref[2][X265HIP_MAX_REFS];          // entries behind nrefs repeat the last one
+    const uint8_t* planes[2][X265HIP_MAX_REFS];
+    int refCost[2][X265HIP_MAX_REFS];
+    int refId[2][X265HIP_MAX_REFS];
+};
+struct BidirRefsArgs
+{
+    BidirArgs b;                                        // b.fref / b.planes / b.refId are not read
+    BdRefTables t;
+    const int8_t* refIdx[2];                            // [ctu][blocks]
+    int nrefs[2];
+};
+__device__ __forceinline__ const BidirArgs& bd_base_args(const BidirArgs& a) { return a; }
+__device__ __forceinline__ const BidirArgs& bd_base_args(const BidirRefsArgs& ra) { return ra.b; }
+
 template <int LEVEL> struct BdGeom
 {
     static constexpr int N = 8 << LEVEL, NPU = 64 >> (2 * LEVEL);
@@ -45,29 +69,49 @@ template <int LEVEL> struct BdGeom
 };
 
 // The decision of one block from the summed SATDs of the bidirectional candidate (sBi) and of the zero candidate (sZ): one lane per block.
-__device__ __forceinline__ void bd_decide(const BidirArgs& a, size_t blk, size_t rec, int2 r0, int2 r1, int sBi, int sZ)
+// tab != NULL (several references per list): i0 / i1 = the block's list indices - the reference bits of both lists stay in the bidirectional
+// candidate and in the zero candidate (search.cpp:2473-2480, 2554-2558), and ref[] gets the picture ids of the block's two references.
+template <bool REFS = false>
+__device__ __forceinline__ void bd_decide(const BidirArgs& a, size_t blk, size_t rec, int2 r0, int2 r1, int sBi, int sZ,
+                                          const BdRefTables* tab = nullptr, const int i0 = 0, const int i1 = 0)
 {
     auto mvc = [&](const int w) { return (int)a.costQ[a.qoff + (int16_t)(w & 0xffff)] + (int)a.costQ[a.qoff + (w >> 16)]; };
     const int c0 = r0.x + a.dirCost[0], c1 = r1.x + a.dirCost[1];
-    const int cRef = sBi + mvc(r0.y) + mvc(r1.y) + a.dirCost[2];
+    int rb = 0;
+    if constexpr (REFS) rb = tab->refCost[0][i0] + tab->refCost[1][i1];
+    const int cRef = REFS ? sBi + mvc(r0.y) + mvc(r1.y) + a.dirCost[2] + rb : sBi + mvc(r0.y) + mvc(r1.y) + a.dirCost[2];
     int cbi = cRef, cz = -1, m0 = r0.y, m1 = r1.y;
     if (m0 != 0 || m1 != 0)                                      // bTryZero
     {
         cz = sZ + 4 * (int)a.costQ[a.qoff] + a.dirCost[2];
+        if constexpr (REFS) cz += rb;
         if (cz < cbi) { cbi = cz; m0 = 0; m1 = 0; }
     }
     const int dir = (cbi < c0 && cbi < c1) ? 3 : (c0 <= c1 ? 1 : 2);
     a.dir[blk] = (uint8_t)dir;
-    if (a.ref[0]) a.ref[0][blk] = (int8_t)((dir & 1) ? a.refId[0] : -1);
-    if (a.ref[1]) a.ref[1][blk] = (int8_t)((dir & 2) ? a.refId[1] : -1);
+    if constexpr (REFS)
+    {
+        if (a.ref[0]) a.ref[0][blk] = (int8_t)((dir & 1) ? tab->refId[0][i0] : -1);
+        if (a.ref[1]) a.ref[1][blk] = (int8_t)((dir & 2) ? tab->refId[1][i1] : -1);
+    }
+    else
+    {
+        if (a.ref[0]) a.ref[0][blk] = (int8_t)((dir & 1) ? a.refId[0] : -1);
+        if (a.ref[1]) a.ref[1][blk] = (int8_t)((dir & 2) ? a.refId[1] : -1);
+    }
     a.mvOut[0][rec] = dir == 3 ? make_int2(cbi, m0) : make_int2(c0, dir == 1 ? m0 : 0);
     a.mvOut[1][rec] = dir == 3 ? make_int2(cbi, m1) : make_int2(c1, dir == 2 ? m1 : 0);
     if (a.costOut) { int* co = a.costOut + blk * 4; co[0] = c0; co[1] = c1; co[2] = cRef; co[3] = cz; }
 }
 
-template <typename Px, int LEVEL, bool PL>
-__global__ void __launch_bounds__(256) bidir_decide_kernel(BidirArgs a)
+// Args = BidirArgs: both lists hold one picture (x265hip_bidir_decide).  Args = BidirRefsArgs (REFS): every block against the two
+// pictures it chose (x265hip_bidir_decide_refs).  REFS is a parameter of the kernel: each instance is compiled from one body with the
+// other flavour's statements discarded, and the single-reference instances keep their code instruction for instruction.
+template <typename Px, int LEVEL, bool PL, class Args = BidirArgs>
+__global__ void __launch_bounds__(256) bidir_decide_kernel(Args ra)
 {
+    constexpr bool REFS = std::is_same<Args, BidirRefsArgs>::value;
+    const BidirArgs& a = bd_base_args(ra);
     typedef BdGeom<LEVEL> G;
     constexpr int BPP = sizeof(Px), N = G::N;
     const int ctu = xcd_swizzle(blockIdx.x, gridDim.x);
@@ -84,6 +128,42 @@ __global__ void __launch_bounds__(256) bidir_decide_kernel(BidirArgs a)
     const size_t rec = (size_t)ctu * 85 + G::LBASE + pu;
     const int2 r0 = a.mv[0][rec], r1 = a.mv[1][rec];
     const long tileOff = (long)py * a.frefStrideB + (long)px * BPP;
+    // REFS: the block's two list indices, clamped into the lists like the TU stages clamp theirs (every lane of the block reads the same
+    // bytes).  Their loads are issued with those of the source tile and the records, in front of the barrier below.
+    int idx[2] = { 0, 0 };
+    const BdRefTables* tab = nullptr;
+    if constexpr (REFS)
+    {
+        const size_t blk = (size_t)ctu * G::NPU + pu;
+        idx[0] = clip3(0, ra.nrefs[0] - 1, (int)ra.refIdx[0][blk]);
+        idx[1] = clip3(0, ra.nrefs[1] - 1, (int)ra.refIdx[1][blk]);
+        if constexpr (G::NTILES == 64)
+        {
+            tab = &ra.t;
+            idx[0] = __builtin_amdgcn_readfirstlane(idx[0]);
+            idx[1] = __builtin_amdgcn_readfirstlane(idx[1]);
+        }
+        else
+        {
+            // wavefront w stages entries [4 (w & 1), + 4) of list w >> 1; nothing reads the tables before the barrier
+            __shared__ BdRefTables sTab;
+            const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+            const int l = w >> 1, k0 = (w & 1) * (X265HIP_MAX_REFS / 2);
+            if ((tid & 63) == 0)
+            {
+#pragma unroll
+                for (int k = 0; k < X265HIP_MAX_REFS / 2; k++)
+                {
+                    sTab.fref[l][k0 + k] = ra.t.fref[l][k0 + k];
+                    if (PL) sTab.planes[l][k0 + k] = ra.t.planes[l][k0 + k];
+                    sTab.refCost[l][k0 + k] = ra.t.refCost[l][k0 + k];
+                    sTab.refId[l][k0 + k] = ra.t.refId[l][k0 + k];
+                }
+            }
+            __syncthreads();
+            tab = &sTab;
+        }
+    }
 
     // P0 + P1 at the refined vectors and at (0,0): one pass per list, the interpolation code exists once
     int sumP[4][4] = {}, sumZ[4][4] = {};
@@ -93,9 +173,21 @@ __global__ void __launch_bounds__(256) bidir_decide_kernel(BidirArgs a)
         const int w = l ? r1.y : r0.y;
         const int qx = (int16_t)(w & 0xffff), qy = w >> 16;
         const int xf = qx & 3, yf = qy & 3, ph = yf * 4 + xf;
-        const uint8_t* z = a.fref[l] + tileOff;
-        const uint8_t* org = ((PL && ph) ? a.planes[l] + (long)(ph - 1) * a.planeBytes + tileOff : z)
-                             + (long)(qy >> 2) * a.frefStrideB + (long)(qx >> 2) * BPP;
+        const uint8_t* z;
+        const uint8_t* org;
+        if constexpr (REFS)
+        {
+            const int i = l ? idx[1] : idx[0];
+            z = tab->fref[l][i] + tileOff;
+            org = ((PL && ph) ? tab->planes[l][i] + (long)(ph - 1) * a.planeBytes + tileOff : z)
+                  + (long)(qy >> 2) * a.frefStrideB + (long)(qx >> 2) * BPP;
+        }
+        else
+        {
+            z = a.fref[l] + tileOff;
+            org = ((PL && ph) ? a.planes[l] + (long)(ph - 1) * a.planeBytes + tileOff : z)
+                  + (long)(qy >> 2) * a.frefStrideB + (long)(qx >> 2) * BPP;
+        }
         int d[4][4];
         tile_predict<BPP>(org, a.frefStrideB, PL ? 0 : xf, PL ? 0 : yf, a.depth, d);
 #pragma unroll
@@ -122,7 +214,8 @@ __global__ void __launch_bounds__(256) bidir_decide_kernel(BidirArgs a)
     if (G::NTILES >= 16) { sBi = row_sum_of_quads(sBi); sZ = row_sum_of_quads(sZ); }
     if (G::NTILES >= 64) { sBi = wave_sum_of_rows(sBi); sZ = wave_sum_of_rows(sZ); }
 
-    if (tile == 0) bd_decide(a, (size_t)ctu * G::NPU + pu, rec, r0, r1, sBi, sZ);
+    if constexpr (REFS) { if (tile == 0) bd_decide<true>(a, (size_t)ctu * G::NPU + pu, rec, r0, r1, sBi, sZ, tab, idx[0], idx[1]); }
+    else if (tile == 0) bd_decide(a, (size_t)ctu * G::NPU + pu, rec, r0, r1, sBi, sZ);
 }
 
 // The chroma flavour (x265hip_bidir_decide_chroma): the records come from the chroma refinement, and the bidirectional candidate is
@@ -216,15 +309,34 @@ static void bidir_chroma_launch(int level, int nctu, hipStream_t s, const BidirA
     }
 }
 
-template <typename Px, bool PL>
-static void bidir_launch(int level, int nctu, hipStream_t s, const BidirArgs& a)
+template <typename Px, bool PL, class Args>
+static void bidir_launch(int level, int nctu, hipStream_t s, const Args& a)
 {
     switch (level)
     {
-    case 0: hipLaunchKernelGGL((bidir_decide_kernel<Px, 0, PL>), dim3(nctu), dim3(256), 0, s, a); break;
-    case 1: hipLaunchKernelGGL((bidir_decide_kernel<Px, 1, PL>), dim3(nctu), dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((bidir_decide_kernel<Px, 2, PL>), dim3(nctu), dim3(256), 0, s, a); break;
+    case 0: hipLaunchKernelGGL((bidir_decide_kernel<Px, 0, PL, Args>), dim3(nctu), dim3(256), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((bidir_decide_kernel<Px, 1, PL, Args>), dim3(nctu), dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((bidir_decide_kernel<Px, 2, PL, Args>), dim3(nctu), dim3(256), 0, s, a); break;
     }
+}
+// the luma decision of either record: phase planes or interpolation, one or two bytes per sample
+template <class Args>
+static void bidir_launch_luma(const bool planes, const int bpp, int level, int nctu, hipStream_t s, const Args& a)
+{
+    if (planes) { if (bpp == 1) bidir_launch<uint8_t, true>(level, nctu, s, a); else bidir_launch<uint16_t, true>(level, nctu, s, a); }
+    else { if (bpp == 1) bidir_launch<uint8_t, false>(level, nctu, s, a); else bidir_launch<uint16_t, false>(level, nctu, s, a); }
+}
+
+// The decision reads both lists' records of a block after other blocks' outputs may have been written: the outputs must be buffers of their
+// own.  True where mv0_out / mv1_out ([nctu * 85][2] int32 each) overlap mv0 / mv1 or each other.
+static bool bidir_records_alias(const int nctu, const void* mv0, const void* mv1, const void* mv0Out, const void* mv1Out)
+{
+    const uintptr_t len = (uintptr_t)nctu * 85 * 8;
+    const uintptr_t in[2] = { (uintptr_t)mv0, (uintptr_t)mv1 }, out[2] = { (uintptr_t)mv0Out, (uintptr_t)mv1Out };
+    bool alias = out[0] < out[1] + len && out[1] < out[0] + len;
+    for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 2; j++) alias = alias || (out[i] < in[j] + len && in[j] < out[i] + len);
+    return alias;
 }
 
 } // namespace x265hip
@@ -245,15 +357,8 @@ extern "C" int x265hip_bidir_decide_chroma(const x265hip_bidir_params* p, const 
     if (p->level < 0 || p->level > 2) { set_error("bidir_decide: level %d out of [0,2]", p->level); return X265HIP_EINVAL; }
     if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("bidir_decide: width/height must be multiples of 64"); return X265HIP_EINVAL; }
     const int nctu = (p->width / 64) * (p->height / 64);
-    {
-        // the decision reads both lists' records of a block after other blocks' outputs may have been written: outputs must be buffers of their own
-        const uintptr_t len = (uintptr_t)nctu * 85 * 8;
-        const uintptr_t in[2] = { (uintptr_t)p->mv0, (uintptr_t)p->mv1 }, out[2] = { (uintptr_t)p->mv0_out, (uintptr_t)p->mv1_out };
-        bool alias = out[0] < out[1] + len && out[1] < out[0] + len;
-        for (int i = 0; i < 2; i++)
-            for (int j = 0; j < 2; j++) alias = alias || (out[i] < in[j] + len && in[j] < out[i] + len);
-        if (alias) { set_error("bidir_decide: mv0_out / mv1_out must not alias mv0 / mv1 or each other"); return X265HIP_EINVAL; }
-    }
+    if (bidir_records_alias(nctu, p->mv0, p->mv1, p->mv0_out, p->mv1_out))
+    { set_error("bidir_decide: mv0_out / mv1_out must not alias mv0 / mv1 or each other"); return X265HIP_EINVAL; }
     const bool planes = p->phase_planes0 || p->phase_planes1;
     if (planes && (!p->phase_planes0 || !p->phase_planes1 || p->phase_plane_samples <= 0))
     { set_error("bidir_decide: phase planes of both lists and phase_plane_samples are needed together"); return X265HIP_EINVAL; }
@@ -290,8 +395,71 @@ extern "C" int x265hip_bidir_decide_chroma(const x265hip_bidir_params* p, const 
         ca.fref1Cb = (const uint8_t*)c->fref1_cb; ca.fref1Cr = (const uint8_t*)c->fref1_cr; ca.frefStrideCB = (long)c->fref_stride_c * bpp;
         if (bpp == 1) bidir_chroma_launch<uint8_t>(p->level, nctu, s, a, ca); else bidir_chroma_launch<uint16_t>(p->level, nctu, s, a, ca);
     }
-    else if (planes) { if (bpp == 1) bidir_launch<uint8_t, true>(p->level, nctu, s, a); else bidir_launch<uint16_t, true>(p->level, nctu, s, a); }
-    else { if (bpp == 1) bidir_launch<uint8_t, false>(p->level, nctu, s, a); else bidir_launch<uint16_t, false>(p->level, nctu, s, a); }
+    else bidir_launch_luma(planes, bpp, p->level, nctu, s, a);
+    X265HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int x265hip_bidir_decide_refs(const x265hip_bidir_refs_params* p, void* stream)
+{
+    // argument checks first: they need no device
+    if (!p || !p->fenc || !p->mv0 || !p->mv1 || !p->ref_idx0 || !p->ref_idx1 || !p->cost_q || !p->dir || !p->mv0_out || !p->mv1_out)
+    { set_error("bidir_decide_refs: NULL operand"); return X265HIP_EINVAL; }
+    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("bidir_decide_refs: depth %d", p->depth); return X265HIP_EINVAL; }
+    if (p->level < 0 || p->level > 2) { set_error("bidir_decide_refs: level %d out of [0,2]", p->level); return X265HIP_EINVAL; }
+    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("bidir_decide_refs: width/height must be multiples of 64"); return X265HIP_EINVAL; }
+    const int nrefs[2] = { p->nrefs0, p->nrefs1 };
+    const void* const* fref[2] = { p->fref0, p->fref1 };
+    const void* const* pplanes[2] = { p->phase_planes0, p->phase_planes1 };
+    int withPlanes = 0;
+    for (int l = 0; l < 2; l++)
+    {
+        if (nrefs[l] < 1 || nrefs[l] > X265HIP_MAX_REFS) { set_error("bidir_decide_refs: nrefs%d %d out of [1,%d]", l, nrefs[l], X265HIP_MAX_REFS); return X265HIP_EINVAL; }
+        for (int k = 0; k < nrefs[l]; k++)
+        {
+            if (!fref[l][k]) { set_error("bidir_decide_refs: NULL plane of reference %d of list %d", k, l); return X265HIP_EINVAL; }
+            withPlanes += pplanes[l][k] != nullptr;
+        }
+    }
+    const int nctu = (p->width / 64) * (p->height / 64);
+    if (bidir_records_alias(nctu, p->mv0, p->mv1, p->mv0_out, p->mv1_out))
+    { set_error("bidir_decide_refs: mv0_out / mv1_out must not alias mv0 / mv1 or each other"); return X265HIP_EINVAL; }
+    const bool planes = withPlanes != 0;
+    if (planes && (withPlanes != nrefs[0] + nrefs[1] || p->phase_plane_samples <= 0))
+    { set_error("bidir_decide_refs: phase planes of every listed reference and phase_plane_samples are needed together"); return X265HIP_EINVAL; }
+    int rc = ensure_device();
+    if (rc) return rc;
+
+    const int bpp = p->depth == 8 ? 1 : 2;
+    BidirRefsArgs ra = {};
+    BidirArgs& a = ra.b;
+    a.fenc = (const uint8_t*)p->fenc; a.fencStrideB = (long)p->fenc_stride * bpp;
+    a.frefStrideB = (long)p->fref_stride * bpp;
+    a.ctusW = p->width / 64; a.depth = p->depth;
+    a.mv[0] = (const int2*)p->mv0; a.mv[1] = (const int2*)p->mv1;
+    a.costQ = p->cost_q; a.qoff = p->qoff;
+    for (int i = 0; i < 3; i++) a.dirCost[i] = p->dir_cost[i];
+    a.planeBytes = (long)p->phase_plane_samples * bpp;
+    a.dir = p->dir; a.ref[0] = p->ref0; a.ref[1] = p->ref1;
+    a.mvOut[0] = (int2*)p->mv0_out; a.mvOut[1] = (int2*)p->mv1_out;
+    a.costOut = p->cost_out;
+    const int32_t* refCost[2] = { p->ref_cost0, p->ref_cost1 };
+    const int* refIds[2] = { p->ref_ids0, p->ref_ids1 };
+    for (int l = 0; l < 2; l++)
+    {
+        // entries behind nrefs repeat the last reference: the kernel clamps the index, and no entry of the tables is left dangling
+        for (int k = 0; k < X265HIP_MAX_REFS; k++)
+        {
+            const int r = k < nrefs[l] ? k : nrefs[l] - 1;
+            ra.t.fref[l][k] = (const uint8_t*)fref[l][r];
+            ra.t.planes[l][k] = planes ? (const uint8_t*)pplanes[l][r] : nullptr;
+            ra.t.refCost[l][k] = refCost[l][r];
+            ra.t.refId[l][k] = refIds[l][r];
+        }
+        ra.nrefs[l] = nrefs[l];
+    }
+    ra.refIdx[0] = p->ref_idx0; ra.refIdx[1] = p->ref_idx1;
+    bidir_launch_luma(planes, bpp, p->level, nctu, (hipStream_t)stream, ra);
     X265HIP_TRY(hipGetLastError());
     return 0;
 }

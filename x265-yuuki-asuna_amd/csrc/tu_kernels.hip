@@ -857,11 +857,30 @@ struct TuBiArgs
     int wHave[2], wPresent[2], w[2], wOff[2], wDenom, wDenomUni[2];   // explicit weights of the two lists (wOff scaled to the bit depth; wDenom = list 0's)
 };
 
+// B pictures with several references per list (x265hip_inter_recon_bi_refs / _chroma_bi_refs): block blk takes list l's prediction from
+// the plane fref[l][refIdx[l][blk]] of the launch's two tables - refIdx[l] = int8 [ctu][blocks], the ref_idx of list l's
+// x265hip_ref_select.  b.t.fref / b.fref1 are not read.  No scaling-list / denoiser tables, no weights.
+struct TuBiRefsArgs
+{
+    TuBiArgs b;
+    const uint8_t* fref[2][X265HIP_MAX_REFS];          // entries behind nrefs repeat the last plane
+    const int8_t* refIdx[2];
+    int nrefs[2];
+};
+__device__ __forceinline__ const TuBiArgs& tu_bi_args(const TuBiArgs& b) { return b; }
+__device__ __forceinline__ const TuBiArgs& tu_bi_args(const TuBiRefsArgs& rb) { return rb.b; }
+
 // CHROMA: one chroma plane of a 4:2:0 picture (N = the chroma block size, 1/8-sample mvs, the 4-tap filters; predInterChromaShort,
 // predict.cpp:355-409, for the short predictions)
-template <typename Px, int N, bool CHROMA, bool TAB = false>
-__global__ void __launch_bounds__(N >= 16 ? 64 : 256, TuWavesPerSimd<N>::value) inter_recon_bi_kernel(TuBiArgs b, int nblocks)
+// Args = TuBiArgs: list l is one plane.  Args = TuBiRefsArgs (REFS): the plane the block's index of list l selects - one block per
+// workgroup pass, so the index is uniform: byte load, readfirstlane, clamp, a scalar-indexed table in the kernel arguments, as in
+// inter_recon_kernel.  One body, the other flavour's statements discarded: the single-reference instances keep their code.
+template <typename Px, int N, bool CHROMA, bool TAB = false, class Args = TuBiArgs>
+__global__ void __launch_bounds__(N >= 16 ? 64 : 256, TuWavesPerSimd<N>::value) inter_recon_bi_kernel(Args rb, int nblocks)
 {
+    constexpr bool REFS = std::is_same<Args, TuBiRefsArgs>::value;
+    static_assert(!(REFS && TAB), "the multi-reference entries take no tables");
+    const TuBiArgs& b = tu_bi_args(rb);
     const TuArgs& a = b.t;
     constexpr int NN = N * N, LOG2N = N == 4 ? 2 : (N == 8 ? 3 : (N == 16 ? 4 : 5));
     constexpr int TAPS = CHROMA ? 4 : 8, APRON = TAPS / 2 - 1, PW = N + TAPS - 1, PP = PW + 1;
@@ -900,7 +919,11 @@ __global__ void __launch_bounds__(N >= 16 ? 64 : 256, TuWavesPerSimd<N>::value) 
             const int xf = qx & MVMASK, yf = qy & MVMASK;
             __syncthreads();                                            // the patch of the other list is no longer read
             {
-                const uint8_t* plane = l ? b.fref1 : a.fref;
+                const uint8_t* plane;
+                // REFS: the index of a list the block does not use is never read (the `continue` above); clamped to the list: no entry
+                // of the table is dereferenced out of range
+                if constexpr (REFS) plane = rb.fref[l][clip3(0, rb.nrefs[l] - 1, __builtin_amdgcn_readfirstlane((int)rb.refIdx[l][blk]))];
+                else plane = l ? b.fref1 : a.fref;
                 const Px* r = reinterpret_cast<const Px*>(plane + (long)(py + (qy >> MVSH) - APRON) * a.frefStrideB) + (px + (qx >> MVSH) - APRON);
                 const long rst = a.frefStrideB / BPP;
                 for (int i = tid; i < PW * PW; i += nth) { const int y = i / PW, x = i - y * PW; patch[y * PP + x] = (int16_t)r[y * rst + x]; }
@@ -908,7 +931,7 @@ __global__ void __launch_bounds__(N >= 16 ? 64 : 256, TuWavesPerSimd<N>::value) 
             __syncthreads();
             int16_t* out = (d == 3 && l == 0) ? ps0 : pred;            // list 0's short prediction waits in ps0
             // addWeightUni works on the short (14-bit) prediction like the bi-directional combination
-            const bool shortOut = d == 3 || (b.wHave[l] && b.wPresent[l]);
+            const bool shortOut = d == 3 || (!REFS && b.wHave[l] && b.wPresent[l]);          // REFS: no weights
             const int shiftPS = 6 - headRoom, offPS = -(8192 << shiftPS);
             if (xf && yf)
             {
@@ -957,7 +980,7 @@ __global__ void __launch_bounds__(N >= 16 ? 64 : 256, TuWavesPerSimd<N>::value) 
         __syncthreads();
         if (d == 3)
         {
-            if (b.wHave[0] && b.wHave[1] && (b.wPresent[0] || b.wPresent[1]))
+            if (!REFS && b.wHave[0] && b.wHave[1] && (b.wPresent[0] || b.wPresent[1]))
             {
                 // addWeightBi (predict.cpp:411-456, weightBidir :52-55): list 0's denominator for both lists
                 const int shift = b.wDenom + headRoom + 1, round = 1 << (shift - 1), offset = (b.wOff[0] + b.wOff[1]) * (1 << (shift - 1));
@@ -971,7 +994,7 @@ __global__ void __launch_bounds__(N >= 16 ? 64 : 256, TuWavesPerSimd<N>::value) 
             }
             __syncthreads();
         }
-        else if (b.wHave[d == 2] && b.wPresent[d == 2])
+        else if (!REFS && b.wHave[d == 2] && b.wPresent[d == 2])
         {
             // addWeightUni = weight_sp (pixel.cpp:493-515) on the short prediction of the one list used
             const int l = d == 2, shift = b.wDenomUni[l] + headRoom, round = shift ? 1 << (shift - 1) : 0;
@@ -1110,6 +1133,12 @@ template <typename Px, bool TB> static const void* tu_kernel_of(const int entry,
     case X265HIP_TU_ENTRY_INTER_CHROMA_REFS:
         return n == 4 ? (K)inter_recon_kernel<Px, 4, true, false, TuRefsArgs> : n == 8 ? (K)inter_recon_kernel<Px, 8, true, false, TuRefsArgs>
              : n == 16 ? (K)inter_recon_kernel<Px, 16, true, false, TuRefsArgs> : nullptr;
+    case X265HIP_TU_ENTRY_INTER_BI_REFS:
+        return n == 8 ? (K)inter_recon_bi_kernel<Px, 8, false, false, TuBiRefsArgs> : n == 16 ? (K)inter_recon_bi_kernel<Px, 16, false, false, TuBiRefsArgs>
+             : n == 32 ? (K)inter_recon_bi_kernel<Px, 32, false, false, TuBiRefsArgs> : nullptr;
+    case X265HIP_TU_ENTRY_INTER_CHROMA_BI_REFS:
+        return n == 4 ? (K)inter_recon_bi_kernel<Px, 4, true, false, TuBiRefsArgs> : n == 8 ? (K)inter_recon_bi_kernel<Px, 8, true, false, TuBiRefsArgs>
+             : n == 16 ? (K)inter_recon_bi_kernel<Px, 16, true, false, TuBiRefsArgs> : nullptr;
     case X265HIP_TU_ENTRY_INTRA:
         return n == 4 ? (dst ? (K)intra_recon_kernel<Px, 4, true, TB> : (K)intra_recon_kernel<Px, 4, false, TB>) : n == 8 ? (K)intra_recon_kernel<Px, 8, false, TB>
              : n == 16 ? (K)intra_recon_kernel<Px, 16, false, TB> : n == 32 ? (K)intra_recon_kernel<Px, 32, false, TB> : nullptr;
@@ -1140,8 +1169,10 @@ static int tu_launch_grid(const int entry, const int n, const int depth, const b
 
 extern "C" int x265hip_tu_launch_grid(int entry, int n, int depth, int tables, int nplanes, int nblocks)
 {
-    const bool chroma = entry == X265HIP_TU_ENTRY_INTER_CHROMA || entry == X265HIP_TU_ENTRY_INTER_CHROMA_BI || entry == X265HIP_TU_ENTRY_INTER_CHROMA_REFS;
-    const bool refs = entry == X265HIP_TU_ENTRY_INTER_REFS || entry == X265HIP_TU_ENTRY_INTER_CHROMA_REFS;
+    const bool chroma = entry == X265HIP_TU_ENTRY_INTER_CHROMA || entry == X265HIP_TU_ENTRY_INTER_CHROMA_BI || entry == X265HIP_TU_ENTRY_INTER_CHROMA_REFS
+                        || entry == X265HIP_TU_ENTRY_INTER_CHROMA_BI_REFS;
+    const bool refs = entry == X265HIP_TU_ENTRY_INTER_REFS || entry == X265HIP_TU_ENTRY_INTER_CHROMA_REFS || entry == X265HIP_TU_ENTRY_INTER_BI_REFS
+                      || entry == X265HIP_TU_ENTRY_INTER_CHROMA_BI_REFS;
     if ((entry < X265HIP_TU_ENTRY_INTER || entry > X265HIP_TU_ENTRY_INTRA) && !refs) { set_error("tu_launch_grid: entry %d", entry); return X265HIP_EINVAL; }
     const bool sizeOk = entry == X265HIP_TU_ENTRY_INTRA ? (n == 4 || n == 8 || n == 16 || n == 32)
                                                         : (chroma ? (n == 4 || n == 8 || n == 16) : (n == 8 || n == 16 || n == 32));
@@ -1166,16 +1197,31 @@ static bool tu_map_with_tables(const x265hip_recon_params* p, const char* who)
 
 // The checks of one base record, in the order and the words every inter entry has always had.  lumaWords: the entries that take a chroma
 // plane say that sizes and levels count luma samples.  refs: the record of a multi-reference entry - base.fref is ignored, the planes come
-// from its table, whose checks sit between those of the operands and those of the geometry.
-static bool tu_record_ok(const x265hip_recon_params* q, const char* who, const bool lumaWords, const x265hip_recon_refs_params* refs = nullptr)
+// from its table (one list for a P picture, two for a B picture), whose checks sit between those of the operands and those of the geometry.
+struct TuRefLists
 {
-    if (!q || !q->fenc || (!refs && !q->fref) || !q->recon || !q->mv || !q->levels || !q->num_sig || !q->dist || (refs && !refs->ref_idx))
+    int nlists;
+    int nrefs[2];
+    const void* const* fref[2];
+    const int8_t* refIdx[2];
+};
+static bool tu_record_ok(const x265hip_recon_params* q, const char* who, const bool lumaWords, const TuRefLists* refs = nullptr)
+{
+    if (!q || !q->fenc || (!refs && !q->fref) || !q->recon || !q->mv || !q->levels || !q->num_sig || !q->dist)
     { set_error("%s: NULL operand", who); return false; }
-    if (refs)
+    for (int l = 0; refs && l < refs->nlists; l++)
+        if (!refs->refIdx[l]) { set_error("%s: NULL operand", who); return false; }
+    for (int l = 0; refs && l < refs->nlists; l++)
     {
-        if (refs->nrefs < 1 || refs->nrefs > X265HIP_MAX_REFS) { set_error("%s: nrefs %d out of [1,%d]", who, refs->nrefs, X265HIP_MAX_REFS); return false; }
-        for (int k = 0; k < refs->nrefs; k++)
-            if (!refs->fref[k]) { set_error("%s: NULL plane of reference %d", who, k); return false; }
+        if (refs->nrefs[l] < 1 || refs->nrefs[l] > X265HIP_MAX_REFS) { set_error("%s: nrefs %d out of [1,%d]", who, refs->nrefs[l], X265HIP_MAX_REFS); return false; }
+        for (int k = 0; k < refs->nrefs[l]; k++)
+            if (!refs->fref[l][k])
+            {
+                // one list: the words the P entries have always had
+                if (refs->nlists == 1) set_error("%s: NULL plane of reference %d", who, k);
+                else set_error("%s: NULL plane of reference %d of list %d", who, k, l);
+                return false;
+            }
     }
     if ((q->width & 63) || (q->height & 63) || q->width <= 0 || q->height <= 0) { set_error("%s: width/height%s must be multiples of 64", who, lumaWords ? " (luma)" : ""); return false; }
     if (q->depth != 8 && q->depth != 10 && q->depth != 12) { set_error("%s: depth %d", who, q->depth); return false; }
@@ -1310,7 +1356,8 @@ static int inter_recon_refs_planes(const x265hip_recon_refs_params* const* pp, c
         if (!r) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
         const x265hip_recon_params* q = &r->base;
         if (q->tables) { set_error("%s: tables (scaling lists / the denoiser) are not supported by this stage", who); return X265HIP_EINVAL; }
-        if (!tu_record_ok(q, who, true, r)) return X265HIP_EINVAL;
+        const TuRefLists lists = { 1, { r->nrefs, 0 }, { r->fref, nullptr }, { r->ref_idx, nullptr } };
+        if (!tu_record_ok(q, who, true, &lists)) return X265HIP_EINVAL;
         if (q->width != p->width || q->height != p->height || q->depth != p->depth || q->level != p->level || r->nrefs != pp[0]->nrefs)
         { set_error("%s: the two planes differ in geometry / depth / level / nrefs", who); return X265HIP_EINVAL; }
         ra.aa.p[i] = tu_args_of(q, r->fref[0]);          // q->tables is NULL here
@@ -1334,6 +1381,38 @@ extern "C" int x265hip_inter_recon_chroma_pair_refs(const x265hip_recon_refs_par
     const x265hip_recon_refs_params* pp[2] = { cb, cr };
     return inter_recon_refs_planes(pp, 2, true, stream);
 }
+
+// B pictures with several references per list: the multi-reference instances of inter_recon_bi_kernel
+static int inter_recon_bi_refs_impl(const x265hip_recon_bi_refs_params* r, void* stream, const bool chroma)
+{
+    const char* who = chroma ? "inter_recon_chroma_bi_refs" : "inter_recon_bi_refs";
+    // argument checks first: they need no device
+    if (!r || !r->base.mv1) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
+    const x265hip_recon_params* p = &r->base.base;
+    if (p->tables) { set_error("%s: tables (scaling lists / the denoiser) are not supported by this stage", who); return X265HIP_EINVAL; }
+    if (r->base.weight0 || r->base.weight1) { set_error("%s: weights (explicit weighted prediction) are not supported by this stage", who); return X265HIP_EINVAL; }
+    const TuRefLists lists = { 2, { r->nrefs0, r->nrefs1 }, { r->fref0, r->fref1 }, { r->ref_idx0, r->ref_idx1 } };
+    if (!tu_record_ok(p, who, chroma, &lists)) return X265HIP_EINVAL;
+    TuBiRefsArgs rb = {};
+    TuBiArgs& b = rb.b;
+    b.t = tu_args_of(p, r->fref0[0]);          // p->tables is NULL here; the kernel walks the blocks in raster order, like its single-reference twin
+    b.fref1 = (const uint8_t*)r->fref1[0]; b.mv1 = (const int2*)r->base.mv1; b.dir = r->base.dir;
+    // no weights: wHave / wPresent and the rest stay zero
+    for (int l = 0; l < 2; l++)
+    {
+        // entries behind nrefs repeat the last plane: the kernel clamps the index, and no entry of the table is left dangling
+        for (int k = 0; k < X265HIP_MAX_REFS; k++) rb.fref[l][k] = (const uint8_t*)lists.fref[l][k < lists.nrefs[l] ? k : lists.nrefs[l] - 1];
+        rb.refIdx[l] = lists.refIdx[l];
+        rb.nrefs[l] = lists.nrefs[l];
+    }
+    int rc = ensure_device();
+    if (rc) return rc;
+    return tu_launch_inter(chroma ? X265HIP_TU_ENTRY_INTER_CHROMA_BI_REFS : X265HIP_TU_ENTRY_INTER_BI_REFS, p, chroma, 1, stream, &rb);
+}
+
+extern "C" int x265hip_inter_recon_bi_refs(const x265hip_recon_bi_refs_params* p, void* stream) { return inter_recon_bi_refs_impl(p, stream, false); }
+/* one chroma plane of a 4:2:0 picture (the conventions of x265hip_inter_recon_chroma_bi) */
+extern "C" int x265hip_inter_recon_chroma_bi_refs(const x265hip_recon_bi_refs_params* p, void* stream) { return inter_recon_bi_refs_impl(p, stream, true); }
 
 extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, void* stream)
 {

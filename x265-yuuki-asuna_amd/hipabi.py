@@ -37,6 +37,7 @@ class MEParams(ctypes.Structure):
 TU_INTRA_SLICE, TU_SIGN_HIDE = 1, 2        # X265HIP_TU_* flag bits of the TU stages' intra_slice field
 TU_ENTRY_INTER, TU_ENTRY_INTER_BI, TU_ENTRY_INTER_CHROMA, TU_ENTRY_INTER_CHROMA_BI, TU_ENTRY_INTRA = range(5)     # enum x265hip_tu_entry
 TU_ENTRY_INTER_REFS, TU_ENTRY_INTER_CHROMA_REFS = 8, 9                                                              # enum x265hip_tu_entry_refs
+TU_ENTRY_INTER_BI_REFS, TU_ENTRY_INTER_CHROMA_BI_REFS = 12, 13                                                      # enum x265hip_tu_entry_bi_refs
 MAX_REFS = 8                               # X265HIP_MAX_REFS
 SURF_I32, SURF_PACKED, SURF_PACKED_T, SURF_PACKED_B = 0, 1, 2, 3
 SURF_GROUP_BYTES_I32, SURF_GROUP_BYTES_PACKED = 1360, 720
@@ -115,6 +116,43 @@ class ReconParams(ctypes.Structure):
 class ReconRefsParams(ctypes.Structure):
     """x265hip_recon_refs_params (include/x265hip.h)."""
     _fields_ = [("base", ReconParams), ("nrefs", ctypes.c_int), ("fref", ctypes.c_void_p * MAX_REFS), ("ref_idx", ctypes.c_void_p)]
+
+
+class PredWeight(ctypes.Structure):
+    """x265hip_pred_weight (include/x265hip.h)."""
+    _fields_ = [("present", ctypes.c_int), ("weight", ctypes.c_int), ("offset", ctypes.c_int), ("log2_denom", ctypes.c_int)]
+
+
+class ReconBiParams(ctypes.Structure):
+    """x265hip_recon_bi_params (include/x265hip.h)."""
+    _fields_ = [("base", ReconParams), ("fref1", ctypes.c_void_p), ("mv1", ctypes.c_void_p), ("dir", ctypes.c_void_p),
+                ("weight0", ctypes.POINTER(PredWeight)), ("weight1", ctypes.POINTER(PredWeight))]
+
+
+class ReconBiRefsParams(ctypes.Structure):
+    """x265hip_recon_bi_refs_params (include/x265hip.h)."""
+    _fields_ = [("base", ReconBiParams), ("nrefs0", ctypes.c_int), ("nrefs1", ctypes.c_int),
+                ("fref0", ctypes.c_void_p * MAX_REFS), ("fref1", ctypes.c_void_p * MAX_REFS),
+                ("ref_idx0", ctypes.c_void_p), ("ref_idx1", ctypes.c_void_p)]
+
+
+class BidirRefsParams(ctypes.Structure):
+    """x265hip_bidir_refs_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("fenc", ctypes.c_void_p), ("fenc_stride", ctypes.c_ssize_t),
+        ("cost_q", ctypes.c_void_p), ("qoff", ctypes.c_int),
+        ("dir_cost", ctypes.c_int32 * 3),
+        ("nrefs0", ctypes.c_int), ("nrefs1", ctypes.c_int),
+        ("fref0", ctypes.c_void_p * MAX_REFS), ("fref1", ctypes.c_void_p * MAX_REFS), ("fref_stride", ctypes.c_ssize_t),
+        ("ref_cost0", ctypes.c_int32 * MAX_REFS), ("ref_cost1", ctypes.c_int32 * MAX_REFS),
+        ("ref_ids0", ctypes.c_int * MAX_REFS), ("ref_ids1", ctypes.c_int * MAX_REFS),
+        ("ref_idx0", ctypes.c_void_p), ("ref_idx1", ctypes.c_void_p),
+        ("mv0", ctypes.c_void_p), ("mv1", ctypes.c_void_p),
+        ("phase_planes0", ctypes.c_void_p * MAX_REFS), ("phase_planes1", ctypes.c_void_p * MAX_REFS), ("phase_plane_samples", ctypes.c_ssize_t),
+        ("dir", ctypes.c_void_p), ("ref0", ctypes.c_void_p), ("ref1", ctypes.c_void_p),
+        ("mv0_out", ctypes.c_void_p), ("mv1_out", ctypes.c_void_p), ("cost_out", ctypes.c_void_p),
+    ]
 
 
 class IntraPictureParams(ctypes.Structure):
@@ -428,6 +466,75 @@ def inter_recon_chroma_pair_refs(cb, cr, stream=None):
     f = lib().x265hip_inter_recon_chroma_pair_refs
     f.argtypes = [ctypes.POINTER(ReconRefsParams), ctypes.POINTER(ReconRefsParams), ctypes.c_void_p]
     check(f(ctypes.byref(cb), ctypes.byref(cr), s), "x265hip_inter_recon_chroma_pair_refs")
+
+
+def b_ref_cost_bits(nrefs, lam=4):
+    """lambda x (MVP_IDX_BITS + getTUBits(r, nrefs)) of one list of a B slice's 2Nx2N for r = 0 .. nrefs - 1 (search.cpp:2403-2404 without
+    the list-selection bits, which dir_cost carries): (4) for one reference, (8, 8) for two, (8, 12, 16, 16) for four at lambda 4."""
+    return tuple(int(lam) * (1 + r + (1 if r < nrefs - 1 else 0)) for r in range(nrefs))
+
+
+def bidir_decide_refs(depth, width, height, level, fenc, fenc_stride, frefs0, frefs1, fref_stride, mv0, mv1, ref_idx0, ref_idx1, ref_cost0, ref_cost1,
+                      cost_q, qoff, dir_cost, dir_out, mv0_out, mv1_out, ref0=None, ref1=None, cost_out=None, ref_ids0=None, ref_ids1=None,
+                      fenc_off=0, fref_off=0, phase_planes0=None, phase_planes1=None, stream=None):
+    """x265hip_bidir_decide_refs: list 0 / list 1 / both for every block of a B picture with several references per list.  frefs0 /
+    frefs1: each list's picture tensors in list order, all of one geometry (sample (0,0) at element fref_off); mv0 / mv1, ref_idx0 /
+    ref_idx1: mv_out and ref_idx of the two x265hip_ref_select passes; ref_cost0 / ref_cost1: one int per reference; ref_ids0 / ref_ids1:
+    picture ids (default: the list indices); phase_planes0 / phase_planes1: per reference the byte tensor of x265hip_phase_planes, or None."""
+    es = 1 if depth == 8 else 2
+    p = BidirRefsParams()
+    p.depth, p.width, p.height, p.level = depth, width, height, level
+    p.fenc, p.fenc_stride, p.fref_stride = fenc.data_ptr() + fenc_off * es, fenc_stride, fref_stride
+    p.cost_q, p.qoff = cost_q.data_ptr(), qoff
+    p.dir_cost[0], p.dir_cost[1], p.dir_cost[2] = (int(c) for c in dir_cost)
+    p.nrefs0, p.nrefs1 = len(frefs0), len(frefs1)
+    lists = ((frefs0, ref_cost0, ref_ids0, phase_planes0, p.fref0, p.ref_cost0, p.ref_ids0, p.phase_planes0),
+             (frefs1, ref_cost1, ref_ids1, phase_planes1, p.fref1, p.ref_cost1, p.ref_ids1, p.phase_planes1))
+    for frefs, cost, ids, planes, d_fref, d_cost, d_ids, d_planes in lists:
+        ids = range(len(frefs)) if ids is None else ids
+        for r, (t, c, i) in enumerate(zip(frefs[:MAX_REFS], cost, ids)):
+            d_fref[r], d_cost[r], d_ids[r] = t.data_ptr() + fref_off * es, int(c), int(i)
+            if planes is not None:
+                d_planes[r] = planes[r].data_ptr() + fref_off * es
+    if phase_planes0 is not None or phase_planes1 is not None:
+        p.phase_plane_samples = frefs0[0].numel() * frefs0[0].element_size() // es
+    p.ref_idx0, p.ref_idx1, p.mv0, p.mv1 = ref_idx0.data_ptr(), ref_idx1.data_ptr(), mv0.data_ptr(), mv1.data_ptr()
+    p.dir, p.ref0, p.ref1 = dir_out.data_ptr(), _p(ref0), _p(ref1)
+    p.mv0_out, p.mv1_out, p.cost_out = mv0_out.data_ptr(), mv1_out.data_ptr(), _p(cost_out)
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_bidir_decide_refs
+    f.argtypes = [ctypes.POINTER(BidirRefsParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_bidir_decide_refs")
+
+
+def recon_bi_refs_params(base, frefs0, frefs1, ref_idx0, ref_idx1):
+    """A ReconBiRefsParams from a filled ReconBiParams (its fref / fref1 are ignored), the plane ADDRESSES of sample (0,0) of each list's
+    references and the two ref_idx tensors."""
+    q = ReconBiRefsParams()
+    q.base = base                      # copied into the record
+    q.nrefs0, q.nrefs1 = len(frefs0), len(frefs1)
+    for r, a in enumerate(frefs0[:MAX_REFS]):
+        q.fref0[r] = a
+    for r, a in enumerate(frefs1[:MAX_REFS]):
+        q.fref1[r] = a
+    q.ref_idx0, q.ref_idx1 = ref_idx0.data_ptr(), ref_idx1.data_ptr()
+    return q
+
+
+def inter_recon_bi_refs(q, stream=None):
+    """x265hip_inter_recon_bi_refs on a ReconBiRefsParams record."""
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_inter_recon_bi_refs
+    f.argtypes = [ctypes.POINTER(ReconBiRefsParams), ctypes.c_void_p]
+    check(f(ctypes.byref(q), s), "x265hip_inter_recon_bi_refs")
+
+
+def inter_recon_chroma_bi_refs(q, stream=None):
+    """x265hip_inter_recon_chroma_bi_refs: one chroma plane of a 4:2:0 picture."""
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_inter_recon_chroma_bi_refs
+    f.argtypes = [ctypes.POINTER(ReconBiRefsParams), ctypes.c_void_p]
+    check(f(ctypes.byref(q), s), "x265hip_inter_recon_chroma_bi_refs")
 
 
 def intra_picture_waves(width, height):

@@ -76,15 +76,8 @@ class InterRecon:
                 "dist": int(self.dist.sum().item())}
 
 
-class PredWeight(ctypes.Structure):
-    """x265hip_pred_weight (include/x265hip.h)."""
-    _fields_ = [("present", ctypes.c_int), ("weight", ctypes.c_int), ("offset", ctypes.c_int), ("log2_denom", ctypes.c_int)]
-
-
-class ReconBiParams(ctypes.Structure):
-    """x265hip_recon_bi_params (include/x265hip.h)."""
-    _fields_ = [("base", ReconParams), ("fref1", ctypes.c_void_p), ("mv1", ctypes.c_void_p), ("dir", ctypes.c_void_p),
-                ("weight0", ctypes.POINTER(PredWeight)), ("weight1", ctypes.POINTER(PredWeight))]
+PredWeight = hipabi.PredWeight            # x265hip_pred_weight and x265hip_recon_bi_params: the records live beside ReconBiRefsParams, which embeds them
+ReconBiParams = hipabi.ReconBiParams
 
 
 class InterReconBi(InterRecon):
@@ -223,6 +216,46 @@ class InterReconChromaBi(InterReconChroma):
         f = hipabi.lib().x265hip_inter_recon_chroma_bi
         f.argtypes = [ctypes.POINTER(ReconBiParams), ctypes.c_void_p]
         hipabi.check(f(ctypes.byref(q), s), "x265hip_inter_recon_chroma_bi")
+
+
+class InterReconBiRefs(InterRecon):
+    """The bi-predictive TU stage of a B picture with several references per list (x265hip_inter_recon_bi_refs): block blk takes list
+    l's prediction from refs_l[ref_idx_l[blk]]; everything else is InterReconBi's contract.  No tables, no weights."""
+
+    def run(self, cur: DevicePicture, refs0, refs1, recon_plane, mv0, mv1, ref_idx0, ref_idx1, dir_flags=None, stream=None):
+        """refs0 / refs1: each list's reference pictures in list order (one geometry); ref_idx0 / ref_idx1: int8 [ctu][blocks] (the two
+        RefSelect.ref_idx); mv0 / mv1, dir_flags: BidirDecideRefs' outputs."""
+        es = 1 if self.depth == 8 else 2
+        first = refs0[0]
+        assert all(r.stride == first.stride and r.org == first.org for r in list(refs0) + list(refs1))
+        q = ReconBiParams()
+        p = q.base
+        p.depth, p.width, p.height, p.level, p.qp, p.intra_slice = self.depth, self.w64, self.h64, self.level, self.qp, self.intra
+        p.fenc, p.fenc_stride = cur.t.data_ptr() + cur.org * es, cur.stride
+        p.fref, p.fref_stride = None, first.stride
+        p.recon, p.recon_stride = recon_plane.data_ptr() + cur.org * es, cur.stride
+        p.mv, p.levels, p.num_sig, p.dist = mv0.data_ptr(), self.levels.data_ptr(), self.num_sig.data_ptr(), self.dist.data_ptr()
+        p.tables = ctypes.addressof(self.tables) if self.tables is not None else None          # refused by the entry
+        p.qp_map = hipabi._p(self.qp_map)
+        q.mv1 = mv1.data_ptr()
+        q.dir = None if dir_flags is None else dir_flags.data_ptr()
+        addr = lambda refs: [r.t.data_ptr() + r.org * es for r in refs]
+        hipabi.inter_recon_bi_refs(hipabi.recon_bi_refs_params(q, addr(refs0), addr(refs1), ref_idx0, ref_idx1), stream)
+
+
+class InterReconChromaBiRefs(InterReconChroma):
+    """One chroma plane of a B picture with several references per list (x265hip_inter_recon_chroma_bi_refs)."""
+
+    def run(self, fenc, frefs0, frefs1, recon, stride, org, mv0, mv1, ref_idx0, ref_idx1, dir_flags=None, stream=None):
+        """frefs0 / frefs1: this plane (Cb or Cr) of every reference picture of each list, list order."""
+        es = 1 if self.depth == 8 else 2
+        q = ReconBiParams()
+        q.base = self.params(fenc, frefs0[0], recon, stride, org, mv0)          # copied into the record
+        q.base.fref = None
+        q.mv1 = mv1.data_ptr()
+        q.dir = None if dir_flags is None else dir_flags.data_ptr()
+        addr = lambda frefs: [f.data_ptr() + org * es for f in frefs]
+        hipabi.inter_recon_chroma_bi_refs(hipabi.recon_bi_refs_params(q, addr(frefs0), addr(frefs1), ref_idx0, ref_idx1), stream)
 
 
 def extend_border_rows(plane, pic: DevicePicture, top: bool, bottom: bool, stream=None, chroma=False):
@@ -1575,6 +1608,116 @@ class MultiRefFramePipeline(_RefListStep):
         return self._checksum(self.rs)
 
 
+class BidirDecideRefs(BidirDecide):
+    """The bidirectional decision of a B picture with several references per list (x265hip_bidir_decide_refs): every block is measured
+    against the two pictures it chose - the two RefSelect outputs - with the reference bits of both lists in the bidirectional and the zero
+    candidate.  Owns what BidirDecide owns; ref0 / ref1 hold the PICTURE ids of the blocks' references (or -1)."""
+
+    def __init__(self, nctu, w64, h64, depth, level, device, dir_cost=(12, 12, 20), want_cost=False):
+        BidirDecide.__init__(self, nctu, w64, h64, depth, level, device, dir_cost=dir_cost, want_cost=want_cost)
+
+    def run(self, cur: DevicePicture, refs0, refs1, mv0, mv1, ref_idx0, ref_idx1, ref_cost0, ref_cost1, cost_q, qoff, ref_ids0=None, ref_ids1=None,
+            phase_planes0=None, phase_planes1=None, stream=None):
+        """refs0 / refs1: each list's pictures in list order; mv0 / mv1, ref_idx0 / ref_idx1: mv_out and ref_idx of the two RefSelect
+        passes; ref_cost0 / ref_cost1: what those passes were given; phase_planes0 / phase_planes1: per reference the planes of
+        x265hip_phase_planes, or None (interpolate)."""
+        first = refs0[0]
+        assert all(r.stride == first.stride and r.org == first.org for r in list(refs0) + list(refs1))
+        hipabi.bidir_decide_refs(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, [r.t for r in refs0], [r.t for r in refs1], first.stride,
+                                 mv0, mv1, ref_idx0, ref_idx1, ref_cost0, ref_cost1, cost_q, qoff, self.dir_cost, self.dir, self.mv0_out, self.mv1_out,
+                                 ref0=self.ref0, ref1=self.ref1, cost_out=self.cost_out, ref_ids0=ref_ids0, ref_ids1=ref_ids1, fenc_off=cur.org,
+                                 fref_off=first.org, phase_planes0=phase_planes0, phase_planes1=phase_planes1, stream=stream)
+
+
+class MultiRefBFramePipeline(_RefListStep):
+    """One B picture with several references per list on the device, the stages of BFramePipeline.run with two reference lists of pictures:
+        per DISTINCT reference picture: exhaustive search (best mv) -> sub-pel refinement;  per list: reference selection (RefSelect);
+        bidirectional decision against the two pictures every block chose (BidirDecideRefs);  bi-predictive luma + 4:2:0 chroma
+        reconstruction from those pictures;  B-picture boundary strengths on picture ids + luma / chroma deblocking;  SAO;  border extension.
+    The constructor switches mean what they mean in BFramePipeline.  Everything runs serially on the caller's stream."""
+
+    def __init__(self, w64, h64, depth, device, max_refs=(2, 2), rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
+                 sign_hide=False, subpel_planes=False, sao_rdo=None, dir_cost=(12, 12, 20), want_cost=False, chroma_satd=False, ref_cost=None):
+        """max_refs: (list 0, list 1), the most references a run() is given per list.  ref_cost: (list 0, list 1), one int per reference
+        of every run() (lambda x the bits of the reference index), None = hipabi.b_ref_cost_bits of each list's length."""
+        if chroma_satd:
+            raise ValueError("MultiRefBFramePipeline: chroma SATD is not part of the decision with several references per list")
+        n0, n1 = (int(n) for n in max_refs)
+        if not (1 <= n0 <= hipabi.MAX_REFS and 1 <= n1 <= hipabi.MAX_REFS):
+            raise ValueError(f"MultiRefBFramePipeline: max_refs {max_refs} out of [1, {hipabi.MAX_REFS}]")
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
+        self.max_refs = (n0, n1)
+        self.ref_cost = None if ref_cost is None else tuple(tuple(int(c) for c in l) for l in ref_cost)
+        self._build_lists(n0 + n1, w64, h64, depth, device, rng, subme, subpel_planes, False)      # one slot per distinct picture
+        self.rs = [RefSelect(self.nctu, w64, h64, depth, level, device, max_refs=n, want_cost=want_cost) for n in (n0, n1)]
+        self.bd = BidirDecideRefs(self.nctu, w64, h64, depth, level, device, dir_cost=dir_cost, want_cost=want_cost)
+        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
+        self.rc = InterReconBiRefs(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        if chroma:
+            qpc = chroma_quant_qp(qp, depth)
+            self.rc_c = [InterReconChromaBiRefs(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
+        self.slots = ([], [])
+
+    def run(self, cur: DevicePicture, refs0, refs1, mark=None, ref_ids=None):
+        """refs0 / refs1: the list-0 / list-1 reference pictures in list order (extended borders; with chroma=True also their Cb / Cr
+        planes).  A picture that sits in both lists - the same object - is searched and refined once; its records and phase planes serve
+        both lists.  ref_ids: (list 0, list 1) picture ids within int8, equal for the same picture and distinct otherwise (two objects
+        may carry one id: copies of one picture); None = derived here (the picture's place among the distinct objects).  Returns the luma plane of the coded picture; mark(name), if given, is
+        called after every stage."""
+        self._qp_maps_run_check()
+        mark = mark or (lambda name: None)
+        lists = (list(refs0), list(refs1))
+        for l in range(2):
+            if not 1 <= len(lists[l]) <= self.max_refs[l]:
+                raise ValueError(f"MultiRefBFramePipeline: {len(lists[l])} references in list {l} for max_refs {self.max_refs}")
+            if self.ref_cost is not None and len(self.ref_cost[l]) != len(lists[l]):
+                raise ValueError(f"MultiRefBFramePipeline: ref_cost has {len(self.ref_cost[l])} entries for {len(lists[l])} references in list {l}")
+        distinct = []
+        for ref in lists[0] + lists[1]:
+            if not any(ref is d for d in distinct):
+                distinct.append(ref)
+        slot_of = lambda ref: next(i for i, d in enumerate(distinct) if d is ref)
+        self.slots = tuple([slot_of(ref) for ref in lists[l]] for l in range(2))
+        if ref_ids is None:
+            ids = self.slots
+        else:
+            ids = tuple([int(i) for i in ref_ids[l]] for l in range(2))
+            by_slot = {}
+            for l in range(2):
+                if len(ids[l]) != len(lists[l]) or any(not -128 <= i <= 127 for i in ids[l]):
+                    raise ValueError("MultiRefBFramePipeline: ref_ids need one int8 per reference")
+                for sl, i in zip(self.slots[l], ids[l]):
+                    if by_slot.setdefault(sl, i) != i:
+                        raise ValueError("MultiRefBFramePipeline: one picture with two ids")
+        self._alloc_planes(cur)
+        self._search_lists(cur, distinct, mark)
+        cost = tuple(hipabi.b_ref_cost_bits(len(lists[l])) if self.ref_cost is None else self.ref_cost[l] for l in range(2))
+        for l in range(2):
+            self.rs[l].run([self.spl[sl].out for sl in self.slots[l]], ref_cost=cost[l], ref_ids=ids[l])
+        mark("ref_select")
+        phases = [[self.spl[sl].planes for sl in self.slots[l]] if self.spl[0].use_planes else None for l in range(2)]
+        self.bd.run(cur, lists[0], lists[1], self.rs[0].mv_out, self.rs[1].mv_out, self.rs[0].ref_idx, self.rs[1].ref_idx, cost[0], cost[1],
+                    self.spl[0].cost_q, self.spl[0].qoff, ref_ids0=ids[0], ref_ids1=ids[1], phase_planes0=phases[0], phase_planes1=phases[1])
+        mark("bidir")
+        mv0, mv1, dirs, i0, i1 = self.bd.mv0_out, self.bd.mv1_out, self.bd.dir, self.rs[0].ref_idx, self.rs[1].ref_idx
+        self.rc.run(cur, lists[0], lists[1], self.recon, mv0, mv1, i0, i1, dir_flags=dirs)
+        mark("recon")
+        if self.chroma:
+            for i in range(2):
+                self.rc_c[i].run(cur.c[i], [r.c[i] for r in lists[0]], [r.c[i] for r in lists[1]], self.recon_c[i], cur.stride_c, cur.org_c, mv0, mv1, i0, i1,
+                                 dir_flags=dirs)
+            mark("recon_chroma")
+        if self.db is not None:
+            self.db.run_b(self.recon, cur, mv0, mv1, self.bd.ref0, self.bd.ref1, self.rc.num_sig)
+        return self._filter_tail(cur, mark)
+
+    def checksum(self):
+        out = self._checksum(self.bd)
+        for l in range(2):
+            out["ref_idx%d" % l] = self.rs[l].checksum()["ref_idx"]
+        return out
+
+
 class IntraPicture:
     """One I picture on the TU stages' block grid (x265hip_intra_picture; reference Predict::initIntraNeighbors / fillReferenceSamples /
     initAdiPattern, predict.cpp:600-876, Search::checkIntraInInter, search.cpp:1344-1446, and the coding contract of
@@ -1690,11 +1833,15 @@ class MiniGop:
     anchor) once the later anchor is done.  B pictures are not referenced.  p_step: a FramePipeline, b_step: a BFramePipeline of the same
     geometry and chroma setting; i_step: an IFramePipeline of that geometry that codes picture 0, or None.
     p_refs > 1: p_step is a MultiRefFramePipeline and every anchor is coded by p_step.run(cur, [up to p_refs previous coded anchors,
-    newest first]); B pictures keep using the two anchors around them."""
+    newest first]); B pictures keep using the two anchors around them unless
+    b_refs = (n0, n1) != (1, 1): b_step is a MultiRefBFramePipeline and a B picture between two anchors is coded by b_step.run(cur, list 0,
+    list 1) with list 0 = the coded anchors before it, newest first, [:n0], and list 1 = ([the later anchor] + those)[:n1] - HEVC's default
+    list order, so with n1 > 1 a picture sits in both lists."""
 
-    def __init__(self, p_step, b_step, gop, i_step=None, p_refs=1):
-        assert gop >= 1 and p_refs >= 1
+    def __init__(self, p_step, b_step, gop, i_step=None, p_refs=1, b_refs=(1, 1)):
+        assert gop >= 1 and p_refs >= 1 and len(b_refs) == 2 and min(b_refs) >= 1
         self.p, self.b, self.gop, self.i, self.p_refs = p_step, b_step, int(gop), i_step, int(p_refs)
+        self.b_refs = (int(b_refs[0]), int(b_refs[1]))
 
     def run(self, pictures):
         """pictures: DevicePictures in display order; picture 0 is the first anchor - coded by i_step where there is one (its output is
@@ -1718,7 +1865,10 @@ class MiniGop:
             order.append(a)
             anchor = pictures[a].like(out[a])
             for k in range(a - self.gop + 1, a):
-                self.b.run(pictures[k], prev, anchor)
+                if self.b_refs != (1, 1):
+                    self.b.run(pictures[k], anchors[:self.b_refs[0]], ([anchor] + anchors)[:self.b_refs[1]])
+                else:
+                    self.b.run(pictures[k], prev, anchor)
                 out[k] = keep(self.b.final_planes())
                 order.append(k)
             prev = anchor

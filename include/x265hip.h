@@ -1732,6 +1732,56 @@ int x265hip_intra_picture_qp(const x265hip_intra_picture_params* p, const int8_t
 /* launches x265hip_intra_picture issues for a picture of this size: width / 64 + 2 * (height / 64 - 1).  Host arithmetic, needs no device. */
 int x265hip_intra_picture_waves(int width, int height);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Intra blocks inside a P picture (csrc/inter_sa8d_cost.h, csrc/intra_picture.h): Analysis::compressInterCU_rd0_4 runs checkIntraInInter
+ * for every CU of a P slice and keeps the intra candidate when its sa8d cost is strictly lower than the best inter candidate's
+ * (analysis.cpp:1649-1671).  On the block grid of the TU stages that is three steps: the inter TU stages code every block as inter,
+ * x265hip_inter_sa8d_cost prices the inter candidates, x265hip_intra_in_inter walks the blocks in coding order, decides, and recodes the
+ * intra winners in place.  Inter reconstruction does not depend on neighbours, so this order gives the reference's result.
+ *
+ * x265hip_inter_sa8d_cost = Analysis::checkInter_rd0_4 at RD level <= 2 (analysis.cpp:3023-3071; luma only, m_bChromaSa8d off), per
+ * N x N block (N = 8 << level), one launch:
+ *   sa8d = cu[].sa8d(fenc, predY), predY = Predict::predInterLumaPixel of the block's quarter-sample vector from fref (extended borders;
+ *          the vectors must keep N + 7 rows and columns inside the padded plane, as for x265hip_inter_recon)
+ *   bits = base_bits + (uint32_t)(bit_sizes[|qx|] + bit_sizes[|qy|] + 0.5f)     BitCost::bitcost against the predictor (0, 0), bitcost.h:48-52
+ *   cost = sa8d + ((bits * lambda8 + 128) >> 8)                                  calcRdSADCost, rdcost.h:148-153
+ * base_bits: m_listSelBits[0] of a P 2Nx2N + MVP_IDX_BITS + getTUBits(ref, nrefs) (search.cpp:2403-2404), in [0, 4096].  bit_sizes: DEVICE
+ * float32 [bit_sizes_len], BitCost::s_bitsizes[0 ..] (bitcost.cpp:105-108); a component whose magnitude is bit_sizes_len or more is priced
+ * with the LAST entry (clamped on the device) - size the table from the search range (4 * range + 4 entries cover every vector of it).
+ * mv: the records x265hip_inter_recon takes.  cost: DEVICE int32 [ctu][blocks][2] = { sa8d, cost }.  qp_map (the LUMA plane of tu_qp, int8
+ * [height/8][width/8]) and lambda8_by_qp (uint32 [52 + 6 (depth - 8)]) are optional: with lambda8_by_qp a block is priced with the entry
+ * of its luma quantiser QP (qp_map's, clamped, or `qp` without a map; entries above 2^24 count as 2^24), as in x265hip_intra_picture_qp.
+ * Refused (X265HIP_EINVAL, before any device call): NULL operands, depth not 8 / 10 / 12, level outside 0..2, sizes that are no
+ * multiples of 64, strides below the width, qp out of range, base_bits outside [0, 4096], lambda8 outside [0, 2^24], bit_sizes_len < 1. */
+typedef struct x265hip_inter_sa8d_cost_params
+{
+    int depth, width, height, level;
+    int qp;                                          /* luma quantiser QP: indexes lambda8_by_qp where there is no qp_map */
+    int base_bits, lambda8;
+    const void* fenc;  intptr_t fenc_stride;         /* sample (0,0) of the source luma plane */
+    const void* fref;  intptr_t fref_stride;         /* sample (0,0) of the reference luma plane */
+    const void* mv;
+    const float* bit_sizes; int bit_sizes_len;
+    int32_t* cost;
+    const int8_t* qp_map; const uint32_t* lambda8_by_qp;
+} x265hip_inter_sa8d_cost_params;
+int x265hip_inter_sa8d_cost(const x265hip_inter_sa8d_cost_params* p, void* stream);
+/* x265hip_intra_in_inter: the record, schedule (one launch per wave, capturable) and per-block work of x265hip_intra_picture_qp, for the
+ * blocks of a P slice.  Differences:
+ *   - recon / recon_cb / recon_cr hold the inter reconstruction of the picture on entry, levels / num_sig / dist (and the chroma twins)
+ *     the inter coding; a CTU's working tiles start from these planes
+ *   - a neighbouring sample is available by position and coding order alone, whatever its block's mode (no constrained intra prediction)
+ *   - the most probable modes take DC for a left / above block that is not intra (getIntraDirLumaPredictor tests isIntra)
+ *   - after the 35-mode scan the block is intra iff its cost < inter_cost[block * inter_cost_stride] (analysis.cpp:1664; a tie stays
+ *     inter).  Inter: intra[block] = 0, mode[block] = 1 (DC), nothing else of the block is touched.  Intra: intra[block] = 1, mode = the
+ *     winner, and the block's levels, num_sig, dist and reconstruction of Y / Cb / Cr are overwritten as x265hip_intra_picture codes them,
+ *     with the P slice's flags.  `cost` (optional) gets the INTRA candidate's { sad, cost } for every block.
+ * inter_cost: DEVICE int32, one word per block at a stride of inter_cost_stride words (x265hip_inter_sa8d_cost's array: pass cost + 1 and
+ * stride 2).  intra: DEVICE uint8 [ctu][blocks] - the `intra` of x265hip_deblock_bs_inter.  The argument checks of x265hip_intra_picture
+ * apply; also refused: NULL inter_cost / intra, inter_cost_stride < 1, X265HIP_TU_INTRA_SLICE in flags. */
+int x265hip_intra_in_inter(const x265hip_intra_picture_params* p, const int32_t* inter_cost, intptr_t inter_cost_stride, uint8_t* intra,
+                           const int8_t* qp_map, const uint32_t* lambda8_by_qp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

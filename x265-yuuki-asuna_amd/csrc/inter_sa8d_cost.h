@@ -1,0 +1,185 @@
+// inter_sa8d_cost.h - the inter candidate's sa8d cost per block of a P picture, on gfx950 (included at the end of tu_kernels.hip behind
+// intra_picture.h: it predicts with that file's luma taps and transforms with ip_hadamard8x8).
+//
+// Analysis::checkInter_rd0_4 at RD level <= 2 (source/encoder/analysis.cpp:3023-3071; m_bChromaSa8d is off, so luma only), per N x N block
+// (N = 8 << level) of the TU stages' grid:
+//   dist = cu[].sa8d(fenc, predY)           predY = Predict::predInterLumaPixel of the block's quarter-sample vector (predict.cpp:245-265)
+//   bits = base_bits + bitcost(mv)          bitcost.h:48-52 against the predictor (0, 0): (uint32_t)(s_bitsizes[x] + s_bitsizes[y] + 0.5f)
+//   cost = dist + ((bits * lambda8 + 128) >> 8)                                                       (calcRdSADCost, rdcost.h:148-153)
+// sa8d: 8x8 = (sum |H8 d| + 2) >> 2; a 16x16 unit sums its four 8x8 transforms and rounds once (sa8d_16x16, pixel.cpp:341-352); a 32x32
+// block is the sum of its four units.
+//
+// Mapping: one workgroup of 256 threads per 32x32 quarter of a CTU (16 / 4 / 1 blocks).  The blocks' reference patches go to LDS, the
+// prediction is formed like inter_recon_kernel's (horizontal pass into `immed` only where both phases are set), the difference to the
+// source lands in LDS, and 128 lanes run the sixteen 8x8 Hadamard transforms - rows in the lane, columns across eight lanes, the four
+// tiles of a 16x16 unit on 32 consecutive lanes.  Blocks are independent: one launch per picture, no atomics.
+#pragma once
+
+namespace x265hip {
+
+struct InterCostArgs
+{
+    const uint8_t* fenc; long fencStrideB;
+    const uint8_t* fref; long frefStrideB;
+    const int2* mv;                     // [ctu*85] {cost, qx | qy << 16}
+    const float* bitSizes; int bitSizesLen;
+    int ctusW, ctusH, depth, qp, baseBits, lambda8;
+    int2* cost;                         // [ctu][blocks] {sa8d, cost}
+    const int8_t* qpMap;                // optional: the luma plane of tu_qp, int8 [ctusH * 8][ctusW * 8]
+    const uint32_t* lambdaByQp;         // optional, indexed by the block's luma quantiser QP
+};
+
+template <typename Px, int N>
+__global__ void __launch_bounds__(256) inter_sa8d_cost_kernel(InterCostArgs a)
+{
+    constexpr int LOG2N = N == 8 ? 3 : (N == 16 ? 4 : 5), BPR = 32 / N, NB = BPR * BPR, BPC = 64 / N, NPU = BPC * BPC;
+    constexpr int APRON = 3, PW = N + 7, PP = PW + 1, BPP = sizeof(Px);
+    __shared__ int16_t patch[NB * PW * PP];
+    __shared__ int16_t immed[NB * PW * N];
+    __shared__ int16_t diff[32 * 32];
+    __shared__ int sMv[NB], sSum[16];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int ctu = (int)blockIdx.x >> 2, quarter = (int)blockIdx.x & 3;
+    const int cx = ctu % a.ctusW, cy = ctu / a.ctusW;
+    const int rx0 = cx * 64 + (quarter & 1) * 32, ry0 = cy * 64 + (quarter >> 1) * 32;         // the quarter's first luma sample
+    const int maxVal = (1 << a.depth) - 1, headRoom = 14 - a.depth;
+    const int lbase = N == 8 ? 0 : (N == 16 ? 64 : 80);
+    // block b of the quarter (raster order inside it) -> its z index inside the CTU
+    auto zof = [&](const int b) { return ip_zidx((quarter & 1) * BPR + (b & (BPR - 1)), (quarter >> 1) * BPR + (b / BPR)); };
+    if (tid < NB) sMv[tid] = a.mv[(size_t)ctu * 85 + lbase + zof(tid)].y;
+    __syncthreads();
+    const long rst = a.frefStrideB / BPP, fst = a.fencStrideB / BPP;
+    const Px* fref = reinterpret_cast<const Px*>(a.fref);
+    const Px* fenc = reinterpret_cast<const Px*>(a.fenc);
+    // ---- the blocks' reference patches: N + 7 rows and columns around the full-sample position ----------------------------------------
+    for (int i = tid; i < NB * PW * PW; i += 256)
+    {
+        const int b = i / (PW * PW), r = i - b * (PW * PW), y = r / PW, x = r - y * PW;
+        const int qx = (int16_t)(sMv[b] & 0xffff), qy = (int16_t)(sMv[b] >> 16);
+        const int px = rx0 + (b & (BPR - 1)) * N + (qx >> 2) - APRON + x, py = ry0 + (b / BPR) * N + (qy >> 2) - APRON + y;
+        patch[b * (PW * PP) + y * PP + x] = (int16_t)fref[(long)py * rst + px];
+    }
+    __syncthreads();
+    // ---- predInterLumaPixel: where both phases are set, the horizontal pass at 14-bit precision first ---------------------------------
+    for (int i = tid; i < NB * PW * N; i += 256)
+    {
+        const int b = i / (PW * N), r = i - b * (PW * N), y = r >> LOG2N, x = r & (N - 1);
+        const int xf = sMv[b] & 3, yf = (sMv[b] >> 16) & 3;
+        if (xf && yf)
+        {
+            const int shiftPS = 6 - headRoom, offPS = -(8192 << shiftPS);
+            int s = 0;
+#pragma unroll
+            for (int t = 0; t < 8; t++) s += (int)patch[b * (PW * PP) + y * PP + x + t] * (int)kTuTaps[xf][t];
+            immed[i] = (int16_t)((s + offPS) >> shiftPS);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < 32 * 32; i += 256)
+    {
+        const int ry = i >> 5, rx = i & 31, b = (ry >> LOG2N) * BPR + (rx >> LOG2N), y = ry & (N - 1), x = rx & (N - 1);
+        const int xf = sMv[b] & 3, yf = (sMv[b] >> 16) & 3;
+        const int16_t* pt = patch + b * (PW * PP);
+        int v;
+        if (xf && yf)
+        {
+            const int shiftSP = 6 + headRoom, offSP = (1 << (shiftSP - 1)) + (8192 << 6);
+            int s = 0;
+#pragma unroll
+            for (int t = 0; t < 8; t++) s += (int)immed[b * (PW * N) + (y + t) * N + x] * (int)kTuTaps[yf][t];
+            v = tu_clip16((s + offSP) >> shiftSP, maxVal);
+        }
+        else if (!(xf | yf)) v = pt[(y + APRON) * PP + x + APRON];
+        else
+        {
+            int s = 0;
+#pragma unroll
+            for (int t = 0; t < 8; t++) s += (int)(xf ? pt[(y + APRON) * PP + x + t] : pt[(y + t) * PP + x + APRON]) * (int)kTuTaps[xf ? xf : yf][t];
+            v = tu_clip16((s + 32) >> 6, maxVal);
+        }
+        diff[i] = (int16_t)((int)fenc[(long)(ry0 + ry) * fst + rx0 + rx] - v);
+    }
+    __syncthreads();
+    // ---- sixteen 8x8 Hadamard transforms on wavefronts 0 and 1: unit u = 16x16 (ux, uy), tile q inside it, row r -----------------------
+    if (tid < 128)
+    {
+        const int row = tid & 7, q = (tid >> 3) & 3, u = tid >> 5;
+        const int tx = (u & 1) * 2 + (q & 1), ty = (u >> 1) * 2 + (q >> 1);
+        int d[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) d[i] = diff[(ty * 8 + row) * 32 + tx * 8 + i];
+        int raw = ip_hadamard8x8(d, lane);
+        if (N == 8) { if (row == 0) sSum[ty * 4 + tx] = (raw + 2) >> 2; }                      // the block at (tx, ty) of the quarter
+        else
+        {
+            raw += __shfl_xor(raw, 8, 64); raw += __shfl_xor(raw, 16, 64);
+            if ((tid & 31) == 0) sSum[u] = (raw + 2) >> 2;
+        }
+    }
+    __syncthreads();
+    if (tid < NB)
+    {
+        const int b = tid;
+        int sad;
+        if (N == 8) sad = sSum[b];
+        else if (N == 16) sad = sSum[b];
+        else sad = sSum[0] + sSum[1] + sSum[2] + sSum[3];
+        const int qx = (int16_t)(sMv[b] & 0xffff), qy = (int16_t)(sMv[b] >> 16);
+        // a component beyond the table prices as the table's last entry
+        const int ix = min(abs(qx), a.bitSizesLen - 1), iy = min(abs(qy), a.bitSizesLen - 1);
+        const int bits = a.baseBits + (int)(uint32_t)(a.bitSizes[ix] + a.bitSizes[iy] + 0.5f);
+        int lambda8 = a.lambda8;
+        if (a.lambdaByQp)
+        {
+            int qp = a.qp;
+            if (a.qpMap)
+            {
+                const int gx8 = (rx0 + (b & (BPR - 1)) * N) >> 3, gy8 = (ry0 + (b / BPR) * N) >> 3;
+                qp = clip3(0, 51 + 6 * (a.depth - 8), (int)a.qpMap[(size_t)gy8 * (a.ctusW * 8) + gx8]);
+            }
+            const uint32_t l = a.lambdaByQp[qp];
+            lambda8 = (int)(l < (1u << 24) ? l : (1u << 24));
+        }
+        const long long cost = (long long)sad + (((long long)bits * lambda8 + 128) >> 8);
+        a.cost[(size_t)ctu * NPU + zof(b)] = make_int2(sad, (int)cost);
+    }
+}
+
+} // namespace x265hip
+
+extern "C" int x265hip_inter_sa8d_cost(const x265hip_inter_sa8d_cost_params* p, void* stream)
+{
+    using namespace x265hip;
+    // argument checks first: they need no device
+    if (!p || !p->fenc || !p->fref || !p->mv || !p->bit_sizes || !p->cost) { set_error("inter_sa8d_cost: NULL operand"); return X265HIP_EINVAL; }
+    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("inter_sa8d_cost: depth %d", p->depth); return X265HIP_EINVAL; }
+    if (p->level < 0 || p->level > 2) { set_error("inter_sa8d_cost: level %d (0..2 = 8x8, 16x16, 32x32)", p->level); return X265HIP_EINVAL; }
+    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("inter_sa8d_cost: width/height must be multiples of 64"); return X265HIP_EINVAL; }
+    if (p->fenc_stride < p->width || p->fref_stride < p->width) { set_error("inter_sa8d_cost: stride below the width"); return X265HIP_EINVAL; }
+    if (p->qp < 0 || p->qp > 51 + 6 * (p->depth - 8)) { set_error("inter_sa8d_cost: qp %d out of range", p->qp); return X265HIP_EINVAL; }
+    // base_bits <= 4096 (+ at most 2 * 33 bits of a vector) and lambda8 <= 2^24 keep the rate term below 2^29 and the cost inside int32
+    if (p->base_bits < 0 || p->base_bits > 4096) { set_error("inter_sa8d_cost: base_bits %d out of [0, 4096]", p->base_bits); return X265HIP_EINVAL; }
+    if (p->lambda8 < 0 || p->lambda8 > (1 << 24)) { set_error("inter_sa8d_cost: lambda8 %d out of [0, 2^24]", p->lambda8); return X265HIP_EINVAL; }
+    if (p->bit_sizes_len < 1) { set_error("inter_sa8d_cost: bit_sizes_len %d below 1", p->bit_sizes_len); return X265HIP_EINVAL; }
+    int rc = ensure_device();
+    if (rc) return rc;
+
+    const int bpp = p->depth == 8 ? 1 : 2;
+    InterCostArgs a = {};
+    a.fenc = (const uint8_t*)p->fenc; a.fencStrideB = (long)p->fenc_stride * bpp;
+    a.fref = (const uint8_t*)p->fref; a.frefStrideB = (long)p->fref_stride * bpp;
+    a.mv = (const int2*)p->mv; a.bitSizes = p->bit_sizes; a.bitSizesLen = p->bit_sizes_len;
+    a.ctusW = p->width / 64; a.ctusH = p->height / 64; a.depth = p->depth; a.qp = p->qp; a.baseBits = p->base_bits; a.lambda8 = p->lambda8;
+    a.cost = (int2*)p->cost; a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(a.ctusW * a.ctusH * 4);
+#define GO(PX) do { \
+    if (p->level == 0) hipLaunchKernelGGL((inter_sa8d_cost_kernel<PX, 8>), grid, dim3(256), 0, s, a); \
+    else if (p->level == 1) hipLaunchKernelGGL((inter_sa8d_cost_kernel<PX, 16>), grid, dim3(256), 0, s, a); \
+    else hipLaunchKernelGGL((inter_sa8d_cost_kernel<PX, 32>), grid, dim3(256), 0, s, a); } while (0)
+    if (p->depth == 8) GO(uint8_t); else GO(uint16_t);
+#undef GO
+    X265HIP_TRY(hipGetLastError());
+    return 0;
+}

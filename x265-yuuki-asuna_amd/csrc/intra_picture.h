@@ -26,6 +26,9 @@
 // lanes), the four tiles of a 16x16 unit sit on 32 consecutive lanes and are rounded once (sa8d_16x16, pixel.cpp:341-352).  Unit sums go
 // to LDS - one writer per slot - and 35 lanes of wavefront 0 form the costs and take the minimum of cost << 6 | scan position by
 // shuffles.  No atomics.
+//
+// x265hip_intra_in_inter is the same kernel body for the blocks of a P picture (Args = IntraInInterArgs): the tiles start as the inter
+// reconstruction, and a block is coded only where its intra cost is strictly below the inter candidate's (x265hip_inter_sa8d_cost).
 #pragma once
 
 namespace x265hip {
@@ -42,6 +45,16 @@ struct IntraPicArgs
     const int8_t* qpMap;                                  // optional int8 [3][ctusH * 8][ctusW * 8]: the quantiser QPs of Y, Cb, Cr per 8x8 cell of the luma grid
     const uint32_t* lambdaByQp;                           // optional, indexed by the block's luma quantiser QP
 };
+
+// x265hip_intra_in_inter: the same record plus the inter candidate's cost per block and the flags the choice leaves
+struct IntraInInterArgs
+{
+    IntraPicArgs a;
+    const int32_t* interCost; long interCostStride;       // inter_cost[blk * stride]: x265hip_inter_sa8d_cost's cost word
+    uint8_t* intra;                                       // [ctu][blocks]: 1 = the block is intra
+};
+__device__ __forceinline__ const IntraPicArgs& ip_args(const IntraPicArgs& a) { return a; }
+__device__ __forceinline__ const IntraPicArgs& ip_args(const IntraInInterArgs& r) { return r.a; }
 
 // z-order index of block (bx, by) of a CTU
 __device__ __forceinline__ int ip_zidx(int bx, int by)
@@ -105,9 +118,16 @@ __device__ __forceinline__ void ip_fill_neighbours(int16_t* nb, const Px* tile, 
     }
 }
 
-template <typename Px, int N>
-__global__ void __launch_bounds__(256) intra_picture_kernel(IntraPicArgs a, const int wave, const int cyLo)
+// Args = IntraPicArgs: an I picture.  Args = IntraInInterArgs (INP): the intra candidate of a P picture's blocks - the CTU's tiles start as
+// the inter reconstruction the inter TU stages left in the recon planes, and a block is coded only where its intra cost is strictly below
+// the inter candidate's (Analysis::compressInterCU_rd0_4, analysis.cpp:1664); a block that stays inter reads as DC to its neighbours' most
+// probable modes (getIntraDirLumaPredictor tests isIntra).  INP is a parameter of the kernel, as REFS is of inter_recon_kernel: the I
+// instances are compiled from the same body with the other flavour's statements discarded.
+template <typename Px, int N, class Args = IntraPicArgs>
+__global__ void __launch_bounds__(256) intra_picture_kernel(Args ra, const int wave, const int cyLo)
 {
+    constexpr bool INP = std::is_same<Args, IntraInInterArgs>::value;
+    const IntraPicArgs& a = ip_args(ra);
     constexpr int NN = N * N, LOG2N = N == 8 ? 3 : (N == 16 ? 4 : 5), NC = N / 2, BPC = 64 / N, NPU = BPC * BPC, BPP = sizeof(Px);
     constexpr int UNITS = N == 32 ? 4 : 1, TPU = N == 8 ? 1 : 4, ITEMS = 35 * UNITS * TPU * 8;
     __shared__ __attribute__((aligned(16))) Px tileY[64 * 64];
@@ -129,6 +149,19 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(IntraPicArgs a, cons
     opsC.init(lane);
     const Px* planeY = reinterpret_cast<const Px*>(a.recon[0] + (long)cyb * 64 * a.reconStrideB[0]) + cxb * 64;
     const long strideY = a.reconStrideB[0] / BPP;
+    if constexpr (INP)
+    {
+        // the CTU's tiles = its inter reconstruction: a block that stays inter keeps it, and later blocks predict from it
+        for (int i = tid; i < 64 * 64; i += nth) tileY[i] = planeY[(long)(i >> 6) * strideY + (i & 63)];
+        if (a.chroma)
+            for (int c = 0; c < 2; c++)
+            {
+                const Px* planeC = reinterpret_cast<const Px*>(a.recon[1 + c] + (long)cyb * 32 * a.reconStrideB[1 + c]) + cxb * 32;
+                const long strideC = a.reconStrideB[1 + c] / BPP;
+                for (int i = tid; i < 32 * 32; i += nth) tileC[c][i] = planeC[(long)(i >> 5) * strideC + (i & 31)];
+            }
+        __syncthreads();
+    }
 
     for (int z = 0; z < NPU; z++)
     {
@@ -252,6 +285,23 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(IntraPicArgs a, cons
             if (tid < 35 && key == best) { sBest[0] = mode; sBest[1] = sad; sBest[2] = (int)cost; }
         }
         __syncthreads();
+        if constexpr (INP)
+        {
+            // intra wins iff its cost is strictly lower; a block that stays inter keeps every output of the inter TU stages
+            const size_t blkP = (size_t)ctu * NPU + z;
+            if (!(sBest[2] < ra.interCost[blkP * ra.interCostStride]))
+            {
+                if (tid == 0)
+                {
+                    a.mode[blkP] = 1;
+                    sMode[z] = 1;
+                    ra.intra[blkP] = 0;
+                    if (a.cost) a.cost[blkP] = make_int2(sBest[1], sBest[2]);
+                }
+                __syncthreads();
+                continue;
+            }
+        }
         const int mode = sBest[0];
         {
             const int16_t* nbm = (mode != 1 && (kIsFilterFlags[mode] & N)) ? nbF : nbU;
@@ -272,6 +322,7 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(IntraPicArgs a, cons
                 a.mode[blk] = (uint8_t)mode;
                 sMode[z] = (uint8_t)mode;
                 if (a.cost) a.cost[blk] = make_int2(sBest[1], sBest[2]);
+                if constexpr (INP) ra.intra[blk] = 1;
             }
         }
         // ---- chroma (4:2:0): the luma mode, unfiltered neighbours of the plane's own reconstruction, no edge smoothing ---------------
@@ -324,34 +375,43 @@ extern "C" int x265hip_intra_picture_waves(int width, int height)
     return width / 64 + 2 * (height / 64 - 1);
 }
 
-extern "C" int x265hip_intra_picture_qp(const x265hip_intra_picture_params* p, const int8_t* qp_map, const uint32_t* lambda8_by_qp, void* stream)
+namespace x265hip {
+
+// The argument checks and the wave-by-wave launches of x265hip_intra_picture_qp and x265hip_intra_in_inter (inP: the P flavour, with its three operands).
+static int intra_picture_launch(const char* who, const x265hip_intra_picture_params* p, const int8_t* qp_map, const uint32_t* lambda8_by_qp,
+                                const int32_t* inter_cost, intptr_t inter_cost_stride, uint8_t* intra, const bool inP, void* stream)
 {
-    using namespace x265hip;
     // argument checks first: they need no device
-    if (!p || !p->fenc || !p->recon || !p->mode || !p->levels || !p->num_sig || !p->dist) { set_error("intra_picture: NULL operand"); return X265HIP_EINVAL; }
-    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("intra_picture: depth %d", p->depth); return X265HIP_EINVAL; }
-    if (p->level < 0 || p->level > 2) { set_error("intra_picture: level %d (0..2 = 8x8, 16x16, 32x32)", p->level); return X265HIP_EINVAL; }
-    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("intra_picture: width/height must be multiples of 64"); return X265HIP_EINVAL; }
+    if (!p || !p->fenc || !p->recon || !p->mode || !p->levels || !p->num_sig || !p->dist) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
+    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("%s: depth %d", who, p->depth); return X265HIP_EINVAL; }
+    if (p->level < 0 || p->level > 2) { set_error("%s: level %d (0..2 = 8x8, 16x16, 32x32)", who, p->level); return X265HIP_EINVAL; }
+    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("%s: width/height must be multiples of 64", who); return X265HIP_EINVAL; }
     const int qpMax = 51 + 6 * (p->depth - 8);
-    if (p->qp < 0 || p->qp > qpMax) { set_error("intra_picture: qp %d out of range", p->qp); return X265HIP_EINVAL; }
+    if (p->qp < 0 || p->qp > qpMax) { set_error("%s: qp %d out of range", who, p->qp); return X265HIP_EINVAL; }
     const bool chroma = p->fenc_cb || p->fenc_cr || p->recon_cb || p->recon_cr;
     if (chroma)
     {
         if (!p->fenc_cb || !p->fenc_cr || !p->recon_cb || !p->recon_cr || !p->levels_cb || !p->levels_cr || !p->num_sig_cb || !p->num_sig_cr || !p->dist_cb || !p->dist_cr)
-        { set_error("intra_picture: the chroma planes and outputs of Cb and Cr are needed together"); return X265HIP_EINVAL; }
-        if (p->qp_cb < 0 || p->qp_cb > qpMax || p->qp_cr < 0 || p->qp_cr > qpMax) { set_error("intra_picture: chroma qp %d / %d out of range", p->qp_cb, p->qp_cr); return X265HIP_EINVAL; }
+        { set_error("%s: the chroma planes and outputs of Cb and Cr are needed together", who); return X265HIP_EINVAL; }
+        if (p->qp_cb < 0 || p->qp_cb > qpMax || p->qp_cr < 0 || p->qp_cr > qpMax) { set_error("%s: chroma qp %d / %d out of range", who, p->qp_cb, p->qp_cr); return X265HIP_EINVAL; }
     }
     // bits <= 4096 and lambda8 <= 2^24 keep (bits * lambda8 + 128) >> 8 below 2^28; the largest sa8d of a 32x32 block of 12-bit samples is below 2^27:
     // the winning cost fits the int32 of `cost`
-    if (p->lambda8 < 0 || p->lambda8 > (1 << 24)) { set_error("intra_picture: lambda8 %d out of [0, 2^24]", p->lambda8); return X265HIP_EINVAL; }
-    if (p->flags & ~(TU_FLAG_INTRA_SLICE | TU_FLAG_SIGN_HIDE)) { set_error("intra_picture: unknown flag bits 0x%x", p->flags); return X265HIP_EINVAL; }
-    if (p->fenc_stride < p->width || p->recon_stride < p->width) { set_error("intra_picture: luma stride below the width"); return X265HIP_EINVAL; }
-    if (chroma && (p->fenc_stride_c < p->width / 2 || p->recon_stride_c < p->width / 2)) { set_error("intra_picture: chroma stride below half the width"); return X265HIP_EINVAL; }
+    if (p->lambda8 < 0 || p->lambda8 > (1 << 24)) { set_error("%s: lambda8 %d out of [0, 2^24]", who, p->lambda8); return X265HIP_EINVAL; }
+    if (inP)
+    {
+        if (!inter_cost || !intra) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
+        if (inter_cost_stride < 1) { set_error("%s: inter_cost_stride %ld below 1", who, (long)inter_cost_stride); return X265HIP_EINVAL; }
+        if (p->flags & TU_FLAG_INTRA_SLICE) { set_error("%s: X265HIP_TU_INTRA_SLICE in the flags of a P slice", who); return X265HIP_EINVAL; }
+    }
+    if (p->flags & ~(TU_FLAG_INTRA_SLICE | TU_FLAG_SIGN_HIDE)) { set_error("%s: unknown flag bits 0x%x", who, p->flags); return X265HIP_EINVAL; }
+    if (p->fenc_stride < p->width || p->recon_stride < p->width) { set_error("%s: luma stride below the width", who); return X265HIP_EINVAL; }
+    if (chroma && (p->fenc_stride_c < p->width / 2 || p->recon_stride_c < p->width / 2)) { set_error("%s: chroma stride below half the width", who); return X265HIP_EINVAL; }
     for (int i = 0; i < 3; i++)
-        if (p->mode_bits[i] < 0 || p->mode_bits[i] > 4096) { set_error("intra_picture: mode_bits[%d] = %d out of [0, 4096]", i, p->mode_bits[i]); return X265HIP_EINVAL; }
+        if (p->mode_bits[i] < 0 || p->mode_bits[i] > 4096) { set_error("%s: mode_bits[%d] = %d out of [0, 4096]", who, i, p->mode_bits[i]); return X265HIP_EINVAL; }
     if (p->fenc == p->recon || (chroma && (p->fenc_cb == p->recon_cb || p->fenc_cr == p->recon_cr || p->recon_cb == p->recon_cr)))
-    { set_error("intra_picture: the recon planes must not alias the source planes or each other"); return X265HIP_EINVAL; }
-    if (p->tables) { set_error("intra_picture: tables are not supported by this stage (pass NULL)"); return X265HIP_EINVAL; }
+    { set_error("%s: the recon planes must not alias the source planes or each other", who); return X265HIP_EINVAL; }
+    if (p->tables) { set_error("%s: tables are not supported by this stage (pass NULL)", who); return X265HIP_EINVAL; }
     int rc = ensure_device();
     if (rc) return rc;
 
@@ -375,6 +435,7 @@ extern "C" int x265hip_intra_picture_qp(const x265hip_intra_picture_params* p, c
     for (int i = 0; i < 3; i++) a.modeBits[i] = p->mode_bits[i];
     a.mode = p->mode; a.cost = (int2*)p->cost;
     a.qpMap = qp_map; a.lambdaByQp = lambda8_by_qp;
+    IntraInInterArgs ia = { a, inter_cost, (long)inter_cost_stride, intra };
     hipStream_t s = (hipStream_t)stream;
     const int waves = a.ctusW + 2 * (a.ctusH - 1);
     for (int w = 0; w < waves; w++)
@@ -384,15 +445,29 @@ extern "C" int x265hip_intra_picture_qp(const x265hip_intra_picture_params* p, c
         const int cyLo = over > 0 ? (over + 1) / 2 : 0, cyHi = w / 2 < a.ctusH - 1 ? w / 2 : a.ctusH - 1;
         const int n = cyHi - cyLo + 1;
         if (n <= 0) continue;                  // a picture one CTU wide has no CTU in its odd waves
-#define GOP(PX) do { \
-        if (p->level == 0) hipLaunchKernelGGL((intra_picture_kernel<PX, 8>), dim3(n), dim3(256), 0, s, a, w, cyLo); \
-        else if (p->level == 1) hipLaunchKernelGGL((intra_picture_kernel<PX, 16>), dim3(n), dim3(256), 0, s, a, w, cyLo); \
-        else hipLaunchKernelGGL((intra_picture_kernel<PX, 32>), dim3(n), dim3(256), 0, s, a, w, cyLo); } while (0)
-        if (p->depth == 8) GOP(uint8_t); else GOP(uint16_t);
+#define GOP(PX, ARGS, REC) do { \
+        if (p->level == 0) hipLaunchKernelGGL((intra_picture_kernel<PX, 8, ARGS>), dim3(n), dim3(256), 0, s, REC, w, cyLo); \
+        else if (p->level == 1) hipLaunchKernelGGL((intra_picture_kernel<PX, 16, ARGS>), dim3(n), dim3(256), 0, s, REC, w, cyLo); \
+        else hipLaunchKernelGGL((intra_picture_kernel<PX, 32, ARGS>), dim3(n), dim3(256), 0, s, REC, w, cyLo); } while (0)
+        if (inP) { if (p->depth == 8) GOP(uint8_t, IntraInInterArgs, ia); else GOP(uint16_t, IntraInInterArgs, ia); }
+        else if (p->depth == 8) GOP(uint8_t, IntraPicArgs, a); else GOP(uint16_t, IntraPicArgs, a);
 #undef GOP
     }
     X265HIP_TRY(hipGetLastError());
     return 0;
+}
+
+} // namespace x265hip
+
+extern "C" int x265hip_intra_picture_qp(const x265hip_intra_picture_params* p, const int8_t* qp_map, const uint32_t* lambda8_by_qp, void* stream)
+{
+    return x265hip::intra_picture_launch("intra_picture", p, qp_map, lambda8_by_qp, nullptr, 0, nullptr, false, stream);
+}
+
+extern "C" int x265hip_intra_in_inter(const x265hip_intra_picture_params* p, const int32_t* inter_cost, intptr_t inter_cost_stride, uint8_t* intra,
+                                      const int8_t* qp_map, const uint32_t* lambda8_by_qp, void* stream)
+{
+    return x265hip::intra_picture_launch("intra_in_inter", p, qp_map, lambda8_by_qp, inter_cost, inter_cost_stride, intra, true, stream);
 }
 
 extern "C" int x265hip_intra_picture(const x265hip_intra_picture_params* p, void* stream) { return x265hip_intra_picture_qp(p, nullptr, nullptr, stream); }

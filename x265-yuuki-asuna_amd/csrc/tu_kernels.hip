@@ -1440,3 +1440,6 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
 
 // the I-picture stage (x265hip_intra_picture): its kernel codes blocks with tu_chain / TuOpsFor above
 #include "intra_picture.h"
+
+// the inter candidate's sa8d cost of a P picture's blocks (x265hip_inter_sa8d_cost): kTuTaps above, ip_hadamard8x8 of intra_picture.h
+#include "inter_sa8d_cost.h"

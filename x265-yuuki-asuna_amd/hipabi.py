@@ -174,6 +174,20 @@ class IntraPictureParams(ctypes.Structure):
     ]
 
 
+class InterSa8dCostParams(ctypes.Structure):
+    """x265hip_inter_sa8d_cost_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("qp", ctypes.c_int), ("base_bits", ctypes.c_int), ("lambda8", ctypes.c_int),
+        ("fenc", ctypes.c_void_p), ("fenc_stride", ctypes.c_ssize_t),
+        ("fref", ctypes.c_void_p), ("fref_stride", ctypes.c_ssize_t),
+        ("mv", ctypes.c_void_p),
+        ("bit_sizes", ctypes.c_void_p), ("bit_sizes_len", ctypes.c_int),
+        ("cost", ctypes.c_void_p),
+        ("qp_map", ctypes.c_void_p), ("lambda8_by_qp", ctypes.c_void_p),
+    ]
+
+
 class LowresInitParams(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_int), ("src", ctypes.c_void_p), ("src_stride", ctypes.c_ssize_t),
                 ("plane", ctypes.c_void_p * 4), ("stride", ctypes.c_ssize_t),
@@ -551,6 +565,22 @@ def intra_picture(depth, width, height, level, qp, flags, lambda8, mode_bits, fe
     row and sample (0,0) at element `org`, qp (Cb, Cr) and per plane levels / num_sig / dist tensors.  qp_map: device int8 tensor, the
     whole tu_qp of cu_qp_maps (3 planes); lambda8_by_qp: device int32 tensor (uint32 bits) indexed by the luma quantiser QP - with either
     the call goes to x265hip_intra_picture_qp."""
+    p = _intra_picture_params(depth, width, height, level, qp, flags, lambda8, mode_bits, fenc, fenc_stride, fenc_off, recon, mode, levels, num_sig, dist,
+                              chroma, cost, strong_intra_smoothing)
+    s = current_stream() if stream is None else stream
+    if qp_map is not None or lambda8_by_qp is not None:
+        f = lib().x265hip_intra_picture_qp
+        f.argtypes = [ctypes.POINTER(IntraPictureParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        check(f(ctypes.byref(p), _p(qp_map), _p(lambda8_by_qp), s), "x265hip_intra_picture_qp")
+        return
+    f = lib().x265hip_intra_picture
+    f.argtypes = [ctypes.POINTER(IntraPictureParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_intra_picture")
+
+
+def _intra_picture_params(depth, width, height, level, qp, flags, lambda8, mode_bits, fenc, fenc_stride, fenc_off, recon, mode, levels, num_sig, dist,
+                          chroma, cost, strong_intra_smoothing):
+    """The record of intra_picture / intra_in_inter from their arguments."""
     es = 1 if depth == 8 else 2
     p = IntraPictureParams()
     p.depth, p.width, p.height, p.level, p.qp, p.flags = depth, width, height, level, qp, flags
@@ -567,15 +597,53 @@ def intra_picture(depth, width, height, level, qp, flags, lambda8, mode_bits, fe
         p.levels_cb, p.levels_cr = (t.data_ptr() for t in chroma["levels"])
         p.num_sig_cb, p.num_sig_cr = (t.data_ptr() for t in chroma["num_sig"])
         p.dist_cb, p.dist_cr = (t.data_ptr() for t in chroma["dist"])
+    return p
+
+
+def intra_in_inter(depth, width, height, level, qp, flags, lambda8, mode_bits, fenc, fenc_stride, fenc_off, recon, mode, levels, num_sig, dist,
+                   inter_cost, intra, inter_cost_stride=2, inter_cost_offset=1, chroma=None, cost=None, strong_intra_smoothing=True, stream=None,
+                   qp_map=None, lambda8_by_qp=None):
+    """x265hip_intra_in_inter: the intra candidates of a P picture's blocks against inter_cost, the winners recoded in place (see
+    intra_picture for the shared arguments; flags are the P slice's, without TU_INTRA_SLICE).  recon (and chroma["recon"]) and the
+    levels / num_sig / dist tensors hold the inter coding on entry.  inter_cost: device int32 tensor, the block's word at element
+    inter_cost_offset + block * inter_cost_stride (the defaults read the cost word of inter_sa8d_cost's pairs); intra: device uint8
+    [ctu][blocks] out."""
+    p = _intra_picture_params(depth, width, height, level, qp, flags, lambda8, mode_bits, fenc, fenc_stride, fenc_off, recon, mode, levels, num_sig, dist,
+                              chroma, cost, strong_intra_smoothing)
     s = current_stream() if stream is None else stream
-    if qp_map is not None or lambda8_by_qp is not None:
-        f = lib().x265hip_intra_picture_qp
-        f.argtypes = [ctypes.POINTER(IntraPictureParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        check(f(ctypes.byref(p), _p(qp_map), _p(lambda8_by_qp), s), "x265hip_intra_picture_qp")
-        return
-    f = lib().x265hip_intra_picture
-    f.argtypes = [ctypes.POINTER(IntraPictureParams), ctypes.c_void_p]
-    check(f(ctypes.byref(p), s), "x265hip_intra_picture")
+    f = lib().x265hip_intra_in_inter
+    f.argtypes = [ctypes.POINTER(IntraPictureParams), ctypes.c_void_p, ctypes.c_ssize_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    check(f(ctypes.byref(p), inter_cost.data_ptr() + 4 * int(inter_cost_offset), int(inter_cost_stride), intra.data_ptr(), _p(qp_map), _p(lambda8_by_qp), s),
+          "x265hip_intra_in_inter")
+
+
+def mv_bit_sizes(length):
+    """BitCost::s_bitsizes[0 .. length - 1] (bitcost.cpp:105-108) in float32: entry i = the bits of a vector component of magnitude i quarter
+    samples - log((float)(i + 1)) * (2.0f / log(2.0f)) + 1.718f, every step rounded to float32 as frames.mv_cost_table rounds its bits (the
+    two give the same uint16 costs).  4 * range + 4 entries cover every vector of a search range."""
+    import numpy as np
+    i = np.arange(int(length), dtype=np.float32)
+    log2_2 = np.float32(2.0) / np.log(np.float32(2.0))
+    bits = (np.log(i + np.float32(1.0)) * log2_2 + np.float32(1.718)).astype(np.float32)
+    bits[0] = np.float32(0.718)
+    return bits
+
+
+def inter_sa8d_cost(depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, base_bits, lambda8, bit_sizes, cost,
+                    qp=0, qp_map=None, lambda8_by_qp=None, stream=None):
+    """x265hip_inter_sa8d_cost: per block the sa8d of the luma prediction at its vector and cost = sa8d + rate (checkInter_rd0_4).  bit_sizes:
+    device float32 tensor (mv_bit_sizes); cost: device int32 [ctu][blocks][2] out; qp_map: the LUMA plane of tu_qp."""
+    es = 1 if depth == 8 else 2
+    p = InterSa8dCostParams()
+    p.depth, p.width, p.height, p.level, p.qp, p.base_bits, p.lambda8 = depth, width, height, level, int(qp), int(base_bits), int(lambda8)
+    p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
+    p.fref, p.fref_stride = fref.data_ptr() + fref_off * es, fref_stride
+    p.mv, p.bit_sizes, p.bit_sizes_len, p.cost = mv.data_ptr(), bit_sizes.data_ptr(), int(bit_sizes.numel()), cost.data_ptr()
+    p.qp_map, p.lambda8_by_qp = _p(qp_map), _p(lambda8_by_qp)
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_inter_sa8d_cost
+    f.argtypes = [ctypes.POINTER(InterSa8dCostParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_inter_sa8d_cost")
 
 
 def lowres_init(depth, src, src_stride, src_off, planes, stride, org, width, lines, margin_x, margin_y, stream=None):

@@ -374,8 +374,9 @@ class Deblock:
         """The luma edge filter with the boundary strengths a run* method has just left."""
         hipabi.deblock_luma(self.depth, plane, pic.stride, pic.org, self.w64, self.h64, self.bs_ver, self.bs_hor, self.qp, qp_map=self.qp_map)
 
-    def run(self, plane, pic: DevicePicture, mv, num_sig):
-        hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv, num_sig, self.bs_ver, self.bs_hor)
+    def run(self, plane, pic: DevicePicture, mv, num_sig, intra=None):
+        """intra: optional device uint8 [ctu][blocks] (IntraInInter.intra) - the edges of its non-zero blocks get Bs 2 (deblock.cpp:198-199)."""
+        hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv, num_sig, self.bs_ver, self.bs_hor, intra=intra)
         self._luma(plane, pic)
 
     def run_b(self, plane, pic: DevicePicture, mv0, mv1, ref0, ref1, num_sig):
@@ -1823,6 +1824,140 @@ class IFramePipeline(_PictureStep):
     def checksum(self):
         import torch
         out = self.ip.checksum()
+        out["recon"] = int(self.final.to(torch.int64).sum().item())
+        return out
+
+
+class InterSa8dCost:
+    """The inter candidate's cost per block of a P picture (x265hip_inter_sa8d_cost; reference Analysis::checkInter_rd0_4 at RD level <= 2,
+    analysis.cpp:3023-3071): sa8d of the luma prediction at the block's vector + the rate of base_bits and the vector.  Owns cost int32
+    [ctu][blocks][2] = {sa8d, cost} and the float bit-size table (BitCost::s_bitsizes) sized from the search range."""
+
+    def __init__(self, nctu, w64, h64, depth, level, device, rng=57, base_bits=2, lambda8=1024, qp=0):
+        """base_bits: m_listSelBits[0] of a P 2Nx2N + MVP_IDX_BITS + getTUBits(0, 1) = hipabi.ref_cost_bits(1, lam=1)[0] = 2 for one
+        reference.  rng: the search range in full samples; a longer vector is priced with the table's last entry."""
+        import torch
+        self.nctu, self.w64, self.h64, self.depth, self.level, self.qp = nctu, w64, h64, depth, level, qp
+        self.base_bits, self.lambda8 = int(base_bits), int(lambda8)
+        self.nblk = (64 >> (3 + level)) ** 2
+        self.cost = torch.zeros(nctu * self.nblk * 2, dtype=torch.int32, device=device)
+        self.bit_sizes = torch.from_numpy(hipabi.mv_bit_sizes(4 * int(rng) + 4)).to(device)
+        # per-block lambda: qp_map = the LUMA plane of CuQpMaps.tu_qp, lambda8_by_qp = device int32 [52 + 6 (depth - 8)] (None = lambda8)
+        self.qp_map, self.lambda8_by_qp = None, None
+
+    def run(self, cur: DevicePicture, ref: DevicePicture, mv, stream=None):
+        hipabi.inter_sa8d_cost(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, cur.org, ref.t, ref.stride, ref.org, mv, self.base_bits,
+                               self.lambda8, self.bit_sizes, self.cost, qp=self.qp, qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+
+    def checksum(self):
+        import torch
+        return {"inter_cost": int(self.cost.to(torch.int64).sum().item())}
+
+
+class IntraInInter:
+    """The intra candidates of a P picture's blocks (x265hip_intra_in_inter; reference Search::checkIntraInInter and the choice of
+    Analysis::compressInterCU_rd0_4, analysis.cpp:1649-1671): per block, in coding order, the 35-mode sa8d decision from the reconstruction
+    around it; where the intra cost is strictly below the inter candidate's the block is recoded as intra IN the inter stages' outputs.
+    Owns mode uint8 and intra uint8 [ctu][blocks] (and, with want_cost, the intra candidates' cost int32 [ctu][blocks][2]); levels /
+    num_sig / dist and the recon planes belong to the inter TU stages it is run behind."""
+
+    def __init__(self, nctu, w64, h64, depth, level, qp, device, flags=0, chroma=False, qp_c=None, lambda8=1024, mode_bits=(2, 3, 6),
+                 strong_intra_smoothing=True, want_cost=False):
+        import torch
+        if flags & hipabi.TU_INTRA_SLICE:
+            raise ValueError("IntraInInter: TU_INTRA_SLICE in the flags of a P slice")
+        self.nctu, self.w64, self.h64, self.depth, self.level, self.qp, self.flags = nctu, w64, h64, depth, level, qp, flags
+        self.chroma, self.qp_c = chroma, (qp_c if qp_c is not None else (qp, qp))
+        self.lambda8, self.mode_bits, self.strong = int(lambda8), tuple(int(b) for b in mode_bits), bool(strong_intra_smoothing)
+        self.n = 8 << level
+        self.nblk = (64 // self.n) ** 2
+        self.waves = hipabi.intra_picture_waves(w64, h64)
+        nb = nctu * self.nblk
+        self.mode = torch.zeros(nb, dtype=torch.uint8, device=device)
+        self.intra = torch.zeros(nb, dtype=torch.uint8, device=device)
+        self.cost = torch.zeros(nb * 2, dtype=torch.int32, device=device) if want_cost else None
+        self.qp_map, self.lambda8_by_qp = None, None          # as IntraPicture's
+
+    def run(self, cur: DevicePicture, recon_plane, rc, inter_cost, recon_c=None, rc_c=None, stream=None):
+        """recon_plane (and recon_c = [Cb, Cr]): the inter reconstruction, rc (and rc_c = [Cb, Cr]): the inter TU stages whose levels / num_sig /
+        dist the intra winners overwrite; inter_cost: InterSa8dCost.cost (the pairs)."""
+        ch = None
+        if self.chroma:
+            ch = dict(fenc=cur.c, recon=recon_c, stride=cur.stride_c, org=cur.org_c, qp=self.qp_c, levels=[r.levels for r in rc_c],
+                      num_sig=[r.num_sig for r in rc_c], dist=[r.dist for r in rc_c])
+        hipabi.intra_in_inter(self.depth, self.w64, self.h64, self.level, self.qp, self.flags, self.lambda8, self.mode_bits, cur.t, cur.stride, cur.org,
+                              recon_plane, self.mode, rc.levels, rc.num_sig, rc.dist, inter_cost, self.intra, chroma=ch, cost=self.cost,
+                              strong_intra_smoothing=self.strong, stream=stream, qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp)
+
+    def checksum(self):
+        import torch
+        return {"mode": int(self.mode.to(torch.int64).sum().item()), "intra": int(self.intra.to(torch.int64).sum().item())}
+
+
+class IntraPFramePipeline(_PictureStep):
+    """One P picture whose blocks may be intra: search -> sub-pel refinement -> inter TU stage (luma + chroma) -> InterSa8dCost ->
+    IntraInInter -> boundary strengths with the intra flags + luma / chroma deblocking -> the shared loop-filter tail.  Inter
+    reconstruction does not depend on neighbours, so coding every block as inter first and overwriting the intra winners in coding order
+    is the reference's result.  run(cur, ref) / final_planes() as FramePipeline's: MiniGop(p_step=...) takes it.
+    The constructor switches mean what they mean in BFramePipeline / IFramePipeline; base_bits: see InterSa8dCost."""
+
+    def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
+                 sign_hide=False, sao_rdo=None, lambda8=1024, mode_bits=(2, 3, 6), strong_intra_smoothing=True, base_bits=2):
+        from .pipeline import MotionSearch, SubpelRefine
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
+        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
+        self.ms = MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True)
+        self.sp = SubpelRefine(self.ms, subme, device)
+        self.rc = InterRecon(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        qpc = chroma_quant_qp(qp, depth)
+        if chroma:
+            self.rc_c = [InterReconChroma(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
+        self.ic = InterSa8dCost(self.nctu, w64, h64, depth, level, device, rng=rng, base_bits=base_bits, lambda8=lambda8, qp=qp)
+        self.ii = IntraInInter(self.nctu, w64, h64, depth, level, qp, device, flags=self.tu_flags, chroma=chroma, qp_c=(qpc, qpc), lambda8=lambda8,
+                               mode_bits=mode_bits, strong_intra_smoothing=strong_intra_smoothing)
+
+    def set_qp_maps(self, maps, lambda8_by_qp=None):
+        """Per-block QPs for the following run() calls (see FramePipeline.set_qp_maps); None = the picture-wide qp again.  lambda8_by_qp: device
+        int32 tensor [52 + 6 (depth - 8)] - 256 x lambda of a CU per luma quantiser QP, for both candidates' rate terms - or None = the
+        constructor's lambda8 for every block."""
+        self._set_qp_maps(maps, self.rc, self.rc_c if self.chroma else [])
+        self.ii.qp_map = None if maps is None else maps.tu_qp
+        self.ic.qp_map = None if maps is None else maps.tu_qp[0]
+        self.ii.lambda8_by_qp = self.ic.lambda8_by_qp = None if maps is None else lambda8_by_qp
+
+    def run(self, cur: DevicePicture, ref: DevicePicture, mark=None):
+        """ref: the reference picture (extended borders, with chroma its Cb / Cr planes); returns the luma plane of the coded picture.
+        mark(name), if given, is called after every stage."""
+        mark = mark or (lambda name: None)
+        self._qp_maps_run_check()
+        self._alloc_planes(cur)
+        self.ms.reset()
+        self.ms.search(cur, ref)
+        mark("me")
+        self.sp.run(cur, ref)
+        mv = self.sp.out
+        mark("subpel")
+        self.rc.run(cur, ref, self.recon, mv)
+        mark("recon")
+        if self.chroma:
+            InterReconChroma.run_pair(self.rc_c, cur.c, ref.c, self.recon_c, cur.stride_c, cur.org_c, mv)
+            mark("recon_chroma")
+        self.ic.run(cur, ref, mv)
+        mark("inter_cost")
+        self.ii.run(cur, self.recon, self.rc, self.ic.cost, self.recon_c, self.rc_c if self.chroma else None)
+        mark("intra")
+        if self.db is not None:
+            self.db.run(self.recon, cur, mv, self.rc.num_sig, intra=self.ii.intra)
+        return self._filter_tail(cur, mark)
+
+    def checksum(self):
+        import torch
+        out = {}
+        out.update(self.ms.checksum())
+        out.update(self.sp.checksum())
+        out.update(self.ic.checksum())
+        out.update(self.ii.checksum())
+        out.update(self.rc.checksum())
         out["recon"] = int(self.final.to(torch.int64).sum().item())
         return out
 

@@ -1782,6 +1782,54 @@ int x265hip_inter_sa8d_cost(const x265hip_inter_sa8d_cost_params* p, void* strea
 int x265hip_intra_in_inter(const x265hip_intra_picture_params* p, const int32_t* inter_cost, intptr_t inter_cost_stride, uint8_t* intra,
                            const int8_t* qp_map, const uint32_t* lambda8_by_qp, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The sa8d choice of a B picture's blocks (csrc/b_sa8d_decide.h).  Every block of the TU stages' grid is one 2Nx2N CU, and for that case
+ * the reference takes the bidirectional decision in Analysis::compressInterCU_rd0_4 (RD level <= 2, analysis.cpp:1649-1671), not in
+ * Search::predInterSearch (its guard at search.cpp:2479 skips 2Nx2N; x265hip_bidir_decide restates that skipped arm):
+ *     l   = c0 <= c1 ? 0 : 1,  c_l = rec_l.cost + dir_cost[l]         the list predInterSearch leaves, list 0 on a tie (search.cpp:2611)
+ *     b_l = base_bits[l] + bitcost(mv_l)                             bitcost = (uint32_t)(bit_sizes[|qx|] + bit_sizes[|qy|] + 0.5f)
+ *     uni = sa8d(fenc, predInterLumaPixel(fref_l, mv_l)) + getCost(b_l)                       checkInter_rd0_4, analysis.cpp:3059-3071
+ *     bi  = sa8d(fenc, addAvg(predInterLumaShort(fref0, mv0), predInterLumaShort(fref1, mv1))) + getCost(b_0 + b_1 + bi_bits_delta)
+ *                                                                       checkBidir2Nx2N, analysis.cpp:3180-3198; predict.cpp:411-456
+ *     if (mv0 != 0 || mv1 != 0) { z = sa8d(fenc, pixelavg_pp(fref0[block], fref1[block]))
+ *                                     + getCost(base_bits[0] + base_bits[1] + 2 * bitcost(0) + bi_bits_delta);
+ *                                 if (z < bi) bi = z, mv0 = mv1 = 0; }                                    analysis.cpp:3200-3269
+ *     dir = bi < uni ? 3 : 1 + l                                        a tie keeps the single list, analysis.cpp:1653-1655
+ * getCost(bits) = (bits * lambda8 + 128) >> 8; sa8d, bit_sizes (clamped to the last entry), qp / qp_map / lambda8_by_qp are those of
+ * x265hip_inter_sa8d_cost.  Luma only (m_bChromaSa8d is off at RD level <= 2), no weights, one reference per list, predictor (0,0) for
+ * both lists: the range check of the zero candidate always passes and checkBestMVP has one candidate.
+ *   base_bits[l]  : m_listSelBits[l] + MVP_IDX_BITS + getTUBits(ref, nrefs) (search.cpp:2403-2404): 4 and 4 for one reference per list
+ *   bi_bits_delta : m_listSelBits[2] - m_listSelBits[0] - m_listSelBits[1] (analysis.cpp:3197): -1 for (3, 3, 5)
+ *   mv0 / mv1, dir_cost[0..1], fref0 / fref1, ref_id0 / ref_id1 : as x265hip_bidir_params takes them (dir_cost[2] is not read)
+ *   dir, ref0 / ref1, mv0_out / mv1_out : the shapes and conventions of x265hip_bidir_decide's - a used list gets { the winning sa8d
+ *                   cost, final vector } (zero where the zero pair won), an unused list { its own c_l, 0 } and ref -1
+ *   cost          : DEVICE int32 [ctu][blocks][4] = { the winner's cost (min(uni, bi)), uni, bi after the zero candidate, flags: bit 0 = l,
+ *                   bit 1 = the zero pair replaced the searched vectors, bit 2 = the zero pair was tried }.  Word 0 is what
+ *                   x265hip_intra_in_inter decides against (inter_cost = cost, inter_cost_stride = 4).
+ * Refused (X265HIP_EINVAL, before any device call): NULL operands (ref0 / ref1 / qp_map / lambda8_by_qp are optional), depth not 8 / 10 /
+ * 12, level outside 0..2, sizes that are no multiples of 64, strides below the width, qp out of range, base_bits[l] outside [0, 4096],
+ * bi_bits_delta outside [-4096, 4096] or below -(base_bits[0] + base_bits[1]), lambda8 outside [0, 2^24], bit_sizes_len < 1, mv0_out /
+ * mv1_out overlapping mv0 / mv1 or each other. */
+typedef struct x265hip_b_sa8d_params
+{
+    int depth, width, height, level;
+    int qp;                                          /* luma quantiser QP: indexes lambda8_by_qp where there is no qp_map */
+    int lambda8;
+    int32_t base_bits[2]; int32_t bi_bits_delta;
+    int32_t dir_cost[3];
+    int ref_id0, ref_id1;
+    const void* fenc;  intptr_t fenc_stride;         /* sample (0,0) of the source luma plane */
+    const void* fref0; const void* fref1; intptr_t fref_stride;
+    const int32_t* mv0; const int32_t* mv1;          /* [ctu*85][2] records of the two refinements */
+    const float* bit_sizes; int bit_sizes_len;
+    uint8_t* dir;                                    /* [ctu][blocks]: 1 / 2 / 3 */
+    int8_t* ref0; int8_t* ref1;                      /* optional [ctu][blocks]: ref_id or -1 */
+    int32_t* mv0_out; int32_t* mv1_out;              /* [ctu*85][2] */
+    int32_t* cost;
+    const int8_t* qp_map; const uint32_t* lambda8_by_qp;
+} x265hip_b_sa8d_params;
+int x265hip_b_sa8d_decide(const x265hip_b_sa8d_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

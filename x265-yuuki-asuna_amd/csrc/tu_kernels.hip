@@ -1443,3 +1443,6 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
 
 // the inter candidate's sa8d cost of a P picture's blocks (x265hip_inter_sa8d_cost): kTuTaps above, ip_hadamard8x8 of intra_picture.h
 #include "inter_sa8d_cost.h"
+
+// the sa8d choice of a B picture's blocks between one list and both (x265hip_b_sa8d_decide): the geometry of inter_sa8d_cost.h
+#include "b_sa8d_decide.h"

@@ -188,6 +188,24 @@ class InterSa8dCostParams(ctypes.Structure):
     ]
 
 
+class BSa8dParams(ctypes.Structure):
+    """x265hip_b_sa8d_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("qp", ctypes.c_int), ("lambda8", ctypes.c_int),
+        ("base_bits", ctypes.c_int32 * 2), ("bi_bits_delta", ctypes.c_int32),
+        ("dir_cost", ctypes.c_int32 * 3),
+        ("ref_id0", ctypes.c_int), ("ref_id1", ctypes.c_int),
+        ("fenc", ctypes.c_void_p), ("fenc_stride", ctypes.c_ssize_t),
+        ("fref0", ctypes.c_void_p), ("fref1", ctypes.c_void_p), ("fref_stride", ctypes.c_ssize_t),
+        ("mv0", ctypes.c_void_p), ("mv1", ctypes.c_void_p),
+        ("bit_sizes", ctypes.c_void_p), ("bit_sizes_len", ctypes.c_int),
+        ("dir", ctypes.c_void_p), ("ref0", ctypes.c_void_p), ("ref1", ctypes.c_void_p),
+        ("mv0_out", ctypes.c_void_p), ("mv1_out", ctypes.c_void_p), ("cost", ctypes.c_void_p),
+        ("qp_map", ctypes.c_void_p), ("lambda8_by_qp", ctypes.c_void_p),
+    ]
+
+
 class LowresInitParams(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_int), ("src", ctypes.c_void_p), ("src_stride", ctypes.c_ssize_t),
                 ("plane", ctypes.c_void_p * 4), ("stride", ctypes.c_ssize_t),
@@ -644,6 +662,42 @@ def inter_sa8d_cost(depth, width, height, level, fenc, fenc_stride, fenc_off, fr
     f = lib().x265hip_inter_sa8d_cost
     f.argtypes = [ctypes.POINTER(InterSa8dCostParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_inter_sa8d_cost")
+
+
+def b_sa8d_bits(nrefs=(1, 1), refs=(0, 0), list_sel_bits=(3, 3, 5)):
+    """(base_bits, bi_bits_delta) of x265hip_b_sa8d_decide for a B slice's 2Nx2N.  base_bits[l] = m_listSelBits[l] + MVP_IDX_BITS +
+    getTUBits(refs[l], nrefs[l]) (search.cpp:2403-2404, search.h:246-249: getTUBits(r, n) = r + (r < n - 1)); bi_bits_delta =
+    m_listSelBits[2] - m_listSelBits[0] - m_listSelBits[1] (analysis.cpp:3197); list_sel_bits = getBlkBits' (3, 3, 5) (search.cpp:2649-2656).
+    ((4, 4), -1) for one reference per list."""
+    tu = [r + (1 if r < n - 1 else 0) for r, n in zip(refs, nrefs)]
+    return tuple(int(list_sel_bits[l]) + 1 + tu[l] for l in range(2)), int(list_sel_bits[2]) - int(list_sel_bits[0]) - int(list_sel_bits[1])
+
+
+def b_sa8d_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, mv0, mv1, dir_cost, base_bits, bi_bits_delta, lambda8,
+                  bit_sizes, dir_out, mv0_out, mv1_out, cost, ref0=None, ref1=None, ref_ids=(0, 1), fenc_off=0, fref_off=0, qp=0, qp_map=None,
+                  lambda8_by_qp=None, stream=None):
+    """x265hip_b_sa8d_decide: the sa8d choice between the cheaper single list and both lists for every block of a B picture
+    (Analysis::compressInterCU_rd0_4 with checkBidir2Nx2N).  fref0 / fref1: tensors of one geometry (sample (0,0) at element fref_off);
+    mv0 / mv1: the two refinements' records; dir_cost: the list-selection costs the records are compared with (two or three entries);
+    base_bits, bi_bits_delta: b_sa8d_bits(); bit_sizes: device float32 tensor (mv_bit_sizes); cost: device int32 [ctu][blocks][4] out;
+    qp_map: the LUMA plane of tu_qp."""
+    es = 1 if depth == 8 else 2
+    p = BSa8dParams()
+    p.depth, p.width, p.height, p.level, p.qp, p.lambda8 = depth, width, height, level, int(qp), int(lambda8)
+    p.base_bits[0], p.base_bits[1], p.bi_bits_delta = int(base_bits[0]), int(base_bits[1]), int(bi_bits_delta)
+    for i, c in enumerate(dir_cost):
+        p.dir_cost[i] = int(c)
+    p.ref_id0, p.ref_id1 = ref_ids
+    p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
+    p.fref0, p.fref1, p.fref_stride = fref0.data_ptr() + fref_off * es, fref1.data_ptr() + fref_off * es, fref_stride
+    p.mv0, p.mv1, p.bit_sizes, p.bit_sizes_len = mv0.data_ptr(), mv1.data_ptr(), bit_sizes.data_ptr(), int(bit_sizes.numel())
+    p.dir, p.ref0, p.ref1 = dir_out.data_ptr(), _p(ref0), _p(ref1)
+    p.mv0_out, p.mv1_out, p.cost = mv0_out.data_ptr(), mv1_out.data_ptr(), cost.data_ptr()
+    p.qp_map, p.lambda8_by_qp = _p(qp_map), _p(lambda8_by_qp)
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_b_sa8d_decide
+    f.argtypes = [ctypes.POINTER(BSa8dParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_b_sa8d_decide")
 
 
 def lowres_init(depth, src, src_stride, src_off, planes, stride, org, width, lines, margin_x, margin_y, stream=None):

@@ -379,10 +379,12 @@ class Deblock:
         hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv, num_sig, self.bs_ver, self.bs_hor, intra=intra)
         self._luma(plane, pic)
 
-    def run_b(self, plane, pic: DevicePicture, mv0, mv1, ref0, ref1, num_sig):
+    def run_b(self, plane, pic: DevicePicture, mv0, mv1, ref0, ref1, num_sig, intra=None):
         """A B picture: the boundary strengths compare (ref0, ref1) x (mv0, mv1) per block (deblock.cpp:217-247); ref0 / ref1 = int8 picture
-        ids per block, -1 = list unused (what BidirDecide leaves)."""
-        hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv0, num_sig, self.bs_ver, self.bs_hor, slice_b=True, mv1=mv1, ref0=ref0, ref1=ref1)
+        ids per block, -1 = list unused (what BidirDecide leaves).  intra: as in run() - Bs 2 on an intra block's edges comes before the B
+        rules (deblock.cpp:198-199)."""
+        hipabi.deblock_bs_inter(self.w64, self.h64, self.level, mv0, num_sig, self.bs_ver, self.bs_hor, slice_b=True, mv1=mv1, ref0=ref0, ref1=ref1,
+                                intra=intra)
         self._luma(plane, pic)
 
     def run_refs(self, plane, pic: DevicePicture, mv, ref_id, num_sig):
@@ -1878,15 +1880,17 @@ class IntraInInter:
         self.cost = torch.zeros(nb * 2, dtype=torch.int32, device=device) if want_cost else None
         self.qp_map, self.lambda8_by_qp = None, None          # as IntraPicture's
 
-    def run(self, cur: DevicePicture, recon_plane, rc, inter_cost, recon_c=None, rc_c=None, stream=None):
+    def run(self, cur: DevicePicture, recon_plane, rc, inter_cost, recon_c=None, rc_c=None, stream=None, inter_cost_stride=2, inter_cost_offset=1):
         """recon_plane (and recon_c = [Cb, Cr]): the inter reconstruction, rc (and rc_c = [Cb, Cr]): the inter TU stages whose levels / num_sig /
-        dist the intra winners overwrite; inter_cost: InterSa8dCost.cost (the pairs)."""
+        dist the intra winners overwrite; inter_cost: InterSa8dCost.cost (the pairs; the defaults read their cost word), or BSa8dDecide.cost
+        with inter_cost_stride = 4, inter_cost_offset = 0."""
         ch = None
         if self.chroma:
             ch = dict(fenc=cur.c, recon=recon_c, stride=cur.stride_c, org=cur.org_c, qp=self.qp_c, levels=[r.levels for r in rc_c],
                       num_sig=[r.num_sig for r in rc_c], dist=[r.dist for r in rc_c])
         hipabi.intra_in_inter(self.depth, self.w64, self.h64, self.level, self.qp, self.flags, self.lambda8, self.mode_bits, cur.t, cur.stride, cur.org,
-                              recon_plane, self.mode, rc.levels, rc.num_sig, rc.dist, inter_cost, self.intra, chroma=ch, cost=self.cost,
+                              recon_plane, self.mode, rc.levels, rc.num_sig, rc.dist, inter_cost, self.intra, inter_cost_stride=inter_cost_stride,
+                              inter_cost_offset=inter_cost_offset, chroma=ch, cost=self.cost,
                               strong_intra_smoothing=self.strong, stream=stream, qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp)
 
     def checksum(self):
@@ -1959,6 +1963,110 @@ class IntraPFramePipeline(_PictureStep):
         out.update(self.ii.checksum())
         out.update(self.rc.checksum())
         out["recon"] = int(self.final.to(torch.int64).sum().item())
+        return out
+
+
+class BSa8dDecide:
+    """The sa8d choice of a B picture's blocks between the cheaper single list and both (x265hip_b_sa8d_decide; reference
+    Analysis::compressInterCU_rd0_4 with checkInter_rd0_4 and checkBidir2Nx2N, analysis.cpp:1649-1655, 3059-3071, 3145-3270).  Owns what
+    BidirDecide owns - dir uint8, ref0 / ref1 int8 [ctu][blocks], mv0_out / mv1_out int32 [ctu*85][2] - plus cost int32 [ctu][blocks][4] =
+    {winning inter sa8d cost, single list, both lists after the zero pair, flags} and the float bit-size table sized from the search range."""
+
+    def __init__(self, nctu, w64, h64, depth, level, device, dir_cost=(12, 12, 20), ref_ids=(0, 1), rng=57, base_bits=None, bi_bits_delta=None,
+                 lambda8=1024, qp=0):
+        """dir_cost: what the two records' costs are compared with, as in BidirDecide.  base_bits / bi_bits_delta: hipabi.b_sa8d_bits() -
+        (4, 4) and -1 for one reference per list - where None."""
+        import torch
+        self.nctu, self.w64, self.h64, self.depth, self.level, self.qp = nctu, w64, h64, depth, level, qp
+        self.nblk = (64 >> (3 + level)) ** 2
+        self.dir_cost, self.ref_ids, self.lambda8 = tuple(int(c) for c in dir_cost), tuple(ref_ids), int(lambda8)
+        bb, delta = hipabi.b_sa8d_bits()
+        self.base_bits = bb if base_bits is None else tuple(int(b) for b in base_bits)
+        self.bi_bits_delta = delta if bi_bits_delta is None else int(bi_bits_delta)
+        self.dir = torch.zeros(nctu * self.nblk, dtype=torch.uint8, device=device)
+        self.ref0 = torch.zeros(nctu * self.nblk, dtype=torch.int8, device=device)
+        self.ref1 = torch.zeros(nctu * self.nblk, dtype=torch.int8, device=device)
+        self.mv0_out = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device)
+        self.mv1_out = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device)
+        self.cost = torch.zeros(nctu * self.nblk * 4, dtype=torch.int32, device=device)
+        self.bit_sizes = torch.from_numpy(hipabi.mv_bit_sizes(4 * int(rng) + 4)).to(device)
+        self.qp_map, self.lambda8_by_qp = None, None          # as InterSa8dCost's
+
+    def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mv0, mv1, stream=None):
+        """mv0 / mv1: the two SubpelRefine outputs."""
+        assert ref0.stride == ref1.stride and ref0.org == ref1.org
+        hipabi.b_sa8d_decide(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, ref0.t, ref1.t, ref0.stride, mv0, mv1, self.dir_cost,
+                             self.base_bits, self.bi_bits_delta, self.lambda8, self.bit_sizes, self.dir, self.mv0_out, self.mv1_out, self.cost,
+                             ref0=self.ref0, ref1=self.ref1, ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org, qp=self.qp, qp_map=self.qp_map,
+                             lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+
+    def checksum(self):
+        import torch
+        return {"dir": int(self.dir.to(torch.int64).sum().item()), "mv0_out": int(self.mv0_out.to(torch.int64).sum().item()),
+                "mv1_out": int(self.mv1_out.to(torch.int64).sum().item()), "b_cost": int(self.cost.to(torch.int64).sum().item())}
+
+
+class Sa8dBFramePipeline(_RefListStep):
+    """One B picture whose decision is the reference's own for the 2Nx2N CUs this pipeline codes: per list search -> sub-pel refinement;
+    BSa8dDecide; bi-predictive luma + 4:2:0 chroma reconstruction; with b_intra (--b-intra, bIntraInBFrames) IntraInInter against word 0 of
+    the decision's cost, with the B slice's flags; B-picture boundary strengths with the intra flags + luma / chroma deblocking; the shared
+    loop-filter tail.  Overwriting the intra winners in coding order is the reference's result as in IntraPFramePipeline: an inter block's
+    reconstruction never depends on a neighbour, whichever lists it uses.  run(cur, ref0, ref1) / final_planes() as
+    BFramePipeline's: MiniGop(b_step=...) takes it.  The constructor switches mean what they mean in BFramePipeline / IntraPFramePipeline."""
+
+    def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
+                 sign_hide=False, sao_rdo=None, dir_cost=(12, 12, 20), b_intra=False, lambda8=1024, mode_bits=(2, 3, 6), strong_intra_smoothing=True,
+                 base_bits=None, bi_bits_delta=None):
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
+        self._build_lists(2, w64, h64, depth, device, rng, subme, False, False)
+        self.bd = BSa8dDecide(self.nctu, w64, h64, depth, level, device, dir_cost=dir_cost, rng=rng, base_bits=base_bits, bi_bits_delta=bi_bits_delta,
+                              lambda8=lambda8, qp=qp)
+        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
+        self.rc = InterReconBi(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        qpc = chroma_quant_qp(qp, depth)
+        if chroma:
+            self.rc_c = [InterReconChromaBi(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
+        self.b_intra = bool(b_intra)
+        self.ii = IntraInInter(self.nctu, w64, h64, depth, level, qp, device, flags=self.tu_flags, chroma=chroma, qp_c=(qpc, qpc), lambda8=lambda8,
+                               mode_bits=mode_bits, strong_intra_smoothing=strong_intra_smoothing) if b_intra else None
+
+    def set_qp_maps(self, maps, lambda8_by_qp=None):
+        """As IntraPFramePipeline.set_qp_maps: the maps reach the TU stages, the deblocking stage, the decision and (with b_intra) the intra
+        walk; lambda8_by_qp prices the rate terms of all candidates per block."""
+        self._set_qp_maps(maps, self.rc, self.rc_c if self.chroma else [])
+        self.bd.qp_map = None if maps is None else maps.tu_qp[0]
+        self.bd.lambda8_by_qp = None if maps is None else lambda8_by_qp
+        if self.ii is not None:
+            self.ii.qp_map = None if maps is None else maps.tu_qp
+            self.ii.lambda8_by_qp = None if maps is None else lambda8_by_qp
+
+    def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mark=None):
+        """ref0 / ref1: the list-0 / list-1 reference pictures (extended borders; with chroma=True also their Cb / Cr planes).  Returns the
+        luma plane of the coded picture; mark(name), if given, is called after every stage."""
+        self._qp_maps_run_check()
+        mark = mark or (lambda name: None)
+        self._alloc_planes(cur)
+        self._search_lists(cur, (ref0, ref1), mark)
+        self.bd.run(cur, ref0, ref1, self.spl[0].out, self.spl[1].out)
+        mark("b_sa8d")
+        mv0, mv1, dirs = self.bd.mv0_out, self.bd.mv1_out, self.bd.dir
+        self.rc.run(cur, ref0, ref1, self.recon, mv0, mv1, dir_flags=dirs)
+        mark("recon")
+        if self.chroma:
+            for i in range(2):
+                self.rc_c[i].run(cur.c[i], ref0.c[i], ref1.c[i], self.recon_c[i], cur.stride_c, cur.org_c, mv0, mv1, dir_flags=dirs)
+            mark("recon_chroma")
+        if self.ii is not None:
+            self.ii.run(cur, self.recon, self.rc, self.bd.cost, self.recon_c, self.rc_c if self.chroma else None, inter_cost_stride=4, inter_cost_offset=0)
+            mark("intra")
+        if self.db is not None:
+            self.db.run_b(self.recon, cur, mv0, mv1, self.bd.ref0, self.bd.ref1, self.rc.num_sig, intra=None if self.ii is None else self.ii.intra)
+        return self._filter_tail(cur, mark)
+
+    def checksum(self):
+        out = self._checksum(self.bd)
+        if self.ii is not None:
+            out.update(self.ii.checksum())
         return out
 
 

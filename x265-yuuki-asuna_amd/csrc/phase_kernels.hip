@@ -303,8 +303,104 @@ __device__ __forceinline__ void phase_luma_wide_body(const PhaseArgs& a)
 // for the kernel above; capped at 128 VGPRs (4 wavefronts per SIMD, a little scratch) 0.079 / 0.138 ms.  So the stage was never waiting for
 // its loads or stores: ~3700 VALU instructions per tile (11 rows x 3 horizontal sets, 12 vertical phases of 16 samples, rounding, clipping,
 // packing) are 60 us of issue time on the 1024 SIMDs - both kernels sit within 20 % of that.  16-bit samples take this kernel (fewer,
-// wider stores matter more when a tile is twice the bytes), 8-bit samples the one above; X265HIP_PHASE_KERNEL=1 / 2 force one or the other.
+// wider stores matter more when a tile is twice the bytes); 8-bit samples took the one above until phase_luma8_kernel below produced the same planes
+// from 1603 instead of 3457 VALU instructions per tile.  X265HIP_PHASE_KERNEL=1 / 2 still force one or the other of these two, at both sample sizes.
 template <typename Px> __global__ void __launch_bounds__(256) phase_luma_wide_kernel(PhaseArgs a) { phase_luma_wide_body<Px>(a); }
+
+// ---- 8-bit samples with the depth fixed at compile time: the same results from half the vector instructions (profiles/phase_planes_8bit.txt).
+//   * headRoom = 6, so luma_hps shifts by 0 and only subtracts 8192, and luma_vsp adds 2048 + (8192 << 6) and shifts by 12.  The vertical taps sum to 64:
+//     with H + 32 in place of H - 8192 as the intermediate, the vertical sum gains 64 * 8224 = 2048 + (8192 << 6), which is that rounding term.  So the
+//     dot4 chain on (pixel - 128) bytes starts at 8192 + 32, its result is shifted and clipped for the yf = 0 plane (luma_hpp) AND paired up for the vertical
+//     filter as it is, and the two-stage dot2 chains start at 0 (the one-stage chains of xf = 0 at 32).
+//   * the 11 source rows stream through the lane once: a row's (pixel - 128) words and its 6 byte alignments serve all three xf, its centre dword pairs up
+//     directly for xf = 0, and an output line of all 15 planes is finished as soon as the row 4 below it has arrived.
+//   * shift, clip and pack of two sums are one v_ashr_pk_u8_i32.
+//   * the first step of every dot chain asks for the clamped form (no sum comes near the int32 ends, so the clamp never acts): only the unclamped form has
+//     an accumulate-in-place encoding, which the compiler always picks and then feeds with a v_mov of the start value per chain.
+// Measured and dropped (same file): 4x8 tiles (9 % fewer instructions, but 203 registers = 2 wavefronts per SIMD, slower) and the quad-transposed
+// 16-byte stores, here of four planes' dwords of one line (slower at both tile heights).  Same grid and tile rule as phase_luma_kernel.
+typedef unsigned short phase_v2u16 __attribute__((ext_vector_type(2)));
+template <int S> __device__ __forceinline__ uint32_t ashr_clip_pack4(const int (&d)[4])                     // (d >> S) clipped to 0 .. 255, four to a dword
+{
+    const phase_v2u16 v = { __builtin_amdgcn_ashr_pk_u8_i32(d[0], d[1], S), __builtin_amdgcn_ashr_pk_u8_i32(d[2], d[3], S) };
+    return __builtin_bit_cast(uint32_t, v);
+}
+
+__global__ void __launch_bounds__(256) phase_luma8_kernel(PhaseArgs a)
+{
+    int bx, by;
+    xcd_swizzle_2d(bx, by);                                                       // a tile row reads 11 sample rows for its 4: vertical neighbours on one XCD's L2
+    const int tx = bx * 256 + threadIdx.x, y0 = 4 + by * 4;                       // the first 4 and the last 8 rows are not produced
+    if (tx >= a.tilesW) return;
+    const uint32_t laneB = threadIdx.x * 4;
+    const uint8_t* __restrict__ org = a.src + (long)(y0 - 3) * a.strideB + (long)bx * 1024 - 3;
+    uint8_t* out = a.dst + (long)y0 * a.strideB + (long)bx * 1024;
+    uint32_t raw[11][3];
+#pragma unroll
+    for (int t = 0; t < 11; t++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) raw[t][k] = ld_u32(org + (long)t * a.strideB + 4 * k + laneB);
+    // Ranges at 8 bits (taps: positive sum 88, negative sum -24): horizontal sum H in [-24 * 255, 88 * 255] = [-6120, 22440], the reference's intermediate
+    // H - 8192 in [-14312, 14248] (ours, H + 32, in [-6088, 22472]); two-stage sum + offSP in [-(88 * 14312 + 24 * 14248) + 526336, 88 * 14248 + 24 * 14312
+    // + 526336], >> 12 = [-263, 518]; one-stage (sum + 32) >> 6 in [-96, 351].  All inside int16: the reference's narrowing before the clip is the identity.
+    uint32_t pairs[4][10][4];                                                     // (row t, row t + 1) as two int16: samples (xf = 0) or H + 32
+    uint32_t prev[4][4];
+#pragma unroll
+    for (int t = 0; t < 11; t++)
+    {
+        const uint32_t cen = __builtin_amdgcn_alignbyte(raw[t][1], raw[t][0], 3);                           // the tile's own samples: bytes 3 .. 6
+        const uint32_t w0 = raw[t][0] ^ 0x80808080u, w1 = raw[t][1] ^ 0x80808080u, w2 = raw[t][2] ^ 0x80808080u;
+        uint32_t lo[4], hi[4];
+#pragma unroll
+        for (int x = 0; x < 4; x++)
+        {
+            lo[x] = x ? __builtin_amdgcn_alignbyte(w1, w0, x) : w0;
+            hi[x] = x ? __builtin_amdgcn_alignbyte(w2, w1, x) : w1;
+        }
+        if (t)
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+                pairs[0][t - 1][x] = __builtin_amdgcn_perm(cen, prev[0][0], 0x0c000c00u | (uint32_t)x | ((uint32_t)(4 + x) << 16));
+        prev[0][0] = cen;
+#pragma unroll
+        for (int xf = 1; xf < 4; xf++)
+        {
+            const uint32_t c03 = tile_sel3(xf, 0x3af604ffu, 0x28f504ffu, 0x11fb0100u), c47 = tile_sel3(xf, 0x0001fb11u, 0xff04f528u, 0xff04f63au);
+            int hs[4];
+#pragma unroll
+            for (int x = 0; x < 4; x++)
+            {
+                hs[x] = __builtin_amdgcn_sdot4((int)hi[x], (int)c47, __builtin_amdgcn_sdot4((int)lo[x], (int)c03, 8192 + 32, true), false);
+                if (t) pairs[xf][t - 1][x] = __builtin_amdgcn_perm((uint32_t)hs[x], prev[xf][x], 0x05040100u);
+                prev[xf][x] = (uint32_t)hs[x];
+            }
+            if (t >= 3 && t < 7)                                                                            // yf = 0: luma_hpp
+                *reinterpret_cast<uint32_t*>(out + (size_t)(xf - 1) * a.planeBytes + (long)(t - 3) * a.strideB + laneB) = ashr_clip_pack4<6>(hs);
+        }
+        if (t < 7) continue;
+        uint8_t* line = out + (long)(t - 7) * a.strideB;                          // this line's last source row has arrived
+#pragma unroll
+        for (int yf = 1; yf < 4; yf++)
+        {
+            const uint32_t cv[4] = { tile_sel3(yf, 0x0004ffffu, 0x0004ffffu, 0x00010000u), tile_sel3(yf, 0x003afff6u, 0x0028fff5u, 0x0011fffbu),
+                                     tile_sel3(yf, 0xfffb0011u, 0xfff50028u, 0xfff6003au), tile_sel3(yf, 0x00000001u, 0xffff0004u, 0xffff0004u) };
+#pragma unroll
+            for (int xf = 0; xf < 4; xf++)
+            {
+                int d[4];
+#pragma unroll
+                for (int x = 0; x < 4; x++)
+                {
+                    d[x] = __builtin_amdgcn_sdot2(__builtin_bit_cast(tile_v2i16, pairs[xf][t - 7][x]), __builtin_bit_cast(tile_v2i16, cv[0]), xf ? 0 : 32, true);
+#pragma unroll
+                    for (int j = 1; j < 4; j++) d[x] = tile_dot2(pairs[xf][t - 7 + 2 * j][x], cv[j], d[x]);
+                }
+                // luma_hps + luma_vsp (the rounding term came with the intermediates) : luma_vpp
+                *reinterpret_cast<uint32_t*>(line + (size_t)(yf * 4 + xf - 1) * a.planeBytes + laneB) = xf ? ashr_clip_pack4<12>(d) : ashr_clip_pack4<6>(d);
+            }
+        }
+    }
+}
 
 // 4-tap chroma set, eighth-sample phases: phase = yf * 8 + xf.  Same structure: one 4x4 tile per lane, the 7 x 7 source samples loaded
 // once, the horizontally filtered columns of an xf shared by its eight vertical phases.
@@ -406,7 +502,9 @@ int x265hip::phase_planes_launch(int depth, int chroma, const void* src, void* d
         // the wide-store kernel needs whole quads per row (pitch a multiple of 16 bytes / 4 tiles)
         const bool wideOk = !(a.tilesW & 3) && !(((uintptr_t)dst | plane_bytes) & 15);
         const bool wide = wideOk && (force == 2 || (force != 1 && bpp == 2));
-        if (wide)
+        // 8 bits: the fixed-depth kernel unless X265HIP_PHASE_KERNEL=1 / 2 asks for one of the two older ones (=3 names the default)
+        if (bpp == 1 && force != 1 && force != 2) hipLaunchKernelGGL(phase_luma8_kernel, gridL, dim3(256), 0, s, a);
+        else if (wide)
         {
             if (bpp == 1) hipLaunchKernelGGL(phase_luma_wide_kernel<uint8_t>, gridL, dim3(256), 0, s, a);
             else hipLaunchKernelGGL(phase_luma_wide_kernel<uint16_t>, gridL, dim3(256), 0, s, a);

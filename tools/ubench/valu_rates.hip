@@ -50,6 +50,15 @@ __global__ void k(uint32_t* out, uint32_t seed)
                 if (OP == 17) a[i] = __builtin_amdgcn_sad_u8(a[(i + 1) & 7], b, a[i]);
                 if (OP == 18) a[i] = __builtin_amdgcn_sad_u16(a[(i + 1) & 7], b, a[i]);
                 if (OP == 19) q[i] = __builtin_amdgcn_qsad_pk_u16_u8(q[(i + 1) & 7], b, q[i]);
+                // OPs 20 - 26: the search kernels' reduction half, one instruction each, written as the kernels write them (inline assembly: the compiler may not
+                // fuse, split or re-select them).  OP 3 above is NOT two instructions on gfx950 - add + xor compiles to one v_xad_u32 - so OP 25 is the two-source case
+                if (OP == 20) asm volatile("v_mad_u32_u16 %0, %1, %2, %0" : "+v"(a[i]) : "v"(a[(i + 1) & 7]), "v"(b));
+                if (OP == 21) asm volatile("v_mad_u32_u16 %0, %1, %2, %0 op_sel:[1,0,0,0]" : "+v"(a[i]) : "v"(a[(i + 1) & 7]), "v"(b));
+                if (OP == 22) asm volatile("v_lshl_add_u32 %0, %1, 8, %0" : "+v"(a[i]) : "v"(a[(i + 1) & 7]));
+                if (OP == 23) asm volatile("v_min3_u32 %0, %1, %2, %0" : "+v"(a[i]) : "v"(a[(i + 1) & 7]), "v"(b));
+                if (OP == 24) asm volatile("v_bfe_u32 %0, %1, 16, 16" : "=v"(a[i]) : "v"(a[(i + 1) & 7]));
+                if (OP == 25) asm volatile("v_add_u32 %0, %1, %0" : "+v"(a[i]) : "v"(a[(i + 1) & 7]));
+                if (OP == 26) asm volatile("v_and_b32 %0, 0xffff, %1" : "=v"(a[i]) : "v"(a[(i + 1) & 7]));   // two sources, one a 32-bit literal (8-byte encoding)
             }
     }
     long long t1 = __builtin_readcyclecounter();
@@ -87,12 +96,16 @@ int main()
             run<8>("v_dot4_i32_i8", 256); run<9>("v_dot2_i32_i16", 256); run<10>("v_mad_i32_i24", 256); run<11>("v_alignbyte", 256);
             run<12>("v_perm_b32", 256); run<13>("mul_lo_u32 + add", 256); run<14>("v_pk_mad_i16", 256); run<15>("v_dot4_u32_u8", 256); run<16>("v_add3_u32", 256);
             run<17>("v_sad_u8 alone", 256); run<18>("v_sad_u16 alone", 256); run<19>("v_qsad_pk_u16_u8 alone", 256);
+            run<20>("v_mad_u32_u16", 256); run<21>("v_mad_u32_u16 op_sel", 256); run<22>("v_lshl_add_u32", 256); run<23>("v_min3_u32", 256);
+            run<24>("v_bfe_u32", 256); run<25>("v_add_u32 alone", 256); run<26>("v_and_b32 literal", 256);
         } else {
             run<0>("v_sad_u8", 1024); run<1>("v_sad_u16", 1024); run<2>("v_qsad_pk_u16_u8", 1024); run<3>("v_add+xor (2 ops)", 1024);
             run<4>("v_alignbit", 1024); run<5>("v_sad_hi_u8", 1024); run<6>("v_msad_u8", 1024); run<7>("dpp add", 1024);
             run<8>("v_dot4_i32_i8", 1024); run<9>("v_dot2_i32_i16", 1024); run<10>("v_mad_i32_i24", 1024); run<11>("v_alignbyte", 1024);
             run<12>("v_perm_b32", 1024); run<13>("mul_lo_u32 + add", 1024); run<14>("v_pk_mad_i16", 1024); run<15>("v_dot4_u32_u8", 1024); run<16>("v_add3_u32", 1024);
             run<17>("v_sad_u8 alone", 1024); run<18>("v_sad_u16 alone", 1024); run<19>("v_qsad_pk_u16_u8 alone", 1024);
+            run<20>("v_mad_u32_u16", 1024); run<21>("v_mad_u32_u16 op_sel", 1024); run<22>("v_lshl_add_u32", 1024); run<23>("v_min3_u32", 1024);
+            run<24>("v_bfe_u32", 1024); run<25>("v_add_u32 alone", 1024); run<26>("v_and_b32 literal", 1024);
         }
     }
     return 0;

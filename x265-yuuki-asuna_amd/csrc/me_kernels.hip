@@ -525,14 +525,20 @@ __global__ void __launch_bounds__(SURF && BEST ? 768 : 1024, SURF && BEST ? 3 : 
 // 128  QUAD64  PAIR64 for FOUR rows: two pair sums {A01,B01,A23,B23} / {C01,D01,C23,D23} change halves in one v_permlane32_swap -> 16-lane row r
 //              holds the 64x64 total of the quad's row r (6 instructions and one key per four rows);
 //  32  MASK    the low halves of the packed 8x8 sums are extracted with an opaque v_and (the compiler turns `(x & 0xffff) << n` into
-//              shift + mask + add; this way it is mask + v_lshl_add_u32).
+//              shift + mask + add; this way it is mask + v_lshl_add_u32);
+// 1024 MAD16   the four 8x8 keys of a row are four v_mad_u32_u16 (`half * 256 + sb`, op_sel picks the high half) that read the packed accumulator halves
+//              in place: no v_and / v_bfe unpacking, 32 of the 347 vector instructions of a block of 8 rows (MASK is meaningless then).  Needs CTAB (sb in
+//              an SGPR) and COLMIN (the key is `s << 8 | sb`).  1107 -> 1064 us per 4K launch (profiles/me_tailcut_mad16.txt).
+// (A flag 512, TAILCUT - skip the ring slots of candidate rows past 2 R in the last seven window rows - was measured and dropped: the compiler removes those of
+// the 2 / 4 / 6-row tail by itself, the 30 quad-SADs left in the last full block cost one more block instantiation with branches (and spills), and the launch did not get faster.)
 // Results are identical for every FL (tests/test_gpu_me.py runs them all against the oracle).
 template <int PITCH, int FL>
 __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOff, int groupsPerWg)
 {
     constexpr bool LD64 = (FL & 1) != 0, CTAB = (FL & 2) != 0, PAIR64 = (FL & 4) != 0, DEFERX = (FL & 8) != 0, COLMIN = (FL & 16) != 0, MASK = (FL & 32) != 0;
-    constexpr bool RING = (FL & 64) != 0, QUAD64 = (FL & 128) != 0, LDA = (FL & 256) != 0;
+    constexpr bool RING = (FL & 64) != 0, QUAD64 = (FL & 128) != 0, LDA = (FL & 256) != 0, MAD16 = (FL & 1024) != 0;
     static_assert(!LDA || (!LD64 && !RING), "LDA is a window-load scheme of its own");
+    static_assert(!MAD16 || (CTAB && COLMIN), "MAD16 builds the per-column keys from an SGPR row constant");
     static_assert(!QUAD64 || (PAIR64 && CTAB), "QUAD64 extends PAIR64 and takes its per-lane row constants from the table");
     static_assert(!(RING && LD64), "RING is the three-dword load path without its copies");
     extern __shared__ __attribute__((aligned(16))) uint8_t win[];
@@ -588,6 +594,8 @@ __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOf
     const int kcol = lane & 3;
     const uint32_t selK = 0x0c0c0000u | (uint32_t)((2 * kcol + 1) << 8) | (uint32_t)(2 * kcol);   // v_perm: u16 #kcol of {qhi, qlo}
     const int oddRow = (lane >> 4) & 1;                     // PAIR64: 0 = this lane ends up with row A's 64x64 total, 1 = row B's
+    uint32_t c256 = 256u;                                   // MAD16: the multiplier lives in a VGPR (VOP3 reads one SGPR - the row constant - and 256 is no inline constant)
+    if (MAD16) asm volatile("" : "+v"(c256));
 
     const int T = 2 * R + 8;
     // a launch of few CTUs (a band of the frame-parallel ring, a small picture) deals a CTU's column groups over blockIdx.y workgroups - each stages the window for
@@ -735,8 +743,9 @@ __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOf
                     const u64 A = acc[slot];
                     const uint32_t lo = (uint32_t)A, hi = (uint32_t)(A >> 32);
                     const uint32_t qlo = (uint32_t)quad_sum((int)lo), qhi = (uint32_t)quad_sum((int)hi);
-                    uint32_t s80, s82;
-                    if (MASK)
+                    uint32_t s80 = 0, s82 = 0;
+                    if (MAD16) { }
+                    else if (MASK)
                     {
                         asm("v_and_b32 %0, 0xffff, %1" : "=v"(s80) : "v"(lo));
                         asm("v_and_b32 %0, 0xffff, %1" : "=v"(s82) : "v"(hi));
@@ -749,7 +758,15 @@ __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOf
                     const uint32_t sb = CTAB ? (uint32_t)__builtin_amdgcn_readlane((int)cb, p) : (((uint32_t)a.costY[m] << 8) | (uint32_t)m);
                     if (COLMIN)
                     {
-                        const uint32_t k0 = (s80 << 8) + sb, k1 = (s81 << 8) + sb, k2 = (s82 << 8) + sb, k3 = (s83 << 8) + sb;
+                        uint32_t k0, k1, k2, k3;
+                        if (MAD16)
+                        {   // u16 half * 256 + sb: the same value as (s << 8) + sb (s <= 16320)
+                            asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(k0) : "v"(lo), "v"(c256), "s"(sb));
+                            asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(k1) : "v"(lo), "v"(c256), "s"(sb));
+                            asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(k2) : "v"(hi), "v"(c256), "s"(sb));
+                            asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(k3) : "v"(hi), "v"(c256), "s"(sb));
+                        }
+                        else { k0 = (s80 << 8) + sb; k1 = (s81 << 8) + sb; k2 = (s82 << 8) + sb; k3 = (s83 << 8) + sb; }
                         r8c[0] = k0 < r8c[0] ? k0 : r8c[0];
                         r8c[1] = k1 < r8c[1] ? k1 : r8c[1];
                         r8c[2] = k2 < r8c[2] ? k2 : r8c[2];
@@ -1277,7 +1294,8 @@ int launch_me_cand(const x265hip_me_params* p, hipStream_t s);       // me_cand_
 
 // the flag set the minima-only 8-bit launch uses by default (-1 = round 4's kernel): what measured fastest on one box, profiles/r05_me_flags_ab.txt
 static const bool W2_DEFAULT = true;          // the 16-bit twin (me_ctu_w2_kernel): 2.60 -> 2.35 ms at 4K, 9.95 -> 8.95 ms at 8K (one box, interleaved: profiles/r05_me10_ab.txt)
-static const int Q2_DEFAULT_FLAGS = 254;      // CTAB | PAIR64 | DEFERX | COLMIN | MASK | RING | QUAD64: 1.24 ms against round 4's 1.42 at 4K (three interleaved rounds)
+static const int Q2_DEFAULT_FLAGS = 1278;     // CTAB | PAIR64 | DEFERX | COLMIN | MASK | RING | QUAD64 (254: 1.24 ms against round 4's 1.42 at 4K, three interleaved rounds) | MAD16
+                                              // (1.107 -> 1.064 ms, every step of five alternating pairs below the parent's: profiles/me_tailcut_mad16.txt)
 
 // Every A/B switch of the search launches, read ONCE (round-5 advisor: some were read per launch - getenv in a hot path, not thread-safe against setenv in the host
 // process - and x265hip_me_minima_kernel_name re-derived the selection on its own and could disagree with the launch).  x265hip_me_env_refresh() re-reads them: a
@@ -1435,7 +1453,7 @@ static int launch_me(const x265hip_me_params* p, hipStream_t s)
                     switch (q2Flags)
                     {
                     /* the single flags, the sets the profile tables name, the default (profiles/r05_me_flags_ab.txt lists more combinations: they were instantiated for the A/B visits) */
-                    LAUNCH_Q2(0) LAUNCH_Q2(1) LAUNCH_Q2(2) LAUNCH_Q2(4) LAUNCH_Q2(8) LAUNCH_Q2(32) LAUNCH_Q2(62) LAUNCH_Q2(254) LAUNCH_Q2P(320, 446) LAUNCH_Q2P(320, 256)
+                    LAUNCH_Q2(0) LAUNCH_Q2(1) LAUNCH_Q2(2) LAUNCH_Q2(4) LAUNCH_Q2(8) LAUNCH_Q2(32) LAUNCH_Q2(62) LAUNCH_Q2(254) LAUNCH_Q2(1278) LAUNCH_Q2P(320, 446) LAUNCH_Q2P(320, 256)
                     default: set_error("me_fullsearch: X265HIP_ME_Q2_FLAGS %d is not an instantiated combination", q2Flags); return X265HIP_EINVAL;
                     }
 #undef LAUNCH_Q2

@@ -1830,6 +1830,60 @@ typedef struct x265hip_b_sa8d_params
 } x265hip_b_sa8d_params;
 int x265hip_b_sa8d_decide(const x265hip_b_sa8d_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Merge / skip blocks of a P picture (csrc/merge_decide.h): the fourth arm of the sa8d choice of Analysis::compressInterCU_rd0_4
+ * ("SA8D choice between merge/skip, inter, bidir, and intra", analysis.cpp:1649), Analysis::checkMerge2Nx2N_rd0_4 at RD level 0
+ * (analysis.cpp:2787-2838, 2870-2871), on the block grid of the TU stages: every N x N block (N = 8 << level) one 2Nx2N CU, CTUs in
+ * raster order, blocks in z-order, one slice, a P slice with one reference, --no-temporal-mvp.
+ *   list   : CUData::getInterMergeCandidates (common/cudata.cpp:1458-1712) with maxNumMergeCand = max_merge: A1 (left), B1 (above), B0
+ *            (above right), A0 (below left), B2 (above left, only while count < 4); pruned pairs B1-A1, B0-B1, A0-A1, B2-A1, B2-B1 and no
+ *            other (a B0 equal to A1 stays, duplicates are priced with their own index); returned once count == max_merge; the rest is
+ *            (0, 0) / refIdx 0.  A neighbour is available inside the picture and before the block in coding order (B0 may lie in the
+ *            above-right CTU, A0 in the left CTU but never below the CTU's last row); every block is inter.  Its motion is what it
+ *            ENDED UP with: its candidate's vector where it merged, its searched vector where it did not.
+ *   price  : dist = cu[].sa8d(fenc, predInterLumaPixel(fref, clipMv(mv_i))), bits = getTUBits(i, max_merge) = i + (i < max_merge - 1)
+ *            (search.h:246-249), cost = dist + ((bits * lambda8 + 128) >> 8); the best with strict <, the lowest index wins a tie.
+ *   clipMv : cudata.cpp:1915-1928 (Predict::motionCompensation, predict.cpp:92), on quarter samples: x into [-((64 + 8 + x0 - 1) << 2),
+ *            (width + 8 - x0 - 1) << 2] for a block whose first sample is (x0, y0), y alike with y0 and the height.  The clip applies to
+ *            the prediction only: the CU keeps the unclipped vector, which later neighbours inherit and Deblock::getBoundaryStrength
+ *            compares.  A clipped vector reaches at most 74 samples before the picture and N + 10 behind it: planes with margins of 80
+ *            rows and 96 columns (frames.py) hold every patch of N + 7 rows and columns at every level; the kernel has no further guard.
+ *   choice : the block keeps its searched vector iff inter_cost[block * inter_cost_stride] < the best merge cost (analysis.cpp:1650; a
+ *            tie stays merge).  inter_cost is x265hip_inter_sa8d_cost's cost word (pass cost + 1, stride 2); qp / qp_map / lambda8_by_qp
+ *            mean what they mean there - one lambda per block for both candidates.
+ *   skip   : not decided here.  At RD level 0 a merged 2Nx2N CU without a coded coefficient becomes MODE_SKIP in encodeResidue
+ *            (analysis.cpp:3358-3359): skip = merge && num_sig(Y) == 0 && num_sig(Cb) == 0 && num_sig(Cr) == 0 over the TU stages' outputs.
+ * mv: the searched records x265hip_inter_recon takes ([ctu*85] {cost, qx | qy << 16}).  Outputs, all DEVICE:
+ *   merge, merge_idx : uint8 [ctu][blocks]: 1 and the winning index where the block merged, 0 and 0 where it did not
+ *   mv_out  : records, the level's slots only: the CU's motion (unclipped) - for boundary strengths and later pictures
+ *   mv_pred : records, the level's slots only: what the inter TU stages predict from - the clipped candidate of a merged block, the
+ *             searched vector, untouched, of another.  The cost word of both is the input record's for an inter block, the merge cost
+ *             for a merged one.
+ *   cost    : int32 [ctu][blocks][2] = {sa8d, cost} of the best merge candidate, for EVERY block
+ *   best    : optional int32 [ctu][blocks][2]: the winner - {sa8d, cost} of the candidate where the block merged, {-1, inter cost} where
+ *             it did not (word 1 at a stride of 2 is what a later intra walk would compare against)
+ * Schedule: x265hip_intra_picture_waves(width, height) launches on the caller's stream (wave = cx + 2 cy; empty waves of a picture one
+ * CTU wide are skipped), one workgroup per CTU of the wave; no spinning, no flags, capturable.
+ * Refused (X265HIP_EINVAL, before any device call): NULL operands (best / qp_map / lambda8_by_qp are optional), depth not 8 / 10 / 12,
+ * level outside 0..2, sizes that are no multiples of 64, strides below the width, qp out of range, lambda8 outside [0, 2^24], max_merge
+ * outside 1..5, inter_cost_stride < 1, mv_out or mv_pred equal to mv or to each other (the walk reads the searched vector of a block and
+ * the final motion of its neighbours: a second run must see the same inputs). */
+typedef struct x265hip_merge_decide_params
+{
+    int depth, width, height, level;
+    int qp;                                          /* luma quantiser QP: indexes lambda8_by_qp where there is no qp_map */
+    int lambda8, max_merge;
+    const void* fenc;  intptr_t fenc_stride;         /* sample (0,0) of the source luma plane */
+    const void* fref;  intptr_t fref_stride;         /* sample (0,0) of the reference luma plane */
+    const void* mv;
+    const int32_t* inter_cost; intptr_t inter_cost_stride;
+    const int8_t* qp_map; const uint32_t* lambda8_by_qp;
+    uint8_t* merge; uint8_t* merge_idx;
+    void* mv_out; void* mv_pred;
+    int32_t* cost; int32_t* best;
+} x265hip_merge_decide_params;
+int x265hip_merge_decide(const x265hip_merge_decide_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@
 // sa8d: 8x8 = (sum |H8 d| + 2) >> 2; a 16x16 unit sums its four 8x8 transforms and rounds once (sa8d_16x16, pixel.cpp:341-352); a 32x32
 // block is the sum of its four units.
 //
+// The body from the patches to the Hadamard sums is sa8d_slots(), which merge_decide_kernel (merge_decide.h) calls too.
 // Mapping: one workgroup of 256 threads per 32x32 quarter of a CTU (16 / 4 / 1 blocks).  The blocks' reference patches go to LDS, the
 // prediction is formed like inter_recon_kernel's (horizontal pass into `immed` only where both phases are set), the difference to the
 // source lands in LDS, and 128 lanes run the sixteen 8x8 Hadamard transforms - rows in the lane, columns across eight lanes, the four
@@ -29,103 +30,130 @@ struct InterCostArgs
     const uint32_t* lambdaByQp;         // optional, indexed by the block's luma quantiser QP
 };
 
-template <typename Px, int N>
-__global__ void __launch_bounds__(256) inter_sa8d_cost_kernel(InterCostArgs a)
+// The LDS of the patch -> prediction -> difference -> Hadamard body below: NB = (32 / N)^2 slots of one N x N block each.
+template <int N>
+struct Sa8dLds
 {
-    constexpr int LOG2N = N == 8 ? 3 : (N == 16 ? 4 : 5), BPR = 32 / N, NB = BPR * BPR, BPC = 64 / N, NPU = BPC * BPC;
-    constexpr int APRON = 3, PW = N + 7, PP = PW + 1, BPP = sizeof(Px);
-    __shared__ int16_t patch[NB * PW * PP];
-    __shared__ int16_t immed[NB * PW * N];
-    __shared__ int16_t diff[32 * 32];
-    __shared__ int sMv[NB], sSum[16];
+    static constexpr int BPR = 32 / N, NB = BPR * BPR, PW = N + 7, PP = PW + 1;
+    int16_t patch[NB * PW * PP];
+    int16_t immed[NB * PW * N];
+    int16_t diff[32 * 32];
+    int mv[NB], sum[16];
+};
 
+// sa8d of the luma prediction of the first nAct slots (nAct <= NB): slot b predicts from fref at pos(b) (the block's first luma sample, int2)
+// displaced by s.mv[b] (qx | qy << 16) and is compared with fenc at pos(b).  s.mv must be visible to the workgroup on entry; s.sum is on
+// return (read it with sa8d_slot_sum).  All 256 threads call it.  inter_sa8d_cost_kernel and merge_decide_kernel (merge_decide.h) share it,
+// so the two price a vector alike.
+template <typename Px, int N, class Pos>
+__device__ __forceinline__ void sa8d_slots(Sa8dLds<N>& s, const int nAct, const Pos pos, const Px* fref, const long rst, const Px* fenc, const long fst,
+                                           const int depth)
+{
+    constexpr int LOG2N = N == 8 ? 3 : (N == 16 ? 4 : 5), BPR = 32 / N;
+    constexpr int APRON = 3, PW = N + 7, PP = PW + 1;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int ctu = (int)blockIdx.x >> 2, quarter = (int)blockIdx.x & 3;
-    const int cx = ctu % a.ctusW, cy = ctu / a.ctusW;
-    const int rx0 = cx * 64 + (quarter & 1) * 32, ry0 = cy * 64 + (quarter >> 1) * 32;         // the quarter's first luma sample
-    const int maxVal = (1 << a.depth) - 1, headRoom = 14 - a.depth;
-    const int lbase = N == 8 ? 0 : (N == 16 ? 64 : 80);
-    // block b of the quarter (raster order inside it) -> its z index inside the CTU
-    auto zof = [&](const int b) { return ip_zidx((quarter & 1) * BPR + (b & (BPR - 1)), (quarter >> 1) * BPR + (b / BPR)); };
-    if (tid < NB) sMv[tid] = a.mv[(size_t)ctu * 85 + lbase + zof(tid)].y;
-    __syncthreads();
-    const long rst = a.frefStrideB / BPP, fst = a.fencStrideB / BPP;
-    const Px* fref = reinterpret_cast<const Px*>(a.fref);
-    const Px* fenc = reinterpret_cast<const Px*>(a.fenc);
+    const int maxVal = (1 << depth) - 1, headRoom = 14 - depth;
     // ---- the blocks' reference patches: N + 7 rows and columns around the full-sample position ----------------------------------------
-    for (int i = tid; i < NB * PW * PW; i += 256)
+    for (int i = tid; i < nAct * PW * PW; i += 256)
     {
         const int b = i / (PW * PW), r = i - b * (PW * PW), y = r / PW, x = r - y * PW;
-        const int qx = (int16_t)(sMv[b] & 0xffff), qy = (int16_t)(sMv[b] >> 16);
-        const int px = rx0 + (b & (BPR - 1)) * N + (qx >> 2) - APRON + x, py = ry0 + (b / BPR) * N + (qy >> 2) - APRON + y;
-        patch[b * (PW * PP) + y * PP + x] = (int16_t)fref[(long)py * rst + px];
+        const int qx = (int16_t)(s.mv[b] & 0xffff), qy = (int16_t)(s.mv[b] >> 16);
+        const int2 o = pos(b);
+        const int px = o.x + (qx >> 2) - APRON + x, py = o.y + (qy >> 2) - APRON + y;
+        s.patch[b * (PW * PP) + y * PP + x] = (int16_t)fref[(long)py * rst + px];
     }
     __syncthreads();
     // ---- predInterLumaPixel: where both phases are set, the horizontal pass at 14-bit precision first ---------------------------------
-    for (int i = tid; i < NB * PW * N; i += 256)
+    for (int i = tid; i < nAct * PW * N; i += 256)
     {
         const int b = i / (PW * N), r = i - b * (PW * N), y = r >> LOG2N, x = r & (N - 1);
-        const int xf = sMv[b] & 3, yf = (sMv[b] >> 16) & 3;
+        const int xf = s.mv[b] & 3, yf = (s.mv[b] >> 16) & 3;
         if (xf && yf)
         {
             const int shiftPS = 6 - headRoom, offPS = -(8192 << shiftPS);
-            int s = 0;
+            int acc = 0;
 #pragma unroll
-            for (int t = 0; t < 8; t++) s += (int)patch[b * (PW * PP) + y * PP + x + t] * (int)kTuTaps[xf][t];
-            immed[i] = (int16_t)((s + offPS) >> shiftPS);
+            for (int t = 0; t < 8; t++) acc += (int)s.patch[b * (PW * PP) + y * PP + x + t] * (int)kTuTaps[xf][t];
+            s.immed[i] = (int16_t)((acc + offPS) >> shiftPS);
         }
     }
     __syncthreads();
     for (int i = tid; i < 32 * 32; i += 256)
     {
         const int ry = i >> 5, rx = i & 31, b = (ry >> LOG2N) * BPR + (rx >> LOG2N), y = ry & (N - 1), x = rx & (N - 1);
-        const int xf = sMv[b] & 3, yf = (sMv[b] >> 16) & 3;
-        const int16_t* pt = patch + b * (PW * PP);
+        if (b >= nAct) continue;
+        const int xf = s.mv[b] & 3, yf = (s.mv[b] >> 16) & 3;
+        const int16_t* pt = s.patch + b * (PW * PP);
         int v;
         if (xf && yf)
         {
             const int shiftSP = 6 + headRoom, offSP = (1 << (shiftSP - 1)) + (8192 << 6);
-            int s = 0;
+            int acc = 0;
 #pragma unroll
-            for (int t = 0; t < 8; t++) s += (int)immed[b * (PW * N) + (y + t) * N + x] * (int)kTuTaps[yf][t];
-            v = tu_clip16((s + offSP) >> shiftSP, maxVal);
+            for (int t = 0; t < 8; t++) acc += (int)s.immed[b * (PW * N) + (y + t) * N + x] * (int)kTuTaps[yf][t];
+            v = tu_clip16((acc + offSP) >> shiftSP, maxVal);
         }
         else if (!(xf | yf)) v = pt[(y + APRON) * PP + x + APRON];
         else
         {
-            int s = 0;
+            int acc = 0;
 #pragma unroll
-            for (int t = 0; t < 8; t++) s += (int)(xf ? pt[(y + APRON) * PP + x + t] : pt[(y + t) * PP + x + APRON]) * (int)kTuTaps[xf ? xf : yf][t];
-            v = tu_clip16((s + 32) >> 6, maxVal);
+            for (int t = 0; t < 8; t++) acc += (int)(xf ? pt[(y + APRON) * PP + x + t] : pt[(y + t) * PP + x + APRON]) * (int)kTuTaps[xf ? xf : yf][t];
+            v = tu_clip16((acc + 32) >> 6, maxVal);
         }
-        diff[i] = (int16_t)((int)fenc[(long)(ry0 + ry) * fst + rx0 + rx] - v);
+        const int2 o = pos(b);
+        s.diff[i] = (int16_t)((int)fenc[(long)(o.y + y) * fst + o.x + x] - v);
     }
     __syncthreads();
     // ---- sixteen 8x8 Hadamard transforms on wavefronts 0 and 1: unit u = 16x16 (ux, uy), tile q inside it, row r -----------------------
+    // (the tiles of a slot at or beyond nAct transform whatever the difference array holds; nothing reads their sums)
     if (tid < 128)
     {
         const int row = tid & 7, q = (tid >> 3) & 3, u = tid >> 5;
         const int tx = (u & 1) * 2 + (q & 1), ty = (u >> 1) * 2 + (q >> 1);
         int d[8];
 #pragma unroll
-        for (int i = 0; i < 8; i++) d[i] = diff[(ty * 8 + row) * 32 + tx * 8 + i];
+        for (int i = 0; i < 8; i++) d[i] = s.diff[(ty * 8 + row) * 32 + tx * 8 + i];
         int raw = ip_hadamard8x8(d, lane);
-        if (N == 8) { if (row == 0) sSum[ty * 4 + tx] = (raw + 2) >> 2; }                      // the block at (tx, ty) of the quarter
+        if (N == 8) { if (row == 0) s.sum[ty * 4 + tx] = (raw + 2) >> 2; }                      // the block at (tx, ty) of the quarter
         else
         {
             raw += __shfl_xor(raw, 8, 64); raw += __shfl_xor(raw, 16, 64);
-            if ((tid & 31) == 0) sSum[u] = (raw + 2) >> 2;
+            if ((tid & 31) == 0) s.sum[u] = (raw + 2) >> 2;
         }
     }
     __syncthreads();
+}
+
+// slot b's sa8d after sa8d_slots: an 8x8 or 16x16 slot is one rounded sum, the 32x32 slot the sum of its four units
+template <int N>
+__device__ __forceinline__ int sa8d_slot_sum(const Sa8dLds<N>& s, const int b)
+{
+    return N == 32 ? s.sum[0] + s.sum[1] + s.sum[2] + s.sum[3] : s.sum[b];
+}
+
+template <typename Px, int N>
+__global__ void __launch_bounds__(256) inter_sa8d_cost_kernel(InterCostArgs a)
+{
+    constexpr int BPR = 32 / N, NB = BPR * BPR, BPC = 64 / N, NPU = BPC * BPC, BPP = sizeof(Px);
+    __shared__ Sa8dLds<N> s;
+
+    const int tid = threadIdx.x;
+    const int ctu = (int)blockIdx.x >> 2, quarter = (int)blockIdx.x & 3;
+    const int cx = ctu % a.ctusW, cy = ctu / a.ctusW;
+    const int rx0 = cx * 64 + (quarter & 1) * 32, ry0 = cy * 64 + (quarter >> 1) * 32;         // the quarter's first luma sample
+    const int lbase = N == 8 ? 0 : (N == 16 ? 64 : 80);
+    // block b of the quarter (raster order inside it) -> its z index inside the CTU
+    auto zof = [&](const int b) { return ip_zidx((quarter & 1) * BPR + (b & (BPR - 1)), (quarter >> 1) * BPR + (b / BPR)); };
+    if (tid < NB) s.mv[tid] = a.mv[(size_t)ctu * 85 + lbase + zof(tid)].y;
+    __syncthreads();
+    sa8d_slots<Px, N>(s, NB, [&](const int b) { return make_int2(rx0 + (b & (BPR - 1)) * N, ry0 + (b / BPR) * N); },
+                      reinterpret_cast<const Px*>(a.fref), a.frefStrideB / BPP, reinterpret_cast<const Px*>(a.fenc), a.fencStrideB / BPP, a.depth);
     if (tid < NB)
     {
         const int b = tid;
-        int sad;
-        if (N == 8) sad = sSum[b];
-        else if (N == 16) sad = sSum[b];
-        else sad = sSum[0] + sSum[1] + sSum[2] + sSum[3];
-        const int qx = (int16_t)(sMv[b] & 0xffff), qy = (int16_t)(sMv[b] >> 16);
+        const int sad = sa8d_slot_sum<N>(s, b);
+        const int qx = (int16_t)(s.mv[b] & 0xffff), qy = (int16_t)(s.mv[b] >> 16);
         // a component beyond the table prices as the table's last entry
         const int ix = min(abs(qx), a.bitSizesLen - 1), iy = min(abs(qy), a.bitSizesLen - 1);
         const int bits = a.baseBits + (int)(uint32_t)(a.bitSizes[ix] + a.bitSizes[iy] + 0.5f);

@@ -62,6 +62,12 @@ __device__ __forceinline__ int ip_zidx(int bx, int by)
     return (bx & 1) | ((by & 1) << 1) | ((bx & 2) << 1) | ((by & 2) << 2) | ((bx & 4) << 2) | ((by & 4) << 3);
 }
 
+// the inverse: block (x, y) of z index z
+__device__ __forceinline__ int2 ip_zpos(int z)
+{
+    return make_int2((z & 1) | ((z >> 1) & 2) | ((z >> 2) & 4), ((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4));
+}
+
 // sum of the absolute 8x8 Hadamard coefficients of a difference block whose row r sits in lane (lane & ~7) + r; valid in all eight lanes
 __device__ __forceinline__ int ip_hadamard8x8(int (&v)[8], const int lane)
 {

@@ -1,0 +1,240 @@
+// merge_decide.h - the merge arm of the sa8d choice of a P picture's blocks, on gfx950 (included at the end of tu_kernels.hip behind
+// inter_sa8d_cost.h: it prices every candidate with that file's sa8d_slots()).
+//
+// Analysis::checkMerge2Nx2N_rd0_4 at RD level 0 (source/encoder/analysis.cpp:2787-2838, 2870-2871) and the comparison of
+// Analysis::compressInterCU_rd0_4 (analysis.cpp:1650), per N x N block (N = 8 << level) of the TU stages' grid - one 2Nx2N CU each, CTUs
+// in raster order, blocks in z-order, one slice, a P slice with one reference, no temporal candidate:
+//   list   CUData::getInterMergeCandidates (common/cudata.cpp:1458-1712): A1 (left), B1 (above), B0 (above right), A0 (below left), B2
+//          (above left, only while count < 4); pruned pairs B1-A1, B0-B1, A0-A1, B2-A1, B2-B1 and no other (a B0 equal to A1 stays);
+//          returned once count == max_merge; the rest (0, 0).  A neighbour is available inside the picture and before the block in
+//          coding order; its motion is what it ENDED UP with (its candidate where it merged, its searched vector where it did not).
+//   price  dist = cu[].sa8d(fenc, predInterLumaPixel(fref, clipMv(mv_i))), bits = getTUBits(i, max_merge) = i + (i < max_merge - 1)
+//          (search.h:246-249), cost = dist + ((bits * lambda8 + 128) >> 8); the best with strict <: the lowest index wins a tie
+//   clipMv cudata.cpp:1915-1928 (from Predict::motionCompensation, predict.cpp:92): x into [-((64 + 8 + x0 - 1) << 2), (width + 8 - x0 - 1)
+//          << 2], y alike - for the prediction only; the CU keeps the unclipped vector, which later neighbours inherit.  A clipped vector
+//          reaches at most 71 + 3 samples before the picture and N + 10 behind it: with the planes' margins (96 / 80) the N + 7 rows and
+//          columns of a patch stay inside the padded plane at every level, so the kernel needs no further guard.
+//   choice the block keeps its searched vector iff inter_cost < merge cost (analysis.cpp:1650; a tie stays merge)
+//
+// Mapping: the candidate list reads motion only, never reconstruction, so the walk is the wave schedule of intra_picture.h without its
+// coding chain: wave = cx + 2 cy, one launch per wave, one workgroup of 256 threads per CTU of the wave, the CTU's blocks in z-order.
+// The CTU's motion field sits in LDS with a border of the left CTU's last column, the above CTU's last row and the two corners (read
+// from mv_out, which the earlier waves wrote); the blocks' searched records, inter costs and lambdas are fetched into LDS once, off the serial
+// chain.  Thread 0 builds the list, clips it and keeps one slot per distinct clipped vector -
+// evaluating equal vectors once is exact; the slots go through sa8d_slots() side by side (16 / 4 / 1 per pass at 8x8 / 16x16 / 32x32),
+// thread 0 prices the candidates and decides.
+#pragma once
+
+namespace x265hip {
+
+struct MergeArgs
+{
+    const uint8_t* fenc; long fencStrideB;
+    const uint8_t* fref; long frefStrideB;
+    const int2* mv;                     // [ctu*85] {cost, qx | qy << 16}: the searched records
+    const int32_t* interCost; long interCostStride;
+    int ctusW, ctusH, depth, qp, lambda8, maxMerge;
+    uint8_t* merge; uint8_t* mergeIdx;  // [ctu][blocks]
+    int2* mvOut; int2* mvPred;          // [ctu*85], the level's slots
+    int2* cost;                         // [ctu][blocks] {sa8d, cost} of the best merge candidate
+    int2* best;                         // optional [ctu][blocks]
+    const int8_t* qpMap;                // optional: the luma plane of tu_qp
+    const uint32_t* lambdaByQp;         // optional
+};
+
+__device__ __forceinline__ int merge_pack(const int qx, const int qy) { return (qx & 0xffff) | (int)((unsigned)qy << 16); }
+
+template <typename Px, int N>
+__global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const int wave, const int cyLo)
+{
+    constexpr int BPC = 64 / N, NPU = BPC * BPC, NB = Sa8dLds<N>::NB, BPP = sizeof(Px), FW = BPC + 2, FH = BPC + 1;
+    __shared__ Sa8dLds<N> s;
+    __shared__ int sField[FH * FW];               // motion at block (bx, by) of the CTU: [(by + 1) * FW + bx + 1]; row 0 / column 0 = the border
+    __shared__ int sCand[5], sSlotOf[5], sSlotMv[5], sSlotSad[5], sSlots;
+    __shared__ int2 sSearched[NPU];
+    __shared__ int sInter[NPU], sLambda[NPU];
+
+    const int tid = threadIdx.x;
+    const int cyb = cyLo + (int)blockIdx.x, cxb = wave - 2 * cyb;
+    const int ctu = cyb * a.ctusW + cxb;
+    const int blocksW = a.ctusW * BPC, blocksH = a.ctusH * BPC;
+    const int width = a.ctusW * 64, height = a.ctusH * 64;
+    const int lbase = N == 8 ? 0 : (N == 16 ? 64 : 80);
+    const Px* fref = reinterpret_cast<const Px*>(a.fref);
+    const Px* fenc = reinterpret_cast<const Px*>(a.fenc);
+    const long rst = a.frefStrideB / BPP, fst = a.fencStrideB / BPP;
+
+    // ---- the border of the motion field: the final motion of the blocks around the CTU that earlier waves left in mv_out ----------------
+    if (tid < FW + BPC)
+    {
+        const int rx = tid < FW ? tid - 1 : -1, ry = tid < FW ? -1 : tid - FW;                  // relative to the CTU's first block
+        const int gbx = cxb * BPC + rx, gby = cyb * BPC + ry;
+        int v = 0;
+        if (gbx >= 0 && gby >= 0 && gbx < blocksW)
+        {
+            const int ncx = gbx / BPC, ncy = gby / BPC;
+            v = a.mvOut[(size_t)(ncy * a.ctusW + ncx) * 85 + lbase + ip_zidx(gbx - ncx * BPC, gby - ncy * BPC)].y;
+        }
+        sField[(ry + 1) * FW + rx + 1] = v;
+    }
+    // ---- what the decisions read of the CTU's own blocks, off the serial chain: the searched record, the inter cost, the block's lambda ---
+    if (tid < NPU)
+    {
+        const int z = tid;
+        const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
+        sSearched[z] = a.mv[(size_t)ctu * 85 + lbase + z];
+        sInter[z] = a.interCost[((size_t)ctu * NPU + z) * a.interCostStride];
+        int lambda8 = a.lambda8;
+        if (a.lambdaByQp)
+        {
+            int qp = a.qp;
+            if (a.qpMap) qp = clip3(0, 51 + 6 * (a.depth - 8), (int)a.qpMap[(size_t)((cyb * 64 + byz * N) >> 3) * (a.ctusW * 8) + ((cxb * 64 + bxz * N) >> 3)]);
+            const uint32_t l = a.lambdaByQp[qp];
+            lambda8 = (int)(l < (1u << 24) ? l : (1u << 24));
+        }
+        sLambda[z] = lambda8;
+    }
+    __syncthreads();
+
+    // thread 0: the candidate list of block z from the motion field, clipped, one slot per distinct clipped vector
+    auto build = [&](const int z)
+    {
+        const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
+        const int gbx = cxb * BPC + bxz, gby = cyb * BPC + byz;
+        const int x0 = gbx * N, y0 = gby * N;
+        // getPULeft / getPUAbove / getPUAboveRight / getPUBelowLeft / getPUAboveLeft on this grid: inside the picture and already coded
+        auto available = [&](const int nbx, const int nby)
+        {
+            if (nbx < 0 || nby < 0 || nbx >= blocksW || nby >= blocksH) return false;
+            const int ncx = nbx / BPC, ncy = nby / BPC;
+            if (ncx != cxb || ncy != cyb) return ncy * a.ctusW + ncx < ctu;
+            return ip_zidx(nbx - ncx * BPC, nby - ncy * BPC) < z;
+        };
+        auto motion = [&](const int dx, const int dy) { return sField[(byz + dy + 1) * FW + bxz + dx + 1]; };
+        const bool avA1 = available(gbx - 1, gby), avB1 = available(gbx, gby - 1), avB0 = available(gbx + 1, gby - 1);
+        const bool avA0 = available(gbx - 1, gby + 1), avB2 = available(gbx - 1, gby - 1);
+        const int mA1 = avA1 ? motion(-1, 0) : 0, mB1 = avB1 ? motion(0, -1) : 0, mB0 = avB0 ? motion(1, -1) : 0;
+        const int mA0 = avA0 ? motion(-1, 1) : 0, mB2 = avB2 ? motion(-1, -1) : 0;
+        const int num = a.maxMerge;
+        int count = 0;
+        if (avA1) sCand[count++] = mA1;                                                                  // cudata.cpp:1495-1510
+        if (count < num && avB1 && (!avA1 || mA1 != mB1)) sCand[count++] = mB1;                          // :1517-1532
+        if (count < num && avB0 && (!avB1 || mB1 != mB0)) sCand[count++] = mB0;                          // :1537-1551
+        if (count < num && avA0 && (!avA1 || mA1 != mA0)) sCand[count++] = mA0;                          // :1556-1570
+        if (count < num && count < 4 && avB2 && (!avA1 || mA1 != mB2) && (!avB1 || mB1 != mB2)) sCand[count++] = mB2;   // :1573-1593
+        while (count < num) sCand[count++] = 0;                                                          // the zero candidates, refIdx 0
+        // clipMv (cudata.cpp:1915-1928)
+        const int xmin = -((64 + 8 + x0 - 1) << 2), xmax = (width + 8 - x0 - 1) << 2;
+        const int ymin = -((64 + 8 + y0 - 1) << 2), ymax = (height + 8 - y0 - 1) << 2;
+        int slots = 0;
+        for (int i = 0; i < num; i++)
+        {
+            const int c = sCand[i];
+            const int qx = min(xmax, max(xmin, (int)(int16_t)(c & 0xffff))), qy = min(ymax, max(ymin, (int)(int16_t)(c >> 16)));
+            const int cl = merge_pack(qx, qy);
+            int k = 0;
+            while (k < slots && sSlotMv[k] != cl) k++;
+            if (k == slots) sSlotMv[slots++] = cl;
+            sSlotOf[i] = k;
+        }
+        sSlots = slots;
+    };
+    if (tid == 0) build(0);
+    __syncthreads();
+
+    for (int z = 0; z < NPU; z++)
+    {
+        const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
+        const int x0 = (cxb * BPC + bxz) * N, y0 = (cyb * BPC + byz) * N;
+        const int slots = sSlots;
+        for (int base = 0; base < slots; base += NB)
+        {
+            const int nAct = min(NB, slots - base);
+            if (tid < nAct) s.mv[tid] = sSlotMv[base + tid];
+            __syncthreads();
+            sa8d_slots<Px, N>(s, nAct, [&](const int) { return make_int2(x0, y0); }, fref, rst, fenc, fst, a.depth);
+            if (tid < nAct) sSlotSad[base + tid] = sa8d_slot_sum<N>(s, tid);
+            __syncthreads();
+        }
+        if (tid == 0)
+        {
+            const int lambda8 = sLambda[z];
+            const int num = a.maxMerge;
+            int bestI = 0, bestSad = 0;
+            long long bestCost = 0;
+            for (int i = 0; i < num; i++)
+            {
+                const int sad = sSlotSad[sSlotOf[i]];
+                const int bits = i + (i < num - 1 ? 1 : 0);                                                  // getTUBits, search.h:246-249
+                const long long cost = (long long)sad + (((long long)bits * lambda8 + 128) >> 8);           // calcRdSADCost, rdcost.h:148-153
+                if (i == 0 || cost < bestCost) { bestI = i; bestSad = sad; bestCost = cost; }                // analysis.cpp:2833
+            }
+            const size_t blk = (size_t)ctu * NPU + z, rec = (size_t)ctu * 85 + lbase + z;
+            const int2 searched = sSearched[z];
+            const int ic = sInter[z];
+            const bool inter = (long long)ic < bestCost;                                                     // analysis.cpp:1650: a tie stays merge
+            const int finalMv = inter ? searched.y : sCand[bestI];
+            a.merge[blk] = inter ? 0 : 1;
+            a.mergeIdx[blk] = inter ? 0 : (uint8_t)bestI;
+            a.mvOut[rec] = make_int2(inter ? searched.x : (int)bestCost, finalMv);
+            a.mvPred[rec] = make_int2(inter ? searched.x : (int)bestCost, inter ? searched.y : sSlotMv[sSlotOf[bestI]]);
+            a.cost[blk] = make_int2(bestSad, (int)bestCost);
+            if (a.best) a.best[blk] = inter ? make_int2(-1, ic) : make_int2(bestSad, (int)bestCost);
+            sField[(byz + 1) * FW + bxz + 1] = finalMv;
+            if (z + 1 < NPU) build(z + 1);                                                                   // the next block's list: no barrier in between
+        }
+        __syncthreads();
+    }
+}
+
+} // namespace x265hip
+
+extern "C" int x265hip_merge_decide(const x265hip_merge_decide_params* p, void* stream)
+{
+    using namespace x265hip;
+    // argument checks first: they need no device
+    if (!p || !p->fenc || !p->fref || !p->mv || !p->inter_cost || !p->merge || !p->merge_idx || !p->mv_out || !p->mv_pred || !p->cost)
+    { set_error("merge_decide: NULL operand"); return X265HIP_EINVAL; }
+    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("merge_decide: depth %d", p->depth); return X265HIP_EINVAL; }
+    if (p->level < 0 || p->level > 2) { set_error("merge_decide: level %d (0..2 = 8x8, 16x16, 32x32)", p->level); return X265HIP_EINVAL; }
+    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("merge_decide: width/height must be multiples of 64"); return X265HIP_EINVAL; }
+    if (p->fenc_stride < p->width || p->fref_stride < p->width) { set_error("merge_decide: stride below the width"); return X265HIP_EINVAL; }
+    if (p->qp < 0 || p->qp > 51 + 6 * (p->depth - 8)) { set_error("merge_decide: qp %d out of range", p->qp); return X265HIP_EINVAL; }
+    // at most 4 bits and lambda8 <= 2^24 keep the rate term below 2^19 and the cost inside int32
+    if (p->lambda8 < 0 || p->lambda8 > (1 << 24)) { set_error("merge_decide: lambda8 %d out of [0, 2^24]", p->lambda8); return X265HIP_EINVAL; }
+    if (p->max_merge < 1 || p->max_merge > 5) { set_error("merge_decide: max_merge %d out of 1..5", p->max_merge); return X265HIP_EINVAL; }
+    if (p->inter_cost_stride < 1) { set_error("merge_decide: inter_cost_stride %ld below 1", (long)p->inter_cost_stride); return X265HIP_EINVAL; }
+    // the walk reads a block's searched vector from mv and its neighbours' final motion from mv_out: one array for both would change what a
+    // second run sees
+    if (p->mv_out == p->mv || p->mv_pred == p->mv || p->mv_out == p->mv_pred)
+    { set_error("merge_decide: mv_out and mv_pred must not alias mv or each other"); return X265HIP_EINVAL; }
+    int rc = ensure_device();
+    if (rc) return rc;
+
+    const int bpp = p->depth == 8 ? 1 : 2;
+    MergeArgs a = {};
+    a.fenc = (const uint8_t*)p->fenc; a.fencStrideB = (long)p->fenc_stride * bpp;
+    a.fref = (const uint8_t*)p->fref; a.frefStrideB = (long)p->fref_stride * bpp;
+    a.mv = (const int2*)p->mv; a.interCost = p->inter_cost; a.interCostStride = (long)p->inter_cost_stride;
+    a.ctusW = p->width / 64; a.ctusH = p->height / 64; a.depth = p->depth; a.qp = p->qp; a.lambda8 = p->lambda8; a.maxMerge = p->max_merge;
+    a.merge = p->merge; a.mergeIdx = p->merge_idx; a.mvOut = (int2*)p->mv_out; a.mvPred = (int2*)p->mv_pred;
+    a.cost = (int2*)p->cost; a.best = (int2*)p->best; a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
+    hipStream_t s = (hipStream_t)stream;
+    const int waves = a.ctusW + 2 * (a.ctusH - 1);
+    for (int w = 0; w < waves; w++)
+    {
+        // the CTUs of wave w: cy from cyLo to cyHi, cx = w - 2 cy
+        const int over = w - (a.ctusW - 1);
+        const int cyLo = over > 0 ? (over + 1) / 2 : 0, cyHi = w / 2 < a.ctusH - 1 ? w / 2 : a.ctusH - 1;
+        const int n = cyHi - cyLo + 1;
+        if (n <= 0) continue;                  // a picture one CTU wide has no CTU in its odd waves
+#define GO(PX) do { \
+        if (p->level == 0) hipLaunchKernelGGL((merge_decide_kernel<PX, 8>), dim3(n), dim3(256), 0, s, a, w, cyLo); \
+        else if (p->level == 1) hipLaunchKernelGGL((merge_decide_kernel<PX, 16>), dim3(n), dim3(256), 0, s, a, w, cyLo); \
+        else hipLaunchKernelGGL((merge_decide_kernel<PX, 32>), dim3(n), dim3(256), 0, s, a, w, cyLo); } while (0)
+        if (p->depth == 8) GO(uint8_t); else GO(uint16_t);
+#undef GO
+    }
+    X265HIP_TRY(hipGetLastError());
+    return 0;
+}

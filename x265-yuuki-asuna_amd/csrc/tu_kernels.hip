@@ -1446,3 +1446,6 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
 
 // the sa8d choice of a B picture's blocks between one list and both (x265hip_b_sa8d_decide): the geometry of inter_sa8d_cost.h
 #include "b_sa8d_decide.h"
+
+// the merge arm of a P picture's sa8d choice (x265hip_merge_decide): sa8d_slots of inter_sa8d_cost.h, the wave schedule of intra_picture.h
+#include "merge_decide.h"

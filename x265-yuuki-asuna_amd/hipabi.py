@@ -206,6 +206,22 @@ class BSa8dParams(ctypes.Structure):
     ]
 
 
+class MergeDecideParams(ctypes.Structure):
+    """x265hip_merge_decide_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("qp", ctypes.c_int), ("lambda8", ctypes.c_int), ("max_merge", ctypes.c_int),
+        ("fenc", ctypes.c_void_p), ("fenc_stride", ctypes.c_ssize_t),
+        ("fref", ctypes.c_void_p), ("fref_stride", ctypes.c_ssize_t),
+        ("mv", ctypes.c_void_p),
+        ("inter_cost", ctypes.c_void_p), ("inter_cost_stride", ctypes.c_ssize_t),
+        ("qp_map", ctypes.c_void_p), ("lambda8_by_qp", ctypes.c_void_p),
+        ("merge", ctypes.c_void_p), ("merge_idx", ctypes.c_void_p),
+        ("mv_out", ctypes.c_void_p), ("mv_pred", ctypes.c_void_p),
+        ("cost", ctypes.c_void_p), ("best", ctypes.c_void_p),
+    ]
+
+
 class LowresInitParams(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_int), ("src", ctypes.c_void_p), ("src_stride", ctypes.c_ssize_t),
                 ("plane", ctypes.c_void_p * 4), ("stride", ctypes.c_ssize_t),
@@ -662,6 +678,27 @@ def inter_sa8d_cost(depth, width, height, level, fenc, fenc_stride, fenc_off, fr
     f = lib().x265hip_inter_sa8d_cost
     f.argtypes = [ctypes.POINTER(InterSa8dCostParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_inter_sa8d_cost")
+
+
+def merge_decide(depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge,
+                 merge_idx, mv_out, mv_pred, cost, best=None, inter_cost_stride=2, inter_cost_offset=1, qp=0, qp_map=None, lambda8_by_qp=None, stream=None):
+    """x265hip_merge_decide: the merge candidates of every block of a P picture in coding order, priced by sa8d, against the inter candidate
+    (Analysis::checkMerge2Nx2N_rd0_4 at RD level 0 and the comparison of compressInterCU_rd0_4).  mv: the searched records; inter_cost:
+    device int32 tensor, the block's word at element inter_cost_offset + block * inter_cost_stride (the defaults read the cost word of
+    inter_sa8d_cost's pairs); merge / merge_idx: device uint8 [ctu][blocks] out; mv_out / mv_pred: device int32 records out (the CU's motion
+    / what the TU stages predict from; neither may be mv); cost (and best): device int32 [ctu][blocks][2] out; qp_map: the LUMA plane of tu_qp."""
+    es = 1 if depth == 8 else 2
+    p = MergeDecideParams()
+    p.depth, p.width, p.height, p.level, p.qp, p.lambda8, p.max_merge = depth, width, height, level, int(qp), int(lambda8), int(max_merge)
+    p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
+    p.fref, p.fref_stride = fref.data_ptr() + fref_off * es, fref_stride
+    p.mv, p.inter_cost, p.inter_cost_stride = mv.data_ptr(), inter_cost.data_ptr() + 4 * int(inter_cost_offset), int(inter_cost_stride)
+    p.qp_map, p.lambda8_by_qp = _p(qp_map), _p(lambda8_by_qp)
+    p.merge, p.merge_idx, p.mv_out, p.mv_pred, p.cost, p.best = merge.data_ptr(), merge_idx.data_ptr(), mv_out.data_ptr(), mv_pred.data_ptr(), cost.data_ptr(), _p(best)
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_merge_decide
+    f.argtypes = [ctypes.POINTER(MergeDecideParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_merge_decide")
 
 
 def b_sa8d_bits(nrefs=(1, 1), refs=(0, 0), list_sel_bits=(3, 3, 5)):

@@ -1966,6 +1966,121 @@ class IntraPFramePipeline(_PictureStep):
         return out
 
 
+class MergeDecide:
+    """The merge arm of a P picture's sa8d choice (x265hip_merge_decide; reference Analysis::checkMerge2Nx2N_rd0_4 at RD level 0,
+    analysis.cpp:2787-2838, CUData::getInterMergeCandidates, cudata.cpp:1458-1712, and the comparison of compressInterCU_rd0_4,
+    analysis.cpp:1650): per block, in coding order, the candidates its neighbours' final motion gives, priced by sa8d; the block merges
+    unless its inter candidate is strictly cheaper.  Owns merge / merge_idx uint8 [ctu][blocks], mv_out (the CUs' motion, unclipped) and
+    mv_pred (what the TU stages predict from) int32 [ctu*85][2], cost and best int32 [ctu][blocks][2]."""
+
+    def __init__(self, nctu, w64, h64, depth, level, device, max_merge=3, lambda8=1024, qp=0):
+        import torch
+        if not 1 <= int(max_merge) <= 5:
+            raise ValueError("MergeDecide: max_merge %r outside 1..5" % (max_merge,))
+        self.nctu, self.w64, self.h64, self.depth, self.level, self.qp = nctu, w64, h64, depth, level, qp
+        self.max_merge, self.lambda8 = int(max_merge), int(lambda8)
+        self.nblk = (64 >> (3 + level)) ** 2
+        self.waves = hipabi.intra_picture_waves(w64, h64)
+        nb = nctu * self.nblk
+        self.merge = torch.zeros(nb, dtype=torch.uint8, device=device)
+        self.merge_idx = torch.zeros(nb, dtype=torch.uint8, device=device)
+        self.mv_out = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device)
+        self.mv_pred = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device)
+        self.cost = torch.zeros(nb * 2, dtype=torch.int32, device=device)
+        self.best = torch.zeros(nb * 2, dtype=torch.int32, device=device)
+        self.qp_map, self.lambda8_by_qp = None, None          # as InterSa8dCost's
+
+    def run(self, cur: DevicePicture, ref: DevicePicture, mv, inter_cost, stream=None, inter_cost_stride=2, inter_cost_offset=1):
+        """mv: the searched records; inter_cost: InterSa8dCost.cost (the pairs; the defaults read their cost word)."""
+        hipabi.merge_decide(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, cur.org, ref.t, ref.stride, ref.org, mv, inter_cost,
+                            self.lambda8, self.max_merge, self.merge, self.merge_idx, self.mv_out, self.mv_pred, self.cost, best=self.best,
+                            inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map,
+                            lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+
+    def skip_flags(self, rc, rc_c=None):
+        """uint8 [ctu][blocks]: a merged block none of whose planes has a coded coefficient (encodeResidue sets MODE_SKIP there,
+        analysis.cpp:3358-3359).  rc (and rc_c = [Cb, Cr]): the TU stages that coded the picture from mv_pred."""
+        import torch
+        skip = (self.merge != 0) & (rc.num_sig == 0)
+        for r in (rc_c or ()):
+            skip = skip & (r.num_sig == 0)
+        return skip.to(torch.uint8)
+
+    def checksum(self):
+        import torch
+        return {"merge": int(self.merge.to(torch.int64).sum().item()), "merge_idx": int(self.merge_idx.to(torch.int64).sum().item()),
+                "mv_out": int(self.mv_out.to(torch.int64).sum().item()), "mv_pred": int(self.mv_pred.to(torch.int64).sum().item()),
+                "merge_cost": int(self.cost.to(torch.int64).sum().item())}
+
+
+class MergePFramePipeline(_PictureStep):
+    """One P picture whose blocks may merge: search -> sub-pel refinement -> InterSa8dCost on the searched vectors -> MergeDecide -> inter TU
+    stage (luma + chroma) on mv_pred -> skip flags -> boundary strengths from mv_out + luma / chroma deblocking -> the shared loop-filter
+    tail.  The candidate list reads motion only, so one walk in coding order before the coding is the reference's result (DESIGN.md
+    section 19).  run(cur, ref) / final_planes() as FramePipeline's: MiniGop(p_step=...) takes it.  The constructor switches mean what they
+    mean in IntraPFramePipeline; max_merge: --max-merge (the reference's default 3, param.cpp:199)."""
+
+    def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
+                 sign_hide=False, sao_rdo=None, lambda8=1024, base_bits=2, max_merge=3):
+        from .pipeline import MotionSearch, SubpelRefine
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
+        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
+        self.ms = MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True)
+        self.sp = SubpelRefine(self.ms, subme, device)
+        self.rc = InterRecon(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        qpc = chroma_quant_qp(qp, depth)
+        if chroma:
+            self.rc_c = [InterReconChroma(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
+        self.ic = InterSa8dCost(self.nctu, w64, h64, depth, level, device, rng=rng, base_bits=base_bits, lambda8=lambda8, qp=qp)
+        self.md = MergeDecide(self.nctu, w64, h64, depth, level, device, max_merge=max_merge, lambda8=lambda8, qp=qp)
+        self.skip = None
+
+    def set_qp_maps(self, maps, lambda8_by_qp=None):
+        """As IntraPFramePipeline.set_qp_maps: the maps reach the TU stages, the deblocking stage and both candidates' rate terms."""
+        self._set_qp_maps(maps, self.rc, self.rc_c if self.chroma else [])
+        self.ic.qp_map = self.md.qp_map = None if maps is None else maps.tu_qp[0]
+        self.ic.lambda8_by_qp = self.md.lambda8_by_qp = None if maps is None else lambda8_by_qp
+
+    def run(self, cur: DevicePicture, ref: DevicePicture, mark=None):
+        """ref: the reference picture (extended borders, with chroma its Cb / Cr planes); returns the luma plane of the coded picture.
+        mark(name), if given, is called after every stage."""
+        mark = mark or (lambda name: None)
+        self._qp_maps_run_check()
+        self._alloc_planes(cur)
+        self.ms.reset()
+        self.ms.search(cur, ref)
+        mark("me")
+        self.sp.run(cur, ref)
+        mv = self.sp.out
+        mark("subpel")
+        self.ic.run(cur, ref, mv)
+        mark("inter_cost")
+        self.md.run(cur, ref, mv, self.ic.cost)
+        mark("merge")
+        self.rc.run(cur, ref, self.recon, self.md.mv_pred)
+        mark("recon")
+        if self.chroma:
+            InterReconChroma.run_pair(self.rc_c, cur.c, ref.c, self.recon_c, cur.stride_c, cur.org_c, self.md.mv_pred)
+            mark("recon_chroma")
+        self.skip = self.md.skip_flags(self.rc, self.rc_c if self.chroma else None)
+        mark("skip")
+        if self.db is not None:
+            self.db.run(self.recon, cur, self.md.mv_out, self.rc.num_sig)
+        return self._filter_tail(cur, mark)
+
+    def checksum(self):
+        import torch
+        out = {}
+        out.update(self.ms.checksum())
+        out.update(self.sp.checksum())
+        out.update(self.ic.checksum())
+        out.update(self.md.checksum())
+        out.update(self.rc.checksum())
+        out["skip"] = int(self.skip.to(torch.int64).sum().item())
+        out["recon"] = int(self.final.to(torch.int64).sum().item())
+        return out
+
+
 class BSa8dDecide:
     """The sa8d choice of a B picture's blocks between the cheaper single list and both (x265hip_b_sa8d_decide; reference
     Analysis::compressInterCU_rd0_4 with checkInter_rd0_4 and checkBidir2Nx2N, analysis.cpp:1649-1655, 3059-3071, 3145-3270).  Owns what

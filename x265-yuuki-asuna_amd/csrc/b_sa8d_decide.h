@@ -1,5 +1,5 @@
 // b_sa8d_decide.h - the sa8d choice of a B picture's 2Nx2N blocks between one list and both, on gfx950 (included at the end of
-// tu_kernels.hip behind inter_sa8d_cost.h: the same luma taps, ip_hadamard8x8 and block geometry).
+// tu_kernels.hip behind inter_sa8d_cost.h: the same luma taps, sa8d_tile_sums and block geometry).
 //
 // Analysis::compressInterCU_rd0_4 at RD level <= 2 for a B slice (source/encoder/analysis.cpp:1649-1671), per N x N block (N = 8 << level):
 //   l    = the cheaper list of Search::predInterSearch: c0 <= c1 ? 0 : 1 with c_l = rec_l.cost + dir_cost[l]          (search.cpp:2611)
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) b_sa8d_decide_kernel(BSa8dArgs a)
     const int cx = ctu % a.ctusW, cy = ctu / a.ctusW;
     const int rx0 = cx * 64 + (quarter & 1) * 32, ry0 = cy * 64 + (quarter >> 1) * 32;         // the quarter's first luma sample
     const int maxVal = (1 << a.depth) - 1, headRoom = 14 - a.depth;
-    const int lbase = N == 8 ? 0 : (N == 16 ? 64 : 80);
+    const int lbase = level_record_base<N>();
     // block b of the quarter (raster order inside it) -> its z index inside the CTU
     auto zof = [&](const int b) { return ip_zidx((quarter & 1) * BPR + (b & (BPR - 1)), (quarter >> 1) * BPR + (b / BPR)); };
     if (tid < 2 * NB) sRec[tid / NB][tid % NB] = a.mv[tid / NB][(size_t)ctu * 85 + lbase + zof(tid % NB)];
@@ -138,48 +138,17 @@ __global__ void __launch_bounds__(256) b_sa8d_decide_kernel(BSa8dArgs a)
         __syncthreads();                                        // patch / immed are free for list 1; after list 1 the planes are complete
     }
     // ---- 3 x 16 8x8 Hadamard transforms: plane 0 and 2 on wavefronts 0 and 1, plane 1 on wavefronts 2 and 3 ----------------------------
-    for (int k = tid >> 7; k < 3; k += 2)
-    {
-        const int t = tid & 127, row = t & 7, q = (t >> 3) & 3, u = t >> 5;
-        const int tx = (u & 1) * 2 + (q & 1), ty = (u >> 1) * 2 + (q >> 1);
-        int d[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) d[i] = diff[k][(ty * 8 + row) * 32 + tx * 8 + i];
-        int raw = ip_hadamard8x8(d, lane);
-        if (N == 8) { if (row == 0) sSum[k][ty * 4 + tx] = (raw + 2) >> 2; }                   // the block at (tx, ty) of the quarter
-        else
-        {
-            raw += __shfl_xor(raw, 8, 64); raw += __shfl_xor(raw, 16, 64);
-            if ((t & 31) == 0) sSum[k][u] = (raw + 2) >> 2;
-        }
-    }
+    for (int k = tid >> 7; k < 3; k += 2) sa8d_tile_sums<N>(diff[k], sSum[k], tid & 127, lane);
     __syncthreads();
     if (tid < NB)
     {
         const int b = tid;
         int sad[3];
 #pragma unroll
-        for (int k = 0; k < 3; k++) sad[k] = N == 32 ? sSum[k][0] + sSum[k][1] + sSum[k][2] + sSum[k][3] : sSum[k][b];
-        // BitCost::bitcost against the predictor (0, 0); a component beyond the table prices as the table's last entry
-        auto bitcost = [&](const int w)
-        {
-            const int qx = (int16_t)(w & 0xffff), qy = (int16_t)(w >> 16);
-            const int ix = min(abs(qx), a.bitSizesLen - 1), iy = min(abs(qy), a.bitSizesLen - 1);
-            return (int)(uint32_t)(a.bitSizes[ix] + a.bitSizes[iy] + 0.5f);
-        };
-        int lambda8 = a.lambda8;
-        if (a.lambdaByQp)
-        {
-            int qp = a.qp;
-            if (a.qpMap)
-            {
-                const int gx8 = (rx0 + (b & (BPR - 1)) * N) >> 3, gy8 = (ry0 + (b / BPR) * N) >> 3;
-                qp = clip3(0, 51 + 6 * (a.depth - 8), (int)a.qpMap[(size_t)gy8 * (a.ctusW * 8) + gx8]);
-            }
-            const uint32_t lq = a.lambdaByQp[qp];
-            lambda8 = (int)(lq < (1u << 24) ? lq : (1u << 24));
-        }
-        auto rate = [&](const int bits) { return ((long long)bits * lambda8 + 128) >> 8; };          // getCost, rdcost.h
+        for (int k = 0; k < 3; k++) sad[k] = sa8d_slot_sum<N>(sSum[k], b);
+        auto bitcost = [&](const int w) { return mv_bitcost(a.bitSizes, a.bitSizesLen, w); };
+        const int lambda8 = block_lambda8(a.lambda8, a.lambdaByQp, a.qpMap, a.qp, a.depth, a.ctusW, (rx0 + (b & (BPR - 1)) * N) >> 3, (ry0 + (b / BPR) * N) >> 3);
+        auto rate = [&](const int bits) { return rd_sad_rate(bits, lambda8); };
         const int2 r0 = sRec[0][b], r1 = sRec[1][b];
         const int l = single_list(b);
         const int uni = (int)(sad[0] + rate(a.baseBits[l] + bitcost(l ? r1.y : r0.y)));
@@ -221,21 +190,15 @@ extern "C" int x265hip_b_sa8d_decide(const x265hip_b_sa8d_params* p, void* strea
 {
     using namespace x265hip;
     // argument checks first: they need no device
-    if (!p || !p->fenc || !p->fref0 || !p->fref1 || !p->mv0 || !p->mv1 || !p->bit_sizes || !p->dir || !p->mv0_out || !p->mv1_out || !p->cost)
-    { set_error("b_sa8d_decide: NULL operand"); return X265HIP_EINVAL; }
-    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("b_sa8d_decide: depth %d", p->depth); return X265HIP_EINVAL; }
-    if (p->level < 0 || p->level > 2) { set_error("b_sa8d_decide: level %d (0..2 = 8x8, 16x16, 32x32)", p->level); return X265HIP_EINVAL; }
-    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("b_sa8d_decide: width/height must be multiples of 64"); return X265HIP_EINVAL; }
-    if (p->fenc_stride < p->width || p->fref_stride < p->width) { set_error("b_sa8d_decide: stride below the width"); return X265HIP_EINVAL; }
-    if (p->qp < 0 || p->qp > 51 + 6 * (p->depth - 8)) { set_error("b_sa8d_decide: qp %d out of range", p->qp); return X265HIP_EINVAL; }
+    if (decision_record_refused("b_sa8d_decide", p, !p || !p->fenc || !p->fref0 || !p->fref1 || !p->mv0 || !p->mv1 || !p->bit_sizes || !p->dir || !p->mv0_out ||
+                                !p->mv1_out || !p->cost)) return X265HIP_EINVAL;
     // base_bits[l] <= 4096, |bi_bits_delta| <= 4096 (+ at most 4 * 33 bits of two vectors) and lambda8 <= 2^24 keep every rate term below
     // 2^30 and every cost inside int32
     for (int l = 0; l < 2; l++)
         if (p->base_bits[l] < 0 || p->base_bits[l] > 4096) { set_error("b_sa8d_decide: base_bits[%d] %d out of [0, 4096]", l, p->base_bits[l]); return X265HIP_EINVAL; }
     if (p->bi_bits_delta < -4096 || p->bi_bits_delta > 4096 || p->base_bits[0] + p->base_bits[1] + p->bi_bits_delta < 0)
     { set_error("b_sa8d_decide: bi_bits_delta %d out of [-4096, 4096] or below -(base_bits[0] + base_bits[1])", p->bi_bits_delta); return X265HIP_EINVAL; }
-    if (p->lambda8 < 0 || p->lambda8 > (1 << 24)) { set_error("b_sa8d_decide: lambda8 %d out of [0, 2^24]", p->lambda8); return X265HIP_EINVAL; }
-    if (p->bit_sizes_len < 1) { set_error("b_sa8d_decide: bit_sizes_len %d below 1", p->bit_sizes_len); return X265HIP_EINVAL; }
+    if (bit_sizes_len_refused("b_sa8d_decide", p->bit_sizes_len)) return X265HIP_EINVAL;
     const int nctu = (p->width / 64) * (p->height / 64);
     if (b_sa8d_records_alias(nctu, p->mv0, p->mv1, p->mv0_out, p->mv1_out))
     { set_error("b_sa8d_decide: mv0_out / mv1_out must not alias mv0 / mv1 or each other"); return X265HIP_EINVAL; }
@@ -256,12 +219,8 @@ extern "C" int x265hip_b_sa8d_decide(const x265hip_b_sa8d_params* p, void* strea
     a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(a.ctusW * a.ctusH * 4);
-#define GO(PX) do { \
-    if (p->level == 0) hipLaunchKernelGGL((b_sa8d_decide_kernel<PX, 8>), grid, dim3(256), 0, s, a); \
-    else if (p->level == 1) hipLaunchKernelGGL((b_sa8d_decide_kernel<PX, 16>), grid, dim3(256), 0, s, a); \
-    else hipLaunchKernelGGL((b_sa8d_decide_kernel<PX, 32>), grid, dim3(256), 0, s, a); } while (0)
-    if (p->depth == 8) GO(uint8_t); else GO(uint16_t);
-#undef GO
+    for_depth_level(p->depth, p->level, [&](auto px, auto size)
+    { hipLaunchKernelGGL((b_sa8d_decide_kernel<decltype(px), decltype(size)::value>), grid, dim3(256), 0, s, a); });
     X265HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,5 +1,5 @@
 // inter_sa8d_cost.h - the inter candidate's sa8d cost per block of a P picture, on gfx950 (included at the end of tu_kernels.hip behind
-// intra_picture.h: it predicts with that file's luma taps and transforms with ip_hadamard8x8).
+// intra_picture.h: it predicts with that file's luma taps and transforms with sa8d_tile_sums of decision_common.h).
 //
 // Analysis::checkInter_rd0_4 at RD level <= 2 (source/encoder/analysis.cpp:3023-3071; m_bChromaSa8d is off, so luma only), per N x N block
 // (N = 8 << level) of the TU stages' grid:
@@ -43,7 +43,7 @@ struct Sa8dLds
 
 // sa8d of the luma prediction of the first nAct slots (nAct <= NB): slot b predicts from fref at pos(b) (the block's first luma sample, int2)
 // displaced by s.mv[b] (qx | qy << 16) and is compared with fenc at pos(b).  s.mv must be visible to the workgroup on entry; s.sum is on
-// return (read it with sa8d_slot_sum).  All 256 threads call it.  inter_sa8d_cost_kernel and merge_decide_kernel (merge_decide.h) share it,
+// return (read it with sa8d_slot_sum<N>(s.sum, b)).  All 256 threads call it.  inter_sa8d_cost_kernel and merge_decide_kernel (merge_decide.h) share it,
 // so the two price a vector alike.
 template <typename Px, int N, class Pos>
 __device__ __forceinline__ void sa8d_slots(Sa8dLds<N>& s, const int nAct, const Pos pos, const Px* fref, const long rst, const Px* fenc, const long fst,
@@ -105,31 +105,10 @@ __device__ __forceinline__ void sa8d_slots(Sa8dLds<N>& s, const int nAct, const 
         s.diff[i] = (int16_t)((int)fenc[(long)(o.y + y) * fst + o.x + x] - v);
     }
     __syncthreads();
-    // ---- sixteen 8x8 Hadamard transforms on wavefronts 0 and 1: unit u = 16x16 (ux, uy), tile q inside it, row r -----------------------
+    // ---- sixteen 8x8 Hadamard transforms on wavefronts 0 and 1 -------------------------------------------------------------------------
     // (the tiles of a slot at or beyond nAct transform whatever the difference array holds; nothing reads their sums)
-    if (tid < 128)
-    {
-        const int row = tid & 7, q = (tid >> 3) & 3, u = tid >> 5;
-        const int tx = (u & 1) * 2 + (q & 1), ty = (u >> 1) * 2 + (q >> 1);
-        int d[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) d[i] = s.diff[(ty * 8 + row) * 32 + tx * 8 + i];
-        int raw = ip_hadamard8x8(d, lane);
-        if (N == 8) { if (row == 0) s.sum[ty * 4 + tx] = (raw + 2) >> 2; }                      // the block at (tx, ty) of the quarter
-        else
-        {
-            raw += __shfl_xor(raw, 8, 64); raw += __shfl_xor(raw, 16, 64);
-            if ((tid & 31) == 0) s.sum[u] = (raw + 2) >> 2;
-        }
-    }
+    if (tid < 128) sa8d_tile_sums<N>(s.diff, s.sum, tid, lane);
     __syncthreads();
-}
-
-// slot b's sa8d after sa8d_slots: an 8x8 or 16x16 slot is one rounded sum, the 32x32 slot the sum of its four units
-template <int N>
-__device__ __forceinline__ int sa8d_slot_sum(const Sa8dLds<N>& s, const int b)
-{
-    return N == 32 ? s.sum[0] + s.sum[1] + s.sum[2] + s.sum[3] : s.sum[b];
 }
 
 template <typename Px, int N>
@@ -142,7 +121,7 @@ __global__ void __launch_bounds__(256) inter_sa8d_cost_kernel(InterCostArgs a)
     const int ctu = (int)blockIdx.x >> 2, quarter = (int)blockIdx.x & 3;
     const int cx = ctu % a.ctusW, cy = ctu / a.ctusW;
     const int rx0 = cx * 64 + (quarter & 1) * 32, ry0 = cy * 64 + (quarter >> 1) * 32;         // the quarter's first luma sample
-    const int lbase = N == 8 ? 0 : (N == 16 ? 64 : 80);
+    const int lbase = level_record_base<N>();
     // block b of the quarter (raster order inside it) -> its z index inside the CTU
     auto zof = [&](const int b) { return ip_zidx((quarter & 1) * BPR + (b & (BPR - 1)), (quarter >> 1) * BPR + (b / BPR)); };
     if (tid < NB) s.mv[tid] = a.mv[(size_t)ctu * 85 + lbase + zof(tid)].y;
@@ -152,24 +131,10 @@ __global__ void __launch_bounds__(256) inter_sa8d_cost_kernel(InterCostArgs a)
     if (tid < NB)
     {
         const int b = tid;
-        const int sad = sa8d_slot_sum<N>(s, b);
-        const int qx = (int16_t)(s.mv[b] & 0xffff), qy = (int16_t)(s.mv[b] >> 16);
-        // a component beyond the table prices as the table's last entry
-        const int ix = min(abs(qx), a.bitSizesLen - 1), iy = min(abs(qy), a.bitSizesLen - 1);
-        const int bits = a.baseBits + (int)(uint32_t)(a.bitSizes[ix] + a.bitSizes[iy] + 0.5f);
-        int lambda8 = a.lambda8;
-        if (a.lambdaByQp)
-        {
-            int qp = a.qp;
-            if (a.qpMap)
-            {
-                const int gx8 = (rx0 + (b & (BPR - 1)) * N) >> 3, gy8 = (ry0 + (b / BPR) * N) >> 3;
-                qp = clip3(0, 51 + 6 * (a.depth - 8), (int)a.qpMap[(size_t)gy8 * (a.ctusW * 8) + gx8]);
-            }
-            const uint32_t l = a.lambdaByQp[qp];
-            lambda8 = (int)(l < (1u << 24) ? l : (1u << 24));
-        }
-        const long long cost = (long long)sad + (((long long)bits * lambda8 + 128) >> 8);
+        const int sad = sa8d_slot_sum<N>(s.sum, b);
+        const int bits = a.baseBits + mv_bitcost(a.bitSizes, a.bitSizesLen, s.mv[b]);
+        const int lambda8 = block_lambda8(a.lambda8, a.lambdaByQp, a.qpMap, a.qp, a.depth, a.ctusW, (rx0 + (b & (BPR - 1)) * N) >> 3, (ry0 + (b / BPR) * N) >> 3);
+        const long long cost = (long long)sad + rd_sad_rate(bits, lambda8);
         a.cost[(size_t)ctu * NPU + zof(b)] = make_int2(sad, (int)cost);
     }
 }
@@ -180,16 +145,10 @@ extern "C" int x265hip_inter_sa8d_cost(const x265hip_inter_sa8d_cost_params* p, 
 {
     using namespace x265hip;
     // argument checks first: they need no device
-    if (!p || !p->fenc || !p->fref || !p->mv || !p->bit_sizes || !p->cost) { set_error("inter_sa8d_cost: NULL operand"); return X265HIP_EINVAL; }
-    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("inter_sa8d_cost: depth %d", p->depth); return X265HIP_EINVAL; }
-    if (p->level < 0 || p->level > 2) { set_error("inter_sa8d_cost: level %d (0..2 = 8x8, 16x16, 32x32)", p->level); return X265HIP_EINVAL; }
-    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("inter_sa8d_cost: width/height must be multiples of 64"); return X265HIP_EINVAL; }
-    if (p->fenc_stride < p->width || p->fref_stride < p->width) { set_error("inter_sa8d_cost: stride below the width"); return X265HIP_EINVAL; }
-    if (p->qp < 0 || p->qp > 51 + 6 * (p->depth - 8)) { set_error("inter_sa8d_cost: qp %d out of range", p->qp); return X265HIP_EINVAL; }
+    if (decision_record_refused("inter_sa8d_cost", p, !p || !p->fenc || !p->fref || !p->mv || !p->bit_sizes || !p->cost)) return X265HIP_EINVAL;
     // base_bits <= 4096 (+ at most 2 * 33 bits of a vector) and lambda8 <= 2^24 keep the rate term below 2^29 and the cost inside int32
     if (p->base_bits < 0 || p->base_bits > 4096) { set_error("inter_sa8d_cost: base_bits %d out of [0, 4096]", p->base_bits); return X265HIP_EINVAL; }
-    if (p->lambda8 < 0 || p->lambda8 > (1 << 24)) { set_error("inter_sa8d_cost: lambda8 %d out of [0, 2^24]", p->lambda8); return X265HIP_EINVAL; }
-    if (p->bit_sizes_len < 1) { set_error("inter_sa8d_cost: bit_sizes_len %d below 1", p->bit_sizes_len); return X265HIP_EINVAL; }
+    if (bit_sizes_len_refused("inter_sa8d_cost", p->bit_sizes_len)) return X265HIP_EINVAL;
     int rc = ensure_device();
     if (rc) return rc;
 
@@ -202,12 +161,8 @@ extern "C" int x265hip_inter_sa8d_cost(const x265hip_inter_sa8d_cost_params* p, 
     a.cost = (int2*)p->cost; a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(a.ctusW * a.ctusH * 4);
-#define GO(PX) do { \
-    if (p->level == 0) hipLaunchKernelGGL((inter_sa8d_cost_kernel<PX, 8>), grid, dim3(256), 0, s, a); \
-    else if (p->level == 1) hipLaunchKernelGGL((inter_sa8d_cost_kernel<PX, 16>), grid, dim3(256), 0, s, a); \
-    else hipLaunchKernelGGL((inter_sa8d_cost_kernel<PX, 32>), grid, dim3(256), 0, s, a); } while (0)
-    if (p->depth == 8) GO(uint8_t); else GO(uint16_t);
-#undef GO
+    for_depth_level(p->depth, p->level, [&](auto px, auto size)
+    { hipLaunchKernelGGL((inter_sa8d_cost_kernel<decltype(px), decltype(size)::value>), grid, dim3(256), 0, s, a); });
     X265HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -56,40 +56,6 @@ struct IntraInInterArgs
 __device__ __forceinline__ const IntraPicArgs& ip_args(const IntraPicArgs& a) { return a; }
 __device__ __forceinline__ const IntraPicArgs& ip_args(const IntraInInterArgs& r) { return r.a; }
 
-// z-order index of block (bx, by) of a CTU
-__device__ __forceinline__ int ip_zidx(int bx, int by)
-{
-    return (bx & 1) | ((by & 1) << 1) | ((bx & 2) << 1) | ((by & 2) << 2) | ((bx & 4) << 2) | ((by & 4) << 3);
-}
-
-// the inverse: block (x, y) of z index z
-__device__ __forceinline__ int2 ip_zpos(int z)
-{
-    return make_int2((z & 1) | ((z >> 1) & 2) | ((z >> 2) & 4), ((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4));
-}
-
-// sum of the absolute 8x8 Hadamard coefficients of a difference block whose row r sits in lane (lane & ~7) + r; valid in all eight lanes
-__device__ __forceinline__ int ip_hadamard8x8(int (&v)[8], const int lane)
-{
-#pragma unroll
-    for (int step = 1; step < 8; step <<= 1)
-#pragma unroll
-        for (int i = 0; i < 8; i += step << 1)
-#pragma unroll
-            for (int j = i; j < i + step; j++) { const int p = v[j], q = v[j + step]; v[j] = p + q; v[j + step] = p - q; }
-#pragma unroll
-    for (int s = 1; s < 8; s <<= 1)
-    {
-        const bool hi = (lane & s) != 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) { const int o = __shfl_xor(v[k], s, 64); v[k] = hi ? o - v[k] : v[k] + o; }
-    }
-    int acc = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) acc += abs(v[k]);
-    return group_sum<8>(acc);
-}
-
 // The 4M + 1 reference samples of an M x M block at (bx0, by0) of its CTU's tile (TW x TW samples of type Px in LDS, the CTU's own
 // reconstruction) into nb[]: [0] corner, [1..2M] above + above-right, [2M+1..4M] left + below-left.  av = availability of the arms
 // below-left, left, corner, above, above-right; plane = sample (0,0) of the CTU in the recon plane (earlier CTUs' samples).
@@ -171,7 +137,7 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(Args ra, const int w
 
     for (int z = 0; z < NPU; z++)
     {
-        const int bxz = (z & 1) | ((z >> 1) & 2) | ((z >> 2) & 4), byz = ((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4);
+        const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
         const int gbx = cxb * BPC + bxz, gby = cyb * BPC + byz;
         // a neighbouring block is available iff it is inside the picture and precedes this one in coding order
         auto available = [&](const int nbx, const int nby)
@@ -196,7 +162,7 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(Args ra, const int w
         {
             typedef const uint32_t __attribute__((address_space(4))) * ConstWords;
             const uint32_t l = ((ConstWords)reinterpret_cast<uintptr_t>(a.lambdaByQp))[__builtin_amdgcn_readfirstlane(qpB[0])];
-            lambda8 = (int)(l < (1u << 24) ? l : (1u << 24));
+            lambda8 = clamp_lambda8(l);
         }
         // ---- luma: reference samples, filtered copy, source block -----------------------------------------------------------------
         ip_fill_neighbours<Px, N, 64>(nbU, tileY, planeY, strideY, bxz * N, byz * N, av, dcValue);
@@ -282,7 +248,7 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(Args ra, const int w
 #pragma unroll
                 for (int u = 0; u < UNITS; u++) sad += sUnit[tid * UNITS + u];
                 const int bits = mode == p0 ? a.modeBits[0] : ((mode == p1 || mode == p2) ? a.modeBits[1] : a.modeBits[2]);
-                cost = (long long)sad + (((long long)bits * lambda8 + 128) >> 8);
+                cost = (long long)sad + rd_sad_rate(bits, lambda8);
                 key = ((unsigned long long)cost << 6) | (unsigned)tid;
             }
             unsigned long long best = key;
@@ -378,7 +344,7 @@ __global__ void __launch_bounds__(256) intra_picture_kernel(Args ra, const int w
 extern "C" int x265hip_intra_picture_waves(int width, int height)
 {
     if ((width & 63) || (height & 63) || width <= 0 || height <= 0) { x265hip::set_error("intra_picture_waves: width/height must be multiples of 64"); return X265HIP_EINVAL; }
-    return width / 64 + 2 * (height / 64 - 1);
+    return x265hip::decision_wave_count(width / 64, height / 64);
 }
 
 namespace x265hip {
@@ -388,12 +354,9 @@ static int intra_picture_launch(const char* who, const x265hip_intra_picture_par
                                 const int32_t* inter_cost, intptr_t inter_cost_stride, uint8_t* intra, const bool inP, void* stream)
 {
     // argument checks first: they need no device
-    if (!p || !p->fenc || !p->recon || !p->mode || !p->levels || !p->num_sig || !p->dist) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
-    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("%s: depth %d", who, p->depth); return X265HIP_EINVAL; }
-    if (p->level < 0 || p->level > 2) { set_error("%s: level %d (0..2 = 8x8, 16x16, 32x32)", who, p->level); return X265HIP_EINVAL; }
-    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("%s: width/height must be multiples of 64", who); return X265HIP_EINVAL; }
+    if (decision_record_refused(who, p, !p || !p->fenc || !p->recon || !p->mode || !p->levels || !p->num_sig || !p->dist || (inP && (!inter_cost || !intra))))
+        return X265HIP_EINVAL;
     const int qpMax = 51 + 6 * (p->depth - 8);
-    if (p->qp < 0 || p->qp > qpMax) { set_error("%s: qp %d out of range", who, p->qp); return X265HIP_EINVAL; }
     const bool chroma = p->fenc_cb || p->fenc_cr || p->recon_cb || p->recon_cr;
     if (chroma)
     {
@@ -401,18 +364,14 @@ static int intra_picture_launch(const char* who, const x265hip_intra_picture_par
         { set_error("%s: the chroma planes and outputs of Cb and Cr are needed together", who); return X265HIP_EINVAL; }
         if (p->qp_cb < 0 || p->qp_cb > qpMax || p->qp_cr < 0 || p->qp_cr > qpMax) { set_error("%s: chroma qp %d / %d out of range", who, p->qp_cb, p->qp_cr); return X265HIP_EINVAL; }
     }
-    // bits <= 4096 and lambda8 <= 2^24 keep (bits * lambda8 + 128) >> 8 below 2^28; the largest sa8d of a 32x32 block of 12-bit samples is below 2^27:
-    // the winning cost fits the int32 of `cost`
-    if (p->lambda8 < 0 || p->lambda8 > (1 << 24)) { set_error("%s: lambda8 %d out of [0, 2^24]", who, p->lambda8); return X265HIP_EINVAL; }
     if (inP)
     {
-        if (!inter_cost || !intra) { set_error("%s: NULL operand", who); return X265HIP_EINVAL; }
-        if (inter_cost_stride < 1) { set_error("%s: inter_cost_stride %ld below 1", who, (long)inter_cost_stride); return X265HIP_EINVAL; }
+        if (inter_cost_stride_refused(who, inter_cost_stride)) return X265HIP_EINVAL;
         if (p->flags & TU_FLAG_INTRA_SLICE) { set_error("%s: X265HIP_TU_INTRA_SLICE in the flags of a P slice", who); return X265HIP_EINVAL; }
     }
     if (p->flags & ~(TU_FLAG_INTRA_SLICE | TU_FLAG_SIGN_HIDE)) { set_error("%s: unknown flag bits 0x%x", who, p->flags); return X265HIP_EINVAL; }
-    if (p->fenc_stride < p->width || p->recon_stride < p->width) { set_error("%s: luma stride below the width", who); return X265HIP_EINVAL; }
     if (chroma && (p->fenc_stride_c < p->width / 2 || p->recon_stride_c < p->width / 2)) { set_error("%s: chroma stride below half the width", who); return X265HIP_EINVAL; }
+    // mode_bits <= 4096: with the shared bound of lambda8 the winning cost fits the int32 of `cost`
     for (int i = 0; i < 3; i++)
         if (p->mode_bits[i] < 0 || p->mode_bits[i] > 4096) { set_error("%s: mode_bits[%d] = %d out of [0, 4096]", who, i, p->mode_bits[i]); return X265HIP_EINVAL; }
     if (p->fenc == p->recon || (chroma && (p->fenc_cb == p->recon_cb || p->fenc_cr == p->recon_cr || p->recon_cb == p->recon_cr)))
@@ -443,22 +402,16 @@ static int intra_picture_launch(const char* who, const x265hip_intra_picture_par
     a.qpMap = qp_map; a.lambdaByQp = lambda8_by_qp;
     IntraInInterArgs ia = { a, inter_cost, (long)inter_cost_stride, intra };
     hipStream_t s = (hipStream_t)stream;
-    const int waves = a.ctusW + 2 * (a.ctusH - 1);
-    for (int w = 0; w < waves; w++)
+    for_each_wave(a.ctusW, a.ctusH, [&](const int w, const int cyLo, const int n)
     {
-        // the CTUs of wave w: cy from cyLo to cyHi, cx = w - 2 cy
-        const int over = w - (a.ctusW - 1);
-        const int cyLo = over > 0 ? (over + 1) / 2 : 0, cyHi = w / 2 < a.ctusH - 1 ? w / 2 : a.ctusH - 1;
-        const int n = cyHi - cyLo + 1;
-        if (n <= 0) continue;                  // a picture one CTU wide has no CTU in its odd waves
-#define GOP(PX, ARGS, REC) do { \
-        if (p->level == 0) hipLaunchKernelGGL((intra_picture_kernel<PX, 8, ARGS>), dim3(n), dim3(256), 0, s, REC, w, cyLo); \
-        else if (p->level == 1) hipLaunchKernelGGL((intra_picture_kernel<PX, 16, ARGS>), dim3(n), dim3(256), 0, s, REC, w, cyLo); \
-        else hipLaunchKernelGGL((intra_picture_kernel<PX, 32, ARGS>), dim3(n), dim3(256), 0, s, REC, w, cyLo); } while (0)
-        if (inP) { if (p->depth == 8) GOP(uint8_t, IntraInInterArgs, ia); else GOP(uint16_t, IntraInInterArgs, ia); }
-        else if (p->depth == 8) GOP(uint8_t, IntraPicArgs, a); else GOP(uint16_t, IntraPicArgs, a);
-#undef GOP
-    }
+        for_depth_level(p->depth, p->level, [&](auto px, auto size)
+        {
+            using Px = decltype(px);
+            constexpr int N = decltype(size)::value;
+            if (inP) hipLaunchKernelGGL((intra_picture_kernel<Px, N, IntraInInterArgs>), dim3(n), dim3(256), 0, s, ia, w, cyLo);
+            else hipLaunchKernelGGL((intra_picture_kernel<Px, N, IntraPicArgs>), dim3(n), dim3(256), 0, s, a, w, cyLo);
+        });
+    });
     X265HIP_TRY(hipGetLastError());
     return 0;
 }

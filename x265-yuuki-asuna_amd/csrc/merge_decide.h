@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
     const int ctu = cyb * a.ctusW + cxb;
     const int blocksW = a.ctusW * BPC, blocksH = a.ctusH * BPC;
     const int width = a.ctusW * 64, height = a.ctusH * 64;
-    const int lbase = N == 8 ? 0 : (N == 16 ? 64 : 80);
+    const int lbase = level_record_base<N>();
     const Px* fref = reinterpret_cast<const Px*>(a.fref);
     const Px* fenc = reinterpret_cast<const Px*>(a.fenc);
     const long rst = a.frefStrideB / BPP, fst = a.fencStrideB / BPP;
@@ -84,15 +84,7 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
         const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
         sSearched[z] = a.mv[(size_t)ctu * 85 + lbase + z];
         sInter[z] = a.interCost[((size_t)ctu * NPU + z) * a.interCostStride];
-        int lambda8 = a.lambda8;
-        if (a.lambdaByQp)
-        {
-            int qp = a.qp;
-            if (a.qpMap) qp = clip3(0, 51 + 6 * (a.depth - 8), (int)a.qpMap[(size_t)((cyb * 64 + byz * N) >> 3) * (a.ctusW * 8) + ((cxb * 64 + bxz * N) >> 3)]);
-            const uint32_t l = a.lambdaByQp[qp];
-            lambda8 = (int)(l < (1u << 24) ? l : (1u << 24));
-        }
-        sLambda[z] = lambda8;
+        sLambda[z] = block_lambda8(a.lambda8, a.lambdaByQp, a.qpMap, a.qp, a.depth, a.ctusW, (cxb * 64 + bxz * N) >> 3, (cyb * 64 + byz * N) >> 3);
     }
     __syncthreads();
 
@@ -153,7 +145,7 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
             if (tid < nAct) s.mv[tid] = sSlotMv[base + tid];
             __syncthreads();
             sa8d_slots<Px, N>(s, nAct, [&](const int) { return make_int2(x0, y0); }, fref, rst, fenc, fst, a.depth);
-            if (tid < nAct) sSlotSad[base + tid] = sa8d_slot_sum<N>(s, tid);
+            if (tid < nAct) sSlotSad[base + tid] = sa8d_slot_sum<N>(s.sum, tid);
             __syncthreads();
         }
         if (tid == 0)
@@ -166,7 +158,7 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
             {
                 const int sad = sSlotSad[sSlotOf[i]];
                 const int bits = i + (i < num - 1 ? 1 : 0);                                                  // getTUBits, search.h:246-249
-                const long long cost = (long long)sad + (((long long)bits * lambda8 + 128) >> 8);           // calcRdSADCost, rdcost.h:148-153
+                const long long cost = (long long)sad + rd_sad_rate(bits, lambda8);
                 if (i == 0 || cost < bestCost) { bestI = i; bestSad = sad; bestCost = cost; }                // analysis.cpp:2833
             }
             const size_t blk = (size_t)ctu * NPU + z, rec = (size_t)ctu * 85 + lbase + z;
@@ -192,18 +184,11 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
 extern "C" int x265hip_merge_decide(const x265hip_merge_decide_params* p, void* stream)
 {
     using namespace x265hip;
-    // argument checks first: they need no device
-    if (!p || !p->fenc || !p->fref || !p->mv || !p->inter_cost || !p->merge || !p->merge_idx || !p->mv_out || !p->mv_pred || !p->cost)
-    { set_error("merge_decide: NULL operand"); return X265HIP_EINVAL; }
-    if (p->depth != 8 && p->depth != 10 && p->depth != 12) { set_error("merge_decide: depth %d", p->depth); return X265HIP_EINVAL; }
-    if (p->level < 0 || p->level > 2) { set_error("merge_decide: level %d (0..2 = 8x8, 16x16, 32x32)", p->level); return X265HIP_EINVAL; }
-    if ((p->width & 63) || (p->height & 63) || p->width <= 0 || p->height <= 0) { set_error("merge_decide: width/height must be multiples of 64"); return X265HIP_EINVAL; }
-    if (p->fenc_stride < p->width || p->fref_stride < p->width) { set_error("merge_decide: stride below the width"); return X265HIP_EINVAL; }
-    if (p->qp < 0 || p->qp > 51 + 6 * (p->depth - 8)) { set_error("merge_decide: qp %d out of range", p->qp); return X265HIP_EINVAL; }
-    // at most 4 bits and lambda8 <= 2^24 keep the rate term below 2^19 and the cost inside int32
-    if (p->lambda8 < 0 || p->lambda8 > (1 << 24)) { set_error("merge_decide: lambda8 %d out of [0, 2^24]", p->lambda8); return X265HIP_EINVAL; }
+    // argument checks first: they need no device (at most 4 bits and lambda8 <= 2^24 keep the rate term below 2^19 and the cost inside int32)
+    if (decision_record_refused("merge_decide", p, !p || !p->fenc || !p->fref || !p->mv || !p->inter_cost || !p->merge || !p->merge_idx || !p->mv_out || !p->mv_pred ||
+                                !p->cost)) return X265HIP_EINVAL;
     if (p->max_merge < 1 || p->max_merge > 5) { set_error("merge_decide: max_merge %d out of 1..5", p->max_merge); return X265HIP_EINVAL; }
-    if (p->inter_cost_stride < 1) { set_error("merge_decide: inter_cost_stride %ld below 1", (long)p->inter_cost_stride); return X265HIP_EINVAL; }
+    if (inter_cost_stride_refused("merge_decide", p->inter_cost_stride)) return X265HIP_EINVAL;
     // the walk reads a block's searched vector from mv and its neighbours' final motion from mv_out: one array for both would change what a
     // second run sees
     if (p->mv_out == p->mv || p->mv_pred == p->mv || p->mv_out == p->mv_pred)
@@ -220,21 +205,11 @@ extern "C" int x265hip_merge_decide(const x265hip_merge_decide_params* p, void* 
     a.merge = p->merge; a.mergeIdx = p->merge_idx; a.mvOut = (int2*)p->mv_out; a.mvPred = (int2*)p->mv_pred;
     a.cost = (int2*)p->cost; a.best = (int2*)p->best; a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
     hipStream_t s = (hipStream_t)stream;
-    const int waves = a.ctusW + 2 * (a.ctusH - 1);
-    for (int w = 0; w < waves; w++)
+    for_each_wave(a.ctusW, a.ctusH, [&](const int w, const int cyLo, const int n)
     {
-        // the CTUs of wave w: cy from cyLo to cyHi, cx = w - 2 cy
-        const int over = w - (a.ctusW - 1);
-        const int cyLo = over > 0 ? (over + 1) / 2 : 0, cyHi = w / 2 < a.ctusH - 1 ? w / 2 : a.ctusH - 1;
-        const int n = cyHi - cyLo + 1;
-        if (n <= 0) continue;                  // a picture one CTU wide has no CTU in its odd waves
-#define GO(PX) do { \
-        if (p->level == 0) hipLaunchKernelGGL((merge_decide_kernel<PX, 8>), dim3(n), dim3(256), 0, s, a, w, cyLo); \
-        else if (p->level == 1) hipLaunchKernelGGL((merge_decide_kernel<PX, 16>), dim3(n), dim3(256), 0, s, a, w, cyLo); \
-        else hipLaunchKernelGGL((merge_decide_kernel<PX, 32>), dim3(n), dim3(256), 0, s, a, w, cyLo); } while (0)
-        if (p->depth == 8) GO(uint8_t); else GO(uint16_t);
-#undef GO
-    }
+        for_depth_level(p->depth, p->level, [&](auto px, auto size)
+        { hipLaunchKernelGGL((merge_decide_kernel<decltype(px), decltype(size)::value>), dim3(n), dim3(256), 0, s, a, w, cyLo); });
+    });
     X265HIP_TRY(hipGetLastError());
     return 0;
 }

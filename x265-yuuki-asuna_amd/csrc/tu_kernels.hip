@@ -1438,14 +1438,17 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
     return tu_launch(tu_kernel(X265HIP_TU_ENTRY_INTRA, p->n, p->depth, p->tables != nullptr, !p->chroma), dim3(grid), stream, args);
 }
 
+// what the four decision stages below share: block grid, lambda, rate and Hadamard helpers; argument checks, wave schedule, launch dispatch
+#include "decision_common.h"
+
 // the I-picture stage (x265hip_intra_picture): its kernel codes blocks with tu_chain / TuOpsFor above
 #include "intra_picture.h"
 
-// the inter candidate's sa8d cost of a P picture's blocks (x265hip_inter_sa8d_cost): kTuTaps above, ip_hadamard8x8 of intra_picture.h
+// the inter candidate's sa8d cost of a P picture's blocks (x265hip_inter_sa8d_cost): kTuTaps above, ip_hadamard8x8 of decision_common.h
 #include "inter_sa8d_cost.h"
 
 // the sa8d choice of a B picture's blocks between one list and both (x265hip_b_sa8d_decide): the geometry of inter_sa8d_cost.h
 #include "b_sa8d_decide.h"
 
-// the merge arm of a P picture's sa8d choice (x265hip_merge_decide): sa8d_slots of inter_sa8d_cost.h, the wave schedule of intra_picture.h
+// the merge arm of a P picture's sa8d choice (x265hip_merge_decide): sa8d_slots of inter_sa8d_cost.h, the wave schedule of decision_common.h
 #include "merge_decide.h"

@@ -14,6 +14,12 @@ from . import hipabi
 from .pipeline import PUS_PER_CTU, DevicePicture
 
 
+def _sum64(t):
+    """A checksum word: the sum of a tensor's elements in int64."""
+    import torch
+    return int(t.to(torch.int64).sum().item())
+
+
 ReconParams = hipabi.ReconParams          # x265hip_recon_params: the record lives beside ReconRefsParams, which embeds it
 
 
@@ -71,9 +77,7 @@ class InterRecon:
         hipabi.check(f(ctypes.byref(p), s), "x265hip_inter_recon")
 
     def checksum(self):
-        import torch
-        return {"levels": int(self.levels.to(torch.int64).sum().item()), "num_sig": int(self.num_sig.sum().item()),
-                "dist": int(self.dist.sum().item())}
+        return {"levels": _sum64(self.levels), "num_sig": int(self.num_sig.sum().item()), "dist": int(self.dist.sum().item())}
 
 
 PredWeight = hipabi.PredWeight            # x265hip_pred_weight and x265hip_recon_bi_params: the records live beside ReconBiRefsParams, which embeds them
@@ -765,6 +769,19 @@ class _PictureStep:
         = the picture-wide qp again.  Not for bands (BandedFramePipeline), captured graphs or scaling-list tables: run() raises there."""
         self._set_qp_maps(maps, self.rc, self.rc_c if self.chroma else [])
 
+    def _set_decision_qp_maps(self, maps, lambda8_by_qp, luma, planes3):
+        """set_qp_maps of a step with decision stages: the maps reach the TU stages and the deblocking stage as above, the stages of `luma`
+        (they price a block by its luma QP) get maps.tu_qp[0], those of `planes3` (the intra walks, which also code) all of maps.tu_qp, and
+        both get lambda8_by_qp: device int32 tensor [52 + 6 (depth - 8)] - 256 x lambda of a CU per luma quantiser QP, for the rate term
+        of every candidate - or None = the constructor's lambda8 for every block."""
+        self._set_qp_maps(maps, self.rc, self.rc_c if self.chroma else [])
+        for st in luma:
+            st.qp_map = None if maps is None else maps.tu_qp[0]
+        for st in planes3:
+            st.qp_map = None if maps is None else maps.tu_qp
+        for st in list(luma) + list(planes3):
+            st.lambda8_by_qp = None if maps is None else lambda8_by_qp
+
     def _qp_maps_run_check(self):
         """run() with maps set, in a mode that would not honour them: raise instead of coding with other QPs than asked for."""
         if self.qp_maps is None:
@@ -872,7 +889,6 @@ class _RefListStep(_PictureStep):
 
     def _checksum(self, choice):
         """choice: the stage that chose between the lists (BidirDecide / RefSelect)."""
-        import torch
         out = {}
         for l in range(len(self.msl)):
             out.update({"%s%d" % (k, l): v for k, v in self.msl[l].checksum().items()})
@@ -882,7 +898,7 @@ class _RefListStep(_PictureStep):
         if self.chroma:
             for i in range(2):
                 out.update({"%s_c%d" % (k, i): v for k, v in InterRecon.checksum(self.rc_c[i]).items()})
-        out["recon"] = int(self.final.to(torch.int64).sum().item())
+        out["recon"] = _sum64(self.final)
         return out
 
 
@@ -1294,11 +1310,11 @@ class FramePipeline(_PictureStep):
         if self.sao is not None:
             out["sao_count"] = int(self.sao.count.sum(dtype=torch.int64).item())
             out["sao_offset_org"] = int(self.sao.offset_org.sum(dtype=torch.int64).item())
-        out["recon"] = int(self.final.view(torch.uint8).to(torch.int64).sum().item())
+        out["recon"] = _sum64(self.final.view(torch.uint8))
         if self.chroma:
-            out["recon_cb"] = int(self.final_c[0].view(torch.uint8).to(torch.int64).sum().item())
-            out["recon_cr"] = int(self.final_c[1].view(torch.uint8).to(torch.int64).sum().item())
-            out["levels_c"] = int(sum(r.levels.to(torch.int64).sum().item() for r in self.rc_c))
+            out["recon_cb"] = _sum64(self.final_c[0].view(torch.uint8))
+            out["recon_cr"] = _sum64(self.final_c[1].view(torch.uint8))
+            out["levels_c"] = sum(_sum64(r.levels) for r in self.rc_c)
         if self.sao_apply:
             out["sao_types"] = int((self.sao.params.view(-1, 7)[:, 0] >= 0).sum().item())
         return out
@@ -1471,9 +1487,7 @@ class BidirDecide:
                             ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org, phase_planes=phase_planes, stream=stream, chroma=chroma)
 
     def checksum(self):
-        import torch
-        return {"dir": int(self.dir.to(torch.int64).sum().item()), "mv0_out": int(self.mv0_out.to(torch.int64).sum().item()),
-                "mv1_out": int(self.mv1_out.to(torch.int64).sum().item())}
+        return {"dir": _sum64(self.dir), "mv0_out": _sum64(self.mv0_out), "mv1_out": _sum64(self.mv1_out)}
 
 
 class BFramePipeline(_RefListStep):
@@ -1555,8 +1569,7 @@ class RefSelect:
                           cost_out=self.cost_out, ref_ids=ref_ids, stream=stream)
 
     def checksum(self):
-        import torch
-        return {"ref_idx": int(self.ref_idx.to(torch.int64).sum().item()), "mv_out": int(self.mv_out.to(torch.int64).sum().item())}
+        return {"ref_idx": _sum64(self.ref_idx), "mv_out": _sum64(self.mv_out)}
 
 
 class MultiRefFramePipeline(_RefListStep):
@@ -1767,12 +1780,10 @@ class IntraPicture:
                              strong_intra_smoothing=self.strong, stream=stream, qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp)
 
     def checksum(self):
-        import torch
-        out = {"mode": int(self.mode.to(torch.int64).sum().item()), "levels": int(self.levels.to(torch.int64).sum().item()),
-               "num_sig": int(self.num_sig.sum().item()), "dist": int(self.dist.sum().item())}
+        out = {"mode": _sum64(self.mode), "levels": _sum64(self.levels), "num_sig": int(self.num_sig.sum().item()), "dist": int(self.dist.sum().item())}
         if self.chroma:
             for i in range(2):
-                out["levels_c%d" % i] = int(self.levels_c[i].to(torch.int64).sum().item())
+                out["levels_c%d" % i] = _sum64(self.levels_c[i])
                 out["num_sig_c%d" % i] = int(self.num_sig_c[i].sum().item())
         return out
 
@@ -1824,9 +1835,8 @@ class IFramePipeline(_PictureStep):
         return self._filter_tail(cur, mark)
 
     def checksum(self):
-        import torch
         out = self.ip.checksum()
-        out["recon"] = int(self.final.to(torch.int64).sum().item())
+        out["recon"] = _sum64(self.final)
         return out
 
 
@@ -1852,8 +1862,7 @@ class InterSa8dCost:
                                self.lambda8, self.bit_sizes, self.cost, qp=self.qp, qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp, stream=stream)
 
     def checksum(self):
-        import torch
-        return {"inter_cost": int(self.cost.to(torch.int64).sum().item())}
+        return {"inter_cost": _sum64(self.cost)}
 
 
 class IntraInInter:
@@ -1894,11 +1903,53 @@ class IntraInInter:
                               strong_intra_smoothing=self.strong, stream=stream, qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp)
 
     def checksum(self):
-        import torch
-        return {"mode": int(self.mode.to(torch.int64).sum().item()), "intra": int(self.intra.to(torch.int64).sum().item())}
+        return {"mode": _sum64(self.mode), "intra": _sum64(self.intra)}
 
 
-class IntraPFramePipeline(_PictureStep):
+class _Sa8dPStep(_PictureStep):
+    """What the P steps with an sa8d decision share: search -> sub-pel refinement, the inter TU stages (luma + chroma pair) and InterSa8dCost.
+    A step adds its decision stage and orders coding and deciding in run()."""
+
+    def __init__(self, w64, h64, depth, device, rng, subme, level, qp, deblock, sao, chroma, sao_apply, sign_hide, sao_rdo, lambda8, base_bits):
+        from .pipeline import MotionSearch, SubpelRefine
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
+        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
+        self.ms = MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True)
+        self.sp = SubpelRefine(self.ms, subme, device)
+        self.rc = InterRecon(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        if chroma:
+            qpc = chroma_quant_qp(qp, depth)
+            self.rc_c = [InterReconChroma(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
+        self.ic = InterSa8dCost(self.nctu, w64, h64, depth, level, device, rng=rng, base_bits=base_bits, lambda8=lambda8, qp=qp)
+
+    def _search(self, cur, ref, mark):
+        """The head of run(): checks, planes, search and sub-pel refinement; returns the refined records."""
+        self._qp_maps_run_check()
+        self._alloc_planes(cur)
+        self.ms.reset()
+        self.ms.search(cur, ref)
+        mark("me")
+        self.sp.run(cur, ref)
+        mark("subpel")
+        return self.sp.out
+
+    def _code(self, cur, ref, mv, mark):
+        """The inter TU stages on the records mv: luma, then the chroma pair."""
+        self.rc.run(cur, ref, self.recon, mv)
+        mark("recon")
+        if self.chroma:
+            InterReconChroma.run_pair(self.rc_c, cur.c, ref.c, self.recon_c, cur.stride_c, cur.org_c, mv)
+            mark("recon_chroma")
+
+    def _checksum(self, decision, **more):
+        out = {}
+        for st in (self.ms, self.sp, self.ic, decision, self.rc):
+            out.update(st.checksum())
+        out.update(more, recon=_sum64(self.final))
+        return out
+
+
+class IntraPFramePipeline(_Sa8dPStep):
     """One P picture whose blocks may be intra: search -> sub-pel refinement -> inter TU stage (luma + chroma) -> InterSa8dCost ->
     IntraInInter -> boundary strengths with the intra flags + luma / chroma deblocking -> the shared loop-filter tail.  Inter
     reconstruction does not depend on neighbours, so coding every block as inter first and overwriting the intra winners in coding order
@@ -1907,45 +1958,22 @@ class IntraPFramePipeline(_PictureStep):
 
     def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
                  sign_hide=False, sao_rdo=None, lambda8=1024, mode_bits=(2, 3, 6), strong_intra_smoothing=True, base_bits=2):
-        from .pipeline import MotionSearch, SubpelRefine
-        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
-        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
-        self.ms = MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True)
-        self.sp = SubpelRefine(self.ms, subme, device)
-        self.rc = InterRecon(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        _Sa8dPStep.__init__(self, w64, h64, depth, device, rng, subme, level, qp, deblock, sao, chroma, sao_apply, sign_hide, sao_rdo, lambda8, base_bits)
         qpc = chroma_quant_qp(qp, depth)
-        if chroma:
-            self.rc_c = [InterReconChroma(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
-        self.ic = InterSa8dCost(self.nctu, w64, h64, depth, level, device, rng=rng, base_bits=base_bits, lambda8=lambda8, qp=qp)
         self.ii = IntraInInter(self.nctu, w64, h64, depth, level, qp, device, flags=self.tu_flags, chroma=chroma, qp_c=(qpc, qpc), lambda8=lambda8,
                                mode_bits=mode_bits, strong_intra_smoothing=strong_intra_smoothing)
 
     def set_qp_maps(self, maps, lambda8_by_qp=None):
-        """Per-block QPs for the following run() calls (see FramePipeline.set_qp_maps); None = the picture-wide qp again.  lambda8_by_qp: device
-        int32 tensor [52 + 6 (depth - 8)] - 256 x lambda of a CU per luma quantiser QP, for both candidates' rate terms - or None = the
-        constructor's lambda8 for every block."""
-        self._set_qp_maps(maps, self.rc, self.rc_c if self.chroma else [])
-        self.ii.qp_map = None if maps is None else maps.tu_qp
-        self.ic.qp_map = None if maps is None else maps.tu_qp[0]
-        self.ii.lambda8_by_qp = self.ic.lambda8_by_qp = None if maps is None else lambda8_by_qp
+        """Per-block QPs for the following run() calls (see FramePipeline.set_qp_maps); None = the picture-wide qp again.  lambda8_by_qp
+        prices both candidates' rate terms per block (see _set_decision_qp_maps)."""
+        self._set_decision_qp_maps(maps, lambda8_by_qp, [self.ic], [self.ii])
 
     def run(self, cur: DevicePicture, ref: DevicePicture, mark=None):
         """ref: the reference picture (extended borders, with chroma its Cb / Cr planes); returns the luma plane of the coded picture.
         mark(name), if given, is called after every stage."""
         mark = mark or (lambda name: None)
-        self._qp_maps_run_check()
-        self._alloc_planes(cur)
-        self.ms.reset()
-        self.ms.search(cur, ref)
-        mark("me")
-        self.sp.run(cur, ref)
-        mv = self.sp.out
-        mark("subpel")
-        self.rc.run(cur, ref, self.recon, mv)
-        mark("recon")
-        if self.chroma:
-            InterReconChroma.run_pair(self.rc_c, cur.c, ref.c, self.recon_c, cur.stride_c, cur.org_c, mv)
-            mark("recon_chroma")
+        mv = self._search(cur, ref, mark)
+        self._code(cur, ref, mv, mark)
         self.ic.run(cur, ref, mv)
         mark("inter_cost")
         self.ii.run(cur, self.recon, self.rc, self.ic.cost, self.recon_c, self.rc_c if self.chroma else None)
@@ -1955,15 +1983,7 @@ class IntraPFramePipeline(_PictureStep):
         return self._filter_tail(cur, mark)
 
     def checksum(self):
-        import torch
-        out = {}
-        out.update(self.ms.checksum())
-        out.update(self.sp.checksum())
-        out.update(self.ic.checksum())
-        out.update(self.ii.checksum())
-        out.update(self.rc.checksum())
-        out["recon"] = int(self.final.to(torch.int64).sum().item())
-        return out
+        return self._checksum(self.ii)
 
 
 class MergeDecide:
@@ -2007,13 +2027,11 @@ class MergeDecide:
         return skip.to(torch.uint8)
 
     def checksum(self):
-        import torch
-        return {"merge": int(self.merge.to(torch.int64).sum().item()), "merge_idx": int(self.merge_idx.to(torch.int64).sum().item()),
-                "mv_out": int(self.mv_out.to(torch.int64).sum().item()), "mv_pred": int(self.mv_pred.to(torch.int64).sum().item()),
-                "merge_cost": int(self.cost.to(torch.int64).sum().item())}
+        return {"merge": _sum64(self.merge), "merge_idx": _sum64(self.merge_idx), "mv_out": _sum64(self.mv_out), "mv_pred": _sum64(self.mv_pred),
+                "merge_cost": _sum64(self.cost)}
 
 
-class MergePFramePipeline(_PictureStep):
+class MergePFramePipeline(_Sa8dPStep):
     """One P picture whose blocks may merge: search -> sub-pel refinement -> InterSa8dCost on the searched vectors -> MergeDecide -> inter TU
     stage (luma + chroma) on mv_pred -> skip flags -> boundary strengths from mv_out + luma / chroma deblocking -> the shared loop-filter
     tail.  The candidate list reads motion only, so one walk in coding order before the coding is the reference's result (DESIGN.md
@@ -2022,46 +2040,24 @@ class MergePFramePipeline(_PictureStep):
 
     def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
                  sign_hide=False, sao_rdo=None, lambda8=1024, base_bits=2, max_merge=3):
-        from .pipeline import MotionSearch, SubpelRefine
-        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
-        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
-        self.ms = MotionSearch(w64, h64, rng, depth, device, want_surf=False, want_best=True)
-        self.sp = SubpelRefine(self.ms, subme, device)
-        self.rc = InterRecon(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
-        qpc = chroma_quant_qp(qp, depth)
-        if chroma:
-            self.rc_c = [InterReconChroma(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
-        self.ic = InterSa8dCost(self.nctu, w64, h64, depth, level, device, rng=rng, base_bits=base_bits, lambda8=lambda8, qp=qp)
+        _Sa8dPStep.__init__(self, w64, h64, depth, device, rng, subme, level, qp, deblock, sao, chroma, sao_apply, sign_hide, sao_rdo, lambda8, base_bits)
         self.md = MergeDecide(self.nctu, w64, h64, depth, level, device, max_merge=max_merge, lambda8=lambda8, qp=qp)
         self.skip = None
 
     def set_qp_maps(self, maps, lambda8_by_qp=None):
         """As IntraPFramePipeline.set_qp_maps: the maps reach the TU stages, the deblocking stage and both candidates' rate terms."""
-        self._set_qp_maps(maps, self.rc, self.rc_c if self.chroma else [])
-        self.ic.qp_map = self.md.qp_map = None if maps is None else maps.tu_qp[0]
-        self.ic.lambda8_by_qp = self.md.lambda8_by_qp = None if maps is None else lambda8_by_qp
+        self._set_decision_qp_maps(maps, lambda8_by_qp, [self.ic, self.md], [])
 
     def run(self, cur: DevicePicture, ref: DevicePicture, mark=None):
         """ref: the reference picture (extended borders, with chroma its Cb / Cr planes); returns the luma plane of the coded picture.
         mark(name), if given, is called after every stage."""
         mark = mark or (lambda name: None)
-        self._qp_maps_run_check()
-        self._alloc_planes(cur)
-        self.ms.reset()
-        self.ms.search(cur, ref)
-        mark("me")
-        self.sp.run(cur, ref)
-        mv = self.sp.out
-        mark("subpel")
+        mv = self._search(cur, ref, mark)
         self.ic.run(cur, ref, mv)
         mark("inter_cost")
         self.md.run(cur, ref, mv, self.ic.cost)
         mark("merge")
-        self.rc.run(cur, ref, self.recon, self.md.mv_pred)
-        mark("recon")
-        if self.chroma:
-            InterReconChroma.run_pair(self.rc_c, cur.c, ref.c, self.recon_c, cur.stride_c, cur.org_c, self.md.mv_pred)
-            mark("recon_chroma")
+        self._code(cur, ref, self.md.mv_pred, mark)
         self.skip = self.md.skip_flags(self.rc, self.rc_c if self.chroma else None)
         mark("skip")
         if self.db is not None:
@@ -2069,16 +2065,7 @@ class MergePFramePipeline(_PictureStep):
         return self._filter_tail(cur, mark)
 
     def checksum(self):
-        import torch
-        out = {}
-        out.update(self.ms.checksum())
-        out.update(self.sp.checksum())
-        out.update(self.ic.checksum())
-        out.update(self.md.checksum())
-        out.update(self.rc.checksum())
-        out["skip"] = int(self.skip.to(torch.int64).sum().item())
-        out["recon"] = int(self.final.to(torch.int64).sum().item())
-        return out
+        return self._checksum(self.md, skip=_sum64(self.skip))
 
 
 class BSa8dDecide:
@@ -2116,9 +2103,7 @@ class BSa8dDecide:
                              lambda8_by_qp=self.lambda8_by_qp, stream=stream)
 
     def checksum(self):
-        import torch
-        return {"dir": int(self.dir.to(torch.int64).sum().item()), "mv0_out": int(self.mv0_out.to(torch.int64).sum().item()),
-                "mv1_out": int(self.mv1_out.to(torch.int64).sum().item()), "b_cost": int(self.cost.to(torch.int64).sum().item())}
+        return {"dir": _sum64(self.dir), "mv0_out": _sum64(self.mv0_out), "mv1_out": _sum64(self.mv1_out), "b_cost": _sum64(self.cost)}
 
 
 class Sa8dBFramePipeline(_RefListStep):
@@ -2148,12 +2133,7 @@ class Sa8dBFramePipeline(_RefListStep):
     def set_qp_maps(self, maps, lambda8_by_qp=None):
         """As IntraPFramePipeline.set_qp_maps: the maps reach the TU stages, the deblocking stage, the decision and (with b_intra) the intra
         walk; lambda8_by_qp prices the rate terms of all candidates per block."""
-        self._set_qp_maps(maps, self.rc, self.rc_c if self.chroma else [])
-        self.bd.qp_map = None if maps is None else maps.tu_qp[0]
-        self.bd.lambda8_by_qp = None if maps is None else lambda8_by_qp
-        if self.ii is not None:
-            self.ii.qp_map = None if maps is None else maps.tu_qp
-            self.ii.lambda8_by_qp = None if maps is None else lambda8_by_qp
+        self._set_decision_qp_maps(maps, lambda8_by_qp, [self.bd], [] if self.ii is None else [self.ii])
 
     def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mark=None):
         """ref0 / ref1: the list-0 / list-1 reference pictures (extended borders; with chroma=True also their Cb / Cr planes).  Returns the

@@ -1884,6 +1884,61 @@ typedef struct x265hip_merge_decide_params
 } x265hip_merge_decide_params;
 int x265hip_merge_decide(const x265hip_merge_decide_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Merge / skip blocks of a B picture (csrc/b_merge_decide.h): Analysis::checkMerge2Nx2N_rd0_4 at RD level 0 for a B slice with one
+ * reference per list, --no-temporal-mvp, no weights, --b-intra off.  Grid, coding order, availability, clipMv, getTUBits, the strict
+ * comparisons, qp / qp_map / lambda8_by_qp, the schedule and the skip rule are those of x265hip_merge_decide; what differs is the list.
+ *   list   : CUData::getInterMergeCandidates (common/cudata.cpp:1458-1712) with isInterB.  A candidate is (dir in {1, 2, 3}, mv[0], mv[1]);
+ *            the vector of an unused list is never read and stored as 0.  Spatial A1, B1, B0, A0, and B2 only while count < 4; pruned
+ *            pairs B1-A1, B0-B1, A0-A1, B2-A1, B2-B1 by hasEqualMotion (cudata.cpp:1439-1455): the directions must be equal first, then
+ *            the vectors of the USED lists.  Combined candidates (:1652-1683): cutoff = count * (count - 1), computed once from the count
+ *            after the spatial candidates; pairs (i, j) in the order of the priority words 0xEDC984 / 0xB73621 - (0,1) (1,0) (0,2) (2,0)
+ *            (1,2) (2,1) (0,3) (3,0) (1,3) (3,1) (2,3) (3,2); a pair yields {3, cand[i].mv[0], cand[j].mv[1]} where cand[i].dir & 1 and
+ *            cand[j].dir & 2, unless ref_id0 == ref_id1 and the two vectors are equal (:1670).  The rest is {3, (0,0), (0,0)} (:1684-1709).
+ *            The list is returned as soon as count == max_merge, at every increment.  A neighbour's motion is what it ENDED UP with: its
+ *            candidate's direction and vectors where it merged, the inter winner's where it did not.
+ *   price  : Predict::motionCompensation (predict.cpp:168-215) after clipMv of every used vector: dir 3 = addAvg(predInterLumaShort(fref0,
+ *            clip(mv0)), predInterLumaShort(fref1, clip(mv1))) - the 14-bit path of x265hip_b_sa8d_decide -, dir 1 / 2 = predInterLumaPixel
+ *            of that list's picture; dist = cu[].sa8d(fenc, pred), bits = getTUBits(i, max_merge), cost = dist + ((bits * lambda8 + 128) >>
+ *            8); the best with strict <.  Luma only.
+ *   choice : the block keeps its inter winner iff inter_cost[block * inter_cost_stride] < the best merge cost; a tie stays merge.  With
+ *            inter_cost = word 0 of x265hip_b_sa8d_decide's cost (stride 4) and its dir this is the reference's sequence of
+ *            analysis.cpp:1650-1655 (merge first, the single list when strictly cheaper, then both lists when strictly cheaper than what
+ *            stands): the proof is in the header comment of csrc/b_merge_decide.h.
+ * Inputs: dir_in uint8 [ctu][blocks] and mv0 / mv1 ([ctu*85] records) - the inter winner, the shapes x265hip_b_sa8d_decide writes.
+ * Outputs, all DEVICE:
+ *   merge, merge_idx : uint8 [ctu][blocks], as x265hip_merge_decide's
+ *   dir              : uint8 [ctu][blocks]: the final direction; ref0 / ref1 (optional int8): ref_id0 / ref_id1, or -1 for an unused list
+ *   mv0_out, mv1_out : records, the level's slots only: the CU's motion (unclipped) - for boundary strengths and later neighbours.  A used
+ *                      list of a merged block is {merge cost, vector}, of another block the input record; an unused list {the input
+ *                      record's cost, 0}
+ *   mv0_pred, mv1_pred : records, the level's slots only: what the two-list TU stages predict from, together with dir - a merged block's
+ *                      CLIPPED vectors (cost words as in mv*_out, 0 in an unused list), the input records, untouched, of another block
+ *   cost, best       : as x265hip_merge_decide's
+ * Refused (X265HIP_EINVAL, before any device call): NULL operands (ref0 / ref1 / best / qp_map / lambda8_by_qp are optional), depth not 8 /
+ * 10 / 12, level outside 0..2, sizes that are no multiples of 64, strides below the width, qp out of range, lambda8 outside [0, 2^24],
+ * max_merge outside 1..5, inter_cost_stride < 1, one of mv0_out / mv1_out / mv0_pred / mv1_pred overlapping mv0 / mv1 or another of the
+ * four, dir equal to dir_in. */
+typedef struct x265hip_b_merge_decide_params
+{
+    int depth, width, height, level;
+    int qp;                                          /* luma quantiser QP: indexes lambda8_by_qp where there is no qp_map */
+    int lambda8, max_merge;
+    int ref_id0, ref_id1;                            /* the pictures the two lists name: equal ids = the same picture */
+    const void* fenc;  intptr_t fenc_stride;         /* sample (0,0) of the source luma plane */
+    const void* fref0; const void* fref1; intptr_t fref_stride;
+    const uint8_t* dir_in;
+    const int32_t* mv0; const int32_t* mv1;
+    const int32_t* inter_cost; intptr_t inter_cost_stride;
+    const int8_t* qp_map; const uint32_t* lambda8_by_qp;
+    uint8_t* merge; uint8_t* merge_idx; uint8_t* dir;
+    int8_t* ref0; int8_t* ref1;
+    int32_t* mv0_out; int32_t* mv1_out;
+    int32_t* mv0_pred; int32_t* mv1_pred;
+    int32_t* cost; int32_t* best;
+} x265hip_b_merge_decide_params;
+int x265hip_b_merge_decide(const x265hip_b_merge_decide_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,477 @@
+"""Expected results of the merge stage of a B picture (x265hip_b_merge_decide) and of stages.MergeBFramePipeline, on the CPU.
+
+Prediction and sa8d come from the oracle only: the luma prediction through oracle_api.pred_capture of the bi stage run on the CLIPPED
+vectors with the candidate's dir (3: addAvg of both lists' 14-bit intermediates, 1 / 2: that list's rounded pixels), its sa8d through the
+table's cu[].sa8d slot; the coding through O.inter_recon_bi / O.inter_recon_chroma_bi on dir / mv*_pred (bsa8d_expect.inter_coding), the
+boundary strengths through O.deblock_bs_b on mv*_out / ref0 / ref1.
+
+Restated here in Python, with the reference's line numbers beside each statement: the B slice's candidate list
+(CUData::getInterMergeCandidates, common/cudata.cpp:1458-1712 with isInterB, one reference per list, no temporal candidate: spatial
+candidates, hasEqualMotion :1439-1455, combined candidates :1652-1683, zero fill :1684-1709, every early return), CUData::clipMv per list
+(cudata.cpp:1915-1928), getTUBits (search.h:246-249), the two strict comparisons (analysis.cpp:2833 among the candidates, :1650-1655
+against the inter winner) and the walk in coding order.  As for the P slice (tests/merge_expect.py) the list cannot be pinned against
+compiled reference code with what oracle/ offers; it is checked by hand-worked lists (tests/test_bmerge_cpu.py) and by the mutations
+below.  clipMv on both lists is pinned where oracle/_ref is built: reference_prediction() hands the final dir and the UNCLIPPED mv*_out
+to x265ref_motion_compensation with sliceB = 1.
+
+A motion is (dir, mv0, mv1) with packed words qx | qy << 16; the vector of an unused list is 0."""
+import ctypes
+
+import numpy as np
+
+import bsa8d_expect as BX
+import intra_expect as IE
+import intra_inter_expect as IX
+import merge_expect as ME
+
+O, F, H, harness = IE.O, IE.F, IE.H, IE.harness
+unpack, pack, clip_mv, tu_bits, records, level_slots, skip_flags, tie_pattern = (ME.unpack, ME.pack, ME.clip_mv, ME.tu_bits, ME.records, ME.level_slots,
+                                                                                 ME.skip_flags, ME.tie_pattern)
+NEIGHBOURS = ME.NEIGHBOURS
+
+P_MASKS = ME.MASKS                                              # the masks of DESIGN.md section 19 (won_zero: the zero fill, here {3, 0, 0})
+B_MASKS = ("won_dir1", "won_dir2", "won_dir3", "won_combined", "won_zero_bi", "pruned_needs_both_lists", "kept_because_dir_differs",
+           "combined_suppressed_same_picture", "cut_inside_combined", "merged_dir_differs_from_inter_dir", "inter_won_dir1", "inter_won_dir2",
+           "inter_won_dir3", "clip_changed_list1_prediction", "inherits_combined")
+MASKS = P_MASKS + B_MASKS
+MUTATIONS = ("le_against_inter", "le_among_candidates", "equal_motion_ignores_dir", "equal_motion_compares_unused", "cutoff_recomputed",
+             "combined_order_swapped", "no_same_picture_suppression", "uni_zero_fill", "avg_of_rounded", "no_clip_list1", "clip_stored_list1",
+             "inter_winner_not_final")
+LIST_FLAGS = ("pruned_B1", "pruned_B0", "pruned_A0", "pruned_B2", "B0_equals_A1_kept", "B2_dropped_at_four", "cut_at_max", "pruned_needs_both_lists",
+              "kept_because_dir_differs", "combined_suppressed_same_picture", "cut_inside_combined")
+PRIORITY0, PRIORITY1 = 0xEDC984, 0xB73621                      # cudata.cpp:1655-1656
+
+
+def motion(d, v0=0, v1=0, stale=None):
+    """(dir, mv0, mv1, stale): the vector of an unused list is 0; stale = what the CU's arrays hold in both lists (a list a CU does not use
+    keeps whatever was stored there - only the `equal_motion_compares_unused` mutation reads it)."""
+    m = (int(d), int(v0) if d & 1 else 0, int(v1) if d & 2 else 0)
+    return m + ((int(v0), int(v1)) if stale is None else tuple(stale),)
+
+
+def has_equal_motion(a, b, mutation=None):
+    """a.hasEqualMotion(b) (cudata.cpp:1439-1455): the directions first, then the vectors of the lists `a` uses."""
+    if mutation == "equal_motion_compares_unused":
+        return a[0] == b[0] and a[3] == b[3]
+    if a[0] != b[0] and mutation != "equal_motion_ignores_dir":                               # :1441-1442
+        return False
+    return all(a[1 + l] == b[1 + l] for l in (0, 1) if a[0] & (1 << l))                       # :1444-1452
+
+
+def combined_pairs(swapped=False):
+    p0, p1 = (PRIORITY1, PRIORITY0) if swapped else (PRIORITY0, PRIORITY1)
+    return [((p0 >> (2 * k)) & 3, (p1 >> (2 * k)) & 3) for k in range(12)]                    # :1658-1661
+
+
+def candidate_list(nb, max_merge, same_picture=False, mutation=None):
+    """getInterMergeCandidates for a B slice with one reference per list and no temporal candidate.  nb: {"A1" | "B1" | "B0" | "A0" | "B2":
+    a motion() or None where the neighbour is not available}; same_picture: both lists name one picture (refPOCL0 == refPOCL1).
+    Returns ([(motion, origin)], flags) - origin is the neighbour's name, "combined" or "zero"."""
+    a1, b1, b0, a0, b2 = (nb.get(k) for k in ("A1", "B1", "B0", "A0", "B2"))
+    out, fl = [], {k: False for k in LIST_FLAGS}
+
+    def same(p, q, name):
+        """p.hasEqualMotion(q) for an available p; records why the pair was pruned or kept."""
+        if p is None:
+            return False
+        eq = has_equal_motion(p, q, mutation)
+        if mutation is None:
+            if eq:
+                fl["pruned_" + name] = True
+                fl["pruned_needs_both_lists"] |= p[0] == 3
+            elif has_equal_motion(p, q, "equal_motion_ignores_dir"):
+                fl["kept_because_dir_differs"] = True
+        elif eq:
+            fl["pruned_" + name] = True
+        return eq
+
+    def cut(later):
+        fl["cut_at_max"] = any(v is not None for v in later)
+        return out, fl
+    if a1 is not None:                                                                        # :1495-1510
+        out.append((a1, "A1"))
+        if len(out) == max_merge:
+            return cut((b1, b0, a0, b2))
+    if b1 is not None and not same(a1, b1, "B1"):                                             # :1517-1532
+        out.append((b1, "B1"))
+        if len(out) == max_merge:
+            return cut((b0, a0, b2))
+    if b0 is not None and not same(b1, b0, "B0"):                                             # :1537-1551: against B1 only
+        fl["B0_equals_A1_kept"] = a1 is not None and has_equal_motion(a1, b0)
+        out.append((b0, "B0"))
+        if len(out) == max_merge:
+            return cut((a0, b2))
+    if a0 is not None and not same(a1, a0, "A0"):                                             # :1556-1570: against A1 only
+        out.append((a0, "A0"))
+        if len(out) == max_merge:
+            return cut((b2,))
+    if len(out) < 4:                                                                          # :1573
+        if b2 is not None and not same(a1, b2, "B2") and not same(b1, b2, "B2"):              # :1577-1592: against A1 and B1
+            out.append((b2, "B2"))
+            if len(out) == max_merge:
+                return out, fl
+    elif b2 is not None:
+        fl["B2_dropped_at_four"] = True
+    cutoff = len(out) * (len(out) - 1)                                                        # :1654: once, from the spatial count
+    k = 0
+    pairs = combined_pairs(mutation == "combined_order_swapped")
+    while k < (len(out) * (len(out) - 1) if mutation == "cutoff_recomputed" else cutoff) and k < 12:      # :1658
+        i, j = pairs[k]
+        k += 1
+        if i >= len(out) or j >= len(out):                        # only a recomputed cutoff gets here (the reference would read an unset entry)
+            continue
+        ci, cj = out[i][0], out[j][0]
+        if (ci[0] & 1) and (cj[0] & 2):                                                       # :1663
+            if same_picture and ci[1] == cj[2] and mutation != "no_same_picture_suppression":     # :1670
+                fl["combined_suppressed_same_picture"] = True
+                continue
+            out.append((motion(3, ci[1], cj[2]), "combined"))                                 # :1672-1676
+            if len(out) == max_merge:                                                         # :1678-1679
+                fl["cut_inside_combined"] = True
+                return out, fl
+    while len(out) < max_merge:                                                               # :1687-1709: refIdx 0 in both lists
+        out.append((motion(1, 0, 0) if mutation == "uni_zero_fill" else motion(3, 0, 0), "zero"))
+    return out, fl
+
+
+class Pricer:
+    """cu[].sa8d(fenc, motionCompensation(dir, mv0, mv1)) of (block, dir, clipped mv0, clipped mv1) through the oracle: one candidate per
+    block per O.inter_recon_bi call (pred_capture), the sa8d through the table's slot.  price() answers from the cache; a miss is recorded
+    and answered with 0 - fixpoint() evaluates the misses and repeats the walk until it met none.  rounded=True (the `avg_of_rounded`
+    mutation) prices a dir-3 candidate as pu[].pixelavg_pp of the two lists' rounded predictions."""
+
+    def __init__(self, depth, cur_y, ref0_y, ref1_y, w64, h64, level):
+        self.depth, self.w64, self.h64, self.level = depth, w64, h64, level
+        self.n = 8 << level
+        self.nblk = (64 // self.n) ** 2
+        self.cw = w64 // 64
+        self.nctu = self.cw * (h64 // 64)
+        _, _, self.stride, self.rows, self.org = F.padded_dims(w64, h64)
+        flat = lambda p: np.ascontiguousarray(p).reshape(-1)
+        self.y, self.r = flat(cur_y), (flat(ref0_y), flat(ref1_y))
+        self.slots = BX.Slots(depth, self.n, with_reference=False)
+        self.cache, self.pred, self.missing = {}, {}, set()
+
+    def position(self, b):
+        ctu, z = divmod(b, self.nblk)
+        bx, by = IE.zorder(z)
+        return (ctu % self.cw) * 64 + bx * self.n, (ctu // self.cw) * 64 + by * self.n
+
+    def _fenc(self, b):
+        gx, gy = self.position(b)
+        return self.y.ctypes.data + (self.org + gy * self.stride + gx) * self.y.itemsize
+
+    def price(self, b, d, c0, c1, rounded=False):
+        key = (b, d, c0 if d & 1 else 0, c1 if d & 2 else 0)
+        if rounded and d == 3:
+            parts = [self.pred.get((b, 1, key[2], 0)), self.pred.get((b, 2, 0, key[3]))]
+            if parts[0] is None or parts[1] is None:
+                self.missing.update({(b, 1, key[2], 0), (b, 2, 0, key[3])})
+                return 0
+            avg = self.slots.average(parts[0].ctypes.data, self.n, parts[1].ctypes.data, self.n)
+            return self.slots.sa8d(self._fenc(b), self.stride, avg)
+        if key in self.cache:
+            return self.cache[key]
+        self.missing.add(key)
+        return 0
+
+    def evaluate(self):
+        lbase = (0, 64, 80)[self.level]
+        todo = {}
+        for key in sorted(k for k in self.missing if k not in self.cache):
+            todo.setdefault(key[0], []).append(key)
+        self.missing = set()
+        layer = 0
+        while any(len(vs) > layer for vs in todo.values()):
+            mv = [np.zeros((self.nctu * 85, 2), np.int32) for _ in (0, 1)]
+            dirs = np.ones(self.nctu * self.nblk, np.uint8)
+            for b, vs in todo.items():
+                if len(vs) > layer:
+                    _, d, c0, c1 = vs[layer]
+                    dirs[b] = d
+                    mv[0][(b // self.nblk) * 85 + lbase + b % self.nblk, 1] = c0
+                    mv[1][(b // self.nblk) * 85 + lbase + b % self.nblk, 1] = c1
+            cap = np.zeros((self.h64, self.w64), self.y.dtype)
+            with O.pred_capture(self.depth, cap):
+                O.inter_recon_bi(self.depth, self.y, self.stride, self.org, self.r[0], self.r[1], self.w64, self.h64, self.level, mv[0], mv[1],
+                                 30 + 6 * (self.depth - 8), dir_flags=dirs)
+            for b, vs in todo.items():
+                if len(vs) > layer:
+                    gx, gy = self.position(b)
+                    p = np.ascontiguousarray(cap[gy:gy + self.n, gx:gx + self.n])
+                    self.pred[vs[layer]] = p
+                    self.cache[vs[layer]] = self.slots.sa8d(self._fenc(b), self.stride, p)
+            layer += 1
+
+    def fixpoint(self, fn, limit=400):
+        for _ in range(limit):
+            out = fn(self.price)
+            if not self.missing:
+                return out
+            self.evaluate()
+        raise AssertionError("the walk did not settle")
+
+
+def walk(w64, h64, level, winners, max_merge, price, lam, inter_cost=None, cost_fn=None, same_picture=False, mutation=None):
+    """The walk in coding order.  winners: (dir, packed mv0, packed mv1) per block (index = ctu * blocks + z) - the inter winner, the
+    vectors as the input records hold them; price(block, dir, clipped mv0, clipped mv1[, rounded]) -> sa8d; lam(block) -> lambda8;
+    inter_cost: int per block, or cost_fn(block, merge cost) -> the inter cost to decide against.  Returns merge, merge_idx, dir (uint8),
+    ref_used [blocks, 2] (bool), vec_out / vec_pred int32 [blocks, 2] (packed, per list), cost / best int32 [blocks, 2], inter_cost and
+    the masks."""
+    assert mutation is None or mutation in MUTATIONS
+    n = 8 << level
+    bpc = 64 // n
+    nblk = bpc * bpc
+    cw, chh = w64 // 64, h64 // 64
+    tot = cw * chh * nblk
+    bw, bh = cw * bpc, chh * bpc
+    final = [None] * tot
+    origin_won = [None] * tot
+    merge, idx, dirs = np.zeros(tot, np.uint8), np.zeros(tot, np.uint8), np.zeros(tot, np.uint8)
+    vec_out, vec_pred = np.zeros((tot, 2), np.int32), np.zeros((tot, 2), np.int32)
+    cost, best, ic_used = np.zeros((tot, 2), np.int32), np.zeros((tot, 2), np.int32), np.zeros(tot, np.int64)
+    masks = {k: np.zeros(tot, bool) for k in MASKS}
+    wrap = lambda v: int(np.int32(np.uint32(v & 0xffffffff)))
+
+    def index(gbx, gby):
+        return ((gby // bpc) * cw + gbx // bpc) * nblk + IE.zindex(gbx % bpc, gby % bpc)
+    for b in range(tot):
+        ctu, z = divmod(b, nblk)
+        bx, by = IE.zorder(z)
+        gbx, gby = (ctu % cw) * bpc + bx, (ctu // cw) * bpc + by
+        x0, y0 = gbx * n, gby * n
+        win = motion(*winners[b])
+        nb, where = {}, {}
+        for name, dx, dy in NEIGHBOURS:
+            nx, ny = gbx + dx, gby + dy
+            nb[name] = None
+            if not (0 <= nx < bw and 0 <= ny < bh):                                           # getPU*: outside the picture
+                continue
+            q = index(nx, ny)
+            where[name] = q
+            if q < b:                                                                         # already coded (CTUs in raster order, z-order inside)
+                nb[name] = motion(*winners[q]) if mutation == "inter_winner_not_final" else final[q]
+            elif name in ("B0", "A0"):
+                below = name == "A0" and by + 1 == bpc
+                masks["A0_below_ctu" if below else name + "_not_yet_coded"][b] = True
+        masks["A0_from_left_ctu"][b] = nb["A0"] is not None and bx == 0
+        masks["B0_from_above_right_ctu"][b] = nb["B0"] is not None and bx + 1 == bpc and by == 0
+        cands, fl = candidate_list(nb, max_merge, same_picture, mutation)
+        for k, v in fl.items():
+            masks[k][b] = v
+        lam8 = lam(b)
+        clip = lambda v: clip_mv(v, x0, y0, w64, h64)
+        top, priced = None, []
+        for i, (m, origin) in enumerate(cands):
+            c0 = clip(m[1]) if m[0] & 1 else 0
+            c1 = (m[2] if mutation == "no_clip_list1" else clip(m[2])) if m[0] & 2 else 0
+            sad = price(b, m[0], c0, c1, True) if mutation == "avg_of_rounded" else price(b, m[0], c0, c1)
+            c = sad + ((tu_bits(i, len(cands)) * lam8 + 128) >> 8)                            # calcRdSADCost, rdcost.h:148-153
+            priced.append(c)
+            if top is None or (c <= top[0] if mutation == "le_among_candidates" else c < top[0]):   # analysis.cpp:2833
+                top = (c, sad, i, m, (c0, c1), origin)
+        c, sad, i, m, cl, origin = top
+        cost[b] = (sad, c)
+        ic = int(cost_fn(b, c)) if cost_fn is not None else int(inter_cost[b])
+        ic_used[b] = ic
+        inter = ic <= c if mutation == "le_against_inter" else ic < c                          # analysis.cpp:1650-1655
+        masks["tie_stays_merge"][b] = ic == c
+        if inter:
+            final[b] = win
+            dirs[b] = win[0]
+            vec_out[b] = (wrap(win[1]), wrap(win[2]))
+            vec_pred[b] = (wrap(winners[b][1]), wrap(winners[b][2]))                           # the input records, untouched
+            best[b] = (-1, ic)
+            masks["inter_won"][b] = True
+            masks["inter_won_dir%d" % win[0]][b] = True
+            continue
+        merge[b], idx[b], dirs[b] = 1, i, m[0]
+        stored1 = cl[1] if mutation == "clip_stored_list1" else m[2]
+        final[b] = motion(m[0], m[1], stored1, stale=(m[3][0], stored1 if m[0] & 2 else m[3][1]))
+        origin_won[b] = origin
+        vec_out[b] = (wrap(final[b][1]), wrap(final[b][2]))
+        vec_pred[b] = (wrap(cl[0]), wrap(cl[1]))
+        best[b] = (sad, c)
+        masks["merge_won"][b] = True
+        masks["tie_lowest_index"][b] = priced.count(c) > 1
+        masks["won_" + ("zero" if origin == "zero" else origin)][b] = True
+        masks["won_zero_bi"][b] = origin == "zero"
+        masks["won_dir%d" % m[0]][b] = True
+        spatial = origin in where
+        masks["inherits_inherited"][b] = spatial and bool(merge[where[origin]])
+        masks["inherits_combined"][b] = spatial and origin_won[where[origin]] == "combined"
+        masks["merged_dir_differs_from_inter_dir"][b] = m[0] != win[0]
+        masks["clip_changed_prediction"][b] = (m[0] & 1 and clip(m[1]) != m[1]) or (m[0] & 2 and clip(m[2]) != m[2])
+        masks["clip_changed_list1_prediction"][b] = bool(m[0] & 2) and clip(m[2]) != m[2]
+    used = np.stack([(dirs & 1) != 0, (dirs & 2) != 0], axis=1)
+    return dict(merge=merge, merge_idx=idx, dir=dirs, ref_used=used, vec_out=vec_out, vec_pred=vec_pred, cost=cost, best=best, inter_cost=ic_used, masks=masks)
+
+
+def winners_of(dir_in, mv0, mv1, level, nctu):
+    """[(dir, packed mv0, packed mv1)] per block from dir_in uint8 [blocks] and the two record arrays [nctu * 85, 2]."""
+    sl = level_slots(level, nctu)
+    v0, v1 = np.asarray(mv0).reshape(-1, 2)[sl, 1], np.asarray(mv1).reshape(-1, 2)[sl, 1]
+    return [(int(d), int(a), int(b)) for d, a, b in zip(dir_in, v0, v1)]
+
+
+def stage_expectation(depth, cur_y, refs_y, w64, h64, level, dir_in, mv0, mv1, max_merge, lambda8, inter_cost=None, cost_fn=None, tu_qp=None,
+                      lambda8_by_qp=None, qp=0, ref_ids=(0, 1), mutation=None, pricer=None):
+    """What x265hip_b_merge_decide leaves for the inter winner (dir_in uint8 [blocks], mv0 / mv1 int32 [ctu*85, 2]).  Returns walk()'s
+    dictionary plus ref0 / ref1 (int8) and mv0_out / mv1_out / mv0_pred / mv1_pred as RECORDS of the level's slots: a merged block's used
+    lists carry the merge cost, an unused list {the input record's cost, 0}; another block's mv*_out are the input records with an unused
+    list's vector 0, its mv*_pred the input records word for word."""
+    pr = pricer or Pricer(depth, cur_y, refs_y[0], refs_y[1], w64, h64, level)
+    nctu = (w64 // 64) * (h64 // 64)
+    sl = level_slots(level, nctu)
+    ins = [np.asarray(m, np.int32).reshape(-1, 2)[sl] for m in (mv0, mv1)]
+
+    def lam(b):
+        gx, gy = pr.position(b)
+        return IX.block_lambda(tu_qp, lambda8_by_qp, lambda8, qp, depth, gx, gy)
+    win = winners_of(dir_in, mv0, mv1, level, nctu)
+    e = pr.fixpoint(lambda price: walk(w64, h64, level, win, max_merge, price, lam, inter_cost=inter_cost, cost_fn=cost_fn,
+                                       same_picture=ref_ids[0] == ref_ids[1], mutation=mutation))
+    merged = e["merge"] != 0
+    for l in (0, 1):
+        words = np.where(merged & e["ref_used"][:, l], e["cost"][:, 1], ins[l][:, 0]).astype(np.int32)
+        e["mv%d_out" % l] = np.stack([words, e["vec_out"][:, l]], axis=1).astype(np.int32)
+        e["mv%d_pred" % l] = np.stack([words, e["vec_pred"][:, l]], axis=1).astype(np.int32)
+        e["ref%d" % l] = np.where(e["ref_used"][:, l], ref_ids[l], -1).astype(np.int8)
+    return e
+
+
+OUTPUTS = ("merge", "merge_idx", "dir", "ref0", "ref1", "mv0_out", "mv1_out", "mv0_pred", "mv1_pred", "cost", "best")
+
+
+def full_records(level_records, level, nctu):
+    return records(level_records[:, 1], level_records[:, 0], level, nctu)
+
+
+def oracle_prediction(depth, cur_y, refs_y, w64, h64, level, dirs, mv0, mv1):
+    """The oracle's luma prediction of the picture for dir and the records mv0 / mv1 (pred_capture of the bi stage)."""
+    _, _, stride, rows, org = F.padded_dims(w64, h64)
+    flat = lambda p: np.ascontiguousarray(p).reshape(-1)
+    cap = np.zeros((h64, w64), np.asarray(cur_y).dtype)
+    with O.pred_capture(depth, cap):
+        O.inter_recon_bi(depth, flat(cur_y), stride, org, flat(refs_y[0]), flat(refs_y[1]), w64, h64, level, mv0, mv1, 30 + 6 * (depth - 8),
+                         dir_flags=np.ascontiguousarray(dirs, dtype=np.uint8))
+    return cap
+
+
+def reference_prediction(lib, refs_y, w64, h64, level, dirs, mv0, mv1):
+    """Predict::motionCompensation of the compiled reference (lib.x265ref_motion_compensation, oracle/ref_predict.cpp) for a B picture of
+    2Nx2N CUs with dir and the records mv0 / mv1: the luma prediction, every used vector clipped by the reference's own CUData::clipMv.
+    refs_y: the two padded planes (PicYuv geometry)."""
+    r = [np.ascontiguousarray(p) for p in refs_y]
+    dt = r[0].dtype
+    mv = [np.ascontiguousarray(m, dtype=np.int32) for m in (mv0, mv1)]
+    d = np.ascontiguousarray(dirs, dtype=np.uint8)
+    chroma = np.zeros((h64 // 2, w64 // 2), dt)                 # the chroma planes are predicted too; nothing here reads them
+    out = [np.zeros((h64, w64), dt), np.zeros((h64 // 2, w64 // 2), dt), np.zeros((h64 // 2, w64 // 2), dt)]
+    weights = np.tile(np.array([0, 1, 0, 0], np.int32), (2, 3, 1))
+    f = lib.x265ref_motion_compensation
+    f.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 4
+    rc = f(r[0].ctypes.data, chroma.ctypes.data, chroma.ctypes.data, r[1].ctypes.data, chroma.ctypes.data, chroma.ctypes.data, w64, h64, level,
+           mv[0].ctypes.data, mv[1].ctypes.data, d.ctypes.data, 1, 0, 0, weights.ctypes.data, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data)
+    assert rc == 0, rc
+    return out[0]
+
+
+def merge_b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, subme, level, qp, max_merge=3, sao_rdo=None, dir_cost=BX.DIR_COST,
+                  tu_flags=H.TU_SIGN_HIDE, lambda8=IE.LAMBDA8, cores=0, avx2=False, tu_qp=None, cu_qp=None, lambda8_by_qp=None):
+    """One B picture with merge blocks through the oracle, stage by stage (the CPU twin of stages.MergeBFramePipeline.run with chroma,
+    deblocking and SAO applied; tu_qp / cu_qp / lambda8_by_qp: what set_qp_maps hands on).  *_planes = padded (Y, Cb, Cr) host planes.
+    Every stage output by name; behind the coding it is the chain of bsa8d_expect.sa8d_b_chain."""
+    S = IE.importlib.import_module("x265-yuuki-asuna_amd.stages")
+    import qp_map_expect as QE
+    _, _, stride, rows, org = F.padded_dims(w64, h64)
+    cur, r0, r1 = cur_planes[0], ref0_planes[0], ref1_planes[0]
+    nctu = (w64 // 64) * (h64 // 64)
+    if tu_qp is not None:                       # the stages clamp a map's entries to the quantiser's range; the oracle runs take them as they are
+        tu_qp = np.clip(tu_qp, 0, 51 + 6 * (depth - 8)).astype(np.int8)
+    cost = F.mv_cost_table(rng_r)
+    cq, qoff = F.qpel_cost_table(rng_r)
+    out, recs = {}, []
+    for l, ref in enumerate((r0, r1)):
+        _, bestv = O.me_fullsearch(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False, nthreads=cores, avx2=avx2)
+        mv = O.subpel_refine(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, bestv, cq, qoff, subme, nthreads=cores, avx2=avx2)
+        out["subpel_mv%d" % l] = mv
+        recs.append(mv)
+    d = BX.decide(depth, cur, (r0, r1), w64, h64, level, recs, dir_cost=dir_cost, lambda8=lambda8, table=IX.s_bitsizes(4 * rng_r + 4), qp=qp, tu_qp=tu_qp,
+                  lambda8_by_qp=lambda8_by_qp, with_reference=False)
+    win0, win1 = BX.BE.full_mv_out(level, nctu, d["mv0"], 0), BX.BE.full_mv_out(level, nctu, d["mv1"], 0)
+    e = stage_expectation(depth, cur, (r0, r1), w64, h64, level, d["dir"], win0, win1, max_merge, lambda8, inter_cost=d["cost"][:, 0], tu_qp=tu_qp,
+                          lambda8_by_qp=lambda8_by_qp, qp=qp)
+    out.update({"b_dir": d["dir"], "b_cost": d["cost"]})
+    out.update({k: e[k] for k in OUTPUTS})
+    out["merge_cost"] = out.pop("cost")
+    qpc = S.chroma_quant_qp(qp, depth)
+    sc, oc = QE._chroma_geometry(w64)
+    flat = lambda p: np.ascontiguousarray(p).reshape(-1)
+    p0, p1 = full_records(e["mv0_pred"], level, nctu), full_records(e["mv1_pred"], level, nctu)
+    o0, o1 = full_records(e["mv0_out"], level, nctu), full_records(e["mv1_out"], level, nctu)
+    planes = (cur_planes, ref0_planes, ref1_planes)
+
+    def luma(q):
+        return O.inter_recon_bi(depth, flat(cur), stride, org, flat(r0), flat(r1), w64, h64, level, p0, p1, q, dir_flags=e["dir"], intra_slice=tu_flags,
+                                nthreads=cores, avx2=avx2)
+
+    def chroma_run(c):
+        return lambda q: O.inter_recon_chroma_bi(depth, flat(planes[0][c]), flat(planes[1][c]), flat(planes[2][c]), sc, oc, w64, h64, level, p0, p1, q,
+                                                 dir_flags=e["dir"], intra_slice=tu_flags, nthreads=cores, avx2=avx2)
+    if tu_qp is None:
+        res = [luma(qp)] + [chroma_run(c)(qpc) for c in (1, 2)]
+    else:                                       # a run per QP of the map, composed block by block (qp_map_expect)
+        res = [QE._composed(luma, tu_qp[0], w64, h64, level, False, stride, org)] + \
+              [QE._composed(chroma_run(c), tu_qp[c], w64, h64, level, True, sc, oc) for c in (1, 2)]
+    it = {}
+    for i, (rec, lev, ns, dist) in enumerate(res):
+        sfx = "" if i == 0 else "_c%d" % (i - 1)
+        it.update({"recon" + sfx: np.ascontiguousarray(rec).reshape(-1), "levels" + sfx: lev, "num_sig" + sfx: ns, "dist" + sfx: dist})
+    out.update({k: it[k] for k in ("levels", "num_sig", "dist", "levels_c0", "levels_c1", "num_sig_c0", "num_sig_c1")})
+    out["skip"] = skip_flags(e["merge"], it["num_sig"], it["num_sig_c0"], it["num_sig_c1"])
+    cuqp = max(qp - 6 * (depth - 8), 0)
+    bv, bh = O.deblock_bs_b(depth, w64, h64, level, o0, o1, e["ref0"], e["ref1"], it["num_sig"], slice_b=True, avx2=avx2)
+    out.update({"bs_ver": bv, "bs_hor": bh})
+    dbk = O.deblock_luma(depth, it["recon"], stride, org, w64, h64, bv, bh, cuqp, qp_map=cu_qp, avx2=avx2)
+    cnt, off = O.sao_stats(depth, cur.reshape(-1), dbk.reshape(-1), stride, org, w64, h64, nthreads=cores, avx2=avx2)
+    cdb = O.deblock_chroma(depth, it["recon_c0"], it["recon_c1"], sc, oc, w64, h64, bv, bh, cuqp, qp_map=cu_qp, avx2=avx2)
+    cstat = [O.sao_stats(depth, np.ascontiguousarray(cur_planes[1 + i]).reshape(-1), cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, nthreads=cores, avx2=avx2,
+                         ctu=(32, 32), plane_offset=2) for i in range(2)]
+    if sao_rdo is not None:
+        lam = np.tile(np.array(sao_rdo["lambdas"], np.int64), (nctu, 1))
+        pars, _ = O.sao_rdo(depth, [cnt, cstat[0][0], cstat[1][0]], [off, cstat[0][1], cstat[1][1]], w64 // 64, h64 // 64, lam, sao_rdo["ctx_merge"],
+                            sao_rdo["ctx_type"], sao_rdo["entropy_bits"], avx2=avx2)
+        par, cpars = pars[0].reshape(-1), [pars[1].reshape(-1), pars[2].reshape(-1)]
+    else:
+        _, par = O.sao_decide(depth, cnt, off, avx2=avx2)
+        cpars = [O.sao_decide(depth, cstat[i][0], cstat[i][1], avx2=avx2)[1] for i in range(2)]
+    fin = O.sao_apply(depth, dbk.reshape(-1), stride, org, w64, h64, par, nthreads=cores, avx2=avx2).reshape(rows, stride)
+    out.update({"sao_count": cnt, "sao_offset_org": off, "sao_params": par})
+    inner = fin[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
+    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
+    for i in range(2):
+        cf = O.sao_apply(depth, cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, cpars[i], nthreads=cores, avx2=avx2, ctu=(32, 32))
+        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = cstat[i][0], cpars[i]
+        ci = cf.reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
+        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
+    return out
+
+
+def device_outputs(pipe, dt):
+    """The same names from a stages.MergeBFramePipeline after run() (chroma, deblocking, SAO applied)."""
+    g = lambda t: t.cpu().numpy()
+    md, bd = pipe.md, pipe.bd
+    sl = level_slots(md.level, pipe.nctu)
+    out = {"subpel_mv0": g(pipe.spl[0].out).reshape(-1, 2), "subpel_mv1": g(pipe.spl[1].out).reshape(-1, 2), "b_dir": g(bd.dir), "b_cost": g(bd.cost).reshape(-1, 4),
+           "merge": g(md.merge), "merge_idx": g(md.merge_idx), "dir": g(md.dir), "ref0": g(md.ref0), "ref1": g(md.ref1),
+           "merge_cost": g(md.cost).reshape(-1, 2), "best": g(md.best).reshape(-1, 2), "skip": g(pipe.skip),
+           "levels": g(pipe.rc.levels), "num_sig": g(pipe.rc.num_sig), "dist": g(pipe.rc.dist), "bs_ver": g(pipe.db.bs_ver), "bs_hor": g(pipe.db.bs_hor),
+           "sao_count": g(pipe.sao.count), "sao_offset_org": g(pipe.sao.offset_org), "sao_params": g(pipe.sao.params), "recon": g(pipe.final).view(dt)}
+    for k in ("mv0_out", "mv1_out", "mv0_pred", "mv1_pred"):
+        out[k] = g(getattr(md, k)).reshape(-1, 2)[sl]
+    for i in range(2):
+        out["levels_c%d" % i], out["num_sig_c%d" % i] = g(pipe.rc_c[i].levels), g(pipe.rc_c[i].num_sig)
+        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = g(pipe.sao_c[i].count), g(pipe.sao_c[i].params)
+        out["recon_c%d" % i] = g(pipe.final_c[i]).view(dt)
+    return out

@@ -1,0 +1,238 @@
+"""GPU parity of the merge stage of a B picture: x265hip_b_merge_decide against the walk of tests/bmerge_expect.py on the cases of
+tests/bmerge_cases.py (with `real` costs behind x265hip_b_sa8d_decide, compared with the oracle's decision first),
+stages.MergeBFramePipeline stage by stage against the oracle chain, and MiniGop with the step as its b_step.  Equal means equal."""
+import importlib
+
+import numpy as np
+import pytest
+
+import bidir_expect as BE
+import bmerge_cases as C
+import bmerge_expect as BM
+import intra_expect as IE
+
+pytestmark = pytest.mark.gpu
+
+P = importlib.import_module("x265-yuuki-asuna_amd.pipeline")
+S = importlib.import_module("x265-yuuki-asuna_amd.stages")
+HT = importlib.import_module("x265-yuuki-asuna_amd.host_tables")
+GARBAGE = -9
+RECORD_ARRAYS = ("mv0_out", "mv1_out", "mv0_pred", "mv1_pred")
+
+
+def _ids(cases):
+    return dict(argvalues=cases, ids=[c.id for c in cases])
+
+
+def _dev():
+    import torch
+    return torch.device("cuda:0")
+
+
+def _up(a):
+    import torch
+    a = np.ascontiguousarray(a)
+    view = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}.get(a.dtype)
+    return torch.from_numpy(a.view(view) if view else a).to(_dev())
+
+
+def _run_case(c):
+    """The stage alone: every output pre-filled with garbage, two runs over the same inputs into the same buffers.  With `real` costs the
+    inter winner is what x265hip_b_sa8d_decide leaves on the device for the kind's records (compared with the oracle's decision first);
+    with `pattern` costs, the kind's motion and the numbers the walk decided against."""
+    import torch
+    dev = _dev()
+    x = C.expectation(c)
+    e = x["e"]
+    r0_y, cur_y, r1_y = C.luma_triple(c.kind, c.level, c.depth, c.w, c.h)
+    cur, r0, r1 = (P.DevicePicture(y, dev) for y in (cur_y, r0_y, r1_y))
+    nctu = x["nctu"]
+    sl = BM.level_slots(c.level, nctu)
+    qp_map = None if x["tu_qp"] is None else _up(x["tu_qp"][0])
+    lam_tab = None if x["lambda8_by_qp"] is None else _up(x["lambda8_by_qp"])
+    md = S.BMergeDecide(nctu, c.w, c.h, c.depth, c.level, dev, max_merge=c.max_merge, lambda8=c.lambda8, qp=x["qp"], ref_ids=x["ref_ids"])
+    md.qp_map, md.lambda8_by_qp = qp_map, lam_tab
+    assert md.waves == IE.waves(c.w, c.h)
+    g = lambda t: t.cpu().numpy()
+    if c.costs == "real":
+        bd = S.BSa8dDecide(nctu, c.w, c.h, c.depth, c.level, dev, rng=C.RANGE, lambda8=c.lambda8, qp=x["qp"], ref_ids=x["ref_ids"])
+        bd.qp_map, bd.lambda8_by_qp = qp_map, lam_tab
+        bd.run(cur, r0, r1, _up(x["recs"][0]), _up(x["recs"][1]))
+        torch.cuda.synchronize()
+        d = x["decision"]
+        assert np.array_equal(g(bd.dir), d["dir"]) and np.array_equal(g(bd.cost).reshape(-1, 4), d["cost"])
+        assert np.array_equal(g(bd.mv0_out).reshape(-1, 2), x["mv0"]) and np.array_equal(g(bd.mv1_out).reshape(-1, 2), x["mv1"])
+        dir_in, mv0, mv1, cost_in, stride = bd.dir, bd.mv0_out, bd.mv1_out, bd.cost, 4
+    else:
+        dir_in, mv0, mv1, cost_in, stride = _up(x["dir_in"]), _up(x["mv0"]), _up(x["mv1"]), _up(e["inter_cost"].astype(np.int32)), 1
+    want = {k: e[k] for k in BM.OUTPUTS}
+    for t, v in ((md.merge, 0xa5), (md.merge_idx, 0x5a), (md.dir, 0x77), (md.ref0, 0x5a), (md.ref1, 0x5a), (md.cost, -3), (md.best, -5)):
+        t.fill_(v)
+    for k in RECORD_ARRAYS:
+        getattr(md, k).fill_(GARBAGE)
+    other = np.setdiff1d(np.arange(nctu * 85), sl)
+    for run in range(2):
+        md.run(cur, r0, r1, dir_in, mv0, mv1, cost_in, inter_cost_stride=stride)
+        torch.cuda.synchronize()
+        recs = {k: g(getattr(md, k)).reshape(-1, 2) for k in RECORD_ARRAYS}
+        got = {"merge": g(md.merge), "merge_idx": g(md.merge_idx), "dir": g(md.dir), "ref0": g(md.ref0), "ref1": g(md.ref1),
+               "cost": g(md.cost).reshape(-1, 2), "best": g(md.best).reshape(-1, 2)}
+        got.update({k: v[sl] for k, v in recs.items()})
+        bad = BE.compare(got, want)
+        assert not bad, (run, bad)
+        assert all((v[other] == GARBAGE).all() for v in recs.values()), "slots of other levels were written"
+    assert np.array_equal(g(mv0).reshape(-1, 2), x["mv0"]) and np.array_equal(g(mv1).reshape(-1, 2), x["mv1"]) and np.array_equal(g(dir_in), x["dir_in"])
+    return e
+
+
+@pytest.mark.parametrize("c", **_ids(C.COVER_CASES))
+def test_b_merge_decide_equals_the_walk(c):
+    """192x128 at 8 bits, levels 0 - 2: every kind, real and pattern inter costs, max_merge 1 / 2 / 3 / 5, lambda8 1024 and 0."""
+    e = _run_case(c)
+    if c.costs == "pattern":
+        b = np.arange(len(e["merge"]))
+        assert np.array_equal(e["merge"], (b % 3 != 0).astype(np.uint8)) and e["masks"]["tie_stays_merge"].mean() > 0.3
+    if c.lambda8 == 0:                                   # the index is free: cost = sa8d
+        assert np.array_equal(e["cost"][:, 0], e["cost"][:, 1])
+
+
+@pytest.mark.parametrize("c", **_ids(C.DEEP_CASES + C.SIZE_CASES))
+def test_b_merge_decide_at_ten_bits_under_maps_and_on_other_grids(c):
+    """Level 1 at 10 bits, a qp_map with a lambda8_by_qp table, and 64x64, 64x192 (empty odd waves) and 256x64."""
+    e = _run_case(c)
+    assert e["merge"].any()
+
+
+def _sao_rdo_inputs(depth, qp, slice_type):
+    tabs = HT.load()
+    cu_qp = max(qp - 6 * (depth - 8), 0)
+    cm, ct = HT.sao_contexts(slice_type, cu_qp)
+    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
+
+
+def _b_step(w64, h64, depth, dev, level, qp, rng, subme, max_merge=3):
+    return S.MergeBFramePipeline(w64, h64, depth, dev, rng=rng, subme=subme, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True,
+                                 sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_B), max_merge=max_merge)
+
+
+def _triple(depth, level, w, h):
+    """(reference 0, current, reference 1) Y / Cb / Cr: the quads triple of the level - vectors of up to 4 samples, equal in 2x2 groups of
+    blocks, all three directions."""
+    ys = C.luma_triple("quads", level, depth, w, h)
+    cs = C.chroma_triple("quads", level, depth, w, h)
+    return [(ys[i],) + cs[i] for i in range(3)]
+
+
+def _padded(yuv):
+    return IE.padded_planes(yuv)[0]
+
+
+def _step_against_chain(depth, level, w, h, qp, max_merge=3, maps=False):
+    """maps: set_qp_maps with a tu_qp / cu_qp map (both range ends, entries outside the range) and a lambda8_by_qp table."""
+    import torch
+    B = importlib.import_module("bench")
+    dev = _dev()
+    rng, subme = 12, 2
+    yuv = _triple(depth, level, w, h)
+    r0, cur, r1 = (P.DevicePicture(y, dev, u, v) for (y, u, v) in yuv)
+    pipe = _b_step(cur.w64, cur.h64, depth, dev, level, qp, rng, subme, max_merge)
+    kw = {}
+    if maps:
+        tu = C.MC.tu_qp_map(depth, level, w, h)
+        kw = dict(tu_qp=tu, cu_qp=np.clip(tu[0].astype(np.int64) - 6 * (depth - 8), 0, 51).astype(np.int8), lambda8_by_qp=C.QE.lambda8_table(depth))
+        m = S.CuQpMaps(cur.w64, cur.h64, depth, level, dev).load(kw["cu_qp"], tu)
+        pipe.set_qp_maps(m, _up(kw["lambda8_by_qp"]))
+        assert pipe.md.qp_map.data_ptr() == pipe.bd.qp_map.data_ptr() == m.tu_qp[0].data_ptr() and pipe.md.lambda8_by_qp is pipe.bd.lambda8_by_qp
+        assert pipe.rc.qp_map.data_ptr() == m.tu_qp[0].data_ptr() and pipe.rc_c[1].qp_map.data_ptr() == m.tu_qp[2].data_ptr() and pipe.db.qp_map is m.cu_qp
+    marks = []
+    pipe.run(cur, r0, r1, mark=marks.append)
+    torch.cuda.synchronize()
+    assert marks == ["me0", "subpel0", "me1", "subpel1", "b_sa8d", "merge", "recon", "recon_chroma", "skip", "deblock", "sao_stats", "sao_rdo", "sao_apply",
+                     "border"]
+    hp = [_padded(p) for p in yuv]
+    chain = lambda **k: BM.merge_b_chain(depth, hp[1], hp[0], hp[2], cur.w64, cur.h64, rng, subme, level, qp, max_merge=max_merge, sao_rdo=pipe.sao_rdo,
+                                         cores=B.effective_cpus(), **k)
+    cpu_out = chain(**kw)
+    bad = BE.compare(BM.device_outputs(pipe, cur.host.dtype), cpu_out)
+    assert not bad, bad
+    assert set(pipe.checksum()) >= {"merge", "merge_idx", "merge_dir", "mv0_out", "mv1_pred", "skip", "b_cost", "levels", "recon"}
+    if maps:                                       # and the picture-wide QP and lambda again
+        pipe.set_qp_maps(None)
+        assert pipe.md.qp_map is None and pipe.bd.lambda8_by_qp is None and pipe.rc.qp_map is None and pipe.db.qp_map is None
+        pipe.run(cur, r0, r1)
+        torch.cuda.synchronize()
+        plain = chain()
+        bad = BE.compare(BM.device_outputs(pipe, cur.host.dtype), plain)
+        assert not bad, bad
+        assert not np.array_equal(plain["merge_cost"], cpu_out["merge_cost"]) and not np.array_equal(plain["levels"], cpu_out["levels"])
+    return cpu_out
+
+
+@pytest.mark.parametrize("depth,level,w,h", [(8, 2, 192, 128), (8, 1, 192, 128), (10, 0, 192, 128), (8, 1, 256, 64)])
+def test_b_step_every_stage_equals_the_oracle_chain(depth, level, w, h):
+    """MergeBFramePipeline.run with chroma, deblocking, SAO applied with the rate-distortion parameters and sign hiding: refined vectors of
+    both lists, the inter winner's direction and costs, merge flags and indices, final directions and reference ids, the four vector
+    records, luma + chroma levels, numSig, SSE, skip flags, Bs maps, SAO statistics + parameters and the final Y / Cb / Cr planes."""
+    out = _step_against_chain(depth, level, w, h, 30 + 6 * (depth - 8))
+    merged = out["merge"] != 0
+    assert merged.any() and not merged.all()
+
+
+def test_b_step_at_the_largest_qp_every_merged_block_skips():
+    out = _step_against_chain(8, 1, 192, 128, 51)
+    merged = out["merge"] != 0
+    assert merged.any() and out["skip"][merged].all() and not out["skip"][~merged].any()
+
+
+def test_b_step_at_qp_zero_no_block_skips():
+    out = _step_against_chain(8, 1, 192, 128, 0, max_merge=5)
+    assert (out["merge"] != 0).any() and not out["skip"].any()
+
+
+def test_b_step_hands_qp_maps_to_every_stage():
+    """set_qp_maps on the step: the TU stages quantise with the map's QPs, the inter winner and every merge candidate are priced with the
+    lambda of the block's luma QP, deblocking reads the CU map - every stage against the chain under the same maps - and
+    set_qp_maps(None) restores the plain step."""
+    out = _step_against_chain(8, 1, 192, 128, 30, maps=True)
+    assert (out["merge"] != 0).any()
+
+
+def test_b_step_refuses_b_intra():
+    with pytest.raises(ValueError):
+        S.MergeBFramePipeline(192, 128, 8, _dev(), b_intra=True)
+
+
+def test_mini_gop_with_the_step_as_b_step():
+    """MiniGop with an i_step, MergePFramePipeline as p_step and MergeBFramePipeline as b_step, gop 3, three anchors (7 pictures of
+    192x128): every B picture is what the step alone produces from the two coded anchors around it, blocks merge in every B picture, and
+    the anchors equal those of a run with Sa8dBFramePipeline as b_step - B pictures change nothing a P picture sees."""
+    import torch
+    dev = _dev()
+    depth, level, qp, gop, rng, subme = 8, 2, 30, 3, 12, 2
+    clip = BE.occluded_clip(192, 128, 7, depth, 71)
+    pics = [P.DevicePicture(y, dev, u, v) for (y, u, v) in clip]
+    w64, h64 = pics[0].w64, pics[0].h64
+    common = dict(rng=rng, subme=subme, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True)
+
+    def steps(b_step):
+        i_step = S.IFramePipeline(w64, h64, depth, dev, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True,
+                                  sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_I))
+        p_step = S.MergePFramePipeline(w64, h64, depth, dev, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_P), **common)
+        return S.MiniGop(p_step, b_step, gop, i_step=i_step)
+    order, out = steps(_b_step(w64, h64, depth, dev, level, qp, rng, subme)).run(pics)
+    torch.cuda.synchronize()
+    assert order == [0, 3, 1, 2, 6, 4, 5] and sorted(out) == list(range(7))
+    old = S.Sa8dBFramePipeline(w64, h64, depth, dev, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_B), **common)
+    _, out_old = steps(old).run(pics)
+    torch.cuda.synchronize()
+    same = lambda a, b: all(torch.equal(x.reshape(-1), y.reshape(-1)) for x, y in zip(a, b))
+    for a in (0, 3, 6):
+        assert same(out[a], out_old[a]), f"anchor {a} depends on the B step"
+    alone = _b_step(w64, h64, depth, dev, level, qp, rng, subme)
+    for a in (3, 6):
+        r0, r1 = pics[a - gop].like([p.clone() for p in out[a - gop]]), pics[a].like([p.clone() for p in out[a]])
+        for k in range(a - gop + 1, a):
+            alone.run(pics[k], r0, r1)
+            torch.cuda.synchronize()
+            assert same(alone.final_planes(), out[k]), f"picture {k}"
+            assert bool(alone.md.merge.any().item()), k

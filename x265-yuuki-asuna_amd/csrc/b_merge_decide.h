@@ -1,0 +1,307 @@
+// b_merge_decide.h - the merge arm of the sa8d choice of a B picture's blocks, on gfx950 (included at the end of tu_kernels.hip behind
+// merge_decide.h: the wave walk of that file, the staging steps of b_sa8d_decide.h, the Hadamard stage of decision_common.h).
+//
+// Analysis::checkMerge2Nx2N_rd0_4 at RD level 0 (source/encoder/analysis.cpp:2787-2838) and the comparisons of
+// Analysis::compressInterCU_rd0_4 (analysis.cpp:1650-1655), per N x N block (N = 8 << level) of the TU stages' grid - one 2Nx2N CU each, CTUs
+// in raster order, blocks in z-order, one slice, a B slice with one reference per list, no temporal candidate:
+//   list   CUData::getInterMergeCandidates (common/cudata.cpp:1458-1712) with isInterB: a candidate is (dir, mv[0], mv[1]), an unused
+//          list's vector is 0.  Spatial A1, B1, B0, A0 and B2 (only while count < 4) with the availability of merge_decide.h; pruned pairs
+//          B1-A1, B0-B1, A0-A1, B2-A1, B2-B1 by hasEqualMotion (cudata.cpp:1439-1455): equal directions first, then the vectors of the
+//          used lists.  Combined candidates (:1652-1683): cutoff = count * (count - 1) once, pairs in the order of 0xEDC984 / 0xB73621,
+//          {3, cand[i].mv[0], cand[j].mv[1]} where cand[i] uses list 0 and cand[j] list 1, unless both lists name one picture and the two
+//          vectors are equal.  The rest {3, (0, 0), (0, 0)} (:1684-1709, one reference per list).  Returned once count == max_merge, at
+//          every increment.  A neighbour's motion is what it ENDED UP with.
+//   price  Predict::motionCompensation (predict.cpp:168-215) after clipMv of every used vector (the limits of merge_decide.h, per list):
+//          dir 3 = addAvg of the two lists' 14-bit intermediates, dir 1 / 2 = predInterLumaPixel of that list; dist = cu[].sa8d, bits =
+//          getTUBits(i, max_merge), cost = dist + ((bits * lambda8 + 128) >> 8); the best with strict <.
+//   choice the block keeps its inter winner iff inter_cost < merge cost, inter_cost = the cost of b_sa8d_decide.h's winner.  The reference
+//          (analysis.cpp:1650-1655) starts with bestMode = merge, replaces it by the single list when uni < merge, then by the
+//          bidirectional candidate when bi < what stands.  With b_sa8d_decide.h's dir = bi < uni ? 3 : 1 + l and inter_cost = min(uni, bi):
+//            bi < uni:   inter_cost = bi.  Whether or not uni < merge, the last comparison is bi < min(uni, merge), and bi < uni: bi wins
+//                        iff bi < merge.
+//            bi >= uni:  inter_cost = uni.  uni wins the first comparison iff uni < merge; then bi < uni fails.  If uni >= merge, bi >= uni
+//                        >= merge fails too: merge stays.
+//            so in both cases an inter mode stands iff inter_cost < merge, and it is the one dir names; a tie stays merge.
+//
+// Mapping: the schedule of merge_decide_kernel - wave = cx + 2 cy, one launch per wave, one workgroup of 256 threads per CTU of the wave,
+// the CTU's blocks in z-order.  The CTU's motion field (dir, mv0, mv1 per block) sits in LDS with its border (read from dir / mv0_out /
+// mv1_out, which earlier waves wrote); the blocks' inter winners, inter costs and lambdas are fetched into LDS once, off the serial chain.
+// Thread 0 builds the list, clips it and keeps one slot per distinct (dir, clipped mv0, clipped mv1) - pricing equal candidates once is
+// exact.  The slots are priced side by side (16 / 4 / 1 per pass): the two lists are staged one after the other through one patch and one
+// `immed` buffer, as in b_sa8d_decide_kernel; a slot takes part in the lists its dir names.  A dir-3 slot's 14-bit prediction of list 0
+// waits in LDS and is combined with list 1's where that is formed; a single-list slot takes the rounded pixel of the same filter sum
+// (sa8d_slots() predicts from one plane only, so the single-list slots of two planes share this path instead).  One Hadamard stage per pass.
+#pragma once
+
+namespace x265hip {
+
+struct BMergeArgs
+{
+    const uint8_t* fenc; long fencStrideB;
+    const uint8_t* fref[2]; long frefStrideB;
+    const uint8_t* dirIn;               // [ctu][blocks]: the inter winner's direction
+    const int2* mv[2];                  // [ctu*85] {cost, qx | qy << 16}: the inter winner's records
+    const int32_t* interCost; long interCostStride;
+    int ctusW, ctusH, depth, qp, lambda8, maxMerge, refId[2];
+    uint8_t* merge; uint8_t* mergeIdx; uint8_t* dir;    // [ctu][blocks]
+    int8_t* ref[2];                     // optional [ctu][blocks]
+    int2* mvOut[2]; int2* mvPred[2];    // [ctu*85], the level's slots
+    int2* cost;                         // [ctu][blocks] {sa8d, cost} of the best merge candidate
+    int2* best;                         // optional [ctu][blocks]
+    const int8_t* qpMap;                // optional: the luma plane of tu_qp
+    const uint32_t* lambdaByQp;         // optional
+};
+
+struct BMotion { int dir, mv0, mv1; };  // an unused list's vector is 0, so hasEqualMotion is equality of the three words
+
+__device__ __forceinline__ bool b_equal_motion(const BMotion& p, const BMotion& q) { return p.dir == q.dir && p.mv0 == q.mv0 && p.mv1 == q.mv1; }
+
+template <typename Px, int N>
+__global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const int wave, const int cyLo)
+{
+    constexpr int BPC = 64 / N, NPU = BPC * BPC, NB = Sa8dLds<N>::NB, BPR = 32 / N, BPP = sizeof(Px), FW = BPC + 2, FH = BPC + 1, FS = FH * FW;
+    constexpr int LOG2N = N == 8 ? 3 : (N == 16 ? 4 : 5), PW = N + 7, PP = PW + 1;
+    __shared__ Sa8dLds<N> s;
+    __shared__ int16_t ps0[32 * 32];              // list 0's 14-bit prediction of the dir-3 slots
+    __shared__ int sField[3][FS];                 // dir, mv0, mv1 at block (bx, by) of the CTU: [(by + 1) * FW + bx + 1]; row 0 / column 0 = the border
+    __shared__ int sCand[3][5], sSlotOf[5], sSlot[3][5], sSlotSad[5], sSlots;
+    __shared__ int2 sWinner[2][NPU];
+    __shared__ int sWinnerDir[NPU], sInter[NPU], sLambda[NPU];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int cyb = cyLo + (int)blockIdx.x, cxb = wave - 2 * cyb;
+    const int ctu = cyb * a.ctusW + cxb;
+    const int blocksW = a.ctusW * BPC, blocksH = a.ctusH * BPC;
+    const int width = a.ctusW * 64, height = a.ctusH * 64;
+    const int lbase = level_record_base<N>();
+    const int maxVal = (1 << a.depth) - 1, headRoom = 14 - a.depth;
+    const Px* fenc = reinterpret_cast<const Px*>(a.fenc);
+    const long rst = a.frefStrideB / BPP, fst = a.fencStrideB / BPP;
+
+    // ---- the border of the motion field: the final motion of the blocks around the CTU that earlier waves left in dir / mv0_out / mv1_out --
+    if (tid < FW + BPC)
+    {
+        const int rx = tid < FW ? tid - 1 : -1, ry = tid < FW ? -1 : tid - FW;                  // relative to the CTU's first block
+        const int gbx = cxb * BPC + rx, gby = cyb * BPC + ry;
+        BMotion m = { 0, 0, 0 };
+        if (gbx >= 0 && gby >= 0 && gbx < blocksW)
+        {
+            const int ncx = gbx / BPC, ncy = gby / BPC, nz = ip_zidx(gbx - ncx * BPC, gby - ncy * BPC);
+            const size_t nctu = (size_t)(ncy * a.ctusW + ncx);
+            m.dir = a.dir[nctu * NPU + nz];
+            m.mv0 = a.mvOut[0][nctu * 85 + lbase + nz].y;
+            m.mv1 = a.mvOut[1][nctu * 85 + lbase + nz].y;
+        }
+        const int f = (ry + 1) * FW + rx + 1;
+        sField[0][f] = m.dir; sField[1][f] = m.mv0; sField[2][f] = m.mv1;
+    }
+    // ---- what the decisions read of the CTU's own blocks, off the serial chain: the inter winner, its cost, the block's lambda ------------
+    if (tid < NPU)
+    {
+        const int z = tid;
+        const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
+        sWinnerDir[z] = a.dirIn[(size_t)ctu * NPU + z];
+        sWinner[0][z] = a.mv[0][(size_t)ctu * 85 + lbase + z];
+        sWinner[1][z] = a.mv[1][(size_t)ctu * 85 + lbase + z];
+        sInter[z] = a.interCost[((size_t)ctu * NPU + z) * a.interCostStride];
+        sLambda[z] = block_lambda8(a.lambda8, a.lambdaByQp, a.qpMap, a.qp, a.depth, a.ctusW, (cxb * 64 + bxz * N) >> 3, (cyb * 64 + byz * N) >> 3);
+    }
+    __syncthreads();
+
+    // thread 0: the candidate list of block z from the motion field, clipped, one slot per distinct clipped candidate
+    auto build = [&](const int z)
+    {
+        const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
+        const int gbx = cxb * BPC + bxz, gby = cyb * BPC + byz;
+        const int x0 = gbx * N, y0 = gby * N;
+        // getPULeft / getPUAbove / getPUAboveRight / getPUBelowLeft / getPUAboveLeft on this grid: inside the picture and already coded
+        auto available = [&](const int nbx, const int nby)
+        {
+            if (nbx < 0 || nby < 0 || nbx >= blocksW || nby >= blocksH) return false;
+            const int ncx = nbx / BPC, ncy = nby / BPC;
+            if (ncx != cxb || ncy != cyb) return ncy * a.ctusW + ncx < ctu;
+            return ip_zidx(nbx - ncx * BPC, nby - ncy * BPC) < z;
+        };
+        auto motion = [&](const int dx, const int dy)
+        {
+            const int f = (byz + dy + 1) * FW + bxz + dx + 1;
+            return BMotion{ sField[0][f], sField[1][f], sField[2][f] };
+        };
+        const int num = a.maxMerge;
+        int count = 0;
+        auto put = [&](const BMotion& m) { sCand[0][count] = m.dir; sCand[1][count] = m.mv0; sCand[2][count] = m.mv1; count++; };
+        const bool avA1 = available(gbx - 1, gby), avB1 = available(gbx, gby - 1), avB0 = available(gbx + 1, gby - 1);
+        const bool avA0 = available(gbx - 1, gby + 1), avB2 = available(gbx - 1, gby - 1);
+        const BMotion none = { 0, 0, 0 };
+        const BMotion mA1 = avA1 ? motion(-1, 0) : none, mB1 = avB1 ? motion(0, -1) : none, mB0 = avB0 ? motion(1, -1) : none;
+        const BMotion mA0 = avA0 ? motion(-1, 1) : none, mB2 = avB2 ? motion(-1, -1) : none;
+        // `count < num` in front of every step is the reference's return at count == maxNumMergeCand
+        if (avA1) put(mA1);                                                                                          // cudata.cpp:1495-1510
+        if (count < num && avB1 && (!avA1 || !b_equal_motion(mA1, mB1))) put(mB1);                                   // :1517-1532
+        if (count < num && avB0 && (!avB1 || !b_equal_motion(mB1, mB0))) put(mB0);                                   // :1537-1551
+        if (count < num && avA0 && (!avA1 || !b_equal_motion(mA1, mA0))) put(mA0);                                   // :1556-1570
+        if (count < num && count < 4 && avB2 && (!avA1 || !b_equal_motion(mA1, mB2)) && (!avB1 || !b_equal_motion(mB1, mB2))) put(mB2);   // :1573-1593
+        if (count < num)                                                                                             // :1652-1683
+        {
+            const int cutoff = count * (count - 1);                   // from the spatial count, once
+            unsigned p0 = 0xEDC984u, p1 = 0xB73621u;
+            for (int k = 0; k < cutoff && count < num; k++, p0 >>= 2, p1 >>= 2)
+            {
+                const int i = p0 & 3, j = p1 & 3;
+                if ((sCand[0][i] & 1) && (sCand[0][j] & 2))
+                {
+                    const BMotion m = { 3, sCand[1][i], sCand[2][j] };
+                    if (!(a.refId[0] == a.refId[1] && m.mv0 == m.mv1)) put(m);                                       // :1670
+                }
+            }
+        }
+        const BMotion zero = { 3, 0, 0 };
+        while (count < num) put(zero);                                                                               // :1684-1709
+        // clipMv (cudata.cpp:1915-1928) of every used vector
+        const int xmin = -((64 + 8 + x0 - 1) << 2), xmax = (width + 8 - x0 - 1) << 2;
+        const int ymin = -((64 + 8 + y0 - 1) << 2), ymax = (height + 8 - y0 - 1) << 2;
+        auto clip = [&](const int c) { return merge_pack(min(xmax, max(xmin, (int)(int16_t)(c & 0xffff))), min(ymax, max(ymin, (int)(int16_t)(c >> 16)))); };
+        int slots = 0;
+        for (int i = 0; i < num; i++)
+        {
+            const int d = sCand[0][i];
+            const int c0 = (d & 1) ? clip(sCand[1][i]) : 0, c1 = (d & 2) ? clip(sCand[2][i]) : 0;
+            int k = 0;
+            while (k < slots && !(sSlot[0][k] == d && sSlot[1][k] == c0 && sSlot[2][k] == c1)) k++;
+            if (k == slots) { sSlot[0][k] = d; sSlot[1][k] = c0; sSlot[2][k] = c1; slots++; }
+            sSlotOf[i] = k;
+        }
+        sSlots = slots;
+    };
+    if (tid == 0) build(0);
+    __syncthreads();
+
+    for (int z = 0; z < NPU; z++)
+    {
+        const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
+        const int x0 = (cxb * BPC + bxz) * N, y0 = (cyb * BPC + byz) * N;
+        const int slots = sSlots;
+        auto pos = [&](const int) { return make_int2(x0, y0); };
+        for (int base = 0; base < slots; base += NB)
+        {
+            const int nAct = min(NB, slots - base);
+#pragma unroll 1
+            for (int l = 0; l < 2; l++)
+            {
+                bool any = false;                                                  // the same for every thread: the barriers below are uniform
+                for (int b = 0; b < nAct; b++) any = any || (sSlot[0][base + b] & (1 << l));
+                if (!any) continue;
+                const Px* fref = reinterpret_cast<const Px*>(a.fref[l]);
+                auto use = [&](const int b) { return (sSlot[0][base + b] & (1 << l)) != 0; };
+                auto mvOf = [&](const int b) { return sSlot[1 + l][base + b]; };
+                luma_stage_patches<Px, N>(s.patch, nAct, use, mvOf, pos, fref, rst);
+                __syncthreads();
+                luma_stage_rows<N>(s.patch, s.immed, nAct, use, mvOf, headRoom);
+                __syncthreads();
+                for (int i = tid; i < 32 * 32; i += 256)
+                {
+                    const int ry = i >> 5, rx = i & 31, b = (ry >> LOG2N) * BPR + (rx >> LOG2N), y = ry & (N - 1), x = rx & (N - 1);
+                    if (b >= nAct || !use(b)) continue;
+                    int sh, px;
+                    luma_short_and_pixel<N>(s.patch + b * (PW * PP), s.immed + b * (PW * N), mvOf(b), x, y, headRoom, maxVal, sh, px);
+                    if (sSlot[0][base + b] != 3) s.diff[i] = (int16_t)((int)fenc[(long)(y0 + y) * fst + x0 + x] - px);
+                    else if (l == 0) ps0[i] = (int16_t)sh;
+                    else s.diff[i] = (int16_t)((int)fenc[(long)(y0 + y) * fst + x0 + x] - luma_add_avg((int)ps0[i], sh, a.depth, maxVal));
+                }
+                __syncthreads();                                    // patch / immed are free for list 1; after list 1 the plane is complete
+            }
+            // (the tiles of a slot at or beyond nAct transform whatever the difference array holds; nothing reads their sums)
+            if (tid < 128) sa8d_tile_sums<N>(s.diff, s.sum, tid, lane);
+            __syncthreads();
+            if (tid < nAct) sSlotSad[base + tid] = sa8d_slot_sum<N>(s.sum, tid);
+            __syncthreads();
+        }
+        if (tid == 0)
+        {
+            const int lambda8 = sLambda[z];
+            const int num = a.maxMerge;
+            int bestI = 0, bestSad = 0;
+            long long bestCost = 0;
+            for (int i = 0; i < num; i++)
+            {
+                const int sad = sSlotSad[sSlotOf[i]];
+                const int bits = i + (i < num - 1 ? 1 : 0);                                                  // getTUBits, search.h:246-249
+                const long long cost = (long long)sad + rd_sad_rate(bits, lambda8);
+                if (i == 0 || cost < bestCost) { bestI = i; bestSad = sad; bestCost = cost; }                // analysis.cpp:2833
+            }
+            const size_t blk = (size_t)ctu * NPU + z, rec = (size_t)ctu * 85 + lbase + z;
+            const int2 w0 = sWinner[0][z], w1 = sWinner[1][z];
+            const int ic = sInter[z];
+            const bool inter = (long long)ic < bestCost;                                                     // analysis.cpp:1650-1655: a tie stays merge
+            const int k = sSlotOf[bestI];
+            const int dir = inter ? sWinnerDir[z] : sCand[0][bestI];
+            const int f0 = (dir & 1) ? (inter ? w0.y : sCand[1][bestI]) : 0, f1 = (dir & 2) ? (inter ? w1.y : sCand[2][bestI]) : 0;
+            // a merged block's used lists carry the merge cost; every other cost word is the input record's
+            const int c0 = (!inter && (dir & 1)) ? (int)bestCost : w0.x, c1 = (!inter && (dir & 2)) ? (int)bestCost : w1.x;
+            a.merge[blk] = inter ? 0 : 1;
+            a.mergeIdx[blk] = inter ? 0 : (uint8_t)bestI;
+            a.dir[blk] = (uint8_t)dir;
+            if (a.ref[0]) a.ref[0][blk] = (int8_t)((dir & 1) ? a.refId[0] : -1);
+            if (a.ref[1]) a.ref[1][blk] = (int8_t)((dir & 2) ? a.refId[1] : -1);
+            a.mvOut[0][rec] = make_int2(c0, f0);
+            a.mvOut[1][rec] = make_int2(c1, f1);
+            a.mvPred[0][rec] = inter ? w0 : make_int2(c0, sSlot[1][k]);
+            a.mvPred[1][rec] = inter ? w1 : make_int2(c1, sSlot[2][k]);
+            a.cost[blk] = make_int2(bestSad, (int)bestCost);
+            if (a.best) a.best[blk] = inter ? make_int2(-1, ic) : make_int2(bestSad, (int)bestCost);
+            const int f = (byz + 1) * FW + bxz + 1;
+            sField[0][f] = dir; sField[1][f] = f0; sField[2][f] = f1;
+            if (z + 1 < NPU) build(z + 1);                                                                   // the next block's list: no barrier in between
+        }
+        __syncthreads();
+    }
+}
+
+// true where two of the six record arrays overlap, or dir is dir_in
+static bool b_merge_records_alias(const int nctu, const x265hip_b_merge_decide_params* p)
+{
+    const uintptr_t len = (uintptr_t)nctu * 85 * 8;
+    const uintptr_t r[6] = { (uintptr_t)p->mv0_out, (uintptr_t)p->mv1_out, (uintptr_t)p->mv0_pred, (uintptr_t)p->mv1_pred, (uintptr_t)p->mv0, (uintptr_t)p->mv1 };
+    bool alias = (const void*)p->dir == (const void*)p->dir_in;
+    for (int i = 0; i < 4; i++)                                                  // every output against every later array; mv0 may be mv1
+        for (int j = i + 1; j < 6; j++) alias = alias || (r[i] < r[j] + len && r[j] < r[i] + len);
+    return alias;
+}
+
+} // namespace x265hip
+
+extern "C" int x265hip_b_merge_decide(const x265hip_b_merge_decide_params* p, void* stream)
+{
+    using namespace x265hip;
+    // argument checks first: they need no device (at most 4 bits and lambda8 <= 2^24 keep the rate term below 2^19 and the cost inside int32)
+    if (decision_record_refused("b_merge_decide", p, !p || !p->fenc || !p->fref0 || !p->fref1 || !p->dir_in || !p->mv0 || !p->mv1 || !p->inter_cost || !p->merge ||
+                                !p->merge_idx || !p->dir || !p->mv0_out || !p->mv1_out || !p->mv0_pred || !p->mv1_pred || !p->cost)) return X265HIP_EINVAL;
+    if (p->max_merge < 1 || p->max_merge > 5) { set_error("b_merge_decide: max_merge %d out of 1..5", p->max_merge); return X265HIP_EINVAL; }
+    if (inter_cost_stride_refused("b_merge_decide", p->inter_cost_stride)) return X265HIP_EINVAL;
+    // the walk reads a block's inter winner from dir_in / mv0 / mv1 and its neighbours' final motion from dir / mv*_out: shared arrays would
+    // change what a second run sees
+    if (b_merge_records_alias((p->width / 64) * (p->height / 64), p))
+    { set_error("b_merge_decide: mv*_out / mv*_pred must not alias mv0 / mv1 or each other, nor dir dir_in"); return X265HIP_EINVAL; }
+    int rc = ensure_device();
+    if (rc) return rc;
+
+    const int bpp = p->depth == 8 ? 1 : 2;
+    BMergeArgs a = {};
+    a.fenc = (const uint8_t*)p->fenc; a.fencStrideB = (long)p->fenc_stride * bpp;
+    a.fref[0] = (const uint8_t*)p->fref0; a.fref[1] = (const uint8_t*)p->fref1; a.frefStrideB = (long)p->fref_stride * bpp;
+    a.dirIn = p->dir_in; a.mv[0] = (const int2*)p->mv0; a.mv[1] = (const int2*)p->mv1;
+    a.interCost = p->inter_cost; a.interCostStride = (long)p->inter_cost_stride;
+    a.ctusW = p->width / 64; a.ctusH = p->height / 64; a.depth = p->depth; a.qp = p->qp; a.lambda8 = p->lambda8; a.maxMerge = p->max_merge;
+    a.refId[0] = p->ref_id0; a.refId[1] = p->ref_id1;
+    a.merge = p->merge; a.mergeIdx = p->merge_idx; a.dir = p->dir; a.ref[0] = p->ref0; a.ref[1] = p->ref1;
+    a.mvOut[0] = (int2*)p->mv0_out; a.mvOut[1] = (int2*)p->mv1_out; a.mvPred[0] = (int2*)p->mv0_pred; a.mvPred[1] = (int2*)p->mv1_pred;
+    a.cost = (int2*)p->cost; a.best = (int2*)p->best; a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
+    hipStream_t s = (hipStream_t)stream;
+    for_each_wave(a.ctusW, a.ctusH, [&](const int w, const int cyLo, const int n)
+    {
+        for_depth_level(p->depth, p->level, [&](auto px, auto size)
+        { hipLaunchKernelGGL((b_merge_decide_kernel<decltype(px), decltype(size)::value>), dim3(n), dim3(256), 0, s, a, w, cyLo); });
+    });
+    X265HIP_TRY(hipGetLastError());
+    return 0;
+}

@@ -16,7 +16,9 @@
 // same patch and `immed` buffers: list 0's 14-bit prediction waits in LDS, list 1's is combined with it where it is formed.  Each filter
 // sum gives the 14-bit intermediate and the rounded pixel of the single-list candidate (they share the sum), so the chosen list's
 // prediction costs no second pass.  Three difference planes (single list, both lists, zero pair) go to LDS, and all four wavefronts run
-// the 3 x 16 8x8 Hadamard transforms.  Blocks are independent: one launch per picture, no atomics.
+// the 3 x 16 8x8 Hadamard transforms.  Blocks are independent: one launch per picture, no atomics.  The staging steps (patches, 14-bit rows,
+// the sample's intermediate and pixel, addAvg) are __device__ functions that b_merge_decide_kernel (b_merge_decide.h) calls too, so the two
+// price a two-list prediction alike.
 #pragma once
 
 namespace x265hip {
@@ -37,11 +39,94 @@ struct BSa8dArgs
     const uint32_t* lambdaByQp;         // optional, indexed by the block's luma quantiser QP
 };
 
+// ---- the staging steps of one list's prediction, which b_merge_decide_kernel (b_merge_decide.h) runs too: slot b of nAct predicts the N x N
+// block at pos(b) (int2, its first luma sample) from fref displaced by mvOf(b) (qx | qy << 16); use(b) = the slot takes part in this
+// list.  All 256 threads call each step; a barrier belongs between two steps. --------------------------------------------------------------
+
+// the slots' reference patches: N + 7 rows and columns around the full-sample position
+template <typename Px, int N, class Use, class Mv, class Pos>
+__device__ __forceinline__ void luma_stage_patches(int16_t* patch, const int nAct, const Use use, const Mv mvOf, const Pos pos, const Px* fref, const long rst)
+{
+    constexpr int APRON = 3, PW = N + 7, PP = PW + 1;
+    for (int i = threadIdx.x; i < nAct * PW * PW; i += 256)
+    {
+        const int b = i / (PW * PW), r = i - b * (PW * PW), y = r / PW, x = r - y * PW;
+        if (!use(b)) continue;
+        const int w = mvOf(b);
+        const int qx = (int16_t)(w & 0xffff), qy = (int16_t)(w >> 16);
+        const int2 o = pos(b);
+        const int px = o.x + (qx >> 2) - APRON + x, py = o.y + (qy >> 2) - APRON + y;
+        patch[b * (PW * PP) + y * PP + x] = (int16_t)fref[(long)py * rst + px];
+    }
+}
+
+// where both phases are set, the horizontal pass at 14-bit precision first (luma_hps with row extension)
+template <int N, class Use, class Mv>
+__device__ __forceinline__ void luma_stage_rows(const int16_t* patch, int16_t* immed, const int nAct, const Use use, const Mv mvOf, const int headRoom)
+{
+    constexpr int LOG2N = N == 8 ? 3 : (N == 16 ? 4 : 5), PW = N + 7, PP = PW + 1;
+    const int shiftPS = 6 - headRoom, offPS = -(8192 << shiftPS);
+    for (int i = threadIdx.x; i < nAct * PW * N; i += 256)
+    {
+        const int b = i / (PW * N), r = i - b * (PW * N), y = r >> LOG2N, x = r & (N - 1);
+        if (!use(b)) continue;
+        const int w = mvOf(b);
+        const int xf = w & 3, yf = (w >> 16) & 3;
+        if (xf && yf)
+        {
+            int s = 0;
+#pragma unroll
+            for (int t = 0; t < 8; t++) s += (int)patch[b * (PW * PP) + y * PP + x + t] * (int)kTuTaps[xf][t];
+            immed[i] = (int16_t)((s + offPS) >> shiftPS);
+        }
+    }
+}
+
+// sample (x, y) of a slot whose patch is pt and whose rows are im: the 14-bit intermediate (predInterLumaShort) and, from the same sum,
+// the rounded pixel (predInterLumaPixel)
+template <int N>
+__device__ __forceinline__ void luma_short_and_pixel(const int16_t* pt, const int16_t* im, const int w, const int x, const int y, const int headRoom,
+                                                     const int maxVal, int& sh, int& px)
+{
+    constexpr int APRON = 3, PP = N + 8;
+    const int xf = w & 3, yf = (w >> 16) & 3;
+    const int shiftPS = 6 - headRoom, offPS = -(8192 << shiftPS);
+    if (xf && yf)
+    {
+        const int shiftSP = 6 + headRoom, offSP = (1 << (shiftSP - 1)) + (8192 << 6);
+        int s = 0;
+#pragma unroll
+        for (int t = 0; t < 8; t++) s += (int)im[(y + t) * N + x] * (int)kTuTaps[yf][t];
+        sh = (int16_t)(s >> 6);                                                                     // luma_vss
+        px = tu_clip16((s + offSP) >> shiftSP, maxVal);                                            // luma_vsp
+    }
+    else if (!(xf | yf))
+    {
+        px = pt[(y + APRON) * PP + x + APRON];
+        sh = (int16_t)((px << headRoom) - 8192);                                                    // convert_p2s
+    }
+    else
+    {
+        int s = 0;
+#pragma unroll
+        for (int t = 0; t < 8; t++) s += (int)(xf ? pt[(y + APRON) * PP + x + t] : pt[(y + t) * PP + x + APRON]) * (int)kTuTaps[xf ? xf : yf][t];
+        sh = (int16_t)((s + offPS) >> shiftPS);                                                     // luma_hps / vps
+        px = tu_clip16((s + 32) >> 6, maxVal);                                                      // luma_hpp / vpp
+    }
+}
+
+// addAvg (pixel.cpp) of two 14-bit intermediates
+__device__ __forceinline__ int luma_add_avg(const int s0, const int s1, const int depth, const int maxVal)
+{
+    const int shiftAvg = 15 - depth, offAvg = (1 << (shiftAvg - 1)) + 2 * 8192;
+    return clip3(0, maxVal, (s0 + s1 + offAvg) >> shiftAvg);
+}
+
 template <typename Px, int N>
 __global__ void __launch_bounds__(256) b_sa8d_decide_kernel(BSa8dArgs a)
 {
     constexpr int LOG2N = N == 8 ? 3 : (N == 16 ? 4 : 5), BPR = 32 / N, NB = BPR * BPR, BPC = 64 / N, NPU = BPC * BPC;
-    constexpr int APRON = 3, PW = N + 7, PP = PW + 1, BPP = sizeof(Px);
+    constexpr int PW = N + 7, PP = PW + 1, BPP = sizeof(Px);
     __shared__ int16_t patch[NB * PW * PP];
     __shared__ int16_t immed[NB * PW * N];
     __shared__ int16_t fe[32 * 32], ps0[32 * 32];
@@ -71,67 +156,25 @@ __global__ void __launch_bounds__(256) b_sa8d_decide_kernel(BSa8dArgs a)
     {
         const Px* fref = reinterpret_cast<const Px*>(a.fref[l]);
         const int2* rec = sRec[l];
-        // ---- the blocks' reference patches of this list: N + 7 rows and columns around the full-sample position ----------------------
-        for (int i = tid; i < NB * PW * PW; i += 256)
-        {
-            const int b = i / (PW * PW), r = i - b * (PW * PW), y = r / PW, x = r - y * PW;
-            const int qx = (int16_t)(rec[b].y & 0xffff), qy = (int16_t)(rec[b].y >> 16);
-            const int px = rx0 + (b & (BPR - 1)) * N + (qx >> 2) - APRON + x, py = ry0 + (b / BPR) * N + (qy >> 2) - APRON + y;
-            patch[b * (PW * PP) + y * PP + x] = (int16_t)fref[(long)py * rst + px];
-        }
+        auto all = [](const int) { return true; };
+        auto mvOf = [&](const int b) { return rec[b].y; };
+        luma_stage_patches<Px, N>(patch, NB, all, mvOf, [&](const int b) { return make_int2(rx0 + (b & (BPR - 1)) * N, ry0 + (b / BPR) * N); }, fref, rst);
         __syncthreads();
-        // ---- where both phases are set, the horizontal pass at 14-bit precision first (luma_hps with row extension) -------------------
-        const int shiftPS = 6 - headRoom, offPS = -(8192 << shiftPS);
-        for (int i = tid; i < NB * PW * N; i += 256)
-        {
-            const int b = i / (PW * N), r = i - b * (PW * N), y = r >> LOG2N, x = r & (N - 1);
-            const int xf = rec[b].y & 3, yf = (rec[b].y >> 16) & 3;
-            if (xf && yf)
-            {
-                int s = 0;
-#pragma unroll
-                for (int t = 0; t < 8; t++) s += (int)patch[b * (PW * PP) + y * PP + x + t] * (int)kTuTaps[xf][t];
-                immed[i] = (int16_t)((s + offPS) >> shiftPS);
-            }
-        }
+        luma_stage_rows<N>(patch, immed, NB, all, mvOf, headRoom);
         __syncthreads();
         // ---- per sample: the 14-bit intermediate (predInterLumaShort) and, from the same sum, the rounded pixel (predInterLumaPixel) ----
         for (int i = tid; i < 32 * 32; i += 256)
         {
             const int ry = i >> 5, rx = i & 31, b = (ry >> LOG2N) * BPR + (rx >> LOG2N), y = ry & (N - 1), x = rx & (N - 1);
-            const int xf = rec[b].y & 3, yf = (rec[b].y >> 16) & 3;
-            const int16_t* pt = patch + b * (PW * PP);
             int sh, px;
-            if (xf && yf)
-            {
-                const int shiftSP = 6 + headRoom, offSP = (1 << (shiftSP - 1)) + (8192 << 6);
-                int s = 0;
-#pragma unroll
-                for (int t = 0; t < 8; t++) s += (int)immed[b * (PW * N) + (y + t) * N + x] * (int)kTuTaps[yf][t];
-                sh = (int16_t)(s >> 6);                                                                     // luma_vss
-                px = tu_clip16((s + offSP) >> shiftSP, maxVal);                                            // luma_vsp
-            }
-            else if (!(xf | yf))
-            {
-                px = pt[(y + APRON) * PP + x + APRON];
-                sh = (int16_t)((px << headRoom) - 8192);                                                    // convert_p2s
-            }
-            else
-            {
-                int s = 0;
-#pragma unroll
-                for (int t = 0; t < 8; t++) s += (int)(xf ? pt[(y + APRON) * PP + x + t] : pt[(y + t) * PP + x + APRON]) * (int)kTuTaps[xf ? xf : yf][t];
-                sh = (int16_t)((s + offPS) >> shiftPS);                                                     // luma_hps / vps
-                px = tu_clip16((s + 32) >> 6, maxVal);                                                      // luma_hpp / vpp
-            }
+            luma_short_and_pixel<N>(patch + b * (PW * PP), immed + b * (PW * N), rec[b].y, x, y, headRoom, maxVal, sh, px);
             const int f = fe[i];
             const int co = (int)fref[(long)(ry0 + ry) * rst + rx0 + rx];                                    // the coincident sample
             if (single_list(b) == l) diff[0][i] = (int16_t)(f - px);
             if (l == 0) { ps0[i] = (int16_t)sh; diff[2][i] = (int16_t)co; }
             else
             {
-                const int shiftAvg = 15 - a.depth, offAvg = (1 << (shiftAvg - 1)) + 2 * 8192;               // addAvg
-                diff[1][i] = (int16_t)(f - clip3(0, maxVal, ((int)ps0[i] + sh + offAvg) >> shiftAvg));
+                diff[1][i] = (int16_t)(f - luma_add_avg((int)ps0[i], sh, a.depth, maxVal));                 // addAvg
                 diff[2][i] = (int16_t)(f - (((int)diff[2][i] + co + 1) >> 1));                              // pixelavg_pp
             }
         }

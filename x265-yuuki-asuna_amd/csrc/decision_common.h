@@ -1,9 +1,9 @@
 // decision_common.h - what the sa8d decision stages share, on gfx950 (included at the end of tu_kernels.hip in front of intra_picture.h,
-// inter_sa8d_cost.h, b_sa8d_decide.h and merge_decide.h; it uses that file's clip3 and group_sum).
+// inter_sa8d_cost.h, b_sa8d_decide.h, merge_decide.h and b_merge_decide.h; it uses that file's clip3 and group_sum).
 //
 // Device side: the block grid (z-order, the 85-slot record table), the block's lambda, the rate term and the vector bit cost of the sa8d
-// costs, and the 8x8 Hadamard stage of a 32x32 difference plane.  Host side: the argument checks all four entries make alike, the wave
-// schedule of the two walks that follow the coding order, and the depth x level dispatch of every launch.
+// costs, and the 8x8 Hadamard stage of a 32x32 difference plane.  Host side: the argument checks all five entries make alike, the wave
+// schedule of the three walks that follow the coding order, and the depth x level dispatch of every launch.
 //
 // Two things stay where they are because sharing them changed the kernels' code for the worse (more instructions, more scalar spills):
 // the "inside the picture and coded before this block" test of intra_picture_kernel and merge_decide_kernel, and the quarter geometry
@@ -104,8 +104,8 @@ __device__ __forceinline__ int sa8d_slot_sum(const int* sum, const int b)
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
 
-// What the four entries refuse alike, before they ask for a device: true, with the error text set, when the record is refused.  P is one
-// of the four parameter records, which name these fields alike; nullOperand = the record or one of the entry's operands is NULL, reported
+// What the five entries refuse alike, before they ask for a device: true, with the error text set, when the record is refused.  P is one
+// of the five parameter records, which name these fields alike; nullOperand = the record or one of the entry's operands is NULL, reported
 // before anything else.  lambda8 <= 2^24 and at most 4096 + 4096 + 4096 + 4 * 33 bits (the entries' own checks) keep every rate term
 // below 2^30; the largest sa8d of a 32x32 block of 12-bit samples is below 2^27: every cost fits its int32.
 template <class P>

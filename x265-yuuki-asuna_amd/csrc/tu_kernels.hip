@@ -1452,3 +1452,7 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
 
 // the merge arm of a P picture's sa8d choice (x265hip_merge_decide): sa8d_slots of inter_sa8d_cost.h, the wave schedule of decision_common.h
 #include "merge_decide.h"
+
+// the merge arm of a B picture's sa8d choice (x265hip_b_merge_decide): the walk of merge_decide.h over two-list candidates, the staging
+// steps of b_sa8d_decide.h
+#include "b_merge_decide.h"

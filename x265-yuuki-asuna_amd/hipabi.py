@@ -222,6 +222,26 @@ class MergeDecideParams(ctypes.Structure):
     ]
 
 
+class BMergeDecideParams(ctypes.Structure):
+    """x265hip_b_merge_decide_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("qp", ctypes.c_int), ("lambda8", ctypes.c_int), ("max_merge", ctypes.c_int),
+        ("ref_id0", ctypes.c_int), ("ref_id1", ctypes.c_int),
+        ("fenc", ctypes.c_void_p), ("fenc_stride", ctypes.c_ssize_t),
+        ("fref0", ctypes.c_void_p), ("fref1", ctypes.c_void_p), ("fref_stride", ctypes.c_ssize_t),
+        ("dir_in", ctypes.c_void_p),
+        ("mv0", ctypes.c_void_p), ("mv1", ctypes.c_void_p),
+        ("inter_cost", ctypes.c_void_p), ("inter_cost_stride", ctypes.c_ssize_t),
+        ("qp_map", ctypes.c_void_p), ("lambda8_by_qp", ctypes.c_void_p),
+        ("merge", ctypes.c_void_p), ("merge_idx", ctypes.c_void_p), ("dir", ctypes.c_void_p),
+        ("ref0", ctypes.c_void_p), ("ref1", ctypes.c_void_p),
+        ("mv0_out", ctypes.c_void_p), ("mv1_out", ctypes.c_void_p),
+        ("mv0_pred", ctypes.c_void_p), ("mv1_pred", ctypes.c_void_p),
+        ("cost", ctypes.c_void_p), ("best", ctypes.c_void_p),
+    ]
+
+
 class LowresInitParams(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_int), ("src", ctypes.c_void_p), ("src_stride", ctypes.c_ssize_t),
                 ("plane", ctypes.c_void_p * 4), ("stride", ctypes.c_ssize_t),
@@ -735,6 +755,33 @@ def b_sa8d_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, 
     f = lib().x265hip_b_sa8d_decide
     f.argtypes = [ctypes.POINTER(BSa8dParams), ctypes.c_void_p]
     check(f(ctypes.byref(p), s), "x265hip_b_sa8d_decide")
+
+
+def b_merge_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge,
+                   merge_idx, dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best=None, ref0=None, ref1=None, ref_ids=(0, 1), fenc_off=0, fref_off=0,
+                   inter_cost_stride=4, inter_cost_offset=0, qp=0, qp_map=None, lambda8_by_qp=None, stream=None):
+    """x265hip_b_merge_decide: the two-list merge candidates of every block of a B picture in coding order, priced by sa8d, against the inter
+    winner (Analysis::checkMerge2Nx2N_rd0_4 at RD level 0 and the comparisons of compressInterCU_rd0_4).  fref0 / fref1: tensors of one
+    geometry (sample (0,0) at element fref_off); dir_in / mv0 / mv1: the inter winner as b_sa8d_decide writes it; inter_cost: device int32
+    tensor, the block's word at element inter_cost_offset + block * inter_cost_stride (the defaults read word 0 of b_sa8d_decide's cost);
+    merge / merge_idx / dir_out: device uint8 [ctu][blocks] out; mv*_out / mv*_pred: device int32 records out (the CU's motion / what the
+    two-list TU stages predict from); cost (and best): device int32 [ctu][blocks][2] out; qp_map: the LUMA plane of tu_qp."""
+    es = 1 if depth == 8 else 2
+    p = BMergeDecideParams()
+    p.depth, p.width, p.height, p.level, p.qp, p.lambda8, p.max_merge = depth, width, height, level, int(qp), int(lambda8), int(max_merge)
+    p.ref_id0, p.ref_id1 = ref_ids
+    p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
+    p.fref0, p.fref1, p.fref_stride = fref0.data_ptr() + fref_off * es, fref1.data_ptr() + fref_off * es, fref_stride
+    p.dir_in, p.mv0, p.mv1 = dir_in.data_ptr(), mv0.data_ptr(), mv1.data_ptr()
+    p.inter_cost, p.inter_cost_stride = inter_cost.data_ptr() + 4 * int(inter_cost_offset), int(inter_cost_stride)
+    p.qp_map, p.lambda8_by_qp = _p(qp_map), _p(lambda8_by_qp)
+    p.merge, p.merge_idx, p.dir, p.ref0, p.ref1 = merge.data_ptr(), merge_idx.data_ptr(), dir_out.data_ptr(), _p(ref0), _p(ref1)
+    p.mv0_out, p.mv1_out, p.mv0_pred, p.mv1_pred = mv0_out.data_ptr(), mv1_out.data_ptr(), mv0_pred.data_ptr(), mv1_pred.data_ptr()
+    p.cost, p.best = cost.data_ptr(), _p(best)
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_b_merge_decide
+    f.argtypes = [ctypes.POINTER(BMergeDecideParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_b_merge_decide")
 
 
 def lowres_init(depth, src, src_stride, src_off, planes, stride, org, width, lines, margin_x, margin_y, stream=None):

@@ -2165,6 +2165,112 @@ class Sa8dBFramePipeline(_RefListStep):
         return out
 
 
+class BMergeDecide:
+    """The merge arm of a B picture's sa8d choice (x265hip_b_merge_decide; reference Analysis::checkMerge2Nx2N_rd0_4 at RD level 0,
+    analysis.cpp:2787-2838, CUData::getInterMergeCandidates with isInterB, cudata.cpp:1458-1712, and the comparisons of
+    compressInterCU_rd0_4, analysis.cpp:1650-1655): per block, in coding order, the two-list candidates its neighbours' final motion gives
+    - spatial, combined bi-predictive, zero -, priced by sa8d; the block merges unless its inter winner is strictly cheaper.  Owns merge /
+    merge_idx / dir uint8 and ref0 / ref1 int8 [ctu][blocks], mv0_out / mv1_out (the CUs' motion, unclipped) and mv0_pred / mv1_pred (what
+    the two-list TU stages predict from, with dir) int32 [ctu*85][2], cost and best int32 [ctu][blocks][2]."""
+
+    def __init__(self, nctu, w64, h64, depth, level, device, max_merge=3, lambda8=1024, qp=0, ref_ids=(0, 1)):
+        import torch
+        if not 1 <= int(max_merge) <= 5:
+            raise ValueError("BMergeDecide: max_merge %r outside 1..5" % (max_merge,))
+        self.nctu, self.w64, self.h64, self.depth, self.level, self.qp = nctu, w64, h64, depth, level, qp
+        self.max_merge, self.lambda8, self.ref_ids = int(max_merge), int(lambda8), tuple(ref_ids)
+        self.nblk = (64 >> (3 + level)) ** 2
+        self.waves = hipabi.intra_picture_waves(w64, h64)
+        nb = nctu * self.nblk
+        self.merge = torch.zeros(nb, dtype=torch.uint8, device=device)
+        self.merge_idx = torch.zeros(nb, dtype=torch.uint8, device=device)
+        self.dir = torch.zeros(nb, dtype=torch.uint8, device=device)
+        self.ref0 = torch.zeros(nb, dtype=torch.int8, device=device)
+        self.ref1 = torch.zeros(nb, dtype=torch.int8, device=device)
+        self.mv0_out, self.mv1_out, self.mv0_pred, self.mv1_pred = (torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device) for _ in range(4))
+        self.cost = torch.zeros(nb * 2, dtype=torch.int32, device=device)
+        self.best = torch.zeros(nb * 2, dtype=torch.int32, device=device)
+        self.qp_map, self.lambda8_by_qp = None, None          # as InterSa8dCost's
+
+    def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, dir_in, mv0, mv1, inter_cost, stream=None, inter_cost_stride=4,
+            inter_cost_offset=0):
+        """dir_in / mv0 / mv1: the inter winner (BSa8dDecide.dir / mv0_out / mv1_out); inter_cost: BSa8dDecide.cost (the defaults read its
+        word 0)."""
+        assert ref0.stride == ref1.stride and ref0.org == ref1.org
+        hipabi.b_merge_decide(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, ref0.t, ref1.t, ref0.stride, dir_in, mv0, mv1, inter_cost,
+                              self.lambda8, self.max_merge, self.merge, self.merge_idx, self.dir, self.mv0_out, self.mv1_out, self.mv0_pred, self.mv1_pred,
+                              self.cost, best=self.best, ref0=self.ref0, ref1=self.ref1, ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org,
+                              inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map,
+                              lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+
+    skip_flags = MergeDecide.skip_flags
+
+    def checksum(self):
+        return {"merge": _sum64(self.merge), "merge_idx": _sum64(self.merge_idx), "merge_dir": _sum64(self.dir), "mv0_out": _sum64(self.mv0_out),
+                "mv1_out": _sum64(self.mv1_out), "mv0_pred": _sum64(self.mv0_pred), "mv1_pred": _sum64(self.mv1_pred), "merge_cost": _sum64(self.cost)}
+
+
+class MergeBFramePipeline(_RefListStep):
+    """One B picture whose blocks may merge: per list search -> sub-pel refinement; BSa8dDecide (the inter winner); BMergeDecide against word
+    0 of its cost; bi-predictive luma + 4:2:0 chroma coding from the merge stage's dir / mv0_pred / mv1_pred; skip flags; B-picture boundary
+    strengths from mv0_out / mv1_out / ref0 / ref1 + luma / chroma deblocking; the shared loop-filter tail.  The candidate list reads motion
+    only, so one walk in coding order before the coding is the reference's result for two lists as for one.
+    run(cur, ref0, ref1) / final_planes() as BFramePipeline's: MiniGop(b_step=...) takes it.  The constructor switches mean what they mean in
+    Sa8dBFramePipeline; max_merge: --max-merge.  b_intra is refused: the intra and merge decisions interleave in coding order (one walk, not
+    built)."""
+
+    def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
+                 sign_hide=False, sao_rdo=None, dir_cost=(12, 12, 20), b_intra=False, lambda8=1024, base_bits=None, bi_bits_delta=None, max_merge=3):
+        if b_intra:
+            raise ValueError("MergeBFramePipeline: b_intra together with merge is one walk in coding order and is not built")
+        _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
+        self._build_lists(2, w64, h64, depth, device, rng, subme, False, False)
+        self.bd = BSa8dDecide(self.nctu, w64, h64, depth, level, device, dir_cost=dir_cost, rng=rng, base_bits=base_bits, bi_bits_delta=bi_bits_delta,
+                              lambda8=lambda8, qp=qp)
+        self.md = BMergeDecide(self.nctu, w64, h64, depth, level, device, max_merge=max_merge, lambda8=lambda8, qp=qp, ref_ids=self.bd.ref_ids)
+        self.tu_flags = hipabi.TU_SIGN_HIDE if sign_hide else 0
+        self.rc = InterReconBi(self.nctu, w64, h64, depth, level, qp, device, intra_slice=self.tu_flags)
+        if chroma:
+            qpc = chroma_quant_qp(qp, depth)
+            self.rc_c = [InterReconChromaBi(self.nctu, w64, h64, depth, level, qpc, device, intra_slice=self.tu_flags) for _ in range(2)]
+        self.skip = None
+
+    def set_qp_maps(self, maps, lambda8_by_qp=None):
+        """As Sa8dBFramePipeline.set_qp_maps: the maps reach the TU stages, the deblocking stage and the rate terms of the inter winner and
+        of every merge candidate."""
+        self._set_decision_qp_maps(maps, lambda8_by_qp, [self.bd, self.md], [])
+
+    def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mark=None):
+        """ref0 / ref1: the list-0 / list-1 reference pictures (extended borders; with chroma=True also their Cb / Cr planes).  Returns the
+        luma plane of the coded picture; mark(name), if given, is called after every stage."""
+        self._qp_maps_run_check()
+        mark = mark or (lambda name: None)
+        self._alloc_planes(cur)
+        self._search_lists(cur, (ref0, ref1), mark)
+        self.bd.run(cur, ref0, ref1, self.spl[0].out, self.spl[1].out)
+        mark("b_sa8d")
+        md = self.md
+        md.run(cur, ref0, ref1, self.bd.dir, self.bd.mv0_out, self.bd.mv1_out, self.bd.cost)
+        mark("merge")
+        self.rc.run(cur, ref0, ref1, self.recon, md.mv0_pred, md.mv1_pred, dir_flags=md.dir)
+        mark("recon")
+        if self.chroma:
+            for i in range(2):
+                self.rc_c[i].run(cur.c[i], ref0.c[i], ref1.c[i], self.recon_c[i], cur.stride_c, cur.org_c, md.mv0_pred, md.mv1_pred, dir_flags=md.dir)
+            mark("recon_chroma")
+        self.skip = md.skip_flags(self.rc, self.rc_c if self.chroma else None)
+        mark("skip")
+        if self.db is not None:
+            self.db.run_b(self.recon, cur, md.mv0_out, md.mv1_out, md.ref0, md.ref1, self.rc.num_sig)
+        return self._filter_tail(cur, mark)
+
+    def checksum(self):
+        out = self._checksum(self.bd)
+        out.update(self.md.checksum())
+        out["skip"] = _sum64(self.skip)
+        return out
+
+
 class MiniGop:
     """Display order in, coding order inside: anchor pictures 0, gop, 2 gop, ... form the P chain (each coded by p_step.run from the
     previous anchor's OUTPUT), and the pictures between two anchors are B pictures coded by b_step.run(cur, previous anchor, this

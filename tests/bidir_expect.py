@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import oracle_api as O          # noqa: E402
 import harness                  # noqa: E402
+import step_chain as SC         # noqa: E402
 
 F = importlib.import_module("x265-yuuki-asuna_amd.frames")
 spec = importlib.import_module("x265-yuuki-asuna_amd.table_spec")
@@ -53,13 +54,7 @@ def six_stripe_lumas(depth, w=768, h=192, seed=21):
     return ys
 
 
-def oracle_records(depth, cur, ref, stride, org, w64, h64, rng_r, subme, lam=4.0):
-    """{cost, qmvx | qmvy << 16} [nctu * 85, 2] of cur searched in and refined against ref (padded host planes)."""
-    nctu = (w64 // 64) * (h64 // 64)
-    cost = F.mv_cost_table(rng_r, lam)
-    cq, qoff = F.qpel_cost_table(rng_r, lam)
-    _, best = O.me_fullsearch(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False)
-    return O.subpel_refine(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, best, cq, qoff, subme)
+oracle_records = SC.oracle_records      # (depth, cur, ref, stride, org, w64, h64, rng_r, subme, lam=4.0) -> the records [nctu * 85, 2]
 
 
 def phases_of(depth, ref, stride):
@@ -192,15 +187,14 @@ def b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, subme,
     FramePipeline takes (x265hip_sao_rdo's host inputs) or None = the distortion-only stand-in.  Returns every stage output by name."""
     S = importlib.import_module("x265-yuuki-asuna_amd.stages")
     _, _, stride, rows, org = F.padded_dims(w64, h64)
+    sc, oc = SC.chroma_geometry(w64)
     cur, r0, r1 = cur_planes[0], ref0_planes[0], ref1_planes[0]
     nctu = (w64 // 64) * (h64 // 64)
-    cost = F.mv_cost_table(rng_r)
     cq, qoff = F.qpel_cost_table(rng_r)
     out, recs, phases = {}, [], []
     for l, ref in enumerate((r0, r1)):
-        _, best = O.me_fullsearch(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False, nthreads=cores, avx2=avx2)
-        mv = O.subpel_refine(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, best, cq, qoff, subme, nthreads=cores, avx2=avx2)
-        out["me_best%d" % l], out["subpel_mv%d" % l] = best, mv
+        out["me_best%d" % l], mv = SC.search_head(depth, cur, ref, stride, org, w64, h64, rng_r, subme, cores=cores, avx2=avx2)
+        out["subpel_mv%d" % l] = mv
         recs.append(mv)
         phases.append(phases_of(depth, ref, stride))
     e = expect(depth, cur, stride, org, w64, h64, level, recs, phases, cq, qoff, dir_cost, with_reference=with_reference)
@@ -210,56 +204,23 @@ def b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, subme,
     rec, lev, ns, dist = O.inter_recon_bi(depth, cur.reshape(-1), stride, org, r0.reshape(-1), r1.reshape(-1), w64, h64, level, mv0, mv1, qp,
                                           dir_flags=e["dir"], intra_slice=tu_flags, nthreads=cores, avx2=avx2)
     out.update({"levels": lev, "num_sig": ns, "dist": dist})
-    cuqp = max(qp - 6 * (depth - 8), 0)
     bv, bh = O.deblock_bs_b(depth, w64, h64, level, mv0, mv1, e["ref0"], e["ref1"], ns, slice_b=True, avx2=avx2)
-    out.update({"bs_ver": bv, "bs_hor": bh})
-    dbk = O.deblock_luma(depth, rec.reshape(-1), stride, org, w64, h64, bv, bh, cuqp, avx2=avx2)
-    cnt, off = O.sao_stats(depth, cur.reshape(-1), dbk.reshape(-1), stride, org, w64, h64, nthreads=cores, avx2=avx2)
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
     qpc = S.chroma_quant_qp(qp, depth)
     crec = [O.inter_recon_chroma_bi(depth, cur_planes[c].reshape(-1), ref0_planes[c].reshape(-1), ref1_planes[c].reshape(-1), sc, oc, w64, h64, level, mv0, mv1,
                                     qpc, dir_flags=e["dir"], intra_slice=tu_flags, nthreads=cores, avx2=avx2) for c in (1, 2)]
-    cdb = O.deblock_chroma(depth, crec[0][0].reshape(-1), crec[1][0].reshape(-1), sc, oc, w64, h64, bv, bh, cuqp, avx2=avx2)
-    cstat = [O.sao_stats(depth, cur_planes[1 + i].reshape(-1), cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, nthreads=cores, avx2=avx2, ctu=(32, 32), plane_offset=2)
-             for i in range(2)]
-    if sao_rdo is not None:
-        lam = np.tile(np.array(sao_rdo["lambdas"], np.int64), (nctu, 1))
-        pars, _ = O.sao_rdo(depth, [cnt, cstat[0][0], cstat[1][0]], [off, cstat[0][1], cstat[1][1]], w64 // 64, h64 // 64, lam, sao_rdo["ctx_merge"],
-                            sao_rdo["ctx_type"], sao_rdo["entropy_bits"], avx2=avx2)
-        par, cpars = pars[0].reshape(-1), [pars[1].reshape(-1), pars[2].reshape(-1)]
-    else:
-        _, par = O.sao_decide(depth, cnt, off, avx2=avx2)
-        cpars = [O.sao_decide(depth, cstat[i][0], cstat[i][1], avx2=avx2)[1] for i in range(2)]
-    fin = O.sao_apply(depth, dbk.reshape(-1), stride, org, w64, h64, par, nthreads=cores, avx2=avx2).reshape(rows, stride)
-    out.update({"sao_count": cnt, "sao_offset_org": off, "sao_params": par})
-    inner = fin[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
-    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
     for i in range(2):
-        cf = O.sao_apply(depth, cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, cpars[i], nthreads=cores, avx2=avx2, ctu=(32, 32))
-        out["levels_c%d" % i], out["num_sig_c%d" % i], out["sao_count_c%d" % i], out["sao_params_c%d" % i] = crec[i][1], crec[i][2], cstat[i][0], cpars[i]
-        ci = cf.reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
-        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
-    return out
+        out["levels_c%d" % i], out["num_sig_c%d" % i] = crec[i][1], crec[i][2]
+    return SC.filter_tail(out, depth, cur_planes, rec, [crec[0][0], crec[1][0]], bv, bh, qp, w64, h64, sao_rdo=sao_rdo, cores=cores, avx2=avx2)
 
 
 def b_device_outputs(pipe, dt):
     """The same names from a stages.BFramePipeline after run() (chroma, deblocking, SAO applied, want_cost)."""
-    out = {}
+    g = lambda t: t.cpu().numpy()
+    out, bd = SC.step_outputs(pipe, dt), pipe.bd
     for l in range(2):
-        out["me_best%d" % l] = pipe.msl[l].best.cpu().numpy().view(np.uint64)
-        out["subpel_mv%d" % l] = pipe.spl[l].out.cpu().numpy().reshape(-1, 2)
-    bd = pipe.bd
-    out.update({"dir": bd.dir.cpu().numpy(), "ref0": bd.ref0.cpu().numpy(), "ref1": bd.ref1.cpu().numpy(), "mv0_out": bd.mv0_out.cpu().numpy().reshape(-1, 2),
-                "mv1_out": bd.mv1_out.cpu().numpy().reshape(-1, 2), "cost_out": bd.cost_out.cpu().numpy().reshape(-1, 4),
-                "levels": pipe.rc.levels.cpu().numpy(), "num_sig": pipe.rc.num_sig.cpu().numpy(), "dist": pipe.rc.dist.cpu().numpy(),
-                "bs_ver": pipe.db.bs_ver.cpu().numpy(), "bs_hor": pipe.db.bs_hor.cpu().numpy(),
-                "sao_count": pipe.sao.count.cpu().numpy(), "sao_offset_org": pipe.sao.offset_org.cpu().numpy(), "sao_params": pipe.sao.params.cpu().numpy(),
-                "recon": pipe.final.cpu().numpy().view(dt)})
-    for i in range(2):
-        out["levels_c%d" % i], out["num_sig_c%d" % i] = pipe.rc_c[i].levels.cpu().numpy(), pipe.rc_c[i].num_sig.cpu().numpy()
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = pipe.sao_c[i].count.cpu().numpy(), pipe.sao_c[i].params.cpu().numpy()
-        out["recon_c%d" % i] = pipe.final_c[i].cpu().numpy().view(dt)
+        out["me_best%d" % l], out["subpel_mv%d" % l] = g(pipe.msl[l].best).view(np.uint64), g(pipe.spl[l].out).reshape(-1, 2)
+    out.update({"dir": g(bd.dir), "ref0": g(bd.ref0), "ref1": g(bd.ref1), "mv0_out": g(bd.mv0_out).reshape(-1, 2), "mv1_out": g(bd.mv1_out).reshape(-1, 2),
+                "cost_out": g(bd.cost_out).reshape(-1, 4)})
     return out
 
 

@@ -24,7 +24,7 @@ import intra_expect as IE
 import intra_inter_expect as IX
 import merge_expect as ME
 
-O, F, H, harness = IE.O, IE.F, IE.H, IE.harness
+O, F, H, harness, SC = IE.O, IE.F, IE.H, IE.harness, IE.SC
 unpack, pack, clip_mv, tu_bits, records, level_slots, skip_flags, tie_pattern = (ME.unpack, ME.pack, ME.clip_mv, ME.tu_bits, ME.records, ME.level_slots,
                                                                                  ME.skip_flags, ME.tie_pattern)
 NEIGHBOURS = ME.NEIGHBOURS
@@ -389,14 +389,10 @@ def merge_b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, 
     nctu = (w64 // 64) * (h64 // 64)
     if tu_qp is not None:                       # the stages clamp a map's entries to the quantiser's range; the oracle runs take them as they are
         tu_qp = np.clip(tu_qp, 0, 51 + 6 * (depth - 8)).astype(np.int8)
-    cost = F.mv_cost_table(rng_r)
-    cq, qoff = F.qpel_cost_table(rng_r)
     out, recs = {}, []
     for l, ref in enumerate((r0, r1)):
-        _, bestv = O.me_fullsearch(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False, nthreads=cores, avx2=avx2)
-        mv = O.subpel_refine(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, bestv, cq, qoff, subme, nthreads=cores, avx2=avx2)
-        out["subpel_mv%d" % l] = mv
-        recs.append(mv)
+        recs.append(SC.search_head(depth, cur, ref, stride, org, w64, h64, rng_r, subme, cores=cores, avx2=avx2)[1])
+        out["subpel_mv%d" % l] = recs[l]
     d = BX.decide(depth, cur, (r0, r1), w64, h64, level, recs, dir_cost=dir_cost, lambda8=lambda8, table=IX.s_bitsizes(4 * rng_r + 4), qp=qp, tu_qp=tu_qp,
                   lambda8_by_qp=lambda8_by_qp, with_reference=False)
     win0, win1 = BX.BE.full_mv_out(level, nctu, d["mv0"], 0), BX.BE.full_mv_out(level, nctu, d["mv1"], 0)
@@ -406,7 +402,7 @@ def merge_b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, 
     out.update({k: e[k] for k in OUTPUTS})
     out["merge_cost"] = out.pop("cost")
     qpc = S.chroma_quant_qp(qp, depth)
-    sc, oc = QE._chroma_geometry(w64)
+    sc, oc = SC.chroma_geometry(w64)
     flat = lambda p: np.ascontiguousarray(p).reshape(-1)
     p0, p1 = full_records(e["mv0_pred"], level, nctu), full_records(e["mv1_pred"], level, nctu)
     o0, o1 = full_records(e["mv0_out"], level, nctu), full_records(e["mv1_out"], level, nctu)
@@ -430,32 +426,9 @@ def merge_b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, 
         it.update({"recon" + sfx: np.ascontiguousarray(rec).reshape(-1), "levels" + sfx: lev, "num_sig" + sfx: ns, "dist" + sfx: dist})
     out.update({k: it[k] for k in ("levels", "num_sig", "dist", "levels_c0", "levels_c1", "num_sig_c0", "num_sig_c1")})
     out["skip"] = skip_flags(e["merge"], it["num_sig"], it["num_sig_c0"], it["num_sig_c1"])
-    cuqp = max(qp - 6 * (depth - 8), 0)
     bv, bh = O.deblock_bs_b(depth, w64, h64, level, o0, o1, e["ref0"], e["ref1"], it["num_sig"], slice_b=True, avx2=avx2)
-    out.update({"bs_ver": bv, "bs_hor": bh})
-    dbk = O.deblock_luma(depth, it["recon"], stride, org, w64, h64, bv, bh, cuqp, qp_map=cu_qp, avx2=avx2)
-    cnt, off = O.sao_stats(depth, cur.reshape(-1), dbk.reshape(-1), stride, org, w64, h64, nthreads=cores, avx2=avx2)
-    cdb = O.deblock_chroma(depth, it["recon_c0"], it["recon_c1"], sc, oc, w64, h64, bv, bh, cuqp, qp_map=cu_qp, avx2=avx2)
-    cstat = [O.sao_stats(depth, np.ascontiguousarray(cur_planes[1 + i]).reshape(-1), cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, nthreads=cores, avx2=avx2,
-                         ctu=(32, 32), plane_offset=2) for i in range(2)]
-    if sao_rdo is not None:
-        lam = np.tile(np.array(sao_rdo["lambdas"], np.int64), (nctu, 1))
-        pars, _ = O.sao_rdo(depth, [cnt, cstat[0][0], cstat[1][0]], [off, cstat[0][1], cstat[1][1]], w64 // 64, h64 // 64, lam, sao_rdo["ctx_merge"],
-                            sao_rdo["ctx_type"], sao_rdo["entropy_bits"], avx2=avx2)
-        par, cpars = pars[0].reshape(-1), [pars[1].reshape(-1), pars[2].reshape(-1)]
-    else:
-        _, par = O.sao_decide(depth, cnt, off, avx2=avx2)
-        cpars = [O.sao_decide(depth, cstat[i][0], cstat[i][1], avx2=avx2)[1] for i in range(2)]
-    fin = O.sao_apply(depth, dbk.reshape(-1), stride, org, w64, h64, par, nthreads=cores, avx2=avx2).reshape(rows, stride)
-    out.update({"sao_count": cnt, "sao_offset_org": off, "sao_params": par})
-    inner = fin[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
-    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
-    for i in range(2):
-        cf = O.sao_apply(depth, cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, cpars[i], nthreads=cores, avx2=avx2, ctu=(32, 32))
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = cstat[i][0], cpars[i]
-        ci = cf.reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
-        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
-    return out
+    return SC.filter_tail(out, depth, cur_planes, it["recon"], [it["recon_c0"], it["recon_c1"]], bv, bh, qp, w64, h64, cu_qp=cu_qp, sao_rdo=sao_rdo, cores=cores,
+                          avx2=avx2)
 
 
 def device_outputs(pipe, dt):
@@ -463,15 +436,10 @@ def device_outputs(pipe, dt):
     g = lambda t: t.cpu().numpy()
     md, bd = pipe.md, pipe.bd
     sl = level_slots(md.level, pipe.nctu)
-    out = {"subpel_mv0": g(pipe.spl[0].out).reshape(-1, 2), "subpel_mv1": g(pipe.spl[1].out).reshape(-1, 2), "b_dir": g(bd.dir), "b_cost": g(bd.cost).reshape(-1, 4),
-           "merge": g(md.merge), "merge_idx": g(md.merge_idx), "dir": g(md.dir), "ref0": g(md.ref0), "ref1": g(md.ref1),
-           "merge_cost": g(md.cost).reshape(-1, 2), "best": g(md.best).reshape(-1, 2), "skip": g(pipe.skip),
-           "levels": g(pipe.rc.levels), "num_sig": g(pipe.rc.num_sig), "dist": g(pipe.rc.dist), "bs_ver": g(pipe.db.bs_ver), "bs_hor": g(pipe.db.bs_hor),
-           "sao_count": g(pipe.sao.count), "sao_offset_org": g(pipe.sao.offset_org), "sao_params": g(pipe.sao.params), "recon": g(pipe.final).view(dt)}
+    out = SC.step_outputs(pipe, dt)
+    out.update({"subpel_mv0": g(pipe.spl[0].out).reshape(-1, 2), "subpel_mv1": g(pipe.spl[1].out).reshape(-1, 2), "b_dir": g(bd.dir), "b_cost": g(bd.cost).reshape(-1, 4),
+                "merge": g(md.merge), "merge_idx": g(md.merge_idx), "dir": g(md.dir), "ref0": g(md.ref0), "ref1": g(md.ref1),
+                "merge_cost": g(md.cost).reshape(-1, 2), "best": g(md.best).reshape(-1, 2), "skip": g(pipe.skip)})
     for k in ("mv0_out", "mv1_out", "mv0_pred", "mv1_pred"):
         out[k] = g(getattr(md, k)).reshape(-1, 2)[sl]
-    for i in range(2):
-        out["levels_c%d" % i], out["num_sig_c%d" % i] = g(pipe.rc_c[i].levels), g(pipe.rc_c[i].num_sig)
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = g(pipe.sao_c[i].count), g(pipe.sao_c[i].params)
-        out["recon_c%d" % i] = g(pipe.final_c[i]).view(dt)
     return out

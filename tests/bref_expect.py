@@ -17,6 +17,7 @@ import multiref_expect as ME
 
 O = BE.O
 F = BE.F
+SC = BE.SC
 
 LEVEL_BASE = BE.LEVEL_BASE
 DIR_COST = BE.DIR_COST
@@ -242,60 +243,22 @@ def b_chain_refs(depth, cur_planes, refs0_planes, refs1_planes, w64, h64, rng_r,
     rec, lev, ns, dist = recon_luma(depth, cur, [p[0] for p in lists[0]], [p[0] for p in lists[1]], stride, org, w64, h64, level, mv0, mv1, i0, i1, dirs, qp,
                                     tu_flags, cells(0), cores)
     out.update({"levels": lev, "num_sig": ns, "dist": dist})
-    cuqp = max(qp - 6 * (depth - 8), 0)
     bv, bh = O.deblock_bs_b(depth, w64, h64, level, mv0, mv1, e["ref0"], e["ref1"], ns, slice_b=True)
-    out.update({"bs_ver": bv, "bs_hor": bh})
-    cu_map = None if cu_qp is None else np.ascontiguousarray(cu_qp, np.int8)
-    dbk = O.deblock_luma(depth, rec.reshape(-1), stride, org, w64, h64, bv, bh, cuqp, qp_map=cu_map)
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
+    sc, oc = SC.chroma_geometry(w64)
     qpc = S.chroma_quant_qp(qp, depth)
     crec = [recon_chroma(depth, cur_planes[c], [p[c] for p in lists[0]], [p[c] for p in lists[1]], sc, oc, w64, h64, level, mv0, mv1, i0, i1, dirs, qpc,
                          tu_flags, cells(c), cores) for c in (1, 2)]
-    cdb = O.deblock_chroma(depth, crec[0][0].reshape(-1), crec[1][0].reshape(-1), sc, oc, w64, h64, bv, bh, cuqp, qp_map=cu_map)
     for i in range(2):
         out["levels_c%d" % i], out["num_sig_c%d" % i] = crec[i][1], crec[i][2]
-    fin, cfin = dbk, list(cdb)
-    if sao:
-        cnt, off = O.sao_stats(depth, cur.reshape(-1), dbk.reshape(-1), stride, org, w64, h64, nthreads=cores)
-        cstat = [O.sao_stats(depth, cur_planes[1 + i].reshape(-1), cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, nthreads=cores, ctu=(32, 32), plane_offset=2)
-                 for i in range(2)]
-        if sao_rdo is not None:
-            lam = np.tile(np.array(sao_rdo["lambdas"], np.int64), (nctu, 1))
-            pars, _ = O.sao_rdo(depth, [cnt, cstat[0][0], cstat[1][0]], [off, cstat[0][1], cstat[1][1]], w64 // 64, h64 // 64, lam, sao_rdo["ctx_merge"],
-                                sao_rdo["ctx_type"], sao_rdo["entropy_bits"])
-            par, cpars = pars[0].reshape(-1), [pars[1].reshape(-1), pars[2].reshape(-1)]
-        else:
-            _, par = O.sao_decide(depth, cnt, off)
-            cpars = [O.sao_decide(depth, cstat[i][0], cstat[i][1])[1] for i in range(2)]
-        fin = O.sao_apply(depth, dbk.reshape(-1), stride, org, w64, h64, par, nthreads=cores)
-        cfin = [O.sao_apply(depth, cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, cpars[i], nthreads=cores, ctu=(32, 32)) for i in range(2)]
-        out.update({"sao_count": cnt, "sao_offset_org": off, "sao_params": par})
-        for i in range(2):
-            out["sao_count_c%d" % i], out["sao_params_c%d" % i] = cstat[i][0], cpars[i]
-    inner = fin.reshape(rows, stride)[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
-    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
-    for i in range(2):
-        ci = cfin[i].reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
-        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
-    return out
+    return SC.filter_tail(out, depth, cur_planes, rec, [crec[0][0], crec[1][0]], bv, bh, qp, w64, h64, cu_qp=cu_qp, sao=sao, sao_rdo=sao_rdo, cores=cores)
 
 
 def device_outputs(pipe, dt, ndistinct):
     """The same names from a stages.MultiRefBFramePipeline after run() (chroma, deblocking, want_cost; the SAO names where it has SAO)."""
     g = lambda t: t.cpu().numpy()
-    out = {"subpel_mv%d" % s: g(pipe.spl[s].out).reshape(-1, 2) for s in range(ndistinct)}
-    bd = pipe.bd
+    out, bd = SC.step_outputs(pipe, dt), pipe.bd
+    out.update({"subpel_mv%d" % s: g(pipe.spl[s].out).reshape(-1, 2) for s in range(ndistinct)})
     out.update({"ref_idx0": g(pipe.rs[0].ref_idx), "ref_idx1": g(pipe.rs[1].ref_idx), "sel_mv0": g(pipe.rs[0].mv_out).reshape(-1, 2),
                 "sel_mv1": g(pipe.rs[1].mv_out).reshape(-1, 2), "dir": g(bd.dir), "ref0": g(bd.ref0), "ref1": g(bd.ref1),
-                "mv0_out": g(bd.mv0_out).reshape(-1, 2), "mv1_out": g(bd.mv1_out).reshape(-1, 2), "cost_out": g(bd.cost_out).reshape(-1, 4),
-                "levels": g(pipe.rc.levels), "num_sig": g(pipe.rc.num_sig), "dist": g(pipe.rc.dist),
-                "bs_ver": g(pipe.db.bs_ver), "bs_hor": g(pipe.db.bs_hor), "recon": g(pipe.final).view(dt)})
-    if pipe.sao is not None:
-        out.update({"sao_count": g(pipe.sao.count), "sao_offset_org": g(pipe.sao.offset_org), "sao_params": g(pipe.sao.params)})
-    for i in range(2):
-        out["levels_c%d" % i], out["num_sig_c%d" % i] = g(pipe.rc_c[i].levels), g(pipe.rc_c[i].num_sig)
-        if pipe.sao is not None:
-            out["sao_count_c%d" % i], out["sao_params_c%d" % i] = g(pipe.sao_c[i].count), g(pipe.sao_c[i].params)
-        out["recon_c%d" % i] = g(pipe.final_c[i]).view(dt)
+                "mv0_out": g(bd.mv0_out).reshape(-1, 2), "mv1_out": g(bd.mv1_out).reshape(-1, 2), "cost_out": g(bd.cost_out).reshape(-1, 4)})
     return out

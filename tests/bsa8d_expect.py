@@ -17,7 +17,7 @@ import bidir_expect as BE
 import intra_expect as IE
 import intra_inter_expect as IX
 
-O, F, H, harness = IE.O, IE.F, IE.H, IE.harness
+O, F, H, harness, SC = IE.O, IE.F, IE.H, IE.harness, IE.SC
 spec = BE.spec
 
 DIR_COST = BE.DIR_COST
@@ -146,9 +146,8 @@ INTRA_MASKS = ("intra_beats_single", "intra_beats_bi", "inter_kept", "intra_besi
 def inter_coding(depth, cur, refs, w64, h64, level, e, qp, qp_c, flags, chroma=True, avx2=False, cores=0):
     """The bi-predictive coding of the decision e (decide()'s dict) in the names intra_inter_expect.walk takes: recon / levels / num_sig / dist
     (+ _c0 / _c1) and inter_cost [blocks, 2] whose second word is the winning inter sa8d cost.  cur / refs: padded (Y, Cb, Cr) planes."""
-    import qp_map_expect as QE
     _, _, stride, rows, org = F.padded_dims(w64, h64)
-    sc, oc = QE._chroma_geometry(w64)
+    sc, oc = SC.chroma_geometry(w64)
     nctu = (w64 // 64) * (h64 // 64)
     flat = lambda p: np.ascontiguousarray(p).reshape(-1)
     mv0, mv1 = BE.full_mv_out(level, nctu, e["mv0"], 0), BE.full_mv_out(level, nctu, e["mv1"], 0)
@@ -188,15 +187,10 @@ def sa8d_b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, s
     S = importlib.import_module("x265-yuuki-asuna_amd.stages")
     _, _, stride, rows, org = F.padded_dims(w64, h64)
     cur, r0, r1 = cur_planes[0], ref0_planes[0], ref1_planes[0]
-    nctu = (w64 // 64) * (h64 // 64)
-    cost = F.mv_cost_table(rng_r)
-    cq, qoff = F.qpel_cost_table(rng_r)
     out, recs = {}, []
     for l, ref in enumerate((r0, r1)):
-        _, best = O.me_fullsearch(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False, nthreads=cores, avx2=avx2)
-        mv = O.subpel_refine(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, best, cq, qoff, subme, nthreads=cores, avx2=avx2)
-        out["subpel_mv%d" % l] = mv
-        recs.append(mv)
+        recs.append(SC.search_head(depth, cur, ref, stride, org, w64, h64, rng_r, subme, cores=cores, avx2=avx2)[1])
+        out["subpel_mv%d" % l] = recs[l]
     e = decide(depth, cur, (r0, r1), w64, h64, level, recs, dir_cost=dir_cost, lambda8=lambda8, table=IX.s_bitsizes(4 * rng_r + 4), qp=qp,
                with_reference=with_reference)
     qpc = S.chroma_quant_qp(qp, depth)
@@ -210,48 +204,16 @@ def sa8d_b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, s
         out.update({"mode": w["mode"], "intra": intra})
         it = w
     out.update({k: it[k] for k in ("levels", "num_sig", "dist", "levels_c0", "levels_c1", "num_sig_c0", "num_sig_c1")})
-    cuqp = max(qp - 6 * (depth - 8), 0)
     bv, bh = O.deblock_bs_b(depth, w64, h64, level, mv0, mv1, e["ref0"], e["ref1"], it["num_sig"], slice_b=True, intra=intra, avx2=avx2)
-    out.update({"bs_ver": bv, "bs_hor": bh})
-    dbk = O.deblock_luma(depth, it["recon"], stride, org, w64, h64, bv, bh, cuqp, avx2=avx2)
-    cnt, off = O.sao_stats(depth, cur.reshape(-1), dbk.reshape(-1), stride, org, w64, h64, nthreads=cores, avx2=avx2)
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
-    cdb = O.deblock_chroma(depth, it["recon_c0"], it["recon_c1"], sc, oc, w64, h64, bv, bh, cuqp, avx2=avx2)
-    cstat = [O.sao_stats(depth, np.ascontiguousarray(cur_planes[1 + i]).reshape(-1), cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, nthreads=cores, avx2=avx2,
-                         ctu=(32, 32), plane_offset=2) for i in range(2)]
-    if sao_rdo is not None:
-        lam = np.tile(np.array(sao_rdo["lambdas"], np.int64), (nctu, 1))
-        pars, _ = O.sao_rdo(depth, [cnt, cstat[0][0], cstat[1][0]], [off, cstat[0][1], cstat[1][1]], w64 // 64, h64 // 64, lam, sao_rdo["ctx_merge"],
-                            sao_rdo["ctx_type"], sao_rdo["entropy_bits"], avx2=avx2)
-        par, cpars = pars[0].reshape(-1), [pars[1].reshape(-1), pars[2].reshape(-1)]
-    else:
-        _, par = O.sao_decide(depth, cnt, off, avx2=avx2)
-        cpars = [O.sao_decide(depth, cstat[i][0], cstat[i][1], avx2=avx2)[1] for i in range(2)]
-    fin = O.sao_apply(depth, dbk.reshape(-1), stride, org, w64, h64, par, nthreads=cores, avx2=avx2).reshape(rows, stride)
-    out.update({"sao_count": cnt, "sao_offset_org": off, "sao_params": par})
-    inner = fin[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
-    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
-    for i in range(2):
-        cf = O.sao_apply(depth, cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, cpars[i], nthreads=cores, avx2=avx2, ctu=(32, 32))
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = cstat[i][0], cpars[i]
-        ci = cf.reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
-        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
-    return out
+    return SC.filter_tail(out, depth, cur_planes, it["recon"], [it["recon_c0"], it["recon_c1"]], bv, bh, qp, w64, h64, sao_rdo=sao_rdo, cores=cores, avx2=avx2)
 
 
 def device_outputs(pipe, dt):
     """The same names from a stages.Sa8dBFramePipeline after run() (chroma, deblocking, SAO applied)."""
     g = lambda t: t.cpu().numpy()
-    bd = pipe.bd
-    out = {"subpel_mv0": g(pipe.spl[0].out).reshape(-1, 2), "subpel_mv1": g(pipe.spl[1].out).reshape(-1, 2), "dir": g(bd.dir), "ref0": g(bd.ref0), "ref1": g(bd.ref1),
-           "mv0_out": g(bd.mv0_out).reshape(-1, 2), "mv1_out": g(bd.mv1_out).reshape(-1, 2), "b_cost": g(bd.cost).reshape(-1, 4),
-           "levels": g(pipe.rc.levels), "num_sig": g(pipe.rc.num_sig), "dist": g(pipe.rc.dist), "bs_ver": g(pipe.db.bs_ver), "bs_hor": g(pipe.db.bs_hor),
-           "sao_count": g(pipe.sao.count), "sao_offset_org": g(pipe.sao.offset_org), "sao_params": g(pipe.sao.params), "recon": g(pipe.final).view(dt)}
+    out, bd = SC.step_outputs(pipe, dt), pipe.bd
+    out.update({"subpel_mv0": g(pipe.spl[0].out).reshape(-1, 2), "subpel_mv1": g(pipe.spl[1].out).reshape(-1, 2), "dir": g(bd.dir), "ref0": g(bd.ref0), "ref1": g(bd.ref1),
+                "mv0_out": g(bd.mv0_out).reshape(-1, 2), "mv1_out": g(bd.mv1_out).reshape(-1, 2), "b_cost": g(bd.cost).reshape(-1, 4)})
     if pipe.ii is not None:
         out.update({"mode": g(pipe.ii.mode), "intra": g(pipe.ii.intra)})
-    for i in range(2):
-        out["levels_c%d" % i], out["num_sig_c%d" % i] = g(pipe.rc_c[i].levels), g(pipe.rc_c[i].num_sig)
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = g(pipe.sao_c[i].count), g(pipe.sao_c[i].params)
-        out["recon_c%d" % i] = g(pipe.final_c[i]).view(dt)
     return out

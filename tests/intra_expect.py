@@ -19,8 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import oracle_api as O          # noqa: E402
 import harness                  # noqa: E402
+import step_chain as SC         # noqa: E402
 
-F = importlib.import_module("x265-yuuki-asuna_amd.frames")
+F =importlib.import_module("x265-yuuki-asuna_amd.frames")
 H = importlib.import_module("x265-yuuki-asuna_amd.hipabi")
 
 MODE_BITS = (2, 3, 6)
@@ -229,8 +230,7 @@ def expect(depth, planes, w64, h64, level, qp, qp_c=None, flags=H.TU_INTRA_SLICE
     cw, chh = w64 // 64, h64 // 64
     nctu = cw * chh
     _, _, stride, rows, org = F.padded_dims(w64, h64)
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
+    sc, oc = SC.chroma_geometry(w64)
     src = [np.ascontiguousarray(planes[0]).reshape(-1)] + ([np.ascontiguousarray(p).reshape(-1) for p in planes[1:3]] if chroma else [])
     init = recon_init if recon_init is not None else garbage_planes(depth, [s.shape for s in src])
     rec = [np.array(p, copy=True).reshape(-1) for p in init]
@@ -403,52 +403,17 @@ def i_chain(depth, planes, w64, h64, level, qp, sao_rdo=None, tu_flags=H.TU_INTR
     applied): the walk, the boundary strengths of an all-intra picture, deblocking, SAO, border extension.  Returns every stage output by
     name (bidir_expect.compare takes it)."""
     S = importlib.import_module("x265-yuuki-asuna_amd.stages")
-    _, _, stride, rows, org = F.padded_dims(w64, h64)
     nctu = (w64 // 64) * (h64 // 64)
     qpc = S.chroma_quant_qp(qp, depth)
     e = expect(depth, planes, w64, h64, level, qp, qp_c=(qpc, qpc), flags=tu_flags, with_reference=with_reference, **kw)
     out = {k: e[k] for k in ("mode", "levels", "num_sig", "dist", "levels_c0", "levels_c1", "num_sig_c0", "num_sig_c1")}
-    cuqp = max(qp - 6 * (depth - 8), 0)
     nblk = 64 >> (2 * level)
     bv, bh = O.deblock_bs_inter(depth, w64, h64, level, np.zeros((nctu * 85, 2), np.int32), e["num_sig"], avx2=avx2, intra=np.ones(nctu * nblk, np.uint8))
-    out.update({"bs_ver": bv, "bs_hor": bh})
-    cur = planes[0]
-    dbk = O.deblock_luma(depth, e["recon"], stride, org, w64, h64, bv, bh, cuqp, avx2=avx2)
-    cnt, off = O.sao_stats(depth, cur.reshape(-1), dbk.reshape(-1), stride, org, w64, h64, nthreads=cores, avx2=avx2)
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
-    cdb = O.deblock_chroma(depth, e["recon_c0"], e["recon_c1"], sc, oc, w64, h64, bv, bh, cuqp, avx2=avx2)
-    cstat = [O.sao_stats(depth, np.ascontiguousarray(planes[1 + i]).reshape(-1), cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, nthreads=cores, avx2=avx2,
-                         ctu=(32, 32), plane_offset=2) for i in range(2)]
-    if sao_rdo is not None:
-        lam = np.tile(np.array(sao_rdo["lambdas"], np.int64), (nctu, 1))
-        pars, _ = O.sao_rdo(depth, [cnt, cstat[0][0], cstat[1][0]], [off, cstat[0][1], cstat[1][1]], w64 // 64, h64 // 64, lam, sao_rdo["ctx_merge"],
-                            sao_rdo["ctx_type"], sao_rdo["entropy_bits"], avx2=avx2)
-        par, cpars = pars[0].reshape(-1), [pars[1].reshape(-1), pars[2].reshape(-1)]
-    else:
-        _, par = O.sao_decide(depth, cnt, off, avx2=avx2)
-        cpars = [O.sao_decide(depth, cstat[i][0], cstat[i][1], avx2=avx2)[1] for i in range(2)]
-    fin = O.sao_apply(depth, dbk.reshape(-1), stride, org, w64, h64, par, nthreads=cores, avx2=avx2).reshape(rows, stride)
-    out.update({"sao_count": cnt, "sao_offset_org": off, "sao_params": par})
-    inner = fin[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
-    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
-    for i in range(2):
-        cf = O.sao_apply(depth, cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, cpars[i], nthreads=cores, avx2=avx2, ctu=(32, 32))
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = cstat[i][0], cpars[i]
-        ci = cf.reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
-        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
-    return out
+    return SC.filter_tail(out, depth, planes, e["recon"], [e["recon_c0"], e["recon_c1"]], bv, bh, qp, w64, h64, sao_rdo=sao_rdo, cores=cores, avx2=avx2)
 
 
 def i_device_outputs(pipe, dt):
     """The same names from a stages.IFramePipeline after run() (chroma, deblocking, SAO applied)."""
-    ip = pipe.ip
-    out = {"mode": ip.mode.cpu().numpy(), "levels": ip.levels.cpu().numpy(), "num_sig": ip.num_sig.cpu().numpy(), "dist": ip.dist.cpu().numpy(),
-           "bs_ver": pipe.db.bs_ver.cpu().numpy(), "bs_hor": pipe.db.bs_hor.cpu().numpy(),
-           "sao_count": pipe.sao.count.cpu().numpy(), "sao_offset_org": pipe.sao.offset_org.cpu().numpy(), "sao_params": pipe.sao.params.cpu().numpy(),
-           "recon": pipe.final.cpu().numpy().view(dt)}
-    for i in range(2):
-        out["levels_c%d" % i], out["num_sig_c%d" % i] = ip.levels_c[i].cpu().numpy(), ip.num_sig_c[i].cpu().numpy()
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = pipe.sao_c[i].count.cpu().numpy(), pipe.sao_c[i].params.cpu().numpy()
-        out["recon_c%d" % i] = pipe.final_c[i].cpu().numpy().view(dt)
+    out = SC.step_outputs(pipe, dt)
+    out["mode"] = pipe.ip.mode.cpu().numpy()
     return out

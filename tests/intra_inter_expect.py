@@ -12,7 +12,7 @@ import numpy as np
 
 import intra_expect as IE
 
-O, F, H, harness = IE.O, IE.F, IE.H, IE.harness
+O, F, H, harness, SC = IE.O, IE.F, IE.H, IE.harness, IE.SC
 
 BASE_BITS = 2                     # m_listSelBits[0] (1) + MVP_IDX_BITS (1) + getTUBits(0, 1) (0): H.ref_cost_bits(1, lam=1)[0]
 MASKS = ("intra_won", "inter_won", "tie_stays_inter", "intra_left_is_inter", "intra_left_is_intra_angular", "intra_reads_inter_recon_across_ctu",
@@ -70,7 +70,7 @@ def inter_side(depth, cur, ref, w64, h64, level, mv, qp, qp_c, flags, chroma=Tru
     cw = w64 // 64
     nctu = cw * (h64 // 64)
     _, _, stride, rows, org = F.padded_dims(w64, h64)
-    sc, oc = QE._chroma_geometry(w64)
+    sc, oc = SC.chroma_geometry(w64)
     table = s_bitsizes(4 * 64 + 4) if table is None else table
     y, r = np.ascontiguousarray(cur[0]).reshape(-1), np.ascontiguousarray(ref[0]).reshape(-1)
     cap = np.zeros((h64, w64), y.dtype)
@@ -121,8 +121,7 @@ def walk(depth, cur, w64, h64, level, qp, inter, qp_c=None, flags=0, lambda8=IE.
     cw, chh = w64 // 64, h64 // 64
     nctu = cw * chh
     _, _, stride, rows, org = F.padded_dims(w64, h64)
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
+    sc, oc = SC.chroma_geometry(w64)
     nplanes = 3 if chroma else 1
     src = [np.ascontiguousarray(cur[c]).reshape(-1) for c in range(nplanes)]
     sfx = ["", "_c0", "_c1"][:nplanes]
@@ -247,55 +246,19 @@ def p_chain(depth, cur, ref, w64, h64, rng_r, subme, level, qp, sao_rdo=None, tu
     borders.  Every stage output by name."""
     S = IE.importlib.import_module("x265-yuuki-asuna_amd.stages")
     _, _, stride, rows, org = F.padded_dims(w64, h64)
-    nctu = (w64 // 64) * (h64 // 64)
     qpc = S.chroma_quant_qp(qp, depth)
-    y, r = cur[0], ref[0]
-    cost = F.mv_cost_table(rng_r)
-    cq, qoff = F.qpel_cost_table(rng_r)
-    _, best = O.me_fullsearch(depth, y, stride, org, r, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False, nthreads=cores, avx2=avx2)
-    mv = O.subpel_refine(depth, y, stride, org, r, stride, org, w64, h64, rng_r, 0, nctu, best, cq, qoff, subme, nthreads=cores, avx2=avx2)
+    _, mv = SC.search_head(depth, cur[0], ref[0], stride, org, w64, h64, rng_r, subme, cores=cores, avx2=avx2)
     it = inter_side(depth, cur, ref, w64, h64, level, mv, qp, (qpc, qpc), tu_flags, base_bits=base_bits, table=s_bitsizes(4 * rng_r + 4), avx2=avx2)
     e = walk(depth, cur, w64, h64, level, qp, it, qp_c=(qpc, qpc), flags=tu_flags)
     out = {"subpel_mv": mv, "inter_cost": it["inter_cost"]}
     out.update({k: e[k] for k in ("mode", "intra", "levels", "num_sig", "dist", "levels_c0", "levels_c1", "num_sig_c0", "num_sig_c1")})
-    cuqp = max(qp - 6 * (depth - 8), 0)
     bv, bh = O.deblock_bs_inter(depth, w64, h64, level, mv, e["num_sig"], avx2=avx2, intra=e["intra"])
-    out.update({"bs_ver": bv, "bs_hor": bh})
-    dbk = O.deblock_luma(depth, e["recon"], stride, org, w64, h64, bv, bh, cuqp, avx2=avx2)
-    cnt, off = O.sao_stats(depth, y.reshape(-1), dbk.reshape(-1), stride, org, w64, h64, nthreads=cores, avx2=avx2)
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
-    cdb = O.deblock_chroma(depth, e["recon_c0"], e["recon_c1"], sc, oc, w64, h64, bv, bh, cuqp, avx2=avx2)
-    cstat = [O.sao_stats(depth, np.ascontiguousarray(cur[1 + i]).reshape(-1), cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, nthreads=cores, avx2=avx2,
-                         ctu=(32, 32), plane_offset=2) for i in range(2)]
-    if sao_rdo is not None:
-        lam = np.tile(np.array(sao_rdo["lambdas"], np.int64), (nctu, 1))
-        pars, _ = O.sao_rdo(depth, [cnt, cstat[0][0], cstat[1][0]], [off, cstat[0][1], cstat[1][1]], w64 // 64, h64 // 64, lam, sao_rdo["ctx_merge"],
-                            sao_rdo["ctx_type"], sao_rdo["entropy_bits"], avx2=avx2)
-        par, cpars = pars[0].reshape(-1), [pars[1].reshape(-1), pars[2].reshape(-1)]
-    else:
-        _, par = O.sao_decide(depth, cnt, off, avx2=avx2)
-        cpars = [O.sao_decide(depth, cstat[i][0], cstat[i][1], avx2=avx2)[1] for i in range(2)]
-    fin = O.sao_apply(depth, dbk.reshape(-1), stride, org, w64, h64, par, nthreads=cores, avx2=avx2).reshape(rows, stride)
-    out.update({"sao_count": cnt, "sao_offset_org": off, "sao_params": par})
-    inner = fin[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
-    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
-    for i in range(2):
-        cf = O.sao_apply(depth, cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, cpars[i], nthreads=cores, avx2=avx2, ctu=(32, 32))
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = cstat[i][0], cpars[i]
-        ci = cf.reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
-        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
-    return out
+    return SC.filter_tail(out, depth, cur, e["recon"], [e["recon_c0"], e["recon_c1"]], bv, bh, qp, w64, h64, sao_rdo=sao_rdo, cores=cores, avx2=avx2)
 
 
 def p_device_outputs(pipe, dt):
     """The same names from a stages.IntraPFramePipeline after run() (chroma, deblocking, SAO applied)."""
     g = lambda t: t.cpu().numpy()
-    out = {"subpel_mv": g(pipe.sp.out).reshape(-1, 2), "inter_cost": g(pipe.ic.cost).reshape(-1, 2), "mode": g(pipe.ii.mode), "intra": g(pipe.ii.intra),
-           "levels": g(pipe.rc.levels), "num_sig": g(pipe.rc.num_sig), "dist": g(pipe.rc.dist), "bs_ver": g(pipe.db.bs_ver), "bs_hor": g(pipe.db.bs_hor),
-           "sao_count": g(pipe.sao.count), "sao_offset_org": g(pipe.sao.offset_org), "sao_params": g(pipe.sao.params), "recon": g(pipe.final).view(dt)}
-    for i in range(2):
-        out["levels_c%d" % i], out["num_sig_c%d" % i] = g(pipe.rc_c[i].levels), g(pipe.rc_c[i].num_sig)
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = g(pipe.sao_c[i].count), g(pipe.sao_c[i].params)
-        out["recon_c%d" % i] = g(pipe.final_c[i]).view(dt)
+    out = SC.step_outputs(pipe, dt)
+    out.update({"subpel_mv": g(pipe.sp.out).reshape(-1, 2), "inter_cost": g(pipe.ic.cost).reshape(-1, 2), "mode": g(pipe.ii.mode), "intra": g(pipe.ii.intra)})
     return out

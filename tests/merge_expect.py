@@ -21,7 +21,7 @@ import numpy as np
 import intra_expect as IE
 import intra_inter_expect as IX
 
-O, F, H, harness = IE.O, IE.F, IE.H, IE.harness
+O, F, H, harness, SC = IE.O, IE.F, IE.H, IE.harness, IE.SC
 
 MASKS = ("merge_won", "inter_won", "tie_stays_merge", "tie_lowest_index", "won_A1", "won_B1", "won_B0", "won_A0", "won_B2", "won_zero",
          "pruned_B1", "pruned_B0", "pruned_A0", "pruned_B2", "B0_equals_A1_kept", "B2_dropped_at_four", "cut_at_max", "inherits_inherited",
@@ -335,14 +335,10 @@ def p_chain(depth, cur, ref, w64, h64, rng_r, subme, level, qp, max_merge=3, sao
     y, r = cur[0], ref[0]
     if tu_qp is not None:                       # the stages clamp a map's entries to the quantiser's range; the oracle runs take them as they are
         tu_qp = np.clip(tu_qp, 0, 51 + 6 * (depth - 8)).astype(np.int8)
-    cost = F.mv_cost_table(rng_r)
-    cq, qoff = F.qpel_cost_table(rng_r)
-    _, bestv = O.me_fullsearch(depth, y, stride, org, r, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False, nthreads=cores)
-    mv = O.subpel_refine(depth, y, stride, org, r, stride, org, w64, h64, rng_r, 0, nctu, bestv, cq, qoff, subme, nthreads=cores)
+    _, mv = SC.search_head(depth, y, r, stride, org, w64, h64, rng_r, subme, cores=cores)
     it = IX.inter_side(depth, cur, ref, w64, h64, level, mv, qp, (qpc, qpc), tu_flags, base_bits=base_bits, lambda8=lambda8, table=IX.s_bitsizes(4 * rng_r + 4),
                        tu_qp=tu_qp, lambda8_by_qp=lambda8_by_qp)
     e = stage_expectation(depth, y, r, w64, h64, level, mv, max_merge, lambda8, inter_cost=it["inter_cost"][:, 1], tu_qp=tu_qp, lambda8_by_qp=lambda8_by_qp, qp=qp)
-    sl = level_slots(level, nctu)
     full = lambda recs: records(recs[:, 1], recs[:, 0], level, nctu)
     mvp, mvo = full(e["mv_pred"]), full(e["mv_out"])
     cd = IX.inter_side(depth, cur, ref, w64, h64, level, mvp, qp, (qpc, qpc), tu_flags, tu_qp=tu_qp)          # the coding from mv_pred
@@ -350,47 +346,16 @@ def p_chain(depth, cur, ref, w64, h64, rng_r, subme, level, qp, max_merge=3, sao
            "mv_out": e["mv_out"], "mv_pred": e["mv_pred"]}
     out.update({k: cd[k] for k in ("levels", "num_sig", "dist", "levels_c0", "levels_c1", "num_sig_c0", "num_sig_c1")})
     out["skip"] = skip_flags(e["merge"], cd["num_sig"], cd["num_sig_c0"], cd["num_sig_c1"])
-    cuqp = max(qp - 6 * (depth - 8), 0)
     bv, bh = O.deblock_bs_inter(depth, w64, h64, level, mvo, cd["num_sig"])
-    out.update({"bs_ver": bv, "bs_hor": bh})
-    dbk = O.deblock_luma(depth, cd["recon"], stride, org, w64, h64, bv, bh, cuqp, qp_map=cu_qp)
-    cnt, off = O.sao_stats(depth, y.reshape(-1), dbk.reshape(-1), stride, org, w64, h64, nthreads=cores)
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
-    cdb = O.deblock_chroma(depth, cd["recon_c0"], cd["recon_c1"], sc, oc, w64, h64, bv, bh, cuqp, qp_map=cu_qp)
-    cstat = [O.sao_stats(depth, np.ascontiguousarray(cur[1 + i]).reshape(-1), cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, nthreads=cores,
-                         ctu=(32, 32), plane_offset=2) for i in range(2)]
-    if sao_rdo is not None:
-        lam = np.tile(np.array(sao_rdo["lambdas"], np.int64), (nctu, 1))
-        pars, _ = O.sao_rdo(depth, [cnt, cstat[0][0], cstat[1][0]], [off, cstat[0][1], cstat[1][1]], w64 // 64, h64 // 64, lam, sao_rdo["ctx_merge"],
-                            sao_rdo["ctx_type"], sao_rdo["entropy_bits"])
-        par, cpars = pars[0].reshape(-1), [pars[1].reshape(-1), pars[2].reshape(-1)]
-    else:
-        _, par = O.sao_decide(depth, cnt, off)
-        cpars = [O.sao_decide(depth, cstat[i][0], cstat[i][1])[1] for i in range(2)]
-    fin = O.sao_apply(depth, dbk.reshape(-1), stride, org, w64, h64, par, nthreads=cores).reshape(rows, stride)
-    out.update({"sao_count": cnt, "sao_offset_org": off, "sao_params": par})
-    inner = fin[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
-    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
-    for i in range(2):
-        cf = O.sao_apply(depth, cdb[i].reshape(-1), sc, oc, w64 // 2, h64 // 2, cpars[i], nthreads=cores, ctu=(32, 32))
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = cstat[i][0], cpars[i]
-        ci = cf.reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
-        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
-    return out
+    return SC.filter_tail(out, depth, cur, cd["recon"], [cd["recon_c0"], cd["recon_c1"]], bv, bh, qp, w64, h64, cu_qp=cu_qp, sao_rdo=sao_rdo, cores=cores)
 
 
 def p_device_outputs(pipe, dt):
     """The same names from a stages.MergePFramePipeline after run() (chroma, deblocking, SAO applied)."""
     g = lambda t: t.cpu().numpy()
     sl = level_slots(pipe.md.level, pipe.nctu)
-    out = {"subpel_mv": g(pipe.sp.out).reshape(-1, 2), "inter_cost": g(pipe.ic.cost).reshape(-1, 2), "merge": g(pipe.md.merge), "merge_idx": g(pipe.md.merge_idx),
-           "merge_cost": g(pipe.md.cost).reshape(-1, 2), "best": g(pipe.md.best).reshape(-1, 2), "mv_out": g(pipe.md.mv_out).reshape(-1, 2)[sl],
-           "mv_pred": g(pipe.md.mv_pred).reshape(-1, 2)[sl], "skip": g(pipe.skip),
-           "levels": g(pipe.rc.levels), "num_sig": g(pipe.rc.num_sig), "dist": g(pipe.rc.dist), "bs_ver": g(pipe.db.bs_ver), "bs_hor": g(pipe.db.bs_hor),
-           "sao_count": g(pipe.sao.count), "sao_offset_org": g(pipe.sao.offset_org), "sao_params": g(pipe.sao.params), "recon": g(pipe.final).view(dt)}
-    for i in range(2):
-        out["levels_c%d" % i], out["num_sig_c%d" % i] = g(pipe.rc_c[i].levels), g(pipe.rc_c[i].num_sig)
-        out["sao_count_c%d" % i], out["sao_params_c%d" % i] = g(pipe.sao_c[i].count), g(pipe.sao_c[i].params)
-        out["recon_c%d" % i] = g(pipe.final_c[i]).view(dt)
+    out = SC.step_outputs(pipe, dt)
+    out.update({"subpel_mv": g(pipe.sp.out).reshape(-1, 2), "inter_cost": g(pipe.ic.cost).reshape(-1, 2), "merge": g(pipe.md.merge), "merge_idx": g(pipe.md.merge_idx),
+                "merge_cost": g(pipe.md.cost).reshape(-1, 2), "best": g(pipe.md.best).reshape(-1, 2), "mv_out": g(pipe.md.mv_out).reshape(-1, 2)[sl],
+                "mv_pred": g(pipe.md.mv_pred).reshape(-1, 2)[sl], "skip": g(pipe.skip)})
     return out

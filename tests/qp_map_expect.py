@@ -16,6 +16,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import step_chain as SC         # noqa: E402
 
 F = importlib.import_module("x265-yuuki-asuna_amd.frames")
 H = importlib.import_module("x265-yuuki-asuna_amd.hipabi")
@@ -178,8 +179,7 @@ def walk(depth, planes, w64, h64, level, tu_qp, lambda8_by_qp=None, lambda8=1024
     cw, chh = w64 // 64, h64 // 64
     nctu = cw * chh
     _, _, stride, rows, org = F.padded_dims(w64, h64)
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    oc = F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
+    sc, oc = SC.chroma_geometry(w64)
     src = [np.ascontiguousarray(p).reshape(-1) for p in planes[:3]]
     init = recon_init if recon_init is not None else IE.garbage_planes(depth, [s.shape for s in src])
     rec = [np.array(p, copy=True).reshape(-1) for p in init]
@@ -260,40 +260,14 @@ def _composed(run, cells, w64, h64, level, chroma, stride, org):
     return compose(run, qpb, sub << level, sample_qps(cells, sub), stride, org, w64 * sub // 8, h64 * sub // 8)
 
 
-def _chroma_geometry(w64):
-    sc = w64 // 2 + 2 * F.CHROMA_MARGIN_X
-    return sc, F.CHROMA_MARGIN_Y * sc + F.CHROMA_MARGIN_X
-
-
-def _finish(out, depth, rec, crec, w64, h64, level, bv, bh, cu_qp, qp, avx2):
-    """deblocking of the three planes with qp_map = cu_qp, then the border extension: the steps' tail without SAO"""
-    import oracle_api as O
-    _, _, stride, rows, org = F.padded_dims(w64, h64)
-    sc, oc = _chroma_geometry(w64)
-    cuqp = max(qp - 6 * (depth - 8), 0)
-    out.update({"bs_ver": bv, "bs_hor": bh})
-    dbk = O.deblock_luma(depth, rec.reshape(-1), stride, org, w64, h64, bv, bh, cuqp, qp_map=cu_qp, avx2=avx2).reshape(rows, stride)
-    cdb = O.deblock_chroma(depth, crec[0].reshape(-1), crec[1].reshape(-1), sc, oc, w64, h64, bv, bh, cuqp, qp_map=cu_qp, avx2=avx2)
-    inner = dbk[F.MARGIN_Y:F.MARGIN_Y + h64, F.MARGIN_X:F.MARGIN_X + w64]
-    out["recon"] = np.pad(inner, ((F.MARGIN_Y, F.MARGIN_Y), (F.MARGIN_X, F.MARGIN_X)), mode="edge")
-    for i in range(2):
-        ci = cdb[i].reshape(-1, sc)[F.CHROMA_MARGIN_Y:F.CHROMA_MARGIN_Y + h64 // 2, F.CHROMA_MARGIN_X:F.CHROMA_MARGIN_X + w64 // 2]
-        out["recon_c%d" % i] = np.pad(ci, ((F.CHROMA_MARGIN_Y, F.CHROMA_MARGIN_Y), (F.CHROMA_MARGIN_X, F.CHROMA_MARGIN_X)), mode="edge")
-    return out
-
-
 def p_chain(depth, cur_planes, ref_planes, w64, h64, rng_r, subme, level, qp, cu_qp, tu_qp, tu_flags=2, cores=0, avx2=False):
     """One P picture through the oracle under maps (the CPU twin of FramePipeline.run with chroma, deblocking, sign hiding, no SAO):
     *_planes = padded (Y [rows, stride], Cb, Cr) host planes; cu_qp [h/8, w/8], tu_qp [3, h/8, w/8].  Every stage output by name."""
     import oracle_api as O
     _, _, stride, rows, org = F.padded_dims(w64, h64)
-    sc, oc = _chroma_geometry(w64)
+    sc, oc = SC.chroma_geometry(w64)
     cur, ref = cur_planes[0], ref_planes[0]
-    nctu = (w64 // 64) * (h64 // 64)
-    cost = F.mv_cost_table(rng_r)
-    cq, qoff = F.qpel_cost_table(rng_r)
-    _, best = O.me_fullsearch(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False, nthreads=cores, avx2=avx2)
-    mv = O.subpel_refine(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, best, cq, qoff, subme, nthreads=cores, avx2=avx2)
+    _, mv = SC.search_head(depth, cur, ref, stride, org, w64, h64, rng_r, subme, cores=cores, avx2=avx2)
     out = {"subpel_mv": mv}
     rec, lev, ns, dist = _composed(lambda q: O.inter_recon(depth, cur, stride, org, ref, stride, org, w64, h64, level, mv, q, intra_slice=tu_flags,
                                                            nthreads=cores, avx2=avx2), tu_qp[0], w64, h64, level, False, stride, org)
@@ -305,7 +279,7 @@ def p_chain(depth, cur_planes, ref_planes, w64, h64, rng_r, subme, level, qp, cu
         crec.append(r)
         out["levels_c%d" % (c - 1)], out["num_sig_c%d" % (c - 1)] = l, s
     bv, bh = O.deblock_bs_inter(depth, w64, h64, level, mv, ns, avx2=avx2)
-    return _finish(out, depth, rec, crec, w64, h64, level, bv, bh, cu_qp, qp, avx2)
+    return SC.filter_tail(out, depth, cur_planes, rec, crec, bv, bh, qp, w64, h64, cu_qp=cu_qp, sao=False, avx2=avx2)
 
 
 def b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, subme, level, qp, cu_qp, tu_qp, tu_flags=2, cores=0, avx2=False):
@@ -314,16 +288,12 @@ def b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, subme,
     import bidir_expect as BE
     O = BE.O
     _, _, stride, rows, org = F.padded_dims(w64, h64)
-    sc, oc = _chroma_geometry(w64)
+    sc, oc = SC.chroma_geometry(w64)
     cur, r0, r1 = cur_planes[0], ref0_planes[0], ref1_planes[0]
     nctu = (w64 // 64) * (h64 // 64)
-    cost = F.mv_cost_table(rng_r)
     cq, qoff = F.qpel_cost_table(rng_r)
-    recs, phases = [], []
-    for ref in (r0, r1):
-        _, best = O.me_fullsearch(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, cost, cost, want_surf=False, nthreads=cores, avx2=avx2)
-        recs.append(O.subpel_refine(depth, cur, stride, org, ref, stride, org, w64, h64, rng_r, 0, nctu, best, cq, qoff, subme, nthreads=cores, avx2=avx2))
-        phases.append(BE.phases_of(depth, ref, stride))
+    recs = [SC.search_head(depth, cur, ref, stride, org, w64, h64, rng_r, subme, cores=cores, avx2=avx2)[1] for ref in (r0, r1)]
+    phases = [BE.phases_of(depth, ref, stride) for ref in (r0, r1)]
     e = BE.expect(depth, cur, stride, org, w64, h64, level, recs, phases, cq, qoff, BE.DIR_COST, with_reference=False)
     mv0, mv1 = BE.full_mv_out(level, nctu, e["mv0"], 0), BE.full_mv_out(level, nctu, e["mv1"], 0)
     out = {"dir": e["dir"], "mv0_out": mv0, "mv1_out": mv1}
@@ -339,7 +309,7 @@ def b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, subme,
         crec.append(r)
         out["levels_c%d" % (c - 1)], out["num_sig_c%d" % (c - 1)] = l, s
     bv, bh = O.deblock_bs_b(depth, w64, h64, level, mv0, mv1, e["ref0"], e["ref1"], ns, slice_b=True, avx2=avx2)
-    return _finish(out, depth, rec, crec, w64, h64, level, bv, bh, cu_qp, qp, avx2)
+    return SC.filter_tail(out, depth, cur_planes, rec, crec, bv, bh, qp, w64, h64, cu_qp=cu_qp, sao=False, avx2=avx2)
 
 
 def i_chain(depth, planes, w64, h64, level, qp, cu_qp, tu_qp, lambda8_by_qp=None, tu_flags=H.TU_INTRA_SLICE | H.TU_SIGN_HIDE, avx2=False):
@@ -349,7 +319,7 @@ def i_chain(depth, planes, w64, h64, level, qp, cu_qp, tu_qp, lambda8_by_qp=None
     e = walk(depth, planes, w64, h64, level, tu_qp, lambda8_by_qp=lambda8_by_qp, flags=tu_flags)
     out = {k: e[k] for k in ("mode", "levels", "num_sig", "dist", "levels_c0", "levels_c1", "num_sig_c0", "num_sig_c1")}
     bv, bh = O.deblock_bs_inter(depth, w64, h64, level, np.zeros((nctu * 85, 2), np.int32), e["num_sig"], avx2=avx2, intra=np.ones(nctu * (64 >> (2 * level)), np.uint8))
-    return _finish(out, depth, e["recon"], [e["recon_c0"], e["recon_c1"]], w64, h64, level, bv, bh, cu_qp, qp, avx2)
+    return SC.filter_tail(out, depth, planes, e["recon"], [e["recon_c0"], e["recon_c1"]], bv, bh, qp, w64, h64, cu_qp=cu_qp, sao=False, avx2=avx2)
 
 
 def varied_clip(clip, depth):
@@ -372,15 +342,11 @@ def varied_clip(clip, depth):
 def step_outputs(pipe, dt, kind):
     """The chains' names from a FramePipeline ("p"), BFramePipeline ("b") or IFramePipeline ("i") after run() (chroma, deblocking, no SAO)."""
     g = lambda t: t.cpu().numpy()
+    out = SC.step_outputs(pipe, dt)
     if kind == "i":
-        tu, tc = pipe.ip, [(pipe.ip.levels_c[i], pipe.ip.num_sig_c[i]) for i in range(2)]
-        out = {"mode": g(tu.mode)}
+        out["mode"] = g(pipe.ip.mode)
+    elif kind == "p":
+        out["subpel_mv"] = g(pipe.sp.out).reshape(-1, 2)
     else:
-        tu, tc = pipe.rc, [(pipe.rc_c[i].levels, pipe.rc_c[i].num_sig) for i in range(2)]
-        out = {"subpel_mv": g(pipe.sp.out).reshape(-1, 2)} if kind == "p" else \
-              {"dir": g(pipe.bd.dir), "mv0_out": g(pipe.bd.mv0_out).reshape(-1, 2), "mv1_out": g(pipe.bd.mv1_out).reshape(-1, 2)}
-    out.update({"levels": g(tu.levels), "num_sig": g(tu.num_sig), "dist": g(tu.dist), "bs_ver": g(pipe.db.bs_ver), "bs_hor": g(pipe.db.bs_hor),
-                "recon": g(pipe.final).view(dt)})
-    for i in range(2):
-        out["levels_c%d" % i], out["num_sig_c%d" % i], out["recon_c%d" % i] = g(tc[i][0]), g(tc[i][1]), g(pipe.final_c[i]).view(dt)
+        out.update({"dir": g(pipe.bd.dir), "mv0_out": g(pipe.bd.mv0_out).reshape(-1, 2), "mv1_out": g(pipe.bd.mv1_out).reshape(-1, 2)})
     return out

@@ -254,7 +254,7 @@ def p_chain(depth, cur_pad, ref_pad, w64, h64, rng_r, subme, level, qp, chroma_s
     """One P picture, the CPU twin of FramePipeline.run: the records are the chroma walk's (chroma_satd) or the oracle's luma-only
     subpel_refine; every later stage is the oracle's, fed with those records.  *_pad = padded (Y, Cb, Cr) host planes."""
     import oracle_api as O
-    import qp_map_expect as QE
+    import step_chain
     S = importlib.import_module("x265-yuuki-asuna_amd.stages")
     cc = CC.refine_inputs(depth, rng_r, cur_pad, ref_pad, w64, h64)
     c = cc.luma
@@ -273,7 +273,7 @@ def p_chain(depth, cur_pad, ref_pad, w64, h64, rng_r, subme, level, qp, chroma_s
         crec.append(r)
         out["levels_c%d" % k], out["num_sig_c%d" % k] = l, s
     bv, bh = O.deblock_bs_inter(depth, w64, h64, level, mv, ns)
-    return QE._finish(out, depth, rec, crec, w64, h64, level, bv, bh, None, qp, False)
+    return step_chain.filter_tail(out, depth, cur_pad, rec, crec, bv, bh, qp, w64, h64, sao=False)
 
 
 def b_chain(depth, pad, w64, h64, rng_r, subme, level, qp, tu_flags=2):
@@ -281,7 +281,7 @@ def b_chain(depth, pad, w64, h64, rng_r, subme, level, qp, tu_flags=2):
     (Y, Cb, Cr) host planes.  Both lists' records are the chroma walk's, the decision is bidir_decision, the rest is the oracle's."""
     import bidir_expect as BE
     import oracle_api as O
-    import qp_map_expect as QE
+    import step_chain
     S = importlib.import_module("x265-yuuki-asuna_amd.stages")
     b = CC.b_inputs(depth, rng_r, pad, w64, h64)
     recs = [walk(cc, subme, with_reference=False)["rec"] for cc in b.lists]
@@ -300,6 +300,6 @@ def b_chain(depth, pad, w64, h64, rng_r, subme, level, qp, tu_flags=2):
         crec.append(r)
         out["levels_c%d" % (c - 1)], out["num_sig_c%d" % (c - 1)] = l, s
     bv, bh = O.deblock_bs_b(depth, w64, h64, level, mv0, mv1, e["ref0"], e["ref1"], ns, slice_b=True)
-    out = QE._finish(out, depth, rec, crec, w64, h64, level, bv, bh, None, qp, False)
+    out = step_chain.filter_tail(out, depth, cur, rec, crec, bv, bh, qp, w64, h64, sao=False)
     out["masks"] = e["masks"]
     return out

@@ -10,6 +10,7 @@ import bidir_expect as BE
 import bmerge_cases as C
 import bmerge_expect as BM
 import intra_expect as IE
+from step_chain import sao_rdo_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -103,16 +104,9 @@ def test_b_merge_decide_at_ten_bits_under_maps_and_on_other_grids(c):
     assert e["merge"].any()
 
 
-def _sao_rdo_inputs(depth, qp, slice_type):
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(slice_type, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 def _b_step(w64, h64, depth, dev, level, qp, rng, subme, max_merge=3):
     return S.MergeBFramePipeline(w64, h64, depth, dev, rng=rng, subme=subme, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True,
-                                 sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_B), max_merge=max_merge)
+                                 sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_B), max_merge=max_merge)
 
 
 def _triple(depth, level, w, h):
@@ -216,13 +210,13 @@ def test_mini_gop_with_the_step_as_b_step():
 
     def steps(b_step):
         i_step = S.IFramePipeline(w64, h64, depth, dev, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True,
-                                  sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_I))
-        p_step = S.MergePFramePipeline(w64, h64, depth, dev, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_P), **common)
+                                  sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_I))
+        p_step = S.MergePFramePipeline(w64, h64, depth, dev, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_P), **common)
         return S.MiniGop(p_step, b_step, gop, i_step=i_step)
     order, out = steps(_b_step(w64, h64, depth, dev, level, qp, rng, subme)).run(pics)
     torch.cuda.synchronize()
     assert order == [0, 3, 1, 2, 6, 4, 5] and sorted(out) == list(range(7))
-    old = S.Sa8dBFramePipeline(w64, h64, depth, dev, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_B), **common)
+    old = S.Sa8dBFramePipeline(w64, h64, depth, dev, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_B), **common)
     _, out_old = steps(old).run(pics)
     torch.cuda.synchronize()
     same = lambda a, b: all(torch.equal(x.reshape(-1), y.reshape(-1)) for x, y in zip(a, b))

@@ -8,6 +8,7 @@ import pytest
 
 import bidir_expect as BE
 import bipred_cases as BC
+from step_chain import sao_rdo_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -17,17 +18,9 @@ S = importlib.import_module("x265-yuuki-asuna_amd.stages")
 HT = importlib.import_module("x265-yuuki-asuna_amd.host_tables")
 
 
-def _sao_rdo_inputs(depth, qp, slice_type):
-    """The host-side inputs of x265hip_sao_rdo at quantiser QP `qp`; the SAO type context starts from the slice type's own state."""
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(slice_type, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 def _b_step(w64, h64, depth, dev, rng, subme, level, qp, subpel_planes=False):
     return S.BFramePipeline(w64, h64, depth, dev, rng=rng, subme=subme, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True,
-                            sign_hide=True, subpel_planes=subpel_planes, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_B), want_cost=True)
+                            sign_hide=True, subpel_planes=subpel_planes, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_B), want_cost=True)
 
 
 def _check_b_step(depth, width, height, rng, subme, level, seed, subpel_planes, min_values, clip=None):
@@ -94,7 +87,7 @@ def test_mini_gop_closed_loop(depth):
     clip = BE.occluded_clip(W, H, 7, depth, 71)
     pics = [P.DevicePicture(y, dev, u, v) for (y, u, v) in clip]
     w64, h64 = pics[0].w64, pics[0].h64
-    srdo_p = _sao_rdo_inputs(depth, qp, HT.SLICE_P)
+    srdo_p = sao_rdo_inputs(depth, qp, HT.SLICE_P)
 
     def p_step():
         return S.FramePipeline(w64, h64, depth, dev, rng=R, subme=subme, level=level, qp=qp, want_surf=False, deblock=True, sao=True, chroma=True,

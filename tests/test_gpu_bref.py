@@ -12,6 +12,7 @@ import pytest
 import bidir_expect as BE
 import bref_expect as BR
 import qp_map_expect as QE
+from step_chain import sao_rdo_inputs
 from test_gpu_tu_passes import _assert_plane, _dev_plane, _fill_outputs, _mvs, _nthreads, _passes, _phases, _picture, _sentinel
 
 pytestmark = pytest.mark.gpu
@@ -347,16 +348,9 @@ def test_copies_of_one_plane_in_every_slot_are_inter_recon_bi(depth, level):
 W, H, R = 256, 192, 12
 
 
-def _sao_rdo_inputs(depth, qp, slice_type=None):
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(HT.SLICE_B if slice_type is None else slice_type, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 def _step(depth, dev, qp, max_refs=(2, 2), level=2, sao=True, **kw):
     return S.MultiRefBFramePipeline(W, H, depth, dev, max_refs=max_refs, rng=R, subme=3, level=level, qp=qp, deblock=True, sao=sao, chroma=True, sao_apply=sao,
-                                    sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp) if sao else None, want_cost=True, **kw)
+                                    sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_B) if sao else None, want_cost=True, **kw)
 
 
 def _pics(clip, dev):

@@ -10,6 +10,7 @@ import bidir_expect as BE
 import bsa8d_cases as C
 import bsa8d_expect as BX
 import intra_inter_cases as PC
+from step_chain import sao_rdo_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -105,16 +106,9 @@ def test_kernel_operating_points_grids_clips_and_ties(c):
         assert (full["cost"][:, :3] != e["cost"][:, :3]).any()
 
 
-def _sao_rdo_inputs(depth, qp, slice_type):
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(slice_type, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 def _b_step(w64, h64, depth, dev, level, qp, b_intra, rng=C.RANGE, subme=C.SUBME):
     return S.Sa8dBFramePipeline(w64, h64, depth, dev, rng=rng, subme=subme, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True,
-                                sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_B), b_intra=b_intra)
+                                sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_B), b_intra=b_intra)
 
 
 @pytest.mark.parametrize("depth,level,b_intra,wide", [(8, 2, False, False), (8, 2, True, False), (8, 1, False, False), (8, 1, True, False), (10, 0, False, False),
@@ -200,16 +194,16 @@ def test_mini_gop_with_the_step_as_b_step():
 
     def steps(b_step):
         i_step = S.IFramePipeline(w64, h64, depth, dev, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True,
-                                  sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_I))
+                                  sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_I))
         p_step = S.IntraPFramePipeline(w64, h64, depth, dev, rng=C.RANGE, subme=C.SUBME, level=level, qp=qp, deblock=True, sao=True, chroma=True,
-                                       sao_apply=True, sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_P))
+                                       sao_apply=True, sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_P))
         return S.MiniGop(p_step, b_step, gop, i_step=i_step)
     b_step = _b_step(w64, h64, depth, dev, level, qp, True)
     order, out = steps(b_step).run(pics)
     torch.cuda.synchronize()
     assert order == [0, 3, 1, 2, 6, 4, 5] and sorted(out) == list(range(7))
     old = S.BFramePipeline(w64, h64, depth, dev, rng=C.RANGE, subme=C.SUBME, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True,
-                           sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_B))
+                           sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_B))
     _, out_old = steps(old).run(pics)
     torch.cuda.synchronize()
     for a in (0, 3, 6):

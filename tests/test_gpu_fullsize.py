@@ -92,14 +92,15 @@ def test_whole_4k_frame_every_stage_equals_oracle_chain(depth, rdo, packed):
     record-per-lane kernel me_ctu_c_kernel - exactly what the default bench line times (round-2 verdict, weak 2 iii); "t": its round-2
     chunk-major format; False (10-bit): int32 records."""
     import torch
-    from test_gpu_pipeline import _sao_rdo_inputs
+    from step_chain import sao_rdo_inputs
+    HT = importlib.import_module("x265-yuuki-asuna_amd.host_tables")
     B = _bench()
     O = _oracle()
     dev = torch.device("cuda:0")
     w, h, qp = 3840, 2160, 27 + 12 * (depth == 10)
     clip = F.synth_clip(w, h, 2, depth=depth, seed=265)
     pics = [P.DevicePicture(y, dev, u, v) for (y, u, v) in clip]
-    srdo = _sao_rdo_inputs(depth, qp) if rdo else None
+    srdo = sao_rdo_inputs(depth, qp, HT.SLICE_P) if rdo else None
     pipe = S.FramePipeline(pics[0].w64, pics[0].h64, depth, dev, rng=57, subme=3, level=2, qp=qp, want_surf=True, packed=packed,
                            lookahead=(w, h), deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True, sao_rdo=srdo)
     dev_out = B.device_outputs(pipe, pics[1], pics[0])

@@ -10,6 +10,7 @@ import bidir_expect as BE
 import intra_expect as IE
 import intra_inter_cases as C
 import intra_inter_expect as IX
+from step_chain import sao_rdo_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -180,16 +181,9 @@ def test_intra_in_inter_degenerate_grids(w, h):
     _run_stage(c, dict(ref=ref, cur=cur, w64=w, h64=h, qp=qp, qp_c=(qpc, qpc), lambda8=lambda8, mode_bits=mode_bits, tu_qp=None, lambda8_by_qp=None, inter=it, e=e))
 
 
-def _sao_rdo_inputs(depth, qp, slice_type):
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(slice_type, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 def _p_step(w64, h64, depth, dev, level, qp, rng, subme):
     return S.IntraPFramePipeline(w64, h64, depth, dev, rng=rng, subme=subme, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True,
-                                 sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_P))
+                                 sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_P))
 
 
 def _wide_pair(depth):
@@ -236,7 +230,7 @@ def test_mini_gop_with_the_step_as_p_step():
     pics = [P.DevicePicture(y, dev, u, v) for (y, u, v) in (ref_yuv, cur_a, ref_yuv)]
     w64, h64 = pics[0].w64, pics[0].h64
     i_step = S.IFramePipeline(w64, h64, depth, dev, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True,
-                              sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_I))
+                              sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_I))
     order, out = S.MiniGop(_p_step(w64, h64, depth, dev, level, qp, rng, subme), None, 1, i_step=i_step).run(pics)
     torch.cuda.synchronize()
     assert order == [0, 1, 2]

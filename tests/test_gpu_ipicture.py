@@ -11,6 +11,7 @@ import pytest
 import bidir_expect as BE
 import intra_cases as IC
 import intra_expect as IE
+from step_chain import sao_rdo_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -160,16 +161,9 @@ def test_intra_picture_without_chroma(c):
     assert "recon_c0" not in e and int(e["num_sig"].sum()) > 0
 
 
-def _sao_rdo_inputs(depth, qp, slice_type):
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(slice_type, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 def _i_step(w64, h64, depth, dev, level, qp):
     return S.IFramePipeline(w64, h64, depth, dev, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True,
-                            sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_I), want_cost=True)
+                            sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_I), want_cost=True)
 
 
 @pytest.mark.parametrize("depth,width,height", [(8, 256, 192), (10, 256, 192), (8, 1920, 1080)])
@@ -209,7 +203,7 @@ def test_mini_gop_with_an_i_step():
     clip = BE.occluded_clip(W, Hh, 7, depth, 71)
     pics = [P.DevicePicture(y, dev, u, v) for (y, u, v) in clip]
     w64, h64 = pics[0].w64, pics[0].h64
-    srdo_p = _sao_rdo_inputs(depth, qp, HT.SLICE_P)
+    srdo_p = sao_rdo_inputs(depth, qp, HT.SLICE_P)
 
     def p_step():
         return S.FramePipeline(w64, h64, depth, dev, rng=R, subme=subme, level=level, qp=qp, want_surf=False, deblock=True, sao=True, chroma=True,
@@ -217,7 +211,7 @@ def test_mini_gop_with_an_i_step():
 
     def b_step():
         return S.BFramePipeline(w64, h64, depth, dev, rng=R, subme=subme, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True,
-                                sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_B))
+                                sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_B))
     order_i, out_i = S.MiniGop(p_step(), b_step(), gop, i_step=_i_step(w64, h64, depth, dev, level, qp)).run(pics)
     order_0, out_0 = S.MiniGop(p_step(), b_step(), gop).run(pics)
     torch.cuda.synchronize()

@@ -10,6 +10,7 @@ import bidir_expect as BE
 import intra_expect as IE
 import merge_cases as C
 import merge_expect as ME
+from step_chain import sao_rdo_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -99,16 +100,9 @@ def test_merge_decide_at_ten_bits_under_maps_and_on_other_grids(c):
     assert e["merge"].any()
 
 
-def _sao_rdo_inputs(depth, qp, slice_type):
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(slice_type, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 def _p_step(w64, h64, depth, dev, level, qp, rng, subme, max_merge=3):
     return S.MergePFramePipeline(w64, h64, depth, dev, rng=rng, subme=subme, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True,
-                                 sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_P), max_merge=max_merge)
+                                 sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_P), max_merge=max_merge)
 
 
 def _pair(depth, level, w, h):
@@ -201,7 +195,7 @@ def test_mini_gop_with_the_step_as_p_step():
     pics = [P.DevicePicture(y, dev, u, v) for (y, u, v) in (ref_yuv, cur_a, ref_yuv)]
     w64, h64 = pics[0].w64, pics[0].h64
     i_step = S.IFramePipeline(w64, h64, depth, dev, level=level, qp=qp, deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True,
-                              sao_rdo=_sao_rdo_inputs(depth, qp, HT.SLICE_I))
+                              sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_I))
     order, out = S.MiniGop(_p_step(w64, h64, depth, dev, level, qp, rng, subme), None, 1, i_step=i_step).run(pics)
     torch.cuda.synchronize()
     assert order == [0, 1, 2]

@@ -10,6 +10,7 @@ import pytest
 import bidir_expect as BE
 import multiref_expect as ME
 import qp_map_expect as QE
+from step_chain import sao_rdo_inputs
 from test_gpu_tu_passes import _assert_plane, _dev_plane, _fill_outputs, _mvs, _nthreads, _passes, _phases, _picture, _sentinel
 
 pytestmark = pytest.mark.gpu
@@ -233,16 +234,9 @@ def test_inter_recon_chroma_pair_refs_multi_pass(depth):
 W, H, R = 256, 192, 12
 
 
-def _sao_rdo_inputs(depth, qp):
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(HT.SLICE_P, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 def _step(depth, dev, qp, subme=3, level=2, max_refs=4, sao=True, **kw):
     return S.MultiRefFramePipeline(W, H, depth, dev, max_refs=max_refs, rng=R, subme=subme, level=level, qp=qp, deblock=True, sao=sao, chroma=True,
-                                   sao_apply=sao, sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp) if sao else None, want_cost=True, **kw)
+                                   sao_apply=sao, sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_P) if sao else None, want_cost=True, **kw)
 
 
 def _clip5(depth, seed=81):
@@ -287,7 +281,7 @@ def test_one_reference_is_the_p_step_and_copies_change_nothing(depth):
     qp = 30 + 12 * (depth == 10)
     pics = _pics(_clip5(depth, 83)[:2], dev)
     fp = S.FramePipeline(W, H, depth, dev, rng=R, subme=3, level=2, qp=qp, want_surf=False, deblock=True, sao=True, chroma=True, sao_apply=True,
-                         sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp))
+                         sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_P))
     fp.run(pics[1], pics[0])
     pipe = _step(depth, dev, qp)
     pipe.run(pics[1], [pics[0]])
@@ -382,7 +376,7 @@ def test_mini_gop_with_three_p_references():
 
     def today(**kw):
         fp = S.FramePipeline(W, H, depth, dev, rng=R, subme=3, level=2, qp=qp, want_surf=False, deblock=True, sao=True, chroma=True, sao_apply=True,
-                             sign_hide=True, sao_rdo=_sao_rdo_inputs(depth, qp))
+                             sign_hide=True, sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_P))
         return S.MiniGop(fp, b_step, gop, **kw).run(pics)
     (o1, out1), (o2, out2) = today(), today(p_refs=1)
     torch.cuda.synchronize()

@@ -7,9 +7,12 @@ import sys
 import numpy as np
 import pytest
 
+from step_chain import sao_rdo_inputs
+
 pytestmark = pytest.mark.gpu
 
 F = importlib.import_module("x265-yuuki-asuna_amd.frames")
+HT = importlib.import_module("x265-yuuki-asuna_amd.host_tables")
 P = importlib.import_module("x265-yuuki-asuna_amd.pipeline")
 S = importlib.import_module("x265-yuuki-asuna_amd.stages")
 
@@ -111,15 +114,6 @@ def test_lookahead_costs_run_ahead_in_batches(depth):
     assert np.array_equal(fp.lc[0].mvs.cpu().numpy().reshape(-1, 2), mvs) and np.array_equal(fp.lc[0].frame.cpu().numpy()[:3], frame)
 
 
-def _sao_rdo_inputs(depth, qp):
-    """The host-side inputs of x265hip_sao_rdo for a P picture at quantiser QP `qp` (bench.py builds the same record)."""
-    HT = importlib.import_module("x265-yuuki-asuna_amd.host_tables")
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(HT.SLICE_P, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 @pytest.mark.parametrize("depth,fast,rdo", [(8, False, False), (10, False, False), (8, True, False), (10, True, False), (8, False, True), (8, True, True), (10, True, True)])
 def test_closed_loop_with_chroma_and_sao_in_the_loop(depth, fast, rdo):
     """The default bench pipeline (luma + 4:2:0 chroma reconstruction, luma + chroma deblocking, SAO statistics -> on-device parameters
@@ -136,7 +130,7 @@ def test_closed_loop_with_chroma_and_sao_in_the_loop(depth, fast, rdo):
     W, Hh, R, subme, level, qp = 256, 192, 12, 3, 2, 30 + 12 * (depth == 10)
     clip = F.synth_clip(W, Hh, 4, depth=depth, seed=67)
     pics = [P.DevicePicture(y, dev, u, v) for (y, u, v) in clip]
-    srdo = _sao_rdo_inputs(depth, qp) if rdo else None
+    srdo = sao_rdo_inputs(depth, qp, HT.SLICE_P) if rdo else None
     pipe = S.FramePipeline(pics[0].w64, pics[0].h64, depth, dev, rng=R, subme=subme, level=level, qp=qp, want_surf=False, lookahead=(W, Hh),
                            deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True, subpel_planes=fast, parallel_planes=fast, sao_rdo=srdo)
     ref_dev = pics[0].like([p.clone() for p in pics[0].planes()])

@@ -11,10 +11,12 @@ import pytest
 
 import subpel_cases as SC
 import subpel_chroma_cases as CC
+from step_chain import sao_rdo_inputs
 
 pytestmark = pytest.mark.gpu
 
 F = importlib.import_module("x265-yuuki-asuna_amd.frames")
+HT = importlib.import_module("x265-yuuki-asuna_amd.host_tables")
 P = importlib.import_module("x265-yuuki-asuna_amd.pipeline")
 S = importlib.import_module("x265-yuuki-asuna_amd.stages")
 
@@ -98,14 +100,6 @@ def test_selected_levels_with_chroma_satd():
     _check_masks(8, "edges", 3, True, True)
 
 
-def _sao_rdo_inputs(depth, qp):
-    HT = importlib.import_module("x265-yuuki-asuna_amd.host_tables")
-    tabs = HT.load()
-    cu_qp = max(qp - 6 * (depth - 8), 0)
-    cm, ct = HT.sao_contexts(HT.SLICE_P, cu_qp)
-    return {"lambdas": HT.sao_lambdas(tabs, cu_qp), "ctx_merge": cm, "ctx_type": ct, "entropy_bits": tabs["entropy_bits"]}
-
-
 def test_deferred_levels_leave_every_output_of_the_default_schedule(monkeypatch):
     """FramePipeline in its default parallel schedule with the SAO decision on, 256 x 128, three closed-loop steps with swap_output: with
     X265HIP_SUBPEL_DEFER=1 (level 2 in front of the reconstruction, levels 0 / 1 / 3 on the side stream) every array of bench.stage_outputs
@@ -123,7 +117,7 @@ def test_deferred_levels_leave_every_output_of_the_default_schedule(monkeypatch)
         monkeypatch.setenv("X265HIP_SUBPEL_DEFER", defer)      # read once, at construction
         pipes.append(S.FramePipeline(pics[0].w64, pics[0].h64, depth, dev, rng=12, subme=3, level=2, qp=qp, want_surf=False, lookahead=(W, Hh),
                                      deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True, subpel_planes=True, parallel_planes=True,
-                                     sao_rdo=_sao_rdo_inputs(depth, qp)))
+                                     sao_rdo=sao_rdo_inputs(depth, qp, HT.SLICE_P)))
         refs.append(pics[0].like([p.clone() for p in pics[0].planes()]))
     monkeypatch.delenv("X265HIP_SUBPEL_DEFER")
     assert pipes[0].subpel_defer is None and pipes[1].subpel_defer is not None

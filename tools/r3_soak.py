@@ -139,8 +139,9 @@ def pipe_case(rng, torch):
     import importlib
     sys.path.insert(0, ROOT)
     import bench as B
-    from test_gpu_pipeline import _sao_rdo_inputs
+    from step_chain import sao_rdo_inputs
     F = importlib.import_module("x265-yuuki-asuna_amd.frames")
+    HT = importlib.import_module("x265-yuuki-asuna_amd.host_tables")
     P = importlib.import_module("x265-yuuki-asuna_amd.pipeline")
     S = importlib.import_module("x265-yuuki-asuna_amd.stages")
     import oracle_api as O
@@ -154,7 +155,7 @@ def pipe_case(rng, torch):
     seed = int(rng.integers(0, 1 << 30))
     clip = F.synth_clip(w, h, 2, depth=depth, seed=seed)
     pics = [P.DevicePicture(y, dev, u, v) for (y, u, v) in clip]
-    srdo = _sao_rdo_inputs(depth, qp)
+    srdo = sao_rdo_inputs(depth, qp, HT.SLICE_P)
     pipe = S.FramePipeline(pics[0].w64, pics[0].h64, depth, dev, rng=R, subme=subme, level=2, qp=qp, want_surf=True, packed=fmt, lookahead=(w, h),
                            deblock=True, sao=True, chroma=True, sao_apply=True, sign_hide=True, sao_rdo=srdo, subpel_planes=bool(rng.integers(0, 2)),
                            parallel_planes=par)

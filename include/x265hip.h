@@ -902,7 +902,10 @@ int x265hip_aq_energy(const x265hip_aq_energy_params* p, void* stream);
  *   (slicetype.cpp:508-632) for AQ modes 1-3 from the block energies - pow(energy * c + 1, 0.1) with the frame-average correction
  *   (modes 2, 3; the bias term of mode 3), log2 (mode 1), the reference's float constants and summation order, through the C
  *   library's pow / log2 as the reference does - and invQscaleFactor = x265_exp2fix8(offset) (common.cpp:96-103).  aq_mode 0 or
- *   aq_strength 0: offsets 0, factors 256. */
+ *   aq_strength 0: offsets 0, factors 256.
+ *   avg_blocks: what the frame averages of modes 2 and 3 are divided by (:564-565), 0 = nblocks.  With qg_size 8 the reference
+ *   divides by the size of its arrays, maxBlocksInRowFullRes * maxBlocksInColFullRes = 4 * ((width / 2 + 7) >> 3) * ((height / 2 + 7) >> 3)
+ *   (:453, lowres.cpp:62-65), which is more than the blocks its loop visits when width or height mod 16 lies in 1 .. 8 (1080 lines). */
 typedef struct x265hip_aq_offsets_params
 {
     int depth, qg_size, aq_mode;
@@ -911,6 +914,7 @@ typedef struct x265hip_aq_offsets_params
     const uint32_t* energy;          /* HOST uint32 [nblocks] */
     double* qp_aq_offset;            /* HOST double [nblocks] */
     int32_t* inv_qscale;             /* HOST int32 [nblocks] */
+    int avg_blocks;
 } x265hip_aq_offsets_params;
 int x265hip_aq_offsets(const x265hip_aq_offsets_params* p);
 /* --hevc-aq (rc.hevcAq): what calcAdaptiveQuantFrame runs instead of the AQ modes - LookaheadTLD::xPreanalyze / xPreanalyzeQp

@@ -264,6 +264,9 @@ void EXPORT(x265oracle_aq_frame)(const pixel* y, const pixel* cb, const pixel* c
     const int inc = qgSize == 8 ? 8 : 16, lshift = qgSize == 8 ? 6 : 8, cshift = qgSize == 8 ? 4 : 6;
     const float modeOneConst = qgSize == 8 ? 11.427f : 14.427f, modeTwoConst = qgSize == 8 ? 8.f : 11.f;
     const int bw = (width + inc - 1) / inc, bh = (height + inc - 1) / inc, blockCount = bw * bh;
+    /* what the frame averages are divided by (:453,460): with qgSize 8 maxBlocksInRowFullRes * maxBlocksInColFullRes, the size of the Lowres
+     * arrays (lowres.cpp:62-65) - more than the blocks the loop visits when width or height mod 16 lies in 1 .. 8 */
+    const int avgCount = qgSize == 8 ? 4 * ((width / 2 + 7) >> 3) * ((height / 2 + 7) >> 3) : blockCount;
     for (int i = 0; i < 3; i++) wpSum[i] = wpSsd[i] = 0;
 #define ENERGY(BX, BY) (aq_block_energy(y + (BX) + (intptr_t)(BY) * stride, stride, inc, lshift, &wpSum[0], &wpSsd[0]) + \
         (cb ? aq_block_energy(cb + ((BX) >> 1) + (intptr_t)((BY) >> 1) * strideC, strideC, inc >> 1, cshift, &wpSum[1], &wpSsd[1]) + \
@@ -290,8 +293,8 @@ void EXPORT(x265oracle_aq_frame)(const pixel* y, const pixel* cb, const pixel* c
                     avg_adj += qp_adj;
                     avg_adj_pow2 += qp_adj * qp_adj;
                 }
-            avg_adj /= blockCount;
-            avg_adj_pow2 /= blockCount;
+            avg_adj /= avgCount;
+            avg_adj_pow2 /= avgCount;
             strength = aqStrength * avg_adj;
             avg_adj = avg_adj - 0.5f * (avg_adj_pow2 - modeTwoConst) / avg_adj;
             bias_strength = aqStrength;

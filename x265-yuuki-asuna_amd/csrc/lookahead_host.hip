@@ -513,6 +513,7 @@ extern "C" int x265hip_aq_frame_host(const x265hip_aq_frame_host_params* p)
     memset(&o, 0, sizeof(o));
     o.depth = p->depth; o.qg_size = q; o.aq_mode = p->aq_mode; o.aq_strength = p->aq_strength; o.nblocks = nblk;
     o.energy = energy; o.qp_aq_offset = p->qp_aq_offset; o.inv_qscale = p->inv_qscale;
+    if (q == 8) o.avg_blocks = 4 * ((p->width / 2 + 7) >> 3) * ((p->height / 2 + 7) >> 3);       // the Lowres arrays' size, slicetype.cpp:453
     rc = x265hip_aq_offsets(&o);
     if (rc) return rc;
     if (p->qp_cutree_offset != p->qp_aq_offset) memcpy(p->qp_cutree_offset, p->qp_aq_offset, (size_t)nblk * sizeof(double));

@@ -697,7 +697,8 @@ struct PictureAdaptiveCurve             // --aq-mode 2 (biased = false) / 3 (bia
     bool biased;
     PictureAdaptiveCurve(int qgSize, int depth, bool withBias) : depthScale(1.f / (1 << (2 * (depth - 8)))), knee(qgSize == 8 ? 8.f : 11.f), biased(withBias) {}
     // first pass: the roots themselves (left in `root`), their two moments -> where the curve sits for this picture
-    void place(const uint32_t* energy, double* root, int n, double aqStrength)
+    // (`count`: what the reference divides the moments by - the blocks, or with --qg-size 8 the size of its arrays, slicetype.cpp:453)
+    void place(const uint32_t* energy, double* root, int n, int count, double aqStrength)
     {
         double sum = 0, sumSq = 0;
         for (int i = 0; i < n; i++)
@@ -707,7 +708,7 @@ struct PictureAdaptiveCurve             // --aq-mode 2 (biased = false) / 3 (bia
             sum += r;
             sumSq += r * r;
         }
-        const double mean = sum / n, meanSq = sumSq / n;
+        const double mean = sum / count, meanSq = sumSq / count;
         gain = aqStrength * mean;
         centre = mean - 0.5f * (meanSq - knee) / mean;
         bias = aqStrength;
@@ -724,6 +725,7 @@ extern "C" int x265hip_aq_offsets(const x265hip_aq_offsets_params* p)
     if (p->qg_size != 16 && p->qg_size != 8) { set_error("aq_offsets: qg_size %d", p->qg_size); return X265HIP_EINVAL; }
     if (p->aq_mode < 0 || p->aq_mode > 3) { set_error("aq_offsets: aq_mode %d (0..3; the edge mode and hevcAq are not covered)", p->aq_mode); return X265HIP_EINVAL; }
     if (p->nblocks <= 0) { set_error("aq_offsets: nblocks %d", p->nblocks); return X265HIP_EINVAL; }
+    if (p->avg_blocks < 0) { set_error("aq_offsets: avg_blocks %d", p->avg_blocks); return X265HIP_EINVAL; }
     const int n = p->nblocks;
     double* out = p->qp_aq_offset;
     if (p->aq_mode == 0 || p->aq_strength == 0)
@@ -739,7 +741,7 @@ extern "C" int x265hip_aq_offsets(const x265hip_aq_offsets_params* p)
     else
     {
         PictureAdaptiveCurve curve(p->qg_size, p->depth, p->aq_mode == 3);
-        curve.place(p->energy, out, n, p->aq_strength);
+        curve.place(p->energy, out, n, p->avg_blocks ? p->avg_blocks : n, p->aq_strength);
         for (int i = 0; i < n; i++) out[i] = curve.offset(out[i]);
     }
     for (int i = 0; i < n; i++) p->inv_qscale[i] = aq_exp2fix8(out[i]);

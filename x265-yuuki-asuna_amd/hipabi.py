@@ -916,16 +916,26 @@ def aq_energy(depth, y, stride, org, width, height, qg_size, energy, wp, cb=None
 class AqOffsetsParams(ctypes.Structure):
     """x265hip_aq_offsets_params (include/x265hip.h)."""
     _fields_ = [("depth", ctypes.c_int), ("qg_size", ctypes.c_int), ("aq_mode", ctypes.c_int), ("aq_strength", ctypes.c_double),
-                ("nblocks", ctypes.c_int), ("energy", ctypes.c_void_p), ("qp_aq_offset", ctypes.c_void_p), ("inv_qscale", ctypes.c_void_p)]
+                ("nblocks", ctypes.c_int), ("energy", ctypes.c_void_p), ("qp_aq_offset", ctypes.c_void_p), ("inv_qscale", ctypes.c_void_p),
+                ("avg_blocks", ctypes.c_int)]
 
 
-def aq_offsets(depth, qg_size, aq_mode, aq_strength, energy):
-    """Host side of the AQ pass (x265hip_aq_offsets): energy = numpy uint32 [blocks]; returns (qp_aq_offset float64, inv_qscale int32)."""
+def aq_average_blocks(width, height, qg_size):
+    """What calcAdaptiveQuantFrame divides the frame averages of AQ modes 2 / 3 by (slicetype.cpp:453,460): with --qg-size 8 the size of the
+    Lowres arrays, 4 * the 8x8 blocks of the half-resolution picture - not always the blocks the loop visits."""
+    if qg_size == 8:
+        return 4 * ((width // 2 + 7) >> 3) * ((height // 2 + 7) >> 3)
+    return ((width + qg_size - 1) // qg_size) * ((height + qg_size - 1) // qg_size)
+
+
+def aq_offsets(depth, qg_size, aq_mode, aq_strength, energy, avg_blocks=0):
+    """Host side of the AQ pass (x265hip_aq_offsets): energy = numpy uint32 [blocks]; returns (qp_aq_offset float64, inv_qscale int32).
+    avg_blocks: aq_average_blocks of the picture (0 = the number of energies)."""
     import numpy as np
     e = np.ascontiguousarray(energy, dtype=np.uint32)
     qp, inv = np.zeros(len(e), np.float64), np.zeros(len(e), np.int32)
     p = AqOffsetsParams()
-    p.depth, p.qg_size, p.aq_mode, p.aq_strength, p.nblocks = depth, qg_size, aq_mode, float(aq_strength), len(e)
+    p.depth, p.qg_size, p.aq_mode, p.aq_strength, p.nblocks, p.avg_blocks = depth, qg_size, aq_mode, float(aq_strength), len(e), int(avg_blocks)
     p.energy, p.qp_aq_offset, p.inv_qscale = e.ctypes.data, qp.ctypes.data, inv.ctypes.data
     f = lib().x265hip_aq_offsets
     f.argtypes = [ctypes.POINTER(AqOffsetsParams)]

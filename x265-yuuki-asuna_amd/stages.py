@@ -506,7 +506,7 @@ class AdaptiveQuant:
         hipabi.aq_energy(self.depth, y.t, y.stride, y.org, self.width, self.height, self.qg, self.energy, self.wp, cb, cr, stride_c, org_c)
         energy = self.energy.cpu().numpy().view(np.uint32)
         wp = self.wp.cpu().numpy().view(np.uint64)
-        qp, inv = hipabi.aq_offsets(self.depth, self.qg, self.mode, self.strength, energy)
+        qp, inv = hipabi.aq_offsets(self.depth, self.qg, self.mode, self.strength, energy, hipabi.aq_average_blocks(self.width, self.height, self.qg))
         wp_sum = [int(v) for v in wp[:3]]
         wp_ssd = [int(v) for v in wp[3:]]
         if self.weightp:                                             # the final normalisation, slicetype.cpp:662-675

@@ -1943,6 +1943,75 @@ typedef struct x265hip_b_merge_decide_params
 } x265hip_b_merge_decide_params;
 int x265hip_b_merge_decide(const x265hip_b_merge_decide_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The temporal merge candidate (csrc/col_field.h): what the two walks above leave out under --no-temporal-mvp.  With temporal MVP (the
+ * reference's default) CUData::getInterMergeCandidates has, after B2 and before the combined and zero candidates, one candidate taken
+ * from the collocated picture's motion field (common/cudata.cpp:1594-1650, getColMVP :1968-2000, scaleMvByPOCDist :2030-2045, scaleMv
+ * :104-110).
+ *
+ * x265hip_col_field_build compresses a coded picture's motion to what getColMVP can see (TMVP_UNIT_MASK = 0xF0): one entry per 16x16
+ * luma unit, 16 per CTU in raster order inside the CTU.
+ *   mv        : the picture's final motion, mv_out-style records [ctu*85] {cost, qx | qy << 16}, unclipped; the level's slots are read
+ *   intra     : optional uint8 [ctu][blocks]: non-zero = the block is intra and has no motion
+ *   ref_idx   : optional int8 [ctu][blocks]: the block's list-0 reference index (negative: no list-0 motion)
+ *   poc_delta : colPOC - colRefPOC per reference index; without ref_idx entry 0 is used for every block
+ *   col_mv    : DEVICE int32 [ctu][16] out: the packed vector (0 where col_delta is 0)
+ *   col_delta : DEVICE int16 [ctu][16] out: the POC distance of that vector; 0 = no motion here (getColMVP returns false)
+ * Unit (ux, uy) takes the motion of the block that covers sample (16 ux, 16 uy): at level 0 the upper-left 8x8 of the four, at level 1 the
+ * block itself, at level 2 the 32x32 block around it.  Only list 0 of the collocated picture is modelled: the collocated picture of every
+ * step here is a P or I anchor, because B pictures are not referenced.  One thread per unit, one launch, capturable.
+ * Refused (X265HIP_EINVAL, before any device call): NULL operands (intra / ref_idx are optional), depth not 8 / 10 / 12, level outside
+ * 0..2, sizes that are no multiples of 64, a poc_delta that is 0 or outside -32768..32767 for an index that can be read (entry 0
+ * without ref_idx, all eight with it). */
+typedef struct x265hip_col_field_params
+{
+    int depth, width, height, level;
+    const void* mv;
+    const uint8_t* intra; const int8_t* ref_idx;
+    int poc_delta[8];
+    int32_t* col_mv; int16_t* col_delta;
+} x265hip_col_field_params;
+int x265hip_col_field_build(const x265hip_col_field_params* p, void* stream);
+
+/* x265hip_merge_decide with the temporal candidate: everything of x265hip_merge_decide, and between B2 and the zero candidates
+ *   position : the bottom-right sample (x0 + N, y0 + N), tried only if x0 + N < width && y0 + N < height (:1601-1602) and if it does not
+ *              lie below the CTU ((y0 % 64) + N < 64); in this CTU if (x0 % 64) + N < 64, otherwise in CTU ctu + 1 at unit column 0
+ *              (:1609-1622).  A block in the CTU's last row, or in its lower right corner, has no such try.  Where the try is absent or
+ *              returns false, the centre (x0 + N / 2, y0 + N / 2) of this CTU (:1630-1634).  Both are masked to their 16x16 unit.
+ *   vector   : getColMVP is false where col_delta == 0, otherwise scaleMvByPOCDist(col_mv, cur_delta, col_delta): unchanged where the
+ *              distances are equal; else tdb = clip(-128, 127, cur_delta), tdd = clip(-128, 127, col_delta), x = (0x4000 + abs(tdd / 2))
+ *              / tdd (C divisions), scale = clip(-4096, 4095, (tdb * x + 32) >> 6), each component clip(-32768, 32767, (scale * v + 127 +
+ *              (scale * v < 0)) >> 8).
+ *   list     : the candidate is not pruned against any spatial one (equal to A1 it is kept and priced with its own index); it is
+ *              appended only while count < max_merge, and if it fills the last slot no zero candidate follows (:1647-1648).
+ * The block's mv_out holds the unclipped scaled vector; clipMv bounds what the prediction reads, as for every other candidate.
+ * cur_delta = curPOC - refPOC, not 0.  col_mv / col_delta: a field of x265hip_col_field_build for a picture of the same size (DEVICE); both
+ * NULL = no collocated field: the entry then writes what x265hip_merge_decide writes.
+ * Refused: what x265hip_merge_decide refuses; one of col_mv / col_delta NULL and the other not; cur_delta 0 or outside -32768..32767. */
+typedef struct x265hip_merge_decide_col_params
+{
+    x265hip_merge_decide_params base;
+    const int32_t* col_mv; const int16_t* col_delta;
+    int cur_delta;
+} x265hip_merge_decide_col_params;
+int x265hip_merge_decide_col(const x265hip_merge_decide_col_params* p, void* stream);
+
+/* x265hip_b_merge_decide with the temporal candidate.  For a B slice here m_bCheckLDC and m_colFromL0Flag are false (dpb.cpp:193-195):
+ * the collocated picture is L1[0], and both lists read list 0 of it, so the availability (bottom-right, then centre, as above) falls out
+ * equal for both lists.  The candidate is {dir 3, mv0 = scale(col, cur_delta0, col_delta), mv1 = scale(col, cur_delta1, col_delta)},
+ * refIdx 0 in both lists; it precedes the combined candidates, cutoff = count * (count - 1) counts it, it is a source of combined pairs
+ * like any other entry, and :1670 applies to pairs built from it unchanged.
+ * cur_delta0 = curPOC - POC(L0[0]), cur_delta1 = curPOC - POC(L1[0]) (negative for a later anchor), neither 0.
+ * Refused: what x265hip_b_merge_decide refuses; one of col_mv / col_delta NULL and the other not; a cur_delta 0 or outside
+ * -32768..32767. */
+typedef struct x265hip_b_merge_decide_col_params
+{
+    x265hip_b_merge_decide_params base;
+    const int32_t* col_mv; const int16_t* col_delta;
+    int cur_delta0, cur_delta1;
+} x265hip_b_merge_decide_col_params;
+int x265hip_b_merge_decide_col(const x265hip_b_merge_decide_col_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,423 @@
+"""CPU-only checks of the temporal merge candidate (x265hip_col_field_build, x265hip_merge_decide_col, x265hip_b_merge_decide_col):
+declaration, export, record layout and argument validation of the three entries, and the expectation the GPU tests compare against
+(tests/tmvp_expect.py): the scaling values, hand-worked positions and lists written out from the statements of cudata.cpp, the compression
+rule of the collocated field, what the cases of tests/tmvp_cases.py reach (the coverage condition), that every mutation of the restated
+walks changes the expectation of a counted number of cases, and that without a collocated field the restated walks give what
+merge_expect / bmerge_expect give."""
+import ctypes
+import importlib
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import bmerge_cases as BC
+import bmerge_expect as BM
+import intra_expect as IE
+import merge_cases as MC
+import merge_expect as ME
+import tmvp_cases as C
+import tmvp_expect as TX
+
+A = importlib.import_module("x265-yuuki-asuna_amd.hipabi")
+EINVAL, ENODEV = -2, -1
+P_KEYS = ("merge", "merge_idx", "mv_out", "mv_pred", "cost", "best")
+
+
+def _layout(repo_root, tmp_path, cname, rec, paths):
+    """sizeof and offsetof of the C struct against the ctypes class; paths: [(C member path, ctypes offset)]."""
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "x265hip.h"', 'int main(void) {', f'  printf(". %zu\\n", sizeof({cname}));']
+    lines += [f'  printf("{p} %zu\\n", offsetof({cname}, {p}));' for p, _ in paths]
+    lines += ['  return 0;', '}']
+    src = tmp_path / f"{cname}.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / cname
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(repo_root, "include"), str(src), "-o", str(exe)], check=True)
+    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n") if line)
+    assert int(out["."]) == ctypes.sizeof(rec), (cname, out["."], ctypes.sizeof(rec))
+    for p, off in paths:
+        assert int(out[p]) == off, f"{cname}.{p}: C says {out[p]}, ctypes says {off}"
+    return int(out["."])
+
+
+def test_the_entries_are_declared_exported_and_laid_out_like_the_header(repo_root, tmp_path):
+    hdr = open(os.path.join(repo_root, "include", "x265hip.h")).read()
+    for name, params in (("col_field_build", "col_field"), ("merge_decide_col", "merge_decide_col"), ("b_merge_decide_col", "b_merge_decide_col")):
+        assert re.search(rf"int x265hip_{name}\(const x265hip_{params}_params\* p, void\* stream\);", hdr)
+        assert f"x265hip_{name}" in A.exported_symbols() and hasattr(A.lib(), f"x265hip_{name}") and callable(getattr(A, name))
+    own = lambda rec: [(f, getattr(rec, f).offset) for f, _ in rec._fields_]
+    _layout(repo_root, tmp_path, "x265hip_col_field_params", A.ColFieldParams, own(A.ColFieldParams))
+    for cname, rec, base in (("x265hip_merge_decide_col_params", A.MergeDecideColParams, A.MergeDecideParams),
+                             ("x265hip_b_merge_decide_col_params", A.BMergeDecideColParams, A.BMergeDecideParams)):
+        assert rec._fields_[0] == ("base", base) and rec.base.offset == 0
+        _layout(repo_root, tmp_path, cname, rec, own(rec) + [(f"base.{f}", getattr(base, f).offset) for f, _ in base._fields_])
+    # the two records of the entries without the candidate are what they were
+    assert _layout(repo_root, tmp_path, "x265hip_merge_decide_params", A.MergeDecideParams, own(A.MergeDecideParams)) == 152
+    assert _layout(repo_root, tmp_path, "x265hip_b_merge_decide_params", A.BMergeDecideParams, own(A.BMergeDecideParams)) == 224
+    assert len(A.MergeDecideParams._fields_) == 22 and len(A.BMergeDecideParams._fields_) == 32
+    assert A.MergeDecideParams.best.offset == 144 and A.BMergeDecideParams.best.offset == 216
+
+
+def _p_base(p):
+    p.depth, p.width, p.height, p.level, p.qp, p.lambda8, p.max_merge = 8, 128, 64, 2, 30, 1024, 3
+    p.fenc, p.fenc_stride, p.fref, p.fref_stride = 0x10000, 320, 0x20000, 320
+    p.mv, p.inter_cost, p.inter_cost_stride = 0x30000, 0x40000, 2
+    p.merge, p.merge_idx, p.mv_out, p.mv_pred, p.cost, p.best = 0x50000, 0x60000, 0x70000, 0x80000, 0x90000, 0xa0000
+
+
+def _b_base(p):
+    p.depth, p.width, p.height, p.level, p.qp, p.lambda8, p.max_merge = 8, 128, 64, 2, 30, 1024, 3
+    p.ref_id0, p.ref_id1 = 0, 1
+    p.fenc, p.fenc_stride, p.fref0, p.fref1, p.fref_stride = 0x10000, 320, 0x20000, 0x28000, 320
+    p.dir_in, p.mv0, p.mv1, p.inter_cost, p.inter_cost_stride = 0x2f000, 0x30000, 0x38000, 0x40000, 4
+    p.merge, p.merge_idx, p.dir = 0x50000, 0x58000, 0x5c000
+    p.mv0_out, p.mv1_out, p.mv0_pred, p.mv1_pred, p.cost, p.best = 0x70000, 0x78000, 0x80000, 0x88000, 0x90000, 0xa0000
+
+
+def _refusals(f, make, required, base_of):
+    """What both _col entries refuse alike; make() -> a valid record; base_of(record) -> the wrapped record."""
+    import torch
+
+    def bad(outer=None, **kw):
+        p = make()
+        for k, v in kw.items():
+            setattr(base_of(p), k, v)
+        for k, v in (outer or {}).items():
+            setattr(p, k, v)
+        return f(ctypes.byref(p), None)
+    assert f(None, None) == EINVAL
+    for req in required:
+        assert bad(**{req: None}) == EINVAL, req
+    for depth in (0, 9, 11, 16):
+        assert bad(depth=depth) == EINVAL
+    for level in (-1, 3):
+        assert bad(level=level) == EINVAL
+    for k, v in (("width", 100), ("height", 32), ("width", 0), ("height", -64), ("fenc_stride", 127), ("fref_stride", 64), ("lambda8", -1),
+                 ("lambda8", (1 << 24) + 1), ("qp", 52), ("qp", -1), ("inter_cost_stride", 0), ("max_merge", 0), ("max_merge", 6)):
+        assert bad(**{k: v}) == EINVAL, (k, v)
+    assert b"_col: max_merge" in A.lib().x265hip_last_error()
+    assert bad(mv0_out=0x30000) == EINVAL if "mv0_out" in required else bad(mv_out=0x30000) == EINVAL
+    assert b"alias" in A.lib().x265hip_last_error()
+    assert bad(outer=dict(col_mv=None)) == EINVAL and bad(outer=dict(col_delta=None)) == EINVAL
+    assert b"go together" in A.lib().x265hip_last_error()
+    deltas = [k for k in ("cur_delta", "cur_delta0", "cur_delta1") if hasattr(make(), k)]
+    for k in deltas:
+        for v in (0, 32768, -32769):
+            assert bad(outer={k: v}) == EINVAL, (k, v)
+        assert k.encode() in A.lib().x265hip_last_error()
+    if not torch.cuda.is_available():
+        assert bad() == ENODEV and bad(outer=dict(col_mv=None, col_delta=None)) == ENODEV
+        assert bad(outer={k: 32767 for k in deltas}) == ENODEV and bad(outer={k: -32768 for k in deltas}) == ENODEV
+
+
+def test_the_col_entries_validate_before_touching_a_device():
+    def p_make():
+        p = A.MergeDecideColParams()
+        _p_base(p.base)
+        p.col_mv, p.col_delta, p.cur_delta = 0xb0000, 0xc0000, 4
+        return p
+
+    def b_make():
+        p = A.BMergeDecideColParams()
+        _b_base(p.base)
+        p.col_mv, p.col_delta, p.cur_delta0, p.cur_delta1 = 0xb0000, 0xc0000, 2, -2
+        return p
+    f = A.lib().x265hip_merge_decide_col
+    f.argtypes = [ctypes.POINTER(A.MergeDecideColParams), ctypes.c_void_p]
+    _refusals(f, p_make, ("fenc", "fref", "mv", "inter_cost", "merge", "merge_idx", "mv_out", "mv_pred", "cost"), lambda p: p.base)
+    g = A.lib().x265hip_b_merge_decide_col
+    g.argtypes = [ctypes.POINTER(A.BMergeDecideColParams), ctypes.c_void_p]
+    _refusals(g, b_make, ("fenc", "fref0", "fref1", "dir_in", "mv0", "mv1", "inter_cost", "merge", "merge_idx", "dir", "mv0_out", "mv1_out", "mv0_pred",
+                          "mv1_pred", "cost"), lambda p: p.base)
+
+
+def test_col_field_build_validates_before_touching_a_device():
+    import torch
+    f = A.lib().x265hip_col_field_build
+    f.argtypes = [ctypes.POINTER(A.ColFieldParams), ctypes.c_void_p]
+    assert f(None, None) == EINVAL
+
+    def bad(deltas=None, **kw):
+        p = A.ColFieldParams()
+        p.depth, p.width, p.height, p.level, p.mv, p.col_mv, p.col_delta = 8, 128, 64, 1, 0x10000, 0x20000, 0x30000
+        for i in range(8):
+            p.poc_delta[i] = 4
+        for k, v in kw.items():
+            setattr(p, k, v)
+        for i, v in (deltas or {}).items():
+            p.poc_delta[i] = v
+        return f(ctypes.byref(p), None)
+    for req in ("mv", "col_mv", "col_delta"):
+        assert bad(**{req: None}) == EINVAL, req
+    for k, v in (("depth", 9), ("depth", 0), ("level", -1), ("level", 3), ("width", 100), ("height", 0), ("width", -64)):
+        assert bad(**{k: v}) == EINVAL, (k, v)
+    for v in (0, 32768, -32769):
+        assert bad(deltas={0: v}) == EINVAL
+        assert bad(deltas={5: v}, ref_idx=0x40000) == EINVAL                 # with ref_idx every entry can be read
+    assert b"poc_delta" in A.lib().x265hip_last_error()
+    if not torch.cuda.is_available():
+        assert bad() == ENODEV and bad(intra=0x50000, ref_idx=0x40000) == ENODEV
+        assert bad(deltas={5: 0}) == ENODEV                                  # without ref_idx only entry 0 is read
+        assert bad(deltas={0: 32767}) == ENODEV and bad(deltas={0: -32768}) == ENODEV
+
+
+# (cur_delta, col_delta) -> the scale (None = the vector is returned as it is), and component checks: computed from the statements of
+# scaleMvByPOCDist (cudata.cpp:2030-2045) and scaleMv (:104-110)
+SCALES = {(4, 4): (None, {5: 5, -32768: -32768}),
+          (2, 4): (128, {5: 2, -5: -2, 1: 0, -1: 0, 32767: 16383, -32768: -16384}),
+          (-2, 4): (-128, {5: -2, -5: 2, -32768: 16384}),
+          (2, -4): (-128, {}),
+          (4, -4): (-256, {32767: -32767, -32768: 32767}),
+          (4, 2): (512, {32767: 32767}),
+          (8, 4): (512, {32767: 32767}),
+          (1, 3): (85, {100: 33, -3000: -996}),
+          (5, 7): (183, {3000: 2145, -32768: -23424}),
+          (3, 1): (768, {}),
+          (17, 1): (4095, {3000: 32767, -3000: -32768}),
+          (-17, 1): (-4096, {3000: -32768, -3000: 32767}),
+          (200, 3): (4095, {}),
+          (1, 200): (2, {32767: 256, -32768: -256})}
+
+
+def test_scaling_values_are_the_reference_statements():
+    for (cur, col), (scale, comps) in SCALES.items():
+        assert TX.scale_factor(cur, col) == scale, (cur, col)
+        for v, want in comps.items():
+            got = TX.scale_mv(ME.pack(v, -v if v > -32768 else 0), cur, col)
+            assert ME.unpack(got)[0] == want, (cur, col, v, ME.unpack(got))
+            assert ME.unpack(TX.scale_mv(ME.pack(0, v), cur, col)) == (0, want)
+    # the packed word round-trips -32768 in both halves
+    assert ME.unpack(ME.pack(-32768, -32768)) == (-32768, -32768) and ME.unpack(ME.pack(32767, -32768)) == (32767, -32768)
+    # C's division truncates toward zero; Python's // does not - the two differ for a negative tdd
+    assert TX.cdiv(-7, 2) == -3 and TX.cdiv(7, -2) == -3 and TX.cdiv(-7, -2) == 3 and -7 // 2 == -4
+    assert TX.scale_factor(6, -7) == -219 and TX.scale_factor(6, -7, "floor_division") != -219
+
+
+# (level, x0, y0) -> (kind, (ctu, unit) of the bottom-right try or None, (ctu, unit) of the centre), worked out by hand for 192x128 (3 x 2
+# CTUs; units in raster order inside the CTU)
+POSITIONS = {
+    (0, 8, 8): ("rb_in_ctu", (0, 5), (0, 0)),                        # sample (16, 16) / (12, 12)
+    (0, 56, 8): ("rb_in_right_ctu", (1, 4), (0, 3)),                 # (64, 16): CTU 1, unit column 0, unit row 1 / (60, 12)
+    (0, 184, 8): ("rb_outside_picture", None, (2, 3)),               # x0 + 8 = 192 / (188, 12)
+    (0, 8, 56): ("rb_absent_last_ctu_row", None, (0, 12)),           # (16, 64) lies below the CTU though inside the picture / (12, 60)
+    (0, 56, 56): ("rb_absent_last_ctu_row", None, (0, 15)),          # the CTU's lower right corner
+    (0, 8, 120): ("rb_outside_picture", None, (3, 12)),              # y0 + 8 = 128 / (12, 124) in CTU 3
+    (1, 16, 16): ("rb_in_ctu", (0, 10), (0, 5)),                     # (32, 32) / (24, 24)
+    (1, 48, 16): ("rb_in_right_ctu", (1, 8), (0, 7)),                # (64, 32): CTU 1, column 0, one unit row down / (56, 24)
+    (1, 176, 16): ("rb_outside_picture", None, (2, 7)),
+    (1, 16, 48): ("rb_absent_last_ctu_row", None, (0, 13)),
+    (1, 48, 48): ("rb_absent_last_ctu_row", None, (0, 15)),
+    (1, 16, 112): ("rb_outside_picture", None, (3, 13)),
+    (2, 0, 0): ("rb_in_ctu", (0, 10), (0, 5)),                       # (32, 32) / (16, 16)
+    (2, 32, 0): ("rb_in_right_ctu", (1, 8), (0, 7)),                 # (64, 32): CTU 1, column 0, two unit rows down / (48, 16)
+    (2, 160, 0): ("rb_outside_picture", None, (2, 7)),
+    (2, 0, 32): ("rb_absent_last_ctu_row", None, (0, 13)),
+    (2, 32, 32): ("rb_absent_last_ctu_row", None, (0, 15)),
+    (2, 0, 96): ("rb_outside_picture", None, (3, 13)),
+    (1, 112, 80): ("rb_in_right_ctu", (5, 8), (4, 7)),               # CTU (1, 1) -> CTU 5 = (2, 1)
+}
+
+
+def test_hand_worked_positions():
+    unit = lambda p: None if p is None else ((p[1] // 64) * 3 + p[0] // 64, ((p[1] % 64) >> 4) * 4 + ((p[0] % 64) >> 4))
+    for (level, x0, y0), (kind, rb, centre) in POSITIONS.items():
+        k, p, c = TX.positions(level, 192, 128, x0, y0)
+        assert (k, unit(p), unit(c)) == (kind, rb, centre), (level, x0, y0)
+    # getColMVP reads the unit's entry whichever cell the sample lies in, and nothing where the distance is 0
+    src = TX.ColSource(192, 128)
+    src.mv[:], src.delta[:] = np.arange(16 * 24).reshape(16, 24), 4
+    src.delta[2, 4] = 0
+    assert src.read(24, 8) == (2, 4) and src.read(31, 15) == (2, 4) and src.read(24, 8, masked=False) == (24 + 3, 4)
+    assert src.read(32, 16) is None and src.read(47, 31) is None and src.read(40, 24, masked=False) == (3 * 24 + 5, 4)
+    mv, dl = src.unit_field()
+    assert mv[5] == 2 * 24 + 2 and dl[5] == 4 and mv[6] == 0 and dl[6] == 0 and mv[16 + 0] == 8 and mv[3 * 16 + 15] == (8 + 6) * 24 + 6
+    # the try, then the centre
+    assert TX.collocated(src, 1, 16, 0) == (2, 4, "rb_in_ctu", True)                                                           # (32, 16) is intra: the centre (24, 8)
+    assert TX.collocated(src, 1, 16, 0, "centre_first") == (2, 4, "rb_in_ctu", False)
+    assert TX.collocated(src, 1, 0, 0) == (2 * 24 + 2, 4, "rb_in_ctu", False)                                                  # (16, 16): unit (1, 1)
+    src.delta[2, 2] = 0
+    assert TX.collocated(src, 1, 0, 0) == (0, 4, "rb_in_ctu", True)                                                            # the centre (8, 8): unit (0, 0)
+    src.delta[0, 0] = 0
+    assert TX.collocated(src, 1, 0, 0) == (None, 0, "rb_in_ctu", False)
+
+
+def test_hand_worked_lists_of_a_p_slice():
+    """Written out from cudata.cpp:1495-1650, 1687-1709."""
+    a, b, c, d, e, t = (ME.pack(*v) for v in ((4, 0), (0, 8), (-12, 3), (7, 7), (-1, -1), (9, -9)))
+    L = lambda nb, mm, tv, mut=None: [m for m, _ in TX.candidate_list_p(nb, mm, tv, mut)[0]]
+    O = lambda nb, mm, tv: [o for _, o in TX.candidate_list_p(nb, mm, tv)[0]]
+    flags = lambda nb, mm, tv: {k for k, v in TX.candidate_list_p(nb, mm, tv)[1].items() if v}
+    none = dict(A1=None, B1=None, B0=None, A0=None, B2=None)
+    full = dict(A1=a, B1=b, B0=c, A0=d, B2=e)
+    # the temporal candidate after B2 (:1594), and filling the last slot: no zero candidate behind it (:1647-1648)
+    assert L(dict(full, A0=None), 5, t) == [a, b, c, e, t] and O(dict(full, A0=None), 5, t)[3:] == ["B2", "temporal"]
+    assert flags(dict(full, A0=None), 5, t) == {"temporal_present", "temporal_fills_last_slot"}
+    assert L(dict(full, A0=None), 5, t, "temporal_before_b2") == [a, b, c, t, 0]           # in front of B2 it would be the fourth: B2 dropped
+    assert L(dict(none, A1=a, B1=b, B2=e), 5, t) == [a, b, e, t, 0] and L(dict(none, A1=a, B1=b, B2=e), 5, t, "temporal_before_b2") == [a, b, t, e, 0]
+    assert L(dict(full, A0=None), 5, t, "zero_fill_after_full") == [a, b, c, e, 0]
+    # after four spatial candidates B2 is not looked at; the temporal one still is
+    assert L(full, 5, t) == [a, b, c, d, t]
+    # before the zero candidates
+    assert L(dict(none, A1=a, B1=b), 5, t) == [a, b, t, 0, 0] and L(none, 3, t) == [t, 0, 0] and O(none, 2, t) == ["temporal", "zero"]
+    # not pruned against any spatial candidate: equal to A1 it is kept and has its own index
+    assert L(dict(none, A1=a), 3, a) == [a, a, 0] and "temporal_equals_spatial_kept" in flags(dict(none, A1=a), 3, a)
+    assert L(dict(none, A1=a), 3, a, "temporal_pruned_against_a1") == [a, 0, 0]
+    assert L(dict(none, A1=a, B1=b), 3, b) == [a, b, b]
+    # cut because count == max_merge in front of it (:1508, :1530, :1549, :1568, :1590)
+    assert L(dict(none, A1=a, B1=b, B0=c), 3, t) == [a, b, c] and flags(dict(none, A1=a, B1=b, B0=c), 3, t) == {"temporal_cut_at_max"}
+    assert L(dict(none, A1=a), 1, t) == [a] and L(none, 1, t) == [t]
+    # both positions without motion: the list of merge_expect
+    for nb in (none, full, dict(full, A0=None), dict(none, A1=0, B1=a)):
+        for mm in (1, 2, 3, 5):
+            assert L(nb, mm, None) == [m for m, _ in ME.candidate_list(nb, mm)[0]] and not flags(nb, mm, None)
+    # a temporal vector of (0, 0) is a candidate like any other
+    assert L(dict(none, A1=a), 3, 0) == [a, 0, 0] and O(dict(none, A1=a), 3, 0) == ["A1", "temporal", "zero"]
+
+
+def test_hand_worked_lists_of_a_b_slice():
+    """Written out from cudata.cpp:1594-1709 with isInterB."""
+    a, b, t0, t1 = (ME.pack(*v) for v in ((4, 0), (0, 8), (6, -2), (-6, 2)))
+    m = BM.motion
+    L = lambda nb, mm, tv, same=False, mut=None: [x[:3] for x, _ in TX.candidate_list_b(nb, mm, tv, same, mut)[0]]
+    O = lambda nb, mm, tv: [o for _, o in TX.candidate_list_b(nb, mm, tv)[0]]
+    none = dict(A1=None, B1=None, B0=None, A0=None, B2=None)
+    T = m(3, t0, t1)
+    two = dict(none, A1=m(1, a), B1=m(2, 0, b))
+    # dir 3 with two differently scaled vectors, in front of the combined candidates; cutoff = 3 * 2 counts it: pairs (0, 1) = A1 x B1,
+    # (1, 0) = B1 has no list 0, (0, 2) = A1 x temporal fills the list
+    assert L(two, 5, T) == [(1, a, 0), (2, 0, b), (3, t0, t1), (3, a, b), (3, a, t1)]
+    assert O(two, 5, T) == ["A1", "B1", "temporal", "combined", "combined_temporal"]
+    # without it cutoff = 2: one pair, then the zero candidates - the list of bmerge_expect
+    assert L(two, 5, None) == [(1, a, 0), (2, 0, b), (3, a, b), (3, 0, 0), (3, 0, 0)] == [x[:3] for x, _ in BM.candidate_list(two, 5)[0]]
+    # left out of the cutoff (2 pairs instead of 6) the third pair is never looked at
+    assert L(two, 5, T, mut="temporal_not_in_cutoff") == [(1, a, 0), (2, 0, b), (3, t0, t1), (3, a, b), (3, 0, 0)]
+    # one spatial candidate: cutoff = 2 * 1, pair (0, 1) = A1 list 0 x temporal list 1; (1, 0) needs A1's list 1, which it does not use
+    one = dict(none, A1=m(1, a))
+    assert L(one, 5, T) == [(1, a, 0), (3, t0, t1), (3, a, t1), (3, 0, 0), (3, 0, 0)]
+    assert L(dict(none, A1=m(2, 0, b)), 4, T) == [(2, 0, b), (3, t0, t1), (3, t0, b), (3, 0, 0)]
+    # :1670 applies to pairs built from it: both lists name one picture and the vectors are equal
+    assert L(one, 5, m(3, t0, a), same=True) == [(1, a, 0), (3, t0, a), (3, 0, 0), (3, 0, 0), (3, 0, 0)]
+    assert L(one, 5, m(3, t0, a), same=False)[2] == (3, a, a)
+    # filling the last slot: neither combined nor zero candidates follow; cut when the spatial candidates fill the list
+    assert L(two, 3, T) == [(1, a, 0), (2, 0, b), (3, t0, t1)] and L(two, 2, T) == [(1, a, 0), (2, 0, b)]
+    fl = TX.candidate_list_b(two, 2, T)[1]
+    assert fl["temporal_cut_at_max"] and not fl["temporal_present"]
+    # hasEqualMotion needs equal directions: a dir-3 temporal candidate never equals a single-list neighbour
+    assert not TX.candidate_list_b(dict(none, A1=m(1, t0)), 3, T)[1]["temporal_equals_spatial_kept"]
+    assert TX.candidate_list_b(dict(none, A1=m(3, t0, t1)), 3, T)[1]["temporal_equals_spatial_kept"]
+    # the two lists' vectors of the candidate: one collocated vector, one scale per list
+    assert (TX.scale_mv(ME.pack(12, -4), 2, 4), TX.scale_mv(ME.pack(12, -4), -2, 4)) == (t0, t1)
+
+
+@pytest.mark.parametrize("level", [0, 1, 2])
+def test_compression_rule_of_the_collocated_field(level):
+    """Unit (ux, uy) takes the motion of the block that covers sample (16 ux, 16 uy)."""
+    nctu, nblk, lbase = 6, 64 >> (2 * level), (0, 64, 80)[level]
+    mv = np.zeros((nctu * 85, 2), np.int32)
+    mv[:, 0], mv[:, 1] = -7, np.arange(nctu * 85) * 65537 + 11                      # every slot its own word; cost words are not read
+    col_mv, col_delta = TX.compress(level, 192, 128, mv, 3)
+    assert (col_delta == 3).all()
+    z_of_unit = {0: {0: 0, 1: 4, 4: 8, 5: 12, 15: 60, 3: 20}, 1: {0: 0, 1: 1, 4: 2, 5: 3, 15: 15, 10: 12},
+                 2: {0: 0, 1: 0, 4: 0, 5: 0, 2: 1, 7: 1, 8: 2, 13: 2, 10: 3, 15: 3}}[level]
+    for ctu in (0, 4):
+        for u, z in z_of_unit.items():
+            assert col_mv[ctu * 16 + u] == mv[ctu * 85 + lbase + z, 1], (level, ctu, u)
+    # intra blocks and blocks without a list-0 reference have no motion; ref_idx selects the distance
+    rng = np.random.default_rng(5)
+    intra = (rng.integers(0, 3, nctu * nblk) == 0).astype(np.uint8)
+    ref = rng.integers(-1, 3, nctu * nblk).astype(np.int8)                           # -1, 0, 1, 2
+    deltas = [4, -2, 9, 1, 1, 1, 1, 32767]
+    cm, cd = TX.compress(level, 192, 128, mv, deltas, intra=intra, ref_idx=ref)
+    n = 8 << level
+    for i in range(nctu * 16):
+        ctu, u = divmod(i, 16)
+        blk = ctu * nblk + IE.zindex(16 * (u % 4) // n, 16 * (u // 4) // n)
+        if intra[blk] or ref[blk] < 0:
+            assert (cm[i], cd[i]) == (0, 0)
+        else:
+            assert cd[i] == deltas[ref[blk]] and cm[i] == col_mv[i]
+    assert (cd == 0).any() and (cd == -2).any() and (cd == 9).any()
+    # a field the device built, read back as a source, is the field
+    src = TX.source_of_units(192, 128, cm, cd)
+    assert all(np.array_equal(x, y) for x, y in zip(src.unit_field(), (cm, cd)))
+
+
+# the four position masks are geometry: blocks of 192x128 per level
+GEOMETRY_COUNTS = {0: dict(rb_in_right_ctu=28, rb_absent_last_ctu_row=23, rb_outside_picture=39, rb_in_ctu=294, total=384),
+                   1: dict(rb_in_right_ctu=12, rb_absent_last_ctu_row=11, rb_outside_picture=19, rb_in_ctu=54, total=96),
+                   2: dict(rb_in_right_ctu=4, rb_absent_last_ctu_row=5, rb_outside_picture=9, rb_in_ctu=6, total=24)}
+
+
+@pytest.mark.parametrize("slice_type", ["P", "B"])
+@pytest.mark.parametrize("level", [0, 1, 2])
+def test_the_cases_reach_every_outcome(level, slice_type):
+    """The coverage condition: at each level every mask holds for at least 3 % of the blocks of at least one 8-bit 192x128 case; the four
+    position masks hold for exactly the blocks geometry gives them, in every case with a field."""
+    cases, names = (C.P_COVER, TX.P_MASKS) if slice_type == "P" else (C.B_COVER, TX.B_MASKS)
+    best = {k: (0.0, None) for k in names}
+    for c in cases:
+        if c.base.level != level:
+            continue
+        masks = C.expectation(c)["e"]["masks"]
+        assert set(masks) == set(names)
+        for k, m in masks.items():
+            if float(m.mean()) > best[k][0]:
+                best[k] = (float(m.mean()), c.id)
+        want = GEOMETRY_COUNTS[level]
+        assert len(masks["rb_in_ctu"]) == want["total"]
+        for k in ("rb_in_right_ctu", "rb_absent_last_ctu_row", "rb_outside_picture", "rb_in_ctu"):
+            assert int(masks[k].sum()) == want[k], (c.id, k)
+    for k, (share, cid) in best.items():
+        print(slice_type, level, k, round(share, 4), cid)
+    print("smallest share of a", slice_type, "slice at level", level, min((s, k) for k, (s, _) in best.items()))
+    for k, (share, cid) in best.items():
+        assert share >= 0.03, (slice_type, level, k, share)
+
+
+# cases of P_COVER (39) / B_COVER (33) whose expectation a mutation of the restated walk changes: the numbers of DESIGN.md section 21
+P_MUTATION_COUNTS = {"temporal_before_b2": 18, "temporal_pruned_against_a1": 6, "centre_first": 17, "rb_below_ctu_allowed": 8, "rb_from_this_ctu": 16,
+                     "no_unit_mask": 19, "no_scaling": 21, "floor_division": 3, "no_negative_rounding": 6, "zero_fill_after_full": 25}
+B_MUTATION_COUNTS = {"temporal_before_b2": 9, "temporal_pruned_against_a1": 6, "centre_first": 12, "rb_below_ctu_allowed": 8, "rb_from_this_ctu": 8,
+                     "no_unit_mask": 16, "no_scaling": 30, "no_negative_rounding": 29, "zero_fill_after_full": 15, "one_scale_both_lists": 30,
+                     "temporal_not_in_cutoff": 17}
+
+
+@pytest.mark.parametrize("slice_type", ["P", "B"])
+def test_mutations_of_the_walks_change_the_counted_cases(slice_type):
+    """Each mutation - what a wrong kernel would compute - changes the expectation of exactly the counted number of cases, at least one
+    each.  `no_unit_mask` must change a level-0 case: only there do the two positions fall inside a unit."""
+    cases, muts, counts, keys = ((C.P_COVER, TX.P_MUTATIONS, P_MUTATION_COUNTS, P_KEYS) if slice_type == "P" else
+                                 (C.B_COVER, TX.B_MUTATIONS, B_MUTATION_COUNTS, BM.OUTPUTS))
+    assert set(counts) == set(muts)
+    for mut in muts:
+        hit = []
+        for c in cases:
+            want, got = C.expectation(c)["e"], C.run_stage(c, tmvp_mutation=mut)
+            if any(not np.array_equal(want[k], got[k]) for k in keys):
+                hit.append(c.id)
+        print(slice_type, mut, len(hit), "of", len(cases), hit)
+        assert hit and len(hit) == counts[mut], (mut, len(hit))
+        if mut == "no_unit_mask":
+            assert any("-l0-" in h for h in hit)
+        if mut in ("one_scale_both_lists", "temporal_not_in_cutoff"):
+            assert slice_type == "B"
+
+
+def test_without_a_field_the_restated_walks_are_the_walks_without_the_candidate():
+    """With the `none` field (and with no field at all) tmvp_expect's walks give, on every case of merge_cases.ALL_CASES and
+    bmerge_cases.ALL_CASES, exactly what merge_expect / bmerge_expect give."""
+    for c in MC.ALL_CASES:
+        want = MC.expectation(c)["e"]
+        tc = C.PCase(c.id, c, "none", 4, 4)
+        for col in (TX.ColSource(c.w, c.h), None):
+            got = C.run_stage(tc, col=col)
+            assert all(np.array_equal(want[k], got[k]) for k in P_KEYS + ("inter_cost",)), c.id
+            assert col is None or (got["masks"]["temporal_absent"].all() and not got["masks"]["temporal_present"].any())
+    for c in BC.ALL_CASES:
+        want = BC.expectation(c)["e"]
+        tc = C.BCase(c.id, c, "none", (2, -2), 4)
+        for col in (TX.ColSource(c.w, c.h), None):
+            got = C.run_stage(tc, col=col)
+            assert all(np.array_equal(want[k], got[k]) for k in BM.OUTPUTS + ("inter_cost",)), c.id

@@ -50,13 +50,16 @@ struct BMergeArgs
     int2* best;                         // optional [ctu][blocks]
     const int8_t* qpMap;                // optional: the luma plane of tu_qp
     const uint32_t* lambdaByQp;         // optional
+    const int32_t* colMv; const int16_t* colDelta; int curDelta[2];   // the COL instances only: the collocated field (col_field.h)
 };
 
 struct BMotion { int dir, mv0, mv1; };  // an unused list's vector is 0, so hasEqualMotion is equality of the three words
 
 __device__ __forceinline__ bool b_equal_motion(const BMotion& p, const BMotion& q) { return p.dir == q.dir && p.mv0 == q.mv0 && p.mv1 == q.mv1; }
 
-template <typename Px, int N>
+// COL: the list has the temporal candidate of col_field.h - {3, the collocated vector scaled for list 0, for list 1} - between B2 and the
+// combined candidates, which count it and pair it like any other entry (x265hip_b_merge_decide_col with a field)
+template <typename Px, int N, bool COL>
 __global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const int wave, const int cyLo)
 {
     constexpr int BPC = 64 / N, NPU = BPC * BPC, NB = Sa8dLds<N>::NB, BPR = 32 / N, BPP = sizeof(Px), FW = BPC + 2, FH = BPC + 1, FS = FH * FW;
@@ -67,6 +70,7 @@ __global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const
     __shared__ int sCand[3][5], sSlotOf[5], sSlot[3][5], sSlotSad[5], sSlots;
     __shared__ int2 sWinner[2][NPU];
     __shared__ int sWinnerDir[NPU], sInter[NPU], sLambda[NPU];
+    __shared__ int sTemporal[2][COL ? NPU : 1], sTemporalOk[COL ? NPU : 1];  // the block's collocated vector scaled per list / whether it has one
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int cyb = cyLo + (int)blockIdx.x, cxb = wave - 2 * cyb;
@@ -105,6 +109,16 @@ __global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const
         sWinner[1][z] = a.mv[1][(size_t)ctu * 85 + lbase + z];
         sInter[z] = a.interCost[((size_t)ctu * NPU + z) * a.interCostStride];
         sLambda[z] = block_lambda8(a.lambda8, a.lambdaByQp, a.qpMap, a.qp, a.depth, a.ctusW, (cxb * 64 + bxz * N) >> 3, (cyb * 64 + byz * N) >> 3);
+        if constexpr (COL)                                                  // another picture's finished field: off the chain as well
+        {
+            // m_bCheckLDC and m_colFromL0Flag are false (dpb.cpp:193-195): both lists read list 0 of the collocated picture, so the
+            // availability (bottom-right, then centre) falls out equal for both
+            int cmv = 0, cd = 0;
+            const bool ok = tmvp_collocated<N>(a.colMv, a.colDelta, ctu, cxb, cyb, a.ctusW, a.ctusH, bxz * N, byz * N, cmv, cd);
+            sTemporalOk[z] = ok ? 1 : 0;
+            sTemporal[0][z] = ok ? tmvp_scale_mv(cmv, a.curDelta[0], cd) : 0;
+            sTemporal[1][z] = ok ? tmvp_scale_mv(cmv, a.curDelta[1], cd) : 0;
+        }
     }
     __syncthreads();
 
@@ -141,9 +155,10 @@ __global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const
         if (count < num && avB0 && (!avB1 || !b_equal_motion(mB1, mB0))) put(mB0);                                   // :1537-1551
         if (count < num && avA0 && (!avA1 || !b_equal_motion(mA1, mA0))) put(mA0);                                   // :1556-1570
         if (count < num && count < 4 && avB2 && (!avA1 || !b_equal_motion(mA1, mB2)) && (!avB1 || !b_equal_motion(mB1, mB2))) put(mB2);   // :1573-1593
+        if constexpr (COL) { if (count < num && sTemporalOk[z]) put(BMotion{ 3, sTemporal[0][z], sTemporal[1][z] }); }   // :1594-1650: never pruned
         if (count < num)                                                                                             // :1652-1683
         {
-            const int cutoff = count * (count - 1);                   // from the spatial count, once
+            const int cutoff = count * (count - 1);                   // from the count in front of the combined candidates, once
             unsigned p0 = 0xEDC984u, p1 = 0xB73621u;
             for (int k = 0; k < cutoff && count < num; k++, p0 >>= 2, p1 >>= 2)
             {
@@ -270,18 +285,21 @@ static bool b_merge_records_alias(const int nctu, const x265hip_b_merge_decide_p
 
 } // namespace x265hip
 
-extern "C" int x265hip_b_merge_decide(const x265hip_b_merge_decide_params* p, void* stream)
+namespace x265hip {
+
+// both entries: colMv / colDelta NULL = the list without a temporal candidate
+static int b_merge_decide_run(const char* who, const x265hip_b_merge_decide_params* p, const int32_t* colMv, const int16_t* colDelta, const int curDelta0,
+                              const int curDelta1, void* stream)
 {
-    using namespace x265hip;
     // argument checks first: they need no device (at most 4 bits and lambda8 <= 2^24 keep the rate term below 2^19 and the cost inside int32)
-    if (decision_record_refused("b_merge_decide", p, !p || !p->fenc || !p->fref0 || !p->fref1 || !p->dir_in || !p->mv0 || !p->mv1 || !p->inter_cost || !p->merge ||
+    if (decision_record_refused(who, p, !p || !p->fenc || !p->fref0 || !p->fref1 || !p->dir_in || !p->mv0 || !p->mv1 || !p->inter_cost || !p->merge ||
                                 !p->merge_idx || !p->dir || !p->mv0_out || !p->mv1_out || !p->mv0_pred || !p->mv1_pred || !p->cost)) return X265HIP_EINVAL;
-    if (p->max_merge < 1 || p->max_merge > 5) { set_error("b_merge_decide: max_merge %d out of 1..5", p->max_merge); return X265HIP_EINVAL; }
-    if (inter_cost_stride_refused("b_merge_decide", p->inter_cost_stride)) return X265HIP_EINVAL;
+    if (p->max_merge < 1 || p->max_merge > 5) { set_error("%s: max_merge %d out of 1..5", who, p->max_merge); return X265HIP_EINVAL; }
+    if (inter_cost_stride_refused(who, p->inter_cost_stride)) return X265HIP_EINVAL;
     // the walk reads a block's inter winner from dir_in / mv0 / mv1 and its neighbours' final motion from dir / mv*_out: shared arrays would
     // change what a second run sees
     if (b_merge_records_alias((p->width / 64) * (p->height / 64), p))
-    { set_error("b_merge_decide: mv*_out / mv*_pred must not alias mv0 / mv1 or each other, nor dir dir_in"); return X265HIP_EINVAL; }
+    { set_error("%s: mv*_out / mv*_pred must not alias mv0 / mv1 or each other, nor dir dir_in", who); return X265HIP_EINVAL; }
     int rc = ensure_device();
     if (rc) return rc;
 
@@ -296,12 +314,33 @@ extern "C" int x265hip_b_merge_decide(const x265hip_b_merge_decide_params* p, vo
     a.merge = p->merge; a.mergeIdx = p->merge_idx; a.dir = p->dir; a.ref[0] = p->ref0; a.ref[1] = p->ref1;
     a.mvOut[0] = (int2*)p->mv0_out; a.mvOut[1] = (int2*)p->mv1_out; a.mvPred[0] = (int2*)p->mv0_pred; a.mvPred[1] = (int2*)p->mv1_pred;
     a.cost = (int2*)p->cost; a.best = (int2*)p->best; a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
+    a.colMv = colMv; a.colDelta = colDelta; a.curDelta[0] = curDelta0; a.curDelta[1] = curDelta1;
     hipStream_t s = (hipStream_t)stream;
     for_each_wave(a.ctusW, a.ctusH, [&](const int w, const int cyLo, const int n)
     {
         for_depth_level(p->depth, p->level, [&](auto px, auto size)
-        { hipLaunchKernelGGL((b_merge_decide_kernel<decltype(px), decltype(size)::value>), dim3(n), dim3(256), 0, s, a, w, cyLo); });
+        {
+            if (colMv) hipLaunchKernelGGL((b_merge_decide_kernel<decltype(px), decltype(size)::value, true>), dim3(n), dim3(256), 0, s, a, w, cyLo);
+            else hipLaunchKernelGGL((b_merge_decide_kernel<decltype(px), decltype(size)::value, false>), dim3(n), dim3(256), 0, s, a, w, cyLo);
+        });
     });
     X265HIP_TRY(hipGetLastError());
     return 0;
+}
+
+} // namespace x265hip
+
+extern "C" int x265hip_b_merge_decide(const x265hip_b_merge_decide_params* p, void* stream)
+{
+    return x265hip::b_merge_decide_run("b_merge_decide", p, nullptr, nullptr, 0, 0, stream);
+}
+
+extern "C" int x265hip_b_merge_decide_col(const x265hip_b_merge_decide_col_params* p, void* stream)
+{
+    using namespace x265hip;
+    if (!p) { set_error("b_merge_decide_col: NULL operand"); return X265HIP_EINVAL; }
+    if (!p->col_mv != !p->col_delta) { set_error("b_merge_decide_col: col_mv and col_delta go together"); return X265HIP_EINVAL; }
+    if (tmvp_delta_refused("b_merge_decide_col", "cur_delta0", p->cur_delta0) || tmvp_delta_refused("b_merge_decide_col", "cur_delta1", p->cur_delta1))
+        return X265HIP_EINVAL;
+    return b_merge_decide_run("b_merge_decide_col", &p->base, p->col_mv, p->col_delta, p->cur_delta0, p->cur_delta1, stream);
 }

@@ -40,11 +40,13 @@ struct MergeArgs
     int2* best;                         // optional [ctu][blocks]
     const int8_t* qpMap;                // optional: the luma plane of tu_qp
     const uint32_t* lambdaByQp;         // optional
+    const int32_t* colMv; const int16_t* colDelta; int curDelta;   // the COL instances only: the collocated field (col_field.h)
 };
 
 __device__ __forceinline__ int merge_pack(const int qx, const int qy) { return (qx & 0xffff) | (int)((unsigned)qy << 16); }
 
-template <typename Px, int N>
+// COL: the list has the temporal candidate of col_field.h between B2 and the zero candidates (x265hip_merge_decide_col with a field)
+template <typename Px, int N, bool COL>
 __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const int wave, const int cyLo)
 {
     constexpr int BPC = 64 / N, NPU = BPC * BPC, NB = Sa8dLds<N>::NB, BPP = sizeof(Px), FW = BPC + 2, FH = BPC + 1;
@@ -53,6 +55,7 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
     __shared__ int sCand[5], sSlotOf[5], sSlotMv[5], sSlotSad[5], sSlots;
     __shared__ int2 sSearched[NPU];
     __shared__ int sInter[NPU], sLambda[NPU];
+    __shared__ int sTemporal[COL ? NPU : 1], sTemporalOk[COL ? NPU : 1];     // the block's scaled collocated vector / whether it has one
 
     const int tid = threadIdx.x;
     const int cyb = cyLo + (int)blockIdx.x, cxb = wave - 2 * cyb;
@@ -85,6 +88,13 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
         sSearched[z] = a.mv[(size_t)ctu * 85 + lbase + z];
         sInter[z] = a.interCost[((size_t)ctu * NPU + z) * a.interCostStride];
         sLambda[z] = block_lambda8(a.lambda8, a.lambdaByQp, a.qpMap, a.qp, a.depth, a.ctusW, (cxb * 64 + bxz * N) >> 3, (cyb * 64 + byz * N) >> 3);
+        if constexpr (COL)                                                  // another picture's finished field: off the chain as well
+        {
+            int cmv = 0, cd = 0;
+            const bool ok = tmvp_collocated<N>(a.colMv, a.colDelta, ctu, cxb, cyb, a.ctusW, a.ctusH, bxz * N, byz * N, cmv, cd);
+            sTemporalOk[z] = ok ? 1 : 0;
+            sTemporal[z] = ok ? tmvp_scale_mv(cmv, a.curDelta, cd) : 0;
+        }
     }
     __syncthreads();
 
@@ -114,6 +124,7 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
         if (count < num && avB0 && (!avB1 || mB1 != mB0)) sCand[count++] = mB0;                          // :1537-1551
         if (count < num && avA0 && (!avA1 || mA1 != mA0)) sCand[count++] = mA0;                          // :1556-1570
         if (count < num && count < 4 && avB2 && (!avA1 || mA1 != mB2) && (!avB1 || mB1 != mB2)) sCand[count++] = mB2;   // :1573-1593
+        if constexpr (COL) { if (count < num && sTemporalOk[z]) sCand[count++] = sTemporal[z]; }          // :1594-1650: never pruned
         while (count < num) sCand[count++] = 0;                                                          // the zero candidates, refIdx 0
         // clipMv (cudata.cpp:1915-1928)
         const int xmin = -((64 + 8 + x0 - 1) << 2), xmax = (width + 8 - x0 - 1) << 2;
@@ -181,18 +192,20 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
 
 } // namespace x265hip
 
-extern "C" int x265hip_merge_decide(const x265hip_merge_decide_params* p, void* stream)
+namespace x265hip {
+
+// both entries: colMv / colDelta NULL = the list without a temporal candidate
+static int merge_decide_run(const char* who, const x265hip_merge_decide_params* p, const int32_t* colMv, const int16_t* colDelta, const int curDelta, void* stream)
 {
-    using namespace x265hip;
     // argument checks first: they need no device (at most 4 bits and lambda8 <= 2^24 keep the rate term below 2^19 and the cost inside int32)
-    if (decision_record_refused("merge_decide", p, !p || !p->fenc || !p->fref || !p->mv || !p->inter_cost || !p->merge || !p->merge_idx || !p->mv_out || !p->mv_pred ||
+    if (decision_record_refused(who, p, !p || !p->fenc || !p->fref || !p->mv || !p->inter_cost || !p->merge || !p->merge_idx || !p->mv_out || !p->mv_pred ||
                                 !p->cost)) return X265HIP_EINVAL;
-    if (p->max_merge < 1 || p->max_merge > 5) { set_error("merge_decide: max_merge %d out of 1..5", p->max_merge); return X265HIP_EINVAL; }
-    if (inter_cost_stride_refused("merge_decide", p->inter_cost_stride)) return X265HIP_EINVAL;
+    if (p->max_merge < 1 || p->max_merge > 5) { set_error("%s: max_merge %d out of 1..5", who, p->max_merge); return X265HIP_EINVAL; }
+    if (inter_cost_stride_refused(who, p->inter_cost_stride)) return X265HIP_EINVAL;
     // the walk reads a block's searched vector from mv and its neighbours' final motion from mv_out: one array for both would change what a
     // second run sees
     if (p->mv_out == p->mv || p->mv_pred == p->mv || p->mv_out == p->mv_pred)
-    { set_error("merge_decide: mv_out and mv_pred must not alias mv or each other"); return X265HIP_EINVAL; }
+    { set_error("%s: mv_out and mv_pred must not alias mv or each other", who); return X265HIP_EINVAL; }
     int rc = ensure_device();
     if (rc) return rc;
 
@@ -204,12 +217,32 @@ extern "C" int x265hip_merge_decide(const x265hip_merge_decide_params* p, void* 
     a.ctusW = p->width / 64; a.ctusH = p->height / 64; a.depth = p->depth; a.qp = p->qp; a.lambda8 = p->lambda8; a.maxMerge = p->max_merge;
     a.merge = p->merge; a.mergeIdx = p->merge_idx; a.mvOut = (int2*)p->mv_out; a.mvPred = (int2*)p->mv_pred;
     a.cost = (int2*)p->cost; a.best = (int2*)p->best; a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
+    a.colMv = colMv; a.colDelta = colDelta; a.curDelta = curDelta;
     hipStream_t s = (hipStream_t)stream;
     for_each_wave(a.ctusW, a.ctusH, [&](const int w, const int cyLo, const int n)
     {
         for_depth_level(p->depth, p->level, [&](auto px, auto size)
-        { hipLaunchKernelGGL((merge_decide_kernel<decltype(px), decltype(size)::value>), dim3(n), dim3(256), 0, s, a, w, cyLo); });
+        {
+            if (colMv) hipLaunchKernelGGL((merge_decide_kernel<decltype(px), decltype(size)::value, true>), dim3(n), dim3(256), 0, s, a, w, cyLo);
+            else hipLaunchKernelGGL((merge_decide_kernel<decltype(px), decltype(size)::value, false>), dim3(n), dim3(256), 0, s, a, w, cyLo);
+        });
     });
     X265HIP_TRY(hipGetLastError());
     return 0;
+}
+
+} // namespace x265hip
+
+extern "C" int x265hip_merge_decide(const x265hip_merge_decide_params* p, void* stream)
+{
+    return x265hip::merge_decide_run("merge_decide", p, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int x265hip_merge_decide_col(const x265hip_merge_decide_col_params* p, void* stream)
+{
+    using namespace x265hip;
+    if (!p) { set_error("merge_decide_col: NULL operand"); return X265HIP_EINVAL; }
+    if (!p->col_mv != !p->col_delta) { set_error("merge_decide_col: col_mv and col_delta go together"); return X265HIP_EINVAL; }
+    if (tmvp_delta_refused("merge_decide_col", "cur_delta", p->cur_delta)) return X265HIP_EINVAL;
+    return merge_decide_run("merge_decide_col", &p->base, p->col_mv, p->col_delta, p->cur_delta, stream);
 }

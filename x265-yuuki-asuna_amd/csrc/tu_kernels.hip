@@ -1450,6 +1450,9 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
 // the sa8d choice of a B picture's blocks between one list and both (x265hip_b_sa8d_decide): the geometry of inter_sa8d_cost.h
 #include "b_sa8d_decide.h"
 
+// the collocated motion field and the temporal merge candidate read from it (x265hip_col_field_build; the _col merge entries)
+#include "col_field.h"
+
 // the merge arm of a P picture's sa8d choice (x265hip_merge_decide): sa8d_slots of inter_sa8d_cost.h, the wave schedule of decision_common.h
 #include "merge_decide.h"
 

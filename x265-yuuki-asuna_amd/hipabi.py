@@ -242,6 +242,27 @@ class BMergeDecideParams(ctypes.Structure):
     ]
 
 
+class ColFieldParams(ctypes.Structure):
+    """x265hip_col_field_params (include/x265hip.h)."""
+    _fields_ = [
+        ("depth", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("level", ctypes.c_int),
+        ("mv", ctypes.c_void_p), ("intra", ctypes.c_void_p), ("ref_idx", ctypes.c_void_p),
+        ("poc_delta", ctypes.c_int * 8),
+        ("col_mv", ctypes.c_void_p), ("col_delta", ctypes.c_void_p),
+    ]
+
+
+class MergeDecideColParams(ctypes.Structure):
+    """x265hip_merge_decide_col_params (include/x265hip.h)."""
+    _fields_ = [("base", MergeDecideParams), ("col_mv", ctypes.c_void_p), ("col_delta", ctypes.c_void_p), ("cur_delta", ctypes.c_int)]
+
+
+class BMergeDecideColParams(ctypes.Structure):
+    """x265hip_b_merge_decide_col_params (include/x265hip.h)."""
+    _fields_ = [("base", BMergeDecideParams), ("col_mv", ctypes.c_void_p), ("col_delta", ctypes.c_void_p), ("cur_delta0", ctypes.c_int),
+                ("cur_delta1", ctypes.c_int)]
+
+
 class LowresInitParams(ctypes.Structure):
     _fields_ = [("depth", ctypes.c_int), ("src", ctypes.c_void_p), ("src_stride", ctypes.c_ssize_t),
                 ("plane", ctypes.c_void_p * 4), ("stride", ctypes.c_ssize_t),
@@ -707,18 +728,59 @@ def merge_decide(depth, width, height, level, fenc, fenc_stride, fenc_off, fref,
     device int32 tensor, the block's word at element inter_cost_offset + block * inter_cost_stride (the defaults read the cost word of
     inter_sa8d_cost's pairs); merge / merge_idx: device uint8 [ctu][blocks] out; mv_out / mv_pred: device int32 records out (the CU's motion
     / what the TU stages predict from; neither may be mv); cost (and best): device int32 [ctu][blocks][2] out; qp_map: the LUMA plane of tu_qp."""
-    es = 1 if depth == 8 else 2
     p = MergeDecideParams()
+    _fill_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge,
+                       merge_idx, mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp)
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_merge_decide
+    f.argtypes = [ctypes.POINTER(MergeDecideParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_merge_decide")
+
+
+def _fill_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge,
+                       merge_idx, mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp):
+    es = 1 if depth == 8 else 2
     p.depth, p.width, p.height, p.level, p.qp, p.lambda8, p.max_merge = depth, width, height, level, int(qp), int(lambda8), int(max_merge)
     p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
     p.fref, p.fref_stride = fref.data_ptr() + fref_off * es, fref_stride
     p.mv, p.inter_cost, p.inter_cost_stride = mv.data_ptr(), inter_cost.data_ptr() + 4 * int(inter_cost_offset), int(inter_cost_stride)
     p.qp_map, p.lambda8_by_qp = _p(qp_map), _p(lambda8_by_qp)
     p.merge, p.merge_idx, p.mv_out, p.mv_pred, p.cost, p.best = merge.data_ptr(), merge_idx.data_ptr(), mv_out.data_ptr(), mv_pred.data_ptr(), cost.data_ptr(), _p(best)
+
+
+def merge_decide_col(depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge,
+                     merge_idx, mv_out, mv_pred, cost, col_mv, col_delta, cur_delta, best=None, inter_cost_stride=2, inter_cost_offset=1, qp=0, qp_map=None,
+                     lambda8_by_qp=None, stream=None):
+    """x265hip_merge_decide_col: merge_decide with the temporal candidate between B2 and the zero candidates.  col_mv / col_delta: a
+    collocated field (col_field_build; device int32 / int16 [ctu][16]) or both None; cur_delta = curPOC - refPOC, not 0."""
+    p = MergeDecideColParams()
+    _fill_merge_decide(p.base, depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge,
+                       merge_idx, mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp)
+    p.col_mv, p.col_delta, p.cur_delta = _p(col_mv), _p(col_delta), int(cur_delta)
     s = current_stream() if stream is None else stream
-    f = lib().x265hip_merge_decide
-    f.argtypes = [ctypes.POINTER(MergeDecideParams), ctypes.c_void_p]
-    check(f(ctypes.byref(p), s), "x265hip_merge_decide")
+    f = lib().x265hip_merge_decide_col
+    f.argtypes = [ctypes.POINTER(MergeDecideColParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_merge_decide_col")
+
+
+def col_field_build(depth, width, height, level, mv, poc_delta, col_mv, col_delta, intra=None, ref_idx=None, stream=None):
+    """x265hip_col_field_build: a coded picture's motion (mv: mv_out-style device int32 records) compressed to one entry per 16x16 unit,
+    what the temporal merge candidate of a later picture reads.  poc_delta: colPOC - colRefPOC, one int (reference index 0) or up to
+    eight per reference index; intra: device uint8, ref_idx: device int8 [ctu][blocks], optional; col_mv / col_delta: device int32 /
+    int16 [ctu][16] out."""
+    p = ColFieldParams()
+    p.depth, p.width, p.height, p.level = depth, width, height, level
+    p.mv, p.intra, p.ref_idx = mv.data_ptr(), _p(intra), _p(ref_idx)
+    deltas = [int(d) for d in poc_delta] if hasattr(poc_delta, "__len__") else [int(poc_delta)]
+    if not 1 <= len(deltas) <= 8:
+        raise ValueError("col_field_build: one to eight poc_delta entries")
+    for i in range(8):
+        p.poc_delta[i] = deltas[i] if i < len(deltas) else deltas[0]
+    p.col_mv, p.col_delta = col_mv.data_ptr(), col_delta.data_ptr()
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_col_field_build
+    f.argtypes = [ctypes.POINTER(ColFieldParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_col_field_build")
 
 
 def b_sa8d_bits(nrefs=(1, 1), refs=(0, 0), list_sel_bits=(3, 3, 5)):
@@ -766,8 +828,20 @@ def b_merge_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1,
     tensor, the block's word at element inter_cost_offset + block * inter_cost_stride (the defaults read word 0 of b_sa8d_decide's cost);
     merge / merge_idx / dir_out: device uint8 [ctu][blocks] out; mv*_out / mv*_pred: device int32 records out (the CU's motion / what the
     two-list TU stages predict from); cost (and best): device int32 [ctu][blocks][2] out; qp_map: the LUMA plane of tu_qp."""
-    es = 1 if depth == 8 else 2
     p = BMergeDecideParams()
+    _fill_b_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge,
+                         merge_idx, dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best, ref0, ref1, ref_ids, fenc_off, fref_off, inter_cost_stride,
+                         inter_cost_offset, qp, qp_map, lambda8_by_qp)
+    s = current_stream() if stream is None else stream
+    f = lib().x265hip_b_merge_decide
+    f.argtypes = [ctypes.POINTER(BMergeDecideParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_b_merge_decide")
+
+
+def _fill_b_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge,
+                         merge_idx, dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best, ref0, ref1, ref_ids, fenc_off, fref_off, inter_cost_stride,
+                         inter_cost_offset, qp, qp_map, lambda8_by_qp):
+    es = 1 if depth == 8 else 2
     p.depth, p.width, p.height, p.level, p.qp, p.lambda8, p.max_merge = depth, width, height, level, int(qp), int(lambda8), int(max_merge)
     p.ref_id0, p.ref_id1 = ref_ids
     p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
@@ -778,10 +852,23 @@ def b_merge_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1,
     p.merge, p.merge_idx, p.dir, p.ref0, p.ref1 = merge.data_ptr(), merge_idx.data_ptr(), dir_out.data_ptr(), _p(ref0), _p(ref1)
     p.mv0_out, p.mv1_out, p.mv0_pred, p.mv1_pred = mv0_out.data_ptr(), mv1_out.data_ptr(), mv0_pred.data_ptr(), mv1_pred.data_ptr()
     p.cost, p.best = cost.data_ptr(), _p(best)
+
+
+def b_merge_decide_col(depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge,
+                       merge_idx, dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, col_mv, col_delta, cur_deltas, best=None, ref0=None, ref1=None,
+                       ref_ids=(0, 1), fenc_off=0, fref_off=0, inter_cost_stride=4, inter_cost_offset=0, qp=0, qp_map=None, lambda8_by_qp=None, stream=None):
+    """x265hip_b_merge_decide_col: b_merge_decide with the bi-predictive temporal candidate between B2 and the combined candidates.
+    col_mv / col_delta: a collocated field (col_field_build) or both None; cur_deltas = (curPOC - POC(L0[0]), curPOC - POC(L1[0])),
+    neither 0."""
+    p = BMergeDecideColParams()
+    _fill_b_merge_decide(p.base, depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge,
+                         merge, merge_idx, dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best, ref0, ref1, ref_ids, fenc_off, fref_off, inter_cost_stride,
+                         inter_cost_offset, qp, qp_map, lambda8_by_qp)
+    p.col_mv, p.col_delta, p.cur_delta0, p.cur_delta1 = _p(col_mv), _p(col_delta), int(cur_deltas[0]), int(cur_deltas[1])
     s = current_stream() if stream is None else stream
-    f = lib().x265hip_b_merge_decide
-    f.argtypes = [ctypes.POINTER(BMergeDecideParams), ctypes.c_void_p]
-    check(f(ctypes.byref(p), s), "x265hip_b_merge_decide")
+    f = lib().x265hip_b_merge_decide_col
+    f.argtypes = [ctypes.POINTER(BMergeDecideColParams), ctypes.c_void_p]
+    check(f(ctypes.byref(p), s), "x265hip_b_merge_decide_col")
 
 
 def lowres_init(depth, src, src_stride, src_off, planes, stride, org, width, lines, margin_x, margin_y, stream=None):

@@ -1986,6 +1986,34 @@ class IntraPFramePipeline(_Sa8dPStep):
         return self._checksum(self.ii)
 
 
+class ColField:
+    """The collocated motion field of a coded picture (x265hip_col_field_build; what CUData::getColMVP, cudata.cpp:1968-2000, can see of
+    it): one entry per 16x16 luma unit.  Owns col_mv int32 and col_delta int16 [ctu][16]; a col_delta of 0 is "no motion here", so a new
+    field is the field of an I picture.  Only list 0 of the picture is modelled: collocated pictures here are P or I anchors."""
+
+    def __init__(self, nctu, w64, h64, depth, device):
+        import torch
+        self.nctu, self.w64, self.h64, self.depth = nctu, w64, h64, depth
+        self.col_mv = torch.zeros(nctu * 16, dtype=torch.int32, device=device)
+        self.col_delta = torch.zeros(nctu * 16, dtype=torch.int16, device=device)
+
+    def build(self, mv_out, level, poc_delta, intra=None, ref_idx=None, stream=None):
+        """mv_out: the picture's final motion (MergeDecide.mv_out-style records); poc_delta: colPOC - colRefPOC, one int or one per
+        reference index; intra uint8 / ref_idx int8 [ctu][blocks], optional."""
+        hipabi.col_field_build(self.depth, self.w64, self.h64, level, mv_out, poc_delta, self.col_mv, self.col_delta, intra=intra, ref_idx=ref_idx,
+                               stream=stream)
+        return self
+
+    def clear(self):
+        """The field of a picture without motion (an I picture, or an anchor taken as it is)."""
+        self.col_mv.zero_()
+        self.col_delta.zero_()
+        return self
+
+    def checksum(self):
+        return {"col_mv": _sum64(self.col_mv), "col_delta": _sum64(self.col_delta)}
+
+
 class MergeDecide:
     """The merge arm of a P picture's sa8d choice (x265hip_merge_decide; reference Analysis::checkMerge2Nx2N_rd0_4 at RD level 0,
     analysis.cpp:2787-2838, CUData::getInterMergeCandidates, cudata.cpp:1458-1712, and the comparison of compressInterCU_rd0_4,
@@ -2010,8 +2038,17 @@ class MergeDecide:
         self.best = torch.zeros(nb * 2, dtype=torch.int32, device=device)
         self.qp_map, self.lambda8_by_qp = None, None          # as InterSa8dCost's
 
-    def run(self, cur: DevicePicture, ref: DevicePicture, mv, inter_cost, stream=None, inter_cost_stride=2, inter_cost_offset=1):
-        """mv: the searched records; inter_cost: InterSa8dCost.cost (the pairs; the defaults read their cost word)."""
+    def run(self, cur: DevicePicture, ref: DevicePicture, mv, inter_cost, stream=None, inter_cost_stride=2, inter_cost_offset=1, col=None, cur_delta=None):
+        """mv: the searched records; inter_cost: InterSa8dCost.cost (the pairs; the defaults read their cost word).  col: a ColField of
+        the collocated picture - the list then has the temporal candidate (x265hip_merge_decide_col) - with cur_delta = curPOC - refPOC."""
+        if col is not None:
+            if cur_delta is None:
+                raise ValueError("MergeDecide.run: a collocated field needs cur_delta")
+            hipabi.merge_decide_col(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, cur.org, ref.t, ref.stride, ref.org, mv, inter_cost,
+                                    self.lambda8, self.max_merge, self.merge, self.merge_idx, self.mv_out, self.mv_pred, self.cost, col.col_mv, col.col_delta,
+                                    cur_delta, best=self.best, inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp,
+                                    qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+            return
         hipabi.merge_decide(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, cur.org, ref.t, ref.stride, ref.org, mv, inter_cost,
                             self.lambda8, self.max_merge, self.merge, self.merge_idx, self.mv_out, self.mv_pred, self.cost, best=self.best,
                             inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map,
@@ -2039,23 +2076,37 @@ class MergePFramePipeline(_Sa8dPStep):
     mean in IntraPFramePipeline; max_merge: --max-merge (the reference's default 3, param.cpp:199)."""
 
     def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
-                 sign_hide=False, sao_rdo=None, lambda8=1024, base_bits=2, max_merge=3):
+                 sign_hide=False, sao_rdo=None, lambda8=1024, base_bits=2, max_merge=3, temporal_mvp=False):
         _Sa8dPStep.__init__(self, w64, h64, depth, device, rng, subme, level, qp, deblock, sao, chroma, sao_apply, sign_hide, sao_rdo, lambda8, base_bits)
         self.md = MergeDecide(self.nctu, w64, h64, depth, level, device, max_merge=max_merge, lambda8=lambda8, qp=qp)
         self.skip = None
+        # temporal_mvp: the merge list has the temporal candidate (DESIGN.md section 21); self.col is then this picture's own field
+        self.temporal_mvp = bool(temporal_mvp)
+        self.col = ColField(self.nctu, w64, h64, depth, device) if self.temporal_mvp else None
 
     def set_qp_maps(self, maps, lambda8_by_qp=None):
         """As IntraPFramePipeline.set_qp_maps: the maps reach the TU stages, the deblocking stage and both candidates' rate terms."""
         self._set_decision_qp_maps(maps, lambda8_by_qp, [self.ic, self.md], [])
 
-    def run(self, cur: DevicePicture, ref: DevicePicture, mark=None):
+    def run(self, cur: DevicePicture, ref: DevicePicture, mark=None, col=None, cur_delta=None):
         """ref: the reference picture (extended borders, with chroma its Cb / Cr planes); returns the luma plane of the coded picture.
-        mark(name), if given, is called after every stage."""
+        mark(name), if given, is called after every stage.  With temporal_mvp: col = the ColField of the collocated picture (the
+        reference; None = a picture without motion) and cur_delta = curPOC - refPOC; after the walk self.col is this picture's field."""
         mark = mark or (lambda name: None)
+        if not self.temporal_mvp and (col is not None or cur_delta is not None):
+            raise ValueError("MergePFramePipeline.run: col / cur_delta need temporal_mvp=True")
+        if self.temporal_mvp and cur_delta is None:
+            raise ValueError("MergePFramePipeline.run: temporal_mvp needs cur_delta")
         mv = self._search(cur, ref, mark)
         self.ic.run(cur, ref, mv)
         mark("inter_cost")
-        self.md.run(cur, ref, mv, self.ic.cost)
+        if self.temporal_mvp:
+            if col is self.col:
+                raise ValueError("MergePFramePipeline.run: col is this step's own field, which the run overwrites: hand a copy")
+            self.md.run(cur, ref, mv, self.ic.cost, col=col if col is not None else self.col.clear(), cur_delta=cur_delta)
+            self.col.build(self.md.mv_out, self.md.level, cur_delta)
+        else:
+            self.md.run(cur, ref, mv, self.ic.cost)
         mark("merge")
         self._code(cur, ref, self.md.mv_pred, mark)
         self.skip = self.md.skip_flags(self.rc, self.rc_c if self.chroma else None)
@@ -2193,10 +2244,20 @@ class BMergeDecide:
         self.qp_map, self.lambda8_by_qp = None, None          # as InterSa8dCost's
 
     def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, dir_in, mv0, mv1, inter_cost, stream=None, inter_cost_stride=4,
-            inter_cost_offset=0):
+            inter_cost_offset=0, col=None, cur_deltas=None):
         """dir_in / mv0 / mv1: the inter winner (BSa8dDecide.dir / mv0_out / mv1_out); inter_cost: BSa8dDecide.cost (the defaults read its
-        word 0)."""
+        word 0).  col: the ColField of the collocated picture (L1[0]) - the list then has the temporal candidate
+        (x265hip_b_merge_decide_col) - with cur_deltas = (curPOC - POC(L0[0]), curPOC - POC(L1[0]))."""
         assert ref0.stride == ref1.stride and ref0.org == ref1.org
+        if col is not None:
+            if cur_deltas is None:
+                raise ValueError("BMergeDecide.run: a collocated field needs cur_deltas")
+            hipabi.b_merge_decide_col(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, ref0.t, ref1.t, ref0.stride, dir_in, mv0, mv1, inter_cost,
+                                      self.lambda8, self.max_merge, self.merge, self.merge_idx, self.dir, self.mv0_out, self.mv1_out, self.mv0_pred,
+                                      self.mv1_pred, self.cost, col.col_mv, col.col_delta, cur_deltas, best=self.best, ref0=self.ref0, ref1=self.ref1,
+                                      ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org, inter_cost_stride=inter_cost_stride,
+                                      inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+            return
         hipabi.b_merge_decide(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, ref0.t, ref1.t, ref0.stride, dir_in, mv0, mv1, inter_cost,
                               self.lambda8, self.max_merge, self.merge, self.merge_idx, self.dir, self.mv0_out, self.mv1_out, self.mv0_pred, self.mv1_pred,
                               self.cost, best=self.best, ref0=self.ref0, ref1=self.ref1, ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org,
@@ -2220,7 +2281,9 @@ class MergeBFramePipeline(_RefListStep):
     built)."""
 
     def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
-                 sign_hide=False, sao_rdo=None, dir_cost=(12, 12, 20), b_intra=False, lambda8=1024, base_bits=None, bi_bits_delta=None, max_merge=3):
+                 sign_hide=False, sao_rdo=None, dir_cost=(12, 12, 20), b_intra=False, lambda8=1024, base_bits=None, bi_bits_delta=None, max_merge=3,
+                 temporal_mvp=False):
+        self.temporal_mvp = bool(temporal_mvp)     # the merge list has the temporal candidate (DESIGN.md section 21)
         if b_intra:
             raise ValueError("MergeBFramePipeline: b_intra together with merge is one walk in coding order and is not built")
         _PictureStep.__init__(self, w64, h64, depth, level, qp, device, deblock, sao, chroma, sao_apply, sao_rdo)
@@ -2240,9 +2303,15 @@ class MergeBFramePipeline(_RefListStep):
         of every merge candidate."""
         self._set_decision_qp_maps(maps, lambda8_by_qp, [self.bd, self.md], [])
 
-    def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mark=None):
+    def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, mark=None, col=None, cur_deltas=None):
         """ref0 / ref1: the list-0 / list-1 reference pictures (extended borders; with chroma=True also their Cb / Cr planes).  Returns the
-        luma plane of the coded picture; mark(name), if given, is called after every stage."""
+        luma plane of the coded picture; mark(name), if given, is called after every stage.  With temporal_mvp: col = the ColField of
+        the collocated picture ref1 (None = a picture without motion: no temporal candidate) and cur_deltas = (curPOC - POC(ref0),
+        curPOC - POC(ref1))."""
+        if not self.temporal_mvp and (col is not None or cur_deltas is not None):
+            raise ValueError("MergeBFramePipeline.run: col / cur_deltas need temporal_mvp=True")
+        if self.temporal_mvp and cur_deltas is None:
+            raise ValueError("MergeBFramePipeline.run: temporal_mvp needs cur_deltas")
         self._qp_maps_run_check()
         mark = mark or (lambda name: None)
         self._alloc_planes(cur)
@@ -2250,7 +2319,7 @@ class MergeBFramePipeline(_RefListStep):
         self.bd.run(cur, ref0, ref1, self.spl[0].out, self.spl[1].out)
         mark("b_sa8d")
         md = self.md
-        md.run(cur, ref0, ref1, self.bd.dir, self.bd.mv0_out, self.bd.mv1_out, self.bd.cost)
+        md.run(cur, ref0, ref1, self.bd.dir, self.bd.mv0_out, self.bd.mv1_out, self.bd.cost, col=col, cur_deltas=cur_deltas if col is not None else None)
         mark("merge")
         self.rc.run(cur, ref0, ref1, self.recon, md.mv0_pred, md.mv1_pred, dir_flags=md.dir)
         mark("recon")
@@ -2282,10 +2351,20 @@ class MiniGop:
     list 1) with list 0 = the coded anchors before it, newest first, [:n0], and list 1 = ([the later anchor] + those)[:n1] - HEVC's default
     list order, so with n1 > 1 a picture sits in both lists."""
 
-    def __init__(self, p_step, b_step, gop, i_step=None, p_refs=1, b_refs=(1, 1)):
+    def __init__(self, p_step, b_step, gop, i_step=None, p_refs=1, b_refs=(1, 1), temporal_mvp=False):
+        """temporal_mvp: p_step / b_step are a MergePFramePipeline / MergeBFramePipeline built with temporal_mvp=True; POC = display index.
+        An anchor coded by i_step or taken as it is leaves a field without motion; a P anchor hands its own field (a copy) to the next
+        anchor (cur_delta = gop) and to the B pictures before it (cur_deltas = (k - (a - gop), k - a))."""
         assert gop >= 1 and p_refs >= 1 and len(b_refs) == 2 and min(b_refs) >= 1
         self.p, self.b, self.gop, self.i, self.p_refs = p_step, b_step, int(gop), i_step, int(p_refs)
         self.b_refs = (int(b_refs[0]), int(b_refs[1]))
+        self.temporal_mvp = bool(temporal_mvp)
+        if self.temporal_mvp:
+            if self.p_refs > 1 or self.b_refs != (1, 1):
+                raise ValueError("MiniGop: temporal_mvp with several references per list (p_refs > 1 or b_refs != (1, 1)) is not built")
+            for name, step in (("p_step", p_step), ("b_step", b_step)):
+                if step is not None and not getattr(step, "temporal_mvp", False):
+                    raise ValueError("MiniGop: temporal_mvp=True needs a %s built with temporal_mvp=True" % name)
 
     def run(self, pictures):
         """pictures: DevicePictures in display order; picture 0 is the first anchor - coded by i_step where there is one (its output is
@@ -2300,8 +2379,15 @@ class MiniGop:
             out[0] = keep(self.i.final_planes())
             prev = pictures[0].like(out[0])
         anchors = [prev]                 # coded anchors, newest first (p_refs > 1)
+        col = None                       # temporal_mvp: the previous anchor's collocated field (None: an anchor without motion)
         for a in range(self.gop, len(pictures), self.gop):
-            if self.p_refs > 1:
+            if self.temporal_mvp:
+                self.p.run(pictures[a], prev, col=col, cur_delta=self.gop)
+                if col is None:
+                    col = ColField(self.p.nctu, self.p.col.w64, self.p.col.h64, self.p.col.depth, self.p.col.col_mv.device)
+                col.col_mv.copy_(self.p.col.col_mv)
+                col.col_delta.copy_(self.p.col.col_delta)
+            elif self.p_refs > 1:
                 self.p.run(pictures[a], anchors[:self.p_refs])
             else:
                 self.p.run(pictures[a], prev)
@@ -2309,7 +2395,9 @@ class MiniGop:
             order.append(a)
             anchor = pictures[a].like(out[a])
             for k in range(a - self.gop + 1, a):
-                if self.b_refs != (1, 1):
+                if self.temporal_mvp:            # the collocated picture is L1[0] = anchor a, whose field col now holds
+                    self.b.run(pictures[k], prev, anchor, col=col, cur_deltas=(k - (a - self.gop), k - a))
+                elif self.b_refs != (1, 1):
                     self.b.run(pictures[k], anchors[:self.b_refs[0]], ([anchor] + anchors)[:self.b_refs[1]])
                 else:
                     self.b.run(pictures[k], prev, anchor)

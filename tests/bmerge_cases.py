@@ -211,14 +211,15 @@ def inputs(c):
     return out
 
 
-def run_stage(c, mutation=None, inter_cost=None, max_merge=None):
-    """The expectation of a case (or of a mutation of the walk / other inter costs / another max_merge on the same inputs)."""
+def run_stage(c, mutation=None, inter_cost=None, max_merge=None, **temporal):
+    """The expectation of a case (or of a mutation of the walk / other inter costs / another max_merge on the same inputs); temporal: the
+    col / cur_deltas / tmvp_mutation of BM.walk."""
     x = inputs(c)
     if inter_cost is None and c.costs == "real":
         inter_cost = x["real"]
     return BM.stage_expectation(c.depth, x["pcur"], x["pref"], c.w, c.h, c.level, x["dir_in"], x["mv0"], x["mv1"], max_merge or c.max_merge, c.lambda8,
                                 inter_cost=inter_cost, cost_fn=BM.tie_pattern if inter_cost is None else None, tu_qp=x["tu_qp"],
-                                lambda8_by_qp=x["lambda8_by_qp"], qp=x["qp"], ref_ids=x["ref_ids"], mutation=mutation, pricer=x["pricer"])
+                                lambda8_by_qp=x["lambda8_by_qp"], qp=x["qp"], ref_ids=x["ref_ids"], mutation=mutation, pricer=x["pricer"], **temporal)
 
 
 @functools.lru_cache(maxsize=None)

@@ -6,8 +6,9 @@ table's cu[].sa8d slot; the coding through O.inter_recon_bi / O.inter_recon_chro
 boundary strengths through O.deblock_bs_b on mv*_out / ref0 / ref1.
 
 Restated here in Python, with the reference's line numbers beside each statement: the B slice's candidate list
-(CUData::getInterMergeCandidates, common/cudata.cpp:1458-1712 with isInterB, one reference per list, no temporal candidate: spatial
-candidates, hasEqualMotion :1439-1455, combined candidates :1652-1683, zero fill :1684-1709, every early return), CUData::clipMv per list
+(CUData::getInterMergeCandidates, common/cudata.cpp:1458-1712 with isInterB, one reference per list: the spatial and temporal
+candidates of merge_expect.spatial_candidates() under hasEqualMotion :1439-1455, the temporal one {3, the collocated vector of
+tests/tmvp_expect.py scaled per list}, combined candidates :1652-1683, zero fill :1684-1709, every early return), CUData::clipMv per list
 (cudata.cpp:1915-1928), getTUBits (search.h:246-249), the two strict comparisons (analysis.cpp:2833 among the candidates, :1650-1655
 against the inter winner) and the walk in coding order.  As for the P slice (tests/merge_expect.py) the list cannot be pinned against
 compiled reference code with what oracle/ offers; it is checked by hand-worked lists (tests/test_bmerge_cpu.py) and by the mutations
@@ -23,11 +24,11 @@ import bsa8d_expect as BX
 import intra_expect as IE
 import intra_inter_expect as IX
 import merge_expect as ME
+import tmvp_expect as TX
 
 O, F, H, harness, SC = IE.O, IE.F, IE.H, IE.harness, IE.SC
 unpack, pack, clip_mv, tu_bits, records, level_slots, skip_flags, tie_pattern = (ME.unpack, ME.pack, ME.clip_mv, ME.tu_bits, ME.records, ME.level_slots,
                                                                                  ME.skip_flags, ME.tie_pattern)
-NEIGHBOURS = ME.NEIGHBOURS
 
 P_MASKS = ME.MASKS                                              # the masks of DESIGN.md section 19 (won_zero: the zero fill, here {3, 0, 0})
 B_MASKS = ("won_dir1", "won_dir2", "won_dir3", "won_combined", "won_zero_bi", "pruned_needs_both_lists", "kept_because_dir_differs",
@@ -37,8 +38,7 @@ MASKS = P_MASKS + B_MASKS
 MUTATIONS = ("le_against_inter", "le_among_candidates", "equal_motion_ignores_dir", "equal_motion_compares_unused", "cutoff_recomputed",
              "combined_order_swapped", "no_same_picture_suppression", "uni_zero_fill", "avg_of_rounded", "no_clip_list1", "clip_stored_list1",
              "inter_winner_not_final")
-LIST_FLAGS = ("pruned_B1", "pruned_B0", "pruned_A0", "pruned_B2", "B0_equals_A1_kept", "B2_dropped_at_four", "cut_at_max", "pruned_needs_both_lists",
-              "kept_because_dir_differs", "combined_suppressed_same_picture", "cut_inside_combined")
+LIST_FLAGS = ("pruned_needs_both_lists", "kept_because_dir_differs", "combined_suppressed_same_picture", "cut_inside_combined", "combined_from_temporal")
 PRIORITY0, PRIORITY1 = 0xEDC984, 0xB73621                      # cudata.cpp:1655-1656
 
 
@@ -63,56 +63,29 @@ def combined_pairs(swapped=False):
     return [((p0 >> (2 * k)) & 3, (p1 >> (2 * k)) & 3) for k in range(12)]                    # :1658-1661
 
 
-def candidate_list(nb, max_merge, same_picture=False, mutation=None):
-    """getInterMergeCandidates for a B slice with one reference per list and no temporal candidate.  nb: {"A1" | "B1" | "B0" | "A0" | "B2":
-    a motion() or None where the neighbour is not available}; same_picture: both lists name one picture (refPOCL0 == refPOCL1).
-    Returns ([(motion, origin)], flags) - origin is the neighbour's name, "combined" or "zero"."""
-    a1, b1, b0, a0, b2 = (nb.get(k) for k in ("A1", "B1", "B0", "A0", "B2"))
-    out, fl = [], {k: False for k in LIST_FLAGS}
+def candidate_list(nb, max_merge, same_picture=False, mutation=None, temporal=None):
+    """getInterMergeCandidates for a B slice with one reference per list.  nb: {"A1" | "B1" | "B0" | "A0" | "B2": a motion() or None where
+    the neighbour is not available}; same_picture: both lists name one picture (refPOCL0 == refPOCL1); temporal: motion(3, the collocated
+    vector scaled for list 0, for list 1) or None.  Returns ([(motion, origin)], flags) - origin is the neighbour's name, "temporal",
+    "combined", "combined_temporal" (a combined candidate with the temporal one as a source) or "zero"."""
+    fl = {k: False for k in LIST_FLAGS}
 
-    def same(p, q, name):
-        """p.hasEqualMotion(q) for an available p; records why the pair was pruned or kept."""
-        if p is None:
-            return False
+    def equal(p, q, record=True):
+        """p.hasEqualMotion(q); a pruning decision (record) notes why the pair was pruned or kept."""
+        if not record:
+            return has_equal_motion(p, q)
         eq = has_equal_motion(p, q, mutation)
-        if mutation is None:
-            if eq:
-                fl["pruned_" + name] = True
-                fl["pruned_needs_both_lists"] |= p[0] == 3
-            elif has_equal_motion(p, q, "equal_motion_ignores_dir"):
-                fl["kept_because_dir_differs"] = True
-        elif eq:
-            fl["pruned_" + name] = True
+        if mutation not in MUTATIONS:
+            fl["pruned_needs_both_lists"] |= eq and p[0] == 3
+            fl["kept_because_dir_differs"] |= not eq and has_equal_motion(p, q, "equal_motion_ignores_dir")
         return eq
-
-    def cut(later):
-        fl["cut_at_max"] = any(v is not None for v in later)
+    zero = motion(1, 0, 0) if mutation == "uni_zero_fill" else motion(3, 0, 0)
+    out, spatial_flags, returned = ME.spatial_candidates(nb, max_merge, equal, zero, temporal, mutation)
+    fl.update(spatial_flags)
+    if returned:
         return out, fl
-    if a1 is not None:                                                                        # :1495-1510
-        out.append((a1, "A1"))
-        if len(out) == max_merge:
-            return cut((b1, b0, a0, b2))
-    if b1 is not None and not same(a1, b1, "B1"):                                             # :1517-1532
-        out.append((b1, "B1"))
-        if len(out) == max_merge:
-            return cut((b0, a0, b2))
-    if b0 is not None and not same(b1, b0, "B0"):                                             # :1537-1551: against B1 only
-        fl["B0_equals_A1_kept"] = a1 is not None and has_equal_motion(a1, b0)
-        out.append((b0, "B0"))
-        if len(out) == max_merge:
-            return cut((a0, b2))
-    if a0 is not None and not same(a1, a0, "A0"):                                             # :1556-1570: against A1 only
-        out.append((a0, "A0"))
-        if len(out) == max_merge:
-            return cut((b2,))
-    if len(out) < 4:                                                                          # :1573
-        if b2 is not None and not same(a1, b2, "B2") and not same(b1, b2, "B2"):              # :1577-1592: against A1 and B1
-            out.append((b2, "B2"))
-            if len(out) == max_merge:
-                return out, fl
-    elif b2 is not None:
-        fl["B2_dropped_at_four"] = True
-    cutoff = len(out) * (len(out) - 1)                                                        # :1654: once, from the spatial count
+    count = len(out) - (1 if mutation == "temporal_not_in_cutoff" and fl["temporal_present"] else 0)
+    cutoff = count * (count - 1)                                                              # :1654: once, the temporal candidate included
     k = 0
     pairs = combined_pairs(mutation == "combined_order_swapped")
     while k < (len(out) * (len(out) - 1) if mutation == "cutoff_recomputed" else cutoff) and k < 12:      # :1658
@@ -120,17 +93,19 @@ def candidate_list(nb, max_merge, same_picture=False, mutation=None):
         k += 1
         if i >= len(out) or j >= len(out):                        # only a recomputed cutoff gets here (the reference would read an unset entry)
             continue
-        ci, cj = out[i][0], out[j][0]
+        (ci, oi), (cj, oj) = out[i], out[j]
         if (ci[0] & 1) and (cj[0] & 2):                                                       # :1663
             if same_picture and ci[1] == cj[2] and mutation != "no_same_picture_suppression":     # :1670
                 fl["combined_suppressed_same_picture"] = True
                 continue
-            out.append((motion(3, ci[1], cj[2]), "combined"))                                 # :1672-1676
+            from_t = "temporal" in (oi, oj)
+            fl["combined_from_temporal"] |= from_t
+            out.append((motion(3, ci[1], cj[2]), "combined_temporal" if from_t else "combined"))   # :1672-1676
             if len(out) == max_merge:                                                         # :1678-1679
                 fl["cut_inside_combined"] = True
                 return out, fl
     while len(out) < max_merge:                                                               # :1687-1709: refIdx 0 in both lists
-        out.append((motion(1, 0, 0) if mutation == "uni_zero_fill" else motion(3, 0, 0), "zero"))
+        out.append((zero, "zero"))
     return out, fl
 
 
@@ -212,51 +187,34 @@ class Pricer:
         raise AssertionError("the walk did not settle")
 
 
-def walk(w64, h64, level, winners, max_merge, price, lam, inter_cost=None, cost_fn=None, same_picture=False, mutation=None):
+def walk(w64, h64, level, winners, max_merge, price, lam, inter_cost=None, cost_fn=None, same_picture=False, mutation=None, col=None, cur_deltas=None,
+         tmvp_mutation=None):
     """The walk in coding order.  winners: (dir, packed mv0, packed mv1) per block (index = ctu * blocks + z) - the inter winner, the
     vectors as the input records hold them; price(block, dir, clipped mv0, clipped mv1[, rounded]) -> sa8d; lam(block) -> lambda8;
-    inter_cost: int per block, or cost_fn(block, merge cost) -> the inter cost to decide against.  Returns merge, merge_idx, dir (uint8),
-    ref_used [blocks, 2] (bool), vec_out / vec_pred int32 [blocks, 2] (packed, per list), cost / best int32 [blocks, 2], inter_cost and
-    the masks."""
-    assert mutation is None or mutation in MUTATIONS
-    n = 8 << level
-    bpc = 64 // n
-    nblk = bpc * bpc
-    cw, chh = w64 // 64, h64 // 64
-    tot = cw * chh * nblk
-    bw, bh = cw * bpc, chh * bpc
+    inter_cost: int per block, or cost_fn(block, merge cost) -> the inter cost to decide against; col: the TX.ColSource of L1[0] - the list
+    then has the temporal candidate - with cur_deltas = (curPOC - POC(L0[0]), curPOC - POC(L1[0])); tmvp_mutation: one of TX.B_MUTATIONS.
+    Returns merge, merge_idx, dir (uint8), ref_used [blocks, 2] (bool), vec_out / vec_pred int32 [blocks, 2] (packed, per list), cost /
+    best int32 [blocks, 2], inter_cost and the masks: MASKS, and TX.B_MASKS as well where the walk is told of a collocated picture (col or
+    cur_deltas)."""
+    assert mutation is None or (mutation in MUTATIONS and tmvp_mutation is None)
+    assert tmvp_mutation is None or tmvp_mutation in TX.P_MUTATIONS + TX.B_MUTATIONS
+    g = ME.Grid(w64, h64, level)
+    tot = g.tot
     final = [None] * tot
     origin_won = [None] * tot
+    from_temporal = np.zeros(tot, bool)                       # the block's motion came from a temporal candidate, directly or inherited
     merge, idx, dirs = np.zeros(tot, np.uint8), np.zeros(tot, np.uint8), np.zeros(tot, np.uint8)
     vec_out, vec_pred = np.zeros((tot, 2), np.int32), np.zeros((tot, 2), np.int32)
     cost, best, ic_used = np.zeros((tot, 2), np.int32), np.zeros((tot, 2), np.int32), np.zeros(tot, np.int64)
-    masks = {k: np.zeros(tot, bool) for k in MASKS}
+    masks = {k: np.zeros(tot, bool) for k in MASKS + TX.B_MASKS}
     wrap = lambda v: int(np.int32(np.uint32(v & 0xffffffff)))
-
-    def index(gbx, gby):
-        return ((gby // bpc) * cw + gbx // bpc) * nblk + IE.zindex(gbx % bpc, gby % bpc)
+    coded = lambda q: motion(*winners[q]) if mutation == "inter_winner_not_final" else final[q]
     for b in range(tot):
-        ctu, z = divmod(b, nblk)
-        bx, by = IE.zorder(z)
-        gbx, gby = (ctu % cw) * bpc + bx, (ctu // cw) * bpc + by
-        x0, y0 = gbx * n, gby * n
+        _, _, x0, y0 = g.block(b)
         win = motion(*winners[b])
-        nb, where = {}, {}
-        for name, dx, dy in NEIGHBOURS:
-            nx, ny = gbx + dx, gby + dy
-            nb[name] = None
-            if not (0 <= nx < bw and 0 <= ny < bh):                                           # getPU*: outside the picture
-                continue
-            q = index(nx, ny)
-            where[name] = q
-            if q < b:                                                                         # already coded (CTUs in raster order, z-order inside)
-                nb[name] = motion(*winners[q]) if mutation == "inter_winner_not_final" else final[q]
-            elif name in ("B0", "A0"):
-                below = name == "A0" and by + 1 == bpc
-                masks["A0_below_ctu" if below else name + "_not_yet_coded"][b] = True
-        masks["A0_from_left_ctu"][b] = nb["A0"] is not None and bx == 0
-        masks["B0_from_above_right_ctu"][b] = nb["B0"] is not None and bx + 1 == bpc and by == 0
-        cands, fl = candidate_list(nb, max_merge, same_picture, mutation)
+        nb, where = g.neighbours(b, coded, masks)
+        temporal = TX.temporal_vectors(col, level, x0, y0, cur_deltas, masks, b, tmvp_mutation)
+        cands, fl = candidate_list(nb, max_merge, same_picture, mutation or tmvp_mutation, temporal and motion(3, *temporal))
         for k, v in fl.items():
             masks[k][b] = v
         lam8 = lam(b)
@@ -294,16 +252,22 @@ def walk(w64, h64, level, winners, max_merge, price, lam, inter_cost=None, cost_
         best[b] = (sad, c)
         masks["merge_won"][b] = True
         masks["tie_lowest_index"][b] = priced.count(c) > 1
-        masks["won_" + ("zero" if origin == "zero" else origin)][b] = True
+        masks["won_" + ("combined" if origin == "combined_temporal" else origin)][b] = True
         masks["won_zero_bi"][b] = origin == "zero"
+        masks["won_temporal_bi"][b] = origin == "temporal"
+        masks["won_combined_from_temporal"][b] = origin == "combined_temporal"
         masks["won_dir%d" % m[0]][b] = True
         spatial = origin in where
         masks["inherits_inherited"][b] = spatial and bool(merge[where[origin]])
-        masks["inherits_combined"][b] = spatial and origin_won[where[origin]] == "combined"
+        masks["inherits_combined"][b] = spatial and origin_won[where[origin]] in ("combined", "combined_temporal")
+        masks["inherits_temporal"][b] = spatial and bool(from_temporal[where[origin]])
+        from_temporal[b] = origin in ("temporal", "combined_temporal") or masks["inherits_temporal"][b]
         masks["merged_dir_differs_from_inter_dir"][b] = m[0] != win[0]
         masks["clip_changed_prediction"][b] = (m[0] & 1 and clip(m[1]) != m[1]) or (m[0] & 2 and clip(m[2]) != m[2])
         masks["clip_changed_list1_prediction"][b] = bool(m[0] & 2) and clip(m[2]) != m[2]
     used = np.stack([(dirs & 1) != 0, (dirs & 2) != 0], axis=1)
+    if col is None and cur_deltas is None:
+        masks = {k: masks[k] for k in MASKS}
     return dict(merge=merge, merge_idx=idx, dir=dirs, ref_used=used, vec_out=vec_out, vec_pred=vec_pred, cost=cost, best=best, inter_cost=ic_used, masks=masks)
 
 
@@ -315,8 +279,8 @@ def winners_of(dir_in, mv0, mv1, level, nctu):
 
 
 def stage_expectation(depth, cur_y, refs_y, w64, h64, level, dir_in, mv0, mv1, max_merge, lambda8, inter_cost=None, cost_fn=None, tu_qp=None,
-                      lambda8_by_qp=None, qp=0, ref_ids=(0, 1), mutation=None, pricer=None):
-    """What x265hip_b_merge_decide leaves for the inter winner (dir_in uint8 [blocks], mv0 / mv1 int32 [ctu*85, 2]).  Returns walk()'s
+                      lambda8_by_qp=None, qp=0, ref_ids=(0, 1), mutation=None, pricer=None, col=None, cur_deltas=None, tmvp_mutation=None):
+    """What x265hip_b_merge_decide (with col: x265hip_b_merge_decide_col) leaves for the inter winner (dir_in uint8 [blocks], mv0 / mv1 int32 [ctu*85, 2]).  Returns walk()'s
     dictionary plus ref0 / ref1 (int8) and mv0_out / mv1_out / mv0_pred / mv1_pred as RECORDS of the level's slots: a merged block's used
     lists carry the merge cost, an unused list {the input record's cost, 0}; another block's mv*_out are the input records with an unused
     list's vector 0, its mv*_pred the input records word for word."""
@@ -330,7 +294,8 @@ def stage_expectation(depth, cur_y, refs_y, w64, h64, level, dir_in, mv0, mv1, m
         return IX.block_lambda(tu_qp, lambda8_by_qp, lambda8, qp, depth, gx, gy)
     win = winners_of(dir_in, mv0, mv1, level, nctu)
     e = pr.fixpoint(lambda price: walk(w64, h64, level, win, max_merge, price, lam, inter_cost=inter_cost, cost_fn=cost_fn,
-                                       same_picture=ref_ids[0] == ref_ids[1], mutation=mutation))
+                                       same_picture=ref_ids[0] == ref_ids[1], mutation=mutation, col=col, cur_deltas=cur_deltas,
+                                       tmvp_mutation=tmvp_mutation))
     merged = e["merge"] != 0
     for l in (0, 1):
         words = np.where(merged & e["ref_used"][:, l], e["cost"][:, 1], ins[l][:, 0]).astype(np.int32)
@@ -378,9 +343,10 @@ def reference_prediction(lib, refs_y, w64, h64, level, dirs, mv0, mv1):
 
 
 def merge_b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, subme, level, qp, max_merge=3, sao_rdo=None, dir_cost=BX.DIR_COST,
-                  tu_flags=H.TU_SIGN_HIDE, lambda8=IE.LAMBDA8, cores=0, avx2=False, tu_qp=None, cu_qp=None, lambda8_by_qp=None):
+                  tu_flags=H.TU_SIGN_HIDE, lambda8=IE.LAMBDA8, cores=0, avx2=False, tu_qp=None, cu_qp=None, lambda8_by_qp=None, col=None, cur_deltas=None):
     """One B picture with merge blocks through the oracle, stage by stage (the CPU twin of stages.MergeBFramePipeline.run with chroma,
-    deblocking and SAO applied; tu_qp / cu_qp / lambda8_by_qp: what set_qp_maps hands on).  *_planes = padded (Y, Cb, Cr) host planes.
+    deblocking and SAO applied; tu_qp / cu_qp / lambda8_by_qp: what set_qp_maps hands on; col / cur_deltas: the handed collocated field of a
+    step with temporal_mvp).  *_planes = padded (Y, Cb, Cr) host planes.
     Every stage output by name; behind the coding it is the chain of bsa8d_expect.sa8d_b_chain."""
     S = IE.importlib.import_module("x265-yuuki-asuna_amd.stages")
     import qp_map_expect as QE
@@ -397,7 +363,7 @@ def merge_b_chain(depth, cur_planes, ref0_planes, ref1_planes, w64, h64, rng_r, 
                   lambda8_by_qp=lambda8_by_qp, with_reference=False)
     win0, win1 = BX.BE.full_mv_out(level, nctu, d["mv0"], 0), BX.BE.full_mv_out(level, nctu, d["mv1"], 0)
     e = stage_expectation(depth, cur, (r0, r1), w64, h64, level, d["dir"], win0, win1, max_merge, lambda8, inter_cost=d["cost"][:, 0], tu_qp=tu_qp,
-                          lambda8_by_qp=lambda8_by_qp, qp=qp)
+                          lambda8_by_qp=lambda8_by_qp, qp=qp, col=col, cur_deltas=cur_deltas)
     out.update({"b_dir": d["dir"], "b_cost": d["cost"]})
     out.update({k: e[k] for k in OUTPUTS})
     out["merge_cost"] = out.pop("cost")

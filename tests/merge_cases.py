@@ -171,14 +171,15 @@ def inputs(c):
                 pricer=ME.Pricer(c.depth, pc, pr, c.w, c.h, c.level))
 
 
-def run_stage(c, mutation=None, inter_cost=None, max_merge=None):
-    """The expectation of a case (or of a mutation of the walk / other inter costs / another max_merge on the same inputs)."""
+def run_stage(c, mutation=None, inter_cost=None, max_merge=None, **temporal):
+    """The expectation of a case (or of a mutation of the walk / other inter costs / another max_merge on the same inputs); temporal: the
+    col / cur_delta / tmvp_mutation of ME.walk."""
     x = inputs(c)
     if inter_cost is None and c.costs == "real":
         inter_cost = x["real"][:, 1]
     return ME.stage_expectation(c.depth, x["pcur"], x["pref"], c.w, c.h, c.level, x["mv"], max_merge or c.max_merge, c.lambda8, inter_cost=inter_cost,
                                 cost_fn=ME.tie_pattern if inter_cost is None else None, tu_qp=x["tu_qp"], lambda8_by_qp=x["lambda8_by_qp"], qp=x["qp"],
-                                mutation=mutation, pricer=x["pricer"])
+                                mutation=mutation, pricer=x["pricer"], **temporal)
 
 
 @functools.lru_cache(maxsize=None)

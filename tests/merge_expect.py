@@ -5,7 +5,8 @@ stage with every block on list 0, run on the CLIPPED vectors, its sa8d through t
 O.inter_recon / O.inter_recon_chroma on mv_pred, the boundary strengths through O.deblock_bs_inter on mv_out.
 
 Restated here in Python, with the reference's line numbers beside each statement: the candidate list
-(CUData::getInterMergeCandidates, common/cudata.cpp:1458-1712, P slice, one reference, no temporal candidate), CUData::clipMv
+(CUData::getInterMergeCandidates, common/cudata.cpp:1458-1712, P slice, one reference; its spatial and temporal part,
+spatial_candidates(), serves tests/bmerge_expect.py as well, the temporal candidate itself comes from tests/tmvp_expect.py), CUData::clipMv
 (cudata.cpp:1915-1928), getTUBits (search.h:246-249), the two strict comparisons (analysis.cpp:2833 among the candidates, :1650 against
 the inter candidate) and the walk in coding order.  The candidate list cannot be pinned against compiled reference code with what
 oracle/ offers: getInterMergeCandidates is a method of CUData that reads the encoder's CU tree, and the reference build exports
@@ -20,6 +21,7 @@ import numpy as np
 
 import intra_expect as IE
 import intra_inter_expect as IX
+import tmvp_expect as TX
 
 O, F, H, harness, SC = IE.O, IE.F, IE.H, IE.harness, IE.SC
 
@@ -31,12 +33,7 @@ MUTATIONS = ("le_against_inter", "le_among_candidates", "prune_every_pair", "b2_
 NEIGHBOURS = (("A1", -1, 0), ("B1", 0, -1), ("B0", 1, -1), ("A0", -1, 1), ("B2", -1, -1))
 
 
-def unpack(v):
-    s16 = lambda x: (x & 0xffff) - ((x & 0x8000) << 1)
-    return s16(int(v)), s16(int(v) >> 16)
-
-
-pack = IX.pack_mv
+unpack, pack = TX.unpack, TX.pack
 
 
 def clip_mv(v, x0, y0, width, height, ctu=64):
@@ -52,59 +49,120 @@ def tu_bits(i, num, mutation=None):
     return i + (1 if (i < num - 1 or mutation == "tu_bits_without_saving") else 0)
 
 
-def candidate_list(nb, max_merge, mutation=None):
-    """getInterMergeCandidates for a P slice with one reference and no temporal candidate.  nb: {"A1" | "B1" | "B0" | "A0" | "B2": packed
-    motion, or None where the neighbour is not available}.  Returns (list of (motion, origin)), flags) - origin is the neighbour's name
-    or "zero"; with one reference hasEqualMotion is equality of the vectors."""
+SPATIAL_FLAGS = ("pruned_B1", "pruned_B0", "pruned_A0", "pruned_B2", "B0_equals_A1_kept", "B2_dropped_at_four", "cut_at_max")
+TEMPORAL_FLAGS = ("temporal_present", "temporal_equals_spatial_kept", "temporal_cut_at_max", "temporal_fills_last_slot")
+
+
+def spatial_candidates(nb, max_merge, equal, zero, temporal=None, mutation=None):
+    """The spatial and the temporal candidates of getInterMergeCandidates (cudata.cpp:1495-1650) with every return at count ==
+    maxNumMergeCand, for a P and a B slice alike.  nb: {"A1" | "B1" | "B0" | "A0" | "B2": a motion, or None where the neighbour is not
+    available}; equal(p, q, record=True): p.hasEqualMotion(q) - with record it is a pruning decision (the caller may note why and may
+    mutate it), without it the reference's plain comparison; zero: the slice's zero candidate; temporal: the scaled collocated motion or
+    None.  Returns ([(motion, origin)], flags, whether the list was returned full) - origin is the neighbour's name or "temporal"."""
     a1, b1, b0, a0, b2 = (nb.get(k) for k in ("A1", "B1", "B0", "A0", "B2"))
-    every = mutation == "prune_every_pair"
-    out, fl = [], {k: False for k in ("pruned_B1", "pruned_B0", "pruned_A0", "pruned_B2", "B0_equals_A1_kept", "B2_dropped_at_four", "cut_at_max")}
+    out, fl = [], {k: False for k in SPATIAL_FLAGS + TEMPORAL_FLAGS}
 
-    def seen(v):
-        return every and any(v == m for m, _ in out)
+    def pruned(v, name, *against):
+        hit = any(p is not None and equal(p, v) for p in against) or (mutation == "prune_every_pair" and any(v == m for m, _ in out))
+        fl["pruned_" + name] |= hit
+        return hit
 
-    def cut(later):
+    def full(later=()):
+        if len(out) < max_merge:
+            return False
         fl["cut_at_max"] = any(v is not None for v in later)
-        return out, fl
+        fl["temporal_cut_at_max"] = temporal is not None and not fl["temporal_present"]
+        return True
     if a1 is not None:                                                                        # :1495-1510
         out.append((a1, "A1"))
-        if len(out) == max_merge:
-            return cut((b1, b0, a0, b2))
-    if b1 is not None:                                                                        # :1517-1532
-        if (a1 is not None and a1 == b1) or seen(b1):
-            fl["pruned_B1"] = True
-        else:
-            out.append((b1, "B1"))
-            if len(out) == max_merge:
-                return cut((b0, a0, b2))
-    if b0 is not None:                                                                        # :1537-1551: against B1 only
-        if (b1 is not None and b1 == b0) or seen(b0):
-            fl["pruned_B0"] = True
-        else:
-            fl["B0_equals_A1_kept"] = a1 is not None and a1 == b0
-            out.append((b0, "B0"))
-            if len(out) == max_merge:
-                return cut((a0, b2))
-    if a0 is not None:                                                                        # :1556-1570: against A1 only
-        if (a1 is not None and a1 == a0) or seen(a0):
-            fl["pruned_A0"] = True
-        else:
-            out.append((a0, "A0"))
-            if len(out) == max_merge:
-                return cut((b2,))
+        if full((b1, b0, a0, b2)):
+            return out, fl, True
+    if b1 is not None and not pruned(b1, "B1", a1):                                           # :1517-1532
+        out.append((b1, "B1"))
+        if full((b0, a0, b2)):
+            return out, fl, True
+    if b0 is not None and not pruned(b0, "B0", b1):                                           # :1537-1551: against B1 only
+        fl["B0_equals_A1_kept"] = a1 is not None and equal(a1, b0, False)
+        out.append((b0, "B0"))
+        if full((a0, b2)):
+            return out, fl, True
+    if a0 is not None and not pruned(a0, "A0", a1):                                           # :1556-1570: against A1 only
+        out.append((a0, "A0"))
+        if full((b2,)):
+            return out, fl, True
+    if mutation == "temporal_before_b2" and temporal is not None:
+        fl["temporal_present"] = True
+        out.append((temporal, "temporal"))
+        if full():
+            return out, fl, True
     if len(out) < 4 or mutation == "b2_regardless_of_count":                                  # :1573
-        if b2 is not None:                                                                    # :1577-1592: against A1 and B1
-            if (a1 is not None and a1 == b2) or (b1 is not None and b1 == b2) or seen(b2):
-                fl["pruned_B2"] = True
-            else:
-                out.append((b2, "B2"))
-                if len(out) == max_merge:
-                    return out, fl
+        if b2 is not None and not pruned(b2, "B2", a1, b1):                                   # :1577-1592: against A1 and B1
+            out.append((b2, "B2"))
+            if full():
+                return out, fl, True
     elif b2 is not None:
         fl["B2_dropped_at_four"] = True
+    if temporal is not None and mutation != "temporal_before_b2" and not (mutation == "temporal_pruned_against_a1" and a1 is not None and
+                                                                          equal(a1, temporal, False)):   # :1594-1650
+        fl["temporal_present"] = True
+        fl["temporal_equals_spatial_kept"] = any(equal(m, temporal, False) and equal(temporal, m, False) for m, _ in out)
+        out.append((temporal, "temporal"))                                                    # :1643-1645: no pruning
+        if len(out) == max_merge:                                                             # :1647-1648
+            fl["temporal_fills_last_slot"] = True
+            if mutation == "zero_fill_after_full":
+                out[-1] = (zero, "zero")                        # a fill that runs once more writes over the last slot
+            return out, fl, True
+    return out, fl, False
+
+
+def candidate_list(nb, max_merge, mutation=None, temporal=None):
+    """getInterMergeCandidates for a P slice with one reference.  nb: {"A1" | "B1" | "B0" | "A0" | "B2": packed motion, or None where the
+    neighbour is not available}; temporal: the scaled packed vector getColMVP gives, or None.  Returns ([(motion, origin)], flags) -
+    origin is the neighbour's name, "temporal" or "zero"; with one reference hasEqualMotion is equality of the vectors."""
+    out, fl, _ = spatial_candidates(nb, max_merge, lambda p, q, record=True: p == q, 0, temporal, mutation)
     while len(out) < max_merge:                                                               # :1676-1710: zero vectors, refIdx 0 (one reference)
         out.append((0, "zero"))
     return out, fl
+
+
+class Grid:
+    """The blocks of a picture in coding order (CTUs in raster order, z-order inside) and a block's five neighbours: what the walks of a P
+    and of a B slice share."""
+
+    def __init__(self, w64, h64, level):
+        self.n, self.bpc, self.nblk, self.cw, self.chh = TX._grid(w64, h64, level)
+        self.tot = self.cw * self.chh * self.nblk
+
+    def index(self, gbx, gby):
+        return ((gby // self.bpc) * self.cw + gbx // self.bpc) * self.nblk + IE.zindex(gbx % self.bpc, gby % self.bpc)
+
+    def block(self, b):
+        """(bx, by) inside the CTU and (x0, y0), the first sample."""
+        ctu, z = divmod(b, self.nblk)
+        bx, by = IE.zorder(z)
+        return bx, by, ((ctu % self.cw) * self.bpc + bx) * self.n, ((ctu // self.cw) * self.bpc + by) * self.n
+
+    def neighbours(self, b, coded, masks, uncoded=None, border_masks=True):
+        """(nb, where) of block b: nb[name] = coded(q) for a neighbour q inside the picture and coded before b, else None (or uncoded(q),
+        what the `available_by_position` mutation reads); where[name] = q for every neighbour inside the picture."""
+        bx, by, x0, y0 = self.block(b)
+        nb, where = {}, {}
+        for name, dx, dy in NEIGHBOURS:
+            nx, ny = x0 // self.n + dx, y0 // self.n + dy
+            nb[name] = None
+            if not (0 <= nx < self.cw * self.bpc and 0 <= ny < self.chh * self.bpc):          # getPU*: outside the picture
+                continue
+            q = where[name] = self.index(nx, ny)
+            if q < b:                                                                         # already coded
+                nb[name] = coded(q)
+            elif uncoded is not None:
+                nb[name] = uncoded(q)
+            elif name in ("B0", "A0"):
+                below = name == "A0" and by + 1 == self.bpc
+                masks["A0_below_ctu" if below else name + "_not_yet_coded"][b] = True
+        masks["A0_from_left_ctu"][b] = nb["A0"] is not None and bx == 0 and border_masks
+        masks["B0_from_above_right_ctu"][b] = nb["B0"] is not None and bx + 1 == self.bpc and by == 0 and border_masks
+        return nb, where
 
 
 class Pricer:
@@ -166,49 +224,29 @@ class Pricer:
         raise AssertionError("the walk did not settle")
 
 
-def walk(w64, h64, level, searched, max_merge, price, lam, inter_cost=None, cost_fn=None, mutation=None):
+def walk(w64, h64, level, searched, max_merge, price, lam, inter_cost=None, cost_fn=None, mutation=None, col=None, cur_delta=None, tmvp_mutation=None):
     """The walk in coding order.  searched: packed vector per block (index = ctu * blocks + z); price(block, packed clipped vector) ->
-    sa8d; lam(block) -> lambda8; inter_cost: int per block, or cost_fn(block, merge cost) -> the inter cost to decide against.  Returns
-    merge, merge_idx (uint8), mv_out, mv_pred (packed int32 per block), cost / best int32 [blocks, 2], inter_cost (what was decided
-    against) and the masks."""
-    assert mutation is None or mutation in MUTATIONS
-    n = 8 << level
-    bpc = 64 // n
-    nblk = bpc * bpc
-    cw, chh = w64 // 64, h64 // 64
-    tot = cw * chh * nblk
-    bw, bh = cw * bpc, chh * bpc
+    sa8d; lam(block) -> lambda8; inter_cost: int per block, or cost_fn(block, merge cost) -> the inter cost to decide against; col: a
+    TX.ColSource - the list then has the temporal candidate - with cur_delta = curPOC - refPOC; tmvp_mutation: one of TX.P_MUTATIONS.
+    Returns merge, merge_idx (uint8), mv_out, mv_pred (packed int32 per block), cost / best int32 [blocks, 2], inter_cost (what was
+    decided against) and the masks: MASKS, and TX.P_MASKS as well where the walk is told of a collocated picture (col or cur_delta)."""
+    assert mutation is None or (mutation in MUTATIONS and tmvp_mutation is None)
+    assert tmvp_mutation is None or tmvp_mutation in TX.P_MUTATIONS
+    g = Grid(w64, h64, level)
+    tot = g.tot
     final = np.zeros(tot, np.int64)
+    from_temporal = np.zeros(tot, bool)                       # the block's motion came from a temporal candidate, directly or inherited
     merge, idx = np.zeros(tot, np.uint8), np.zeros(tot, np.uint8)
     mv_out, mv_pred = np.zeros(tot, np.int32), np.zeros(tot, np.int32)
     cost, best, ic_used = np.zeros((tot, 2), np.int32), np.zeros((tot, 2), np.int32), np.zeros(tot, np.int64)
-    masks = {k: np.zeros(tot, bool) for k in MASKS}
-
-    def index(gbx, gby):
-        return ((gby // bpc) * cw + gbx // bpc) * nblk + IE.zindex(gbx % bpc, gby % bpc)
+    masks = {k: np.zeros(tot, bool) for k in MASKS + TX.P_MASKS}
+    coded = lambda q: int(searched[q]) if mutation == "searched_not_final" else int(final[q])
+    uncoded = (lambda q: int(searched[q])) if mutation == "available_by_position" else None     # what a block that is not yet decided holds
     for b in range(tot):
-        ctu, z = divmod(b, nblk)
-        bx, by = IE.zorder(z)
-        gbx, gby = (ctu % cw) * bpc + bx, (ctu // cw) * bpc + by
-        x0, y0 = gbx * n, gby * n
-        nb, where = {}, {}
-        for name, dx, dy in NEIGHBOURS:
-            nx, ny = gbx + dx, gby + dy
-            nb[name] = None
-            if not (0 <= nx < bw and 0 <= ny < bh):                                           # getPU*: outside the picture
-                continue
-            q = index(nx, ny)
-            where[name] = q
-            if q < b:                                                                         # already coded (CTUs in raster order, z-order inside)
-                nb[name] = int(searched[q]) if mutation == "searched_not_final" else int(final[q])
-            elif mutation == "available_by_position":
-                nb[name] = int(searched[q])                                                   # what a block that is not yet decided holds
-            elif name in ("B0", "A0"):
-                below = name == "A0" and by + 1 == bpc
-                masks["A0_below_ctu" if below else name + "_not_yet_coded"][b] = True
-        masks["A0_from_left_ctu"][b] = nb["A0"] is not None and bx == 0 and mutation is None
-        masks["B0_from_above_right_ctu"][b] = nb["B0"] is not None and bx + 1 == bpc and by == 0 and mutation is None
-        cands, fl = candidate_list(nb, max_merge, mutation)
+        _, _, x0, y0 = g.block(b)
+        nb, where = g.neighbours(b, coded, masks, uncoded, mutation is None)
+        temporal = TX.temporal_vectors(col, level, x0, y0, (cur_delta,), masks, b, tmvp_mutation)
+        cands, fl = candidate_list(nb, max_merge, mutation or tmvp_mutation, temporal and temporal[0])
         for k, v in fl.items():
             masks[k][b] = v
         lam8 = lam(b)
@@ -240,8 +278,13 @@ def walk(w64, h64, level, searched, max_merge, price, lam, inter_cost=None, cost
         masks["merge_won"][b] = True
         masks["tie_lowest_index"][b] = ties > 0
         masks["won_" + origin][b] = True
-        masks["inherits_inherited"][b] = origin != "zero" and where[origin] < b and bool(merge[where[origin]])
+        spatial = origin in where and where[origin] < b
+        masks["inherits_inherited"][b] = spatial and bool(merge[where[origin]])
+        masks["inherits_temporal"][b] = spatial and bool(from_temporal[where[origin]])
+        from_temporal[b] = origin == "temporal" or masks["inherits_temporal"][b]
         masks["clip_changed_prediction"][b] = clip_mv(v, x0, y0, w64, h64) != v
+    if col is None and cur_delta is None:
+        masks = {k: masks[k] for k in MASKS}
     return dict(merge=merge, merge_idx=idx, mv_out=mv_out, mv_pred=mv_pred, cost=cost, best=best, inter_cost=ic_used, masks=masks)
 
 
@@ -262,9 +305,10 @@ def level_slots(level, nctu):
 
 
 def stage_expectation(depth, cur_y, ref_y, w64, h64, level, mv, max_merge, lambda8, inter_cost=None, cost_fn=None, tu_qp=None, lambda8_by_qp=None, qp=0,
-                      mutation=None, pricer=None):
-    """What x265hip_merge_decide leaves for the searched records mv (int32 [ctu*85, 2]).  Returns walk()'s dictionary with mv_out / mv_pred
-    as RECORDS of the level's slots (the cost word the input's for an inter block, the merge cost for a merged one)."""
+                      mutation=None, pricer=None, col=None, cur_delta=None, tmvp_mutation=None):
+    """What x265hip_merge_decide (with col: x265hip_merge_decide_col) leaves for the searched records mv (int32 [ctu*85, 2]).  Returns
+    walk()'s dictionary with mv_out / mv_pred as RECORDS of the level's slots (the cost word the input's for an inter block, the merge cost
+    for a merged one)."""
     pr = pricer or Pricer(depth, cur_y, ref_y, w64, h64, level)
     nctu = (w64 // 64) * (h64 // 64)
     sl = level_slots(level, nctu)
@@ -273,7 +317,8 @@ def stage_expectation(depth, cur_y, ref_y, w64, h64, level, mv, max_merge, lambd
     def lam(b):
         gx, gy = pr.position(b)
         return IX.block_lambda(tu_qp, lambda8_by_qp, lambda8, qp, depth, gx, gy)
-    e = pr.fixpoint(lambda price: walk(w64, h64, level, searched, max_merge, price, lam, inter_cost=inter_cost, cost_fn=cost_fn, mutation=mutation))
+    e = pr.fixpoint(lambda price: walk(w64, h64, level, searched, max_merge, price, lam, inter_cost=inter_cost, cost_fn=cost_fn, mutation=mutation,
+                                       col=col, cur_delta=cur_delta, tmvp_mutation=tmvp_mutation))
     words = np.where(e["merge"] != 0, e["cost"][:, 1], np.asarray(mv).reshape(-1, 2)[sl, 0])
     e["vec_out"], e["vec_pred"] = e["mv_out"], e["mv_pred"]
     e["mv_out"], e["mv_pred"] = records(e["vec_out"], words, level, nctu)[sl], records(e["vec_pred"], words, level, nctu)[sl]
@@ -325,9 +370,10 @@ def reference_prediction(lib, ref_y, w64, h64, level, mv):
 
 
 def p_chain(depth, cur, ref, w64, h64, rng_r, subme, level, qp, max_merge=3, sao_rdo=None, tu_flags=H.TU_SIGN_HIDE, base_bits=IX.BASE_BITS, lambda8=IE.LAMBDA8,
-            cores=0, tu_qp=None, cu_qp=None, lambda8_by_qp=None):
+            cores=0, tu_qp=None, cu_qp=None, lambda8_by_qp=None, col=None, cur_delta=None):
     """One P picture with merge blocks through the oracle, stage by stage (the CPU twin of stages.MergePFramePipeline.run with chroma,
-    deblocking and SAO applied; tu_qp / cu_qp / lambda8_by_qp: what set_qp_maps hands on).  Every stage output by name."""
+    deblocking and SAO applied; tu_qp / cu_qp / lambda8_by_qp: what set_qp_maps hands on; col / cur_delta: the handed collocated field of
+    a step with temporal_mvp).  Every stage output by name."""
     S = IE.importlib.import_module("x265-yuuki-asuna_amd.stages")
     _, _, stride, rows, org = F.padded_dims(w64, h64)
     nctu = (w64 // 64) * (h64 // 64)
@@ -338,7 +384,8 @@ def p_chain(depth, cur, ref, w64, h64, rng_r, subme, level, qp, max_merge=3, sao
     _, mv = SC.search_head(depth, y, r, stride, org, w64, h64, rng_r, subme, cores=cores)
     it = IX.inter_side(depth, cur, ref, w64, h64, level, mv, qp, (qpc, qpc), tu_flags, base_bits=base_bits, lambda8=lambda8, table=IX.s_bitsizes(4 * rng_r + 4),
                        tu_qp=tu_qp, lambda8_by_qp=lambda8_by_qp)
-    e = stage_expectation(depth, y, r, w64, h64, level, mv, max_merge, lambda8, inter_cost=it["inter_cost"][:, 1], tu_qp=tu_qp, lambda8_by_qp=lambda8_by_qp, qp=qp)
+    e = stage_expectation(depth, y, r, w64, h64, level, mv, max_merge, lambda8, inter_cost=it["inter_cost"][:, 1], tu_qp=tu_qp, lambda8_by_qp=lambda8_by_qp, qp=qp,
+                          col=col, cur_delta=cur_delta)
     full = lambda recs: records(recs[:, 1], recs[:, 0], level, nctu)
     mvp, mvo = full(e["mv_pred"]), full(e["mv_out"])
     cd = IX.inter_side(depth, cur, ref, w64, h64, level, mvp, qp, (qpc, qpc), tu_flags, tu_qp=tu_qp)          # the coding from mv_pred

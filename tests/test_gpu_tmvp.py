@@ -1,8 +1,7 @@
 """GPU parity of the temporal merge candidate: x265hip_col_field_build against the restatement of tests/tmvp_expect.py, both _col entries
 without a field against the entries without the candidate (word for word: the guard of the shared kernel bodies), both _col entries on
 the cases of tests/tmvp_cases.py against the restated walks, stages.MergePFramePipeline / MergeBFramePipeline with temporal_mvp stage by
-stage against the oracle chains run around the restated walks, and MiniGop with temporal_mvp.  Equal means equal."""
-import functools
+stage against the oracle chains run with the handed field, and MiniGop with temporal_mvp.  Equal means equal."""
 import importlib
 
 import numpy as np
@@ -222,8 +221,8 @@ def _handed_source(level, w, h, vector_of, cur_delta, col_delta):
 
 @pytest.mark.parametrize("depth,level", [(8, 1), (10, 0)])
 def test_p_step_with_temporal_mvp_every_stage_equals_the_oracle_chain(depth, level):
-    """MergePFramePipeline(temporal_mvp=True).run with a handed field: every stage against merge_expect.p_chain with the walk swapped for
-    the restated one; afterwards the step's own field is the compression of its mv_out."""
+    """MergePFramePipeline(temporal_mvp=True).run with a handed field: every stage against merge_expect.p_chain with that field;
+    afterwards the step's own field is the compression of its mv_out."""
     import torch
     B = importlib.import_module("bench")
     dev = _dev()
@@ -239,9 +238,8 @@ def test_p_step_with_temporal_mvp_every_stage_equals_the_oracle_chain(depth, lev
     torch.cuda.synchronize()
     assert marks[:4] == ["me", "subpel", "inter_cost", "merge"]
     pad = lambda yuv: IE.padded_planes(yuv)[0]
-    walk = functools.partial(TX.walk_p, col=src, cur_delta=cur_delta)
-    with TX.swapped(ME, walk):
-        cpu_out = ME.p_chain(depth, pad((cy,) + cc), pad((ry,) + rc), w, h, 12, 2, level, qp, sao_rdo=pipe.sao_rdo, cores=B.effective_cpus())
+    cpu_out = ME.p_chain(depth, pad((cy,) + cc), pad((ry,) + rc), w, h, 12, 2, level, qp, sao_rdo=pipe.sao_rdo, cores=B.effective_cpus(), col=src,
+                         cur_delta=cur_delta)
     bad = BE.compare(ME.p_device_outputs(pipe, cur.host.dtype), cpu_out)
     assert not bad, bad
     nctu = (w // 64) * (h // 64)
@@ -270,9 +268,8 @@ def test_b_step_with_temporal_mvp_every_stage_equals_the_oracle_chain(depth, lev
     pipe.run(cur, r0, r1, col=_col_field(src, depth), cur_deltas=cur_deltas)
     torch.cuda.synchronize()
     hp = [IE.padded_planes(p)[0] for p in yuv]
-    walk = functools.partial(TX.walk_b, col=src, cur_deltas=cur_deltas)
-    with TX.swapped(BM, walk):
-        cpu_out = BM.merge_b_chain(depth, hp[1], hp[0], hp[2], w, h, 12, 2, level, qp, sao_rdo=pipe.sao_rdo, cores=B.effective_cpus())
+    cpu_out = BM.merge_b_chain(depth, hp[1], hp[0], hp[2], w, h, 12, 2, level, qp, sao_rdo=pipe.sao_rdo, cores=B.effective_cpus(), col=src,
+                               cur_deltas=cur_deltas)
     bad = BE.compare(BM.device_outputs(pipe, cur.host.dtype), cpu_out)
     assert not bad, bad
     with pytest.raises(ValueError):

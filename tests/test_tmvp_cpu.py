@@ -1,9 +1,9 @@
 """CPU-only checks of the temporal merge candidate (x265hip_col_field_build, x265hip_merge_decide_col, x265hip_b_merge_decide_col):
 declaration, export, record layout and argument validation of the three entries, and the expectation the GPU tests compare against
-(tests/tmvp_expect.py): the scaling values, hand-worked positions and lists written out from the statements of cudata.cpp, the compression
-rule of the collocated field, what the cases of tests/tmvp_cases.py reach (the coverage condition), that every mutation of the restated
-walks changes the expectation of a counted number of cases, and that without a collocated field the restated walks give what
-merge_expect / bmerge_expect give."""
+(tests/tmvp_expect.py and the temporal part of tests/merge_expect.py / bmerge_expect.py): the scaling values, hand-worked positions and
+lists written out from the statements of cudata.cpp, the compression rule of the collocated field, what the cases of tests/tmvp_cases.py
+reach (the coverage condition), that every mutation of the walks' temporal part changes the expectation of a counted number of cases, and
+that with a collocated field without motion the walks give what they give without a field."""
 import ctypes
 import importlib
 import os
@@ -246,9 +246,9 @@ def test_hand_worked_positions():
 def test_hand_worked_lists_of_a_p_slice():
     """Written out from cudata.cpp:1495-1650, 1687-1709."""
     a, b, c, d, e, t = (ME.pack(*v) for v in ((4, 0), (0, 8), (-12, 3), (7, 7), (-1, -1), (9, -9)))
-    L = lambda nb, mm, tv, mut=None: [m for m, _ in TX.candidate_list_p(nb, mm, tv, mut)[0]]
-    O = lambda nb, mm, tv: [o for _, o in TX.candidate_list_p(nb, mm, tv)[0]]
-    flags = lambda nb, mm, tv: {k for k, v in TX.candidate_list_p(nb, mm, tv)[1].items() if v}
+    L = lambda nb, mm, tv, mut=None: [m for m, _ in ME.candidate_list(nb, mm, mut, temporal=tv)[0]]
+    O = lambda nb, mm, tv: [o for _, o in ME.candidate_list(nb, mm, temporal=tv)[0]]
+    flags = lambda nb, mm, tv: {k for k, v in ME.candidate_list(nb, mm, temporal=tv)[1].items() if v and k in ME.TEMPORAL_FLAGS}
     none = dict(A1=None, B1=None, B0=None, A0=None, B2=None)
     full = dict(A1=a, B1=b, B0=c, A0=d, B2=e)
     # the temporal candidate after B2 (:1594), and filling the last slot: no zero candidate behind it (:1647-1648)
@@ -268,10 +268,11 @@ def test_hand_worked_lists_of_a_p_slice():
     # cut because count == max_merge in front of it (:1508, :1530, :1549, :1568, :1590)
     assert L(dict(none, A1=a, B1=b, B0=c), 3, t) == [a, b, c] and flags(dict(none, A1=a, B1=b, B0=c), 3, t) == {"temporal_cut_at_max"}
     assert L(dict(none, A1=a), 1, t) == [a] and L(none, 1, t) == [t]
-    # both positions without motion: the list of merge_expect
-    for nb in (none, full, dict(full, A0=None), dict(none, A1=0, B1=a)):
+    # both positions without motion: the list without the candidate (with four spatial candidates B2 is not looked at; a shorter list is
+    # the longer one cut at max_merge)
+    for nb, five in ((none, [0] * 5), (full, [a, b, c, d, 0]), (dict(full, A0=None), [a, b, c, e, 0]), (dict(none, A1=0, B1=a), [0, a, 0, 0, 0])):
         for mm in (1, 2, 3, 5):
-            assert L(nb, mm, None) == [m for m, _ in ME.candidate_list(nb, mm)[0]] and not flags(nb, mm, None)
+            assert L(nb, mm, None) == five[:mm] and not flags(nb, mm, None)
     # a temporal vector of (0, 0) is a candidate like any other
     assert L(dict(none, A1=a), 3, 0) == [a, 0, 0] and O(dict(none, A1=a), 3, 0) == ["A1", "temporal", "zero"]
 
@@ -280,8 +281,8 @@ def test_hand_worked_lists_of_a_b_slice():
     """Written out from cudata.cpp:1594-1709 with isInterB."""
     a, b, t0, t1 = (ME.pack(*v) for v in ((4, 0), (0, 8), (6, -2), (-6, 2)))
     m = BM.motion
-    L = lambda nb, mm, tv, same=False, mut=None: [x[:3] for x, _ in TX.candidate_list_b(nb, mm, tv, same, mut)[0]]
-    O = lambda nb, mm, tv: [o for _, o in TX.candidate_list_b(nb, mm, tv)[0]]
+    L = lambda nb, mm, tv, same=False, mut=None: [x[:3] for x, _ in BM.candidate_list(nb, mm, same, mut, temporal=tv)[0]]
+    O = lambda nb, mm, tv: [o for _, o in BM.candidate_list(nb, mm, temporal=tv)[0]]
     none = dict(A1=None, B1=None, B0=None, A0=None, B2=None)
     T = m(3, t0, t1)
     two = dict(none, A1=m(1, a), B1=m(2, 0, b))
@@ -290,7 +291,7 @@ def test_hand_worked_lists_of_a_b_slice():
     assert L(two, 5, T) == [(1, a, 0), (2, 0, b), (3, t0, t1), (3, a, b), (3, a, t1)]
     assert O(two, 5, T) == ["A1", "B1", "temporal", "combined", "combined_temporal"]
     # without it cutoff = 2: one pair, then the zero candidates - the list of bmerge_expect
-    assert L(two, 5, None) == [(1, a, 0), (2, 0, b), (3, a, b), (3, 0, 0), (3, 0, 0)] == [x[:3] for x, _ in BM.candidate_list(two, 5)[0]]
+    assert L(two, 5, None) == [(1, a, 0), (2, 0, b), (3, a, b), (3, 0, 0), (3, 0, 0)]
     # left out of the cutoff (2 pairs instead of 6) the third pair is never looked at
     assert L(two, 5, T, mut="temporal_not_in_cutoff") == [(1, a, 0), (2, 0, b), (3, t0, t1), (3, a, b), (3, 0, 0)]
     # one spatial candidate: cutoff = 2 * 1, pair (0, 1) = A1 list 0 x temporal list 1; (1, 0) needs A1's list 1, which it does not use
@@ -302,11 +303,11 @@ def test_hand_worked_lists_of_a_b_slice():
     assert L(one, 5, m(3, t0, a), same=False)[2] == (3, a, a)
     # filling the last slot: neither combined nor zero candidates follow; cut when the spatial candidates fill the list
     assert L(two, 3, T) == [(1, a, 0), (2, 0, b), (3, t0, t1)] and L(two, 2, T) == [(1, a, 0), (2, 0, b)]
-    fl = TX.candidate_list_b(two, 2, T)[1]
+    fl = BM.candidate_list(two, 2, temporal=T)[1]
     assert fl["temporal_cut_at_max"] and not fl["temporal_present"]
     # hasEqualMotion needs equal directions: a dir-3 temporal candidate never equals a single-list neighbour
-    assert not TX.candidate_list_b(dict(none, A1=m(1, t0)), 3, T)[1]["temporal_equals_spatial_kept"]
-    assert TX.candidate_list_b(dict(none, A1=m(3, t0, t1)), 3, T)[1]["temporal_equals_spatial_kept"]
+    assert not BM.candidate_list(dict(none, A1=m(1, t0)), 3, temporal=T)[1]["temporal_equals_spatial_kept"]
+    assert BM.candidate_list(dict(none, A1=m(3, t0, t1)), 3, temporal=T)[1]["temporal_equals_spatial_kept"]
     # the two lists' vectors of the candidate: one collocated vector, one scale per list
     assert (TX.scale_mv(ME.pack(12, -4), 2, 4), TX.scale_mv(ME.pack(12, -4), -2, 4)) == (t0, t1)
 
@@ -355,14 +356,15 @@ GEOMETRY_COUNTS = {0: dict(rb_in_right_ctu=28, rb_absent_last_ctu_row=23, rb_out
 def test_the_cases_reach_every_outcome(level, slice_type):
     """The coverage condition: at each level every mask holds for at least 3 % of the blocks of at least one 8-bit 192x128 case; the four
     position masks hold for exactly the blocks geometry gives them, in every case with a field."""
-    cases, names = (C.P_COVER, TX.P_MASKS) if slice_type == "P" else (C.B_COVER, TX.B_MASKS)
+    cases, names, others = (C.P_COVER, TX.P_MASKS, ME.MASKS) if slice_type == "P" else (C.B_COVER, TX.B_MASKS, BM.MASKS)
     best = {k: (0.0, None) for k in names}
     for c in cases:
         if c.base.level != level:
             continue
         masks = C.expectation(c)["e"]["masks"]
-        assert set(masks) == set(names)
-        for k, m in masks.items():
+        assert set(masks) == set(names + others)               # (the others' coverage: tests/test_merge_cpu.py, tests/test_bmerge_cpu.py)
+        for k in names:
+            m = masks[k]
             if float(m.mean()) > best[k][0]:
                 best[k] = (float(m.mean()), c.id)
         want = GEOMETRY_COUNTS[level]
@@ -376,7 +378,7 @@ def test_the_cases_reach_every_outcome(level, slice_type):
         assert share >= 0.03, (slice_type, level, k, share)
 
 
-# cases of P_COVER (39) / B_COVER (33) whose expectation a mutation of the restated walk changes: the numbers of DESIGN.md section 21
+# cases of P_COVER (39) / B_COVER (33) whose expectation a mutation of the walk's temporal part changes: the numbers of DESIGN.md section 21
 P_MUTATION_COUNTS = {"temporal_before_b2": 18, "temporal_pruned_against_a1": 6, "centre_first": 17, "rb_below_ctu_allowed": 8, "rb_from_this_ctu": 16,
                      "no_unit_mask": 19, "no_scaling": 21, "floor_division": 3, "no_negative_rounding": 6, "zero_fill_after_full": 25}
 B_MUTATION_COUNTS = {"temporal_before_b2": 9, "temporal_pruned_against_a1": 6, "centre_first": 12, "rb_below_ctu_allowed": 8, "rb_from_this_ctu": 8,
@@ -406,8 +408,8 @@ def test_mutations_of_the_walks_change_the_counted_cases(slice_type):
 
 
 def test_without_a_field_the_restated_walks_are_the_walks_without_the_candidate():
-    """With the `none` field (and with no field at all) tmvp_expect's walks give, on every case of merge_cases.ALL_CASES and
-    bmerge_cases.ALL_CASES, exactly what merge_expect / bmerge_expect give."""
+    """With the `none` field (and with no field at all) the walks give, on every case of merge_cases.ALL_CASES and bmerge_cases.ALL_CASES,
+    exactly what they give when they are not told about a collocated picture."""
     for c in MC.ALL_CASES:
         want = MC.expectation(c)["e"]
         tc = C.PCase(c.id, c, "none", 4, 4)

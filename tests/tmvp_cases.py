@@ -34,8 +34,6 @@ import functools
 import numpy as np
 
 import bmerge_cases as BC
-import bmerge_expect as BM
-import intra_expect as IE
 import merge_cases as MC
 import merge_expect as ME
 import tmvp_expect as TX
@@ -206,15 +204,11 @@ def inputs(tc):
 
 
 def run_stage(tc, tmvp_mutation=None, col="case"):
-    """The expectation of a case, of a mutation of the restated walk on it, or (col=None) of the walk without a collocated field."""
+    """The expectation of a case, of a mutation of the walk's temporal part on it, or (col=None) of the walk without a collocated field."""
     src = source(tc) if col == "case" else col
     if isinstance(tc, PCase):
-        walk = functools.partial(TX.walk_p, col=src, cur_delta=tc.cur_delta, tmvp_mutation=tmvp_mutation)
-        with TX.swapped(ME, walk):
-            return MC.run_stage(tc.base)
-    walk = functools.partial(TX.walk_b, col=src, cur_deltas=tc.cur_deltas, tmvp_mutation=tmvp_mutation)
-    with TX.swapped(BM, walk):
-        return BC.run_stage(tc.base)
+        return MC.run_stage(tc.base, col=src, cur_delta=tc.cur_delta, tmvp_mutation=tmvp_mutation)
+    return BC.run_stage(tc.base, col=src, cur_deltas=tc.cur_deltas, tmvp_mutation=tmvp_mutation)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,17 +1,18 @@
 // b_merge_decide.h - the merge arm of the sa8d choice of a B picture's blocks, on gfx950 (included at the end of tu_kernels.hip behind
-// merge_decide.h: the wave walk of that file, the staging steps of b_sa8d_decide.h, the Hadamard stage of decision_common.h).
+// merge_decide.h: the candidate walk of merge_walk.h, the staging steps of b_sa8d_decide.h, the Hadamard stage of decision_common.h).
 //
 // Analysis::checkMerge2Nx2N_rd0_4 at RD level 0 (source/encoder/analysis.cpp:2787-2838) and the comparisons of
 // Analysis::compressInterCU_rd0_4 (analysis.cpp:1650-1655), per N x N block (N = 8 << level) of the TU stages' grid - one 2Nx2N CU each, CTUs
-// in raster order, blocks in z-order, one slice, a B slice with one reference per list, no temporal candidate:
+// in raster order, blocks in z-order, one slice, a B slice with one reference per list; the COL instances (x265hip_b_merge_decide_col with
+// a field) have the temporal candidate of col_field.h, the others none:
 //   list   CUData::getInterMergeCandidates (common/cudata.cpp:1458-1712) with isInterB: a candidate is (dir, mv[0], mv[1]), an unused
-//          list's vector is 0.  Spatial A1, B1, B0, A0 and B2 (only while count < 4) with the availability of merge_decide.h; pruned pairs
-//          B1-A1, B0-B1, A0-A1, B2-A1, B2-B1 by hasEqualMotion (cudata.cpp:1439-1455): equal directions first, then the vectors of the
-//          used lists.  Combined candidates (:1652-1683): cutoff = count * (count - 1) once, pairs in the order of 0xEDC984 / 0xB73621,
-//          {3, cand[i].mv[0], cand[j].mv[1]} where cand[i] uses list 0 and cand[j] list 1, unless both lists name one picture and the two
-//          vectors are equal.  The rest {3, (0, 0), (0, 0)} (:1684-1709, one reference per list).  Returned once count == max_merge, at
-//          every increment.  A neighbour's motion is what it ENDED UP with.
-//   price  Predict::motionCompensation (predict.cpp:168-215) after clipMv of every used vector (the limits of merge_decide.h, per list):
+//          list's vector is 0.  The spatial candidates of merge_walk.h, pruned by hasEqualMotion (cudata.cpp:1439-1455): equal directions
+//          first, then the vectors of the used lists; the temporal one, never pruned (:1594-1650).  Combined candidates (:1652-1683):
+//          cutoff = count * (count - 1) once, pairs in the order of 0xEDC984 / 0xB73621, {3, cand[i].mv[0], cand[j].mv[1]} where cand[i]
+//          uses list 0 and cand[j] list 1, unless both lists name one picture and the two vectors are equal.  The rest {3, (0, 0), (0, 0)}
+//          (:1684-1709, one reference per list).  Returned once count == max_merge, at every increment.  A neighbour's motion is what it
+//          ENDED UP with.
+//   price  Predict::motionCompensation (predict.cpp:168-215) after clipMv of every used vector (the limits of merge_walk.h, per list):
 //          dir 3 = addAvg of the two lists' 14-bit intermediates, dir 1 / 2 = predInterLumaPixel of that list; dist = cu[].sa8d, bits =
 //          getTUBits(i, max_merge), cost = dist + ((bits * lambda8 + 128) >> 8); the best with strict <.
 //   choice the block keeps its inter winner iff inter_cost < merge cost, inter_cost = the cost of b_sa8d_decide.h's winner.  The reference
@@ -83,22 +84,10 @@ __global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const
     const long rst = a.frefStrideB / BPP, fst = a.fencStrideB / BPP;
 
     // ---- the border of the motion field: the final motion of the blocks around the CTU that earlier waves left in dir / mv0_out / mv1_out --
-    if (tid < FW + BPC)
+    merge_field_border<N, BMotion>(tid, cxb, cyb, a.ctusW, [&](const size_t nctu, const int nz)
     {
-        const int rx = tid < FW ? tid - 1 : -1, ry = tid < FW ? -1 : tid - FW;                  // relative to the CTU's first block
-        const int gbx = cxb * BPC + rx, gby = cyb * BPC + ry;
-        BMotion m = { 0, 0, 0 };
-        if (gbx >= 0 && gby >= 0 && gbx < blocksW)
-        {
-            const int ncx = gbx / BPC, ncy = gby / BPC, nz = ip_zidx(gbx - ncx * BPC, gby - ncy * BPC);
-            const size_t nctu = (size_t)(ncy * a.ctusW + ncx);
-            m.dir = a.dir[nctu * NPU + nz];
-            m.mv0 = a.mvOut[0][nctu * 85 + lbase + nz].y;
-            m.mv1 = a.mvOut[1][nctu * 85 + lbase + nz].y;
-        }
-        const int f = (ry + 1) * FW + rx + 1;
-        sField[0][f] = m.dir; sField[1][f] = m.mv0; sField[2][f] = m.mv1;
-    }
+        return BMotion{ a.dir[nctu * NPU + nz], a.mvOut[0][nctu * 85 + lbase + nz].y, a.mvOut[1][nctu * 85 + lbase + nz].y };
+    }, [&](const int f, const BMotion& m) { sField[0][f] = m.dir; sField[1][f] = m.mv0; sField[2][f] = m.mv1; });
     // ---- what the decisions read of the CTU's own blocks, off the serial chain: the inter winner, its cost, the block's lambda ------------
     if (tid < NPU)
     {
@@ -107,8 +96,7 @@ __global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const
         sWinnerDir[z] = a.dirIn[(size_t)ctu * NPU + z];
         sWinner[0][z] = a.mv[0][(size_t)ctu * 85 + lbase + z];
         sWinner[1][z] = a.mv[1][(size_t)ctu * 85 + lbase + z];
-        sInter[z] = a.interCost[((size_t)ctu * NPU + z) * a.interCostStride];
-        sLambda[z] = block_lambda8(a.lambda8, a.lambdaByQp, a.qpMap, a.qp, a.depth, a.ctusW, (cxb * 64 + bxz * N) >> 3, (cyb * 64 + byz * N) >> 3);
+        merge_prefetch_block<N>(a, ctu, cxb, cyb, z, sInter, sLambda);
         if constexpr (COL)                                                  // another picture's finished field: off the chain as well
         {
             // m_bCheckLDC and m_colFromL0Flag are false (dpb.cpp:193-195): both lists read list 0 of the collocated picture, so the
@@ -128,33 +116,14 @@ __global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const
         const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
         const int gbx = cxb * BPC + bxz, gby = cyb * BPC + byz;
         const int x0 = gbx * N, y0 = gby * N;
-        // getPULeft / getPUAbove / getPUAboveRight / getPUBelowLeft / getPUAboveLeft on this grid: inside the picture and already coded
-        auto available = [&](const int nbx, const int nby)
-        {
-            if (nbx < 0 || nby < 0 || nbx >= blocksW || nby >= blocksH) return false;
-            const int ncx = nbx / BPC, ncy = nby / BPC;
-            if (ncx != cxb || ncy != cyb) return ncy * a.ctusW + ncx < ctu;
-            return ip_zidx(nbx - ncx * BPC, nby - ncy * BPC) < z;
-        };
-        auto motion = [&](const int dx, const int dy)
-        {
-            const int f = (byz + dy + 1) * FW + bxz + dx + 1;
-            return BMotion{ sField[0][f], sField[1][f], sField[2][f] };
-        };
         const int num = a.maxMerge;
         int count = 0;
         auto put = [&](const BMotion& m) { sCand[0][count] = m.dir; sCand[1][count] = m.mv0; sCand[2][count] = m.mv1; count++; };
-        const bool avA1 = available(gbx - 1, gby), avB1 = available(gbx, gby - 1), avB0 = available(gbx + 1, gby - 1);
-        const bool avA0 = available(gbx - 1, gby + 1), avB2 = available(gbx - 1, gby - 1);
-        const BMotion none = { 0, 0, 0 };
-        const BMotion mA1 = avA1 ? motion(-1, 0) : none, mB1 = avB1 ? motion(0, -1) : none, mB0 = avB0 ? motion(1, -1) : none;
-        const BMotion mA0 = avA0 ? motion(-1, 1) : none, mB2 = avB2 ? motion(-1, -1) : none;
-        // `count < num` in front of every step is the reference's return at count == maxNumMergeCand
-        if (avA1) put(mA1);                                                                                          // cudata.cpp:1495-1510
-        if (count < num && avB1 && (!avA1 || !b_equal_motion(mA1, mB1))) put(mB1);                                   // :1517-1532
-        if (count < num && avB0 && (!avB1 || !b_equal_motion(mB1, mB0))) put(mB0);                                   // :1537-1551
-        if (count < num && avA0 && (!avA1 || !b_equal_motion(mA1, mA0))) put(mA0);                                   // :1556-1570
-        if (count < num && count < 4 && avB2 && (!avA1 || !b_equal_motion(mA1, mB2)) && (!avB1 || !b_equal_motion(mB1, mB2))) put(mB2);   // :1573-1593
+        merge_spatial_candidates<BMotion>(gbx, gby, num, count, merge_available<N>(cxb, cyb, ctu, a.ctusW, blocksW, blocksH, z), [&](const int dx, const int dy)
+        {
+            const int f = (byz + dy + 1) * FW + bxz + dx + 1;
+            return BMotion{ sField[0][f], sField[1][f], sField[2][f] };
+        }, b_equal_motion, put);
         if constexpr (COL) { if (count < num && sTemporalOk[z]) put(BMotion{ 3, sTemporal[0][z], sTemporal[1][z] }); }   // :1594-1650: never pruned
         if (count < num)                                                                                             // :1652-1683
         {
@@ -172,10 +141,7 @@ __global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const
         }
         const BMotion zero = { 3, 0, 0 };
         while (count < num) put(zero);                                                                               // :1684-1709
-        // clipMv (cudata.cpp:1915-1928) of every used vector
-        const int xmin = -((64 + 8 + x0 - 1) << 2), xmax = (width + 8 - x0 - 1) << 2;
-        const int ymin = -((64 + 8 + y0 - 1) << 2), ymax = (height + 8 - y0 - 1) << 2;
-        auto clip = [&](const int c) { return merge_pack(min(xmax, max(xmin, (int)(int16_t)(c & 0xffff))), min(ymax, max(ymin, (int)(int16_t)(c >> 16)))); };
+        const auto clip = merge_clip(x0, y0, width, height);               // of every used vector
         int slots = 0;
         for (int i = 0; i < num; i++)
         {
@@ -233,17 +199,9 @@ __global__ void __launch_bounds__(256) b_merge_decide_kernel(BMergeArgs a, const
         }
         if (tid == 0)
         {
-            const int lambda8 = sLambda[z];
-            const int num = a.maxMerge;
-            int bestI = 0, bestSad = 0;
-            long long bestCost = 0;
-            for (int i = 0; i < num; i++)
-            {
-                const int sad = sSlotSad[sSlotOf[i]];
-                const int bits = i + (i < num - 1 ? 1 : 0);                                                  // getTUBits, search.h:246-249
-                const long long cost = (long long)sad + rd_sad_rate(bits, lambda8);
-                if (i == 0 || cost < bestCost) { bestI = i; bestSad = sad; bestCost = cost; }                // analysis.cpp:2833
-            }
+            const MergeBest won = merge_price(a.maxMerge, sLambda[z], sSlotSad, sSlotOf);
+            const int bestI = won.i, bestSad = won.sad;
+            const long long bestCost = won.cost;
             const size_t blk = (size_t)ctu * NPU + z, rec = (size_t)ctu * 85 + lbase + z;
             const int2 w0 = sWinner[0][z], w1 = sWinner[1][z];
             const int ic = sInter[z];
@@ -291,11 +249,9 @@ namespace x265hip {
 static int b_merge_decide_run(const char* who, const x265hip_b_merge_decide_params* p, const int32_t* colMv, const int16_t* colDelta, const int curDelta0,
                               const int curDelta1, void* stream)
 {
-    // argument checks first: they need no device (at most 4 bits and lambda8 <= 2^24 keep the rate term below 2^19 and the cost inside int32)
-    if (decision_record_refused(who, p, !p || !p->fenc || !p->fref0 || !p->fref1 || !p->dir_in || !p->mv0 || !p->mv1 || !p->inter_cost || !p->merge ||
-                                !p->merge_idx || !p->dir || !p->mv0_out || !p->mv1_out || !p->mv0_pred || !p->mv1_pred || !p->cost)) return X265HIP_EINVAL;
-    if (p->max_merge < 1 || p->max_merge > 5) { set_error("%s: max_merge %d out of 1..5", who, p->max_merge); return X265HIP_EINVAL; }
-    if (inter_cost_stride_refused(who, p->inter_cost_stride)) return X265HIP_EINVAL;
+    // argument checks first: they need no device
+    if (merge_operands_refused(who, p, !p || !p->fenc || !p->fref0 || !p->fref1 || !p->dir_in || !p->mv0 || !p->mv1 || !p->inter_cost || !p->merge ||
+                               !p->merge_idx || !p->dir || !p->mv0_out || !p->mv1_out || !p->mv0_pred || !p->mv1_pred || !p->cost)) return X265HIP_EINVAL;
     // the walk reads a block's inter winner from dir_in / mv0 / mv1 and its neighbours' final motion from dir / mv*_out: shared arrays would
     // change what a second run sees
     if (b_merge_records_alias((p->width / 64) * (p->height / 64), p))
@@ -316,13 +272,9 @@ static int b_merge_decide_run(const char* who, const x265hip_b_merge_decide_para
     a.cost = (int2*)p->cost; a.best = (int2*)p->best; a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
     a.colMv = colMv; a.colDelta = colDelta; a.curDelta[0] = curDelta0; a.curDelta[1] = curDelta1;
     hipStream_t s = (hipStream_t)stream;
-    for_each_wave(a.ctusW, a.ctusH, [&](const int w, const int cyLo, const int n)
+    merge_launch_waves(a.ctusW, a.ctusH, p->depth, p->level, colMv != nullptr, [&](auto px, auto size, auto col, const int n, const int w, const int cyLo)
     {
-        for_depth_level(p->depth, p->level, [&](auto px, auto size)
-        {
-            if (colMv) hipLaunchKernelGGL((b_merge_decide_kernel<decltype(px), decltype(size)::value, true>), dim3(n), dim3(256), 0, s, a, w, cyLo);
-            else hipLaunchKernelGGL((b_merge_decide_kernel<decltype(px), decltype(size)::value, false>), dim3(n), dim3(256), 0, s, a, w, cyLo);
-        });
+        hipLaunchKernelGGL((b_merge_decide_kernel<decltype(px), decltype(size)::value, decltype(col)::value>), dim3(n), dim3(256), 0, s, a, w, cyLo);
     });
     X265HIP_TRY(hipGetLastError());
     return 0;
@@ -339,8 +291,7 @@ extern "C" int x265hip_b_merge_decide_col(const x265hip_b_merge_decide_col_param
 {
     using namespace x265hip;
     if (!p) { set_error("b_merge_decide_col: NULL operand"); return X265HIP_EINVAL; }
-    if (!p->col_mv != !p->col_delta) { set_error("b_merge_decide_col: col_mv and col_delta go together"); return X265HIP_EINVAL; }
-    if (tmvp_delta_refused("b_merge_decide_col", "cur_delta0", p->cur_delta0) || tmvp_delta_refused("b_merge_decide_col", "cur_delta1", p->cur_delta1))
-        return X265HIP_EINVAL;
+    if (col_operands_refused("b_merge_decide_col", p->col_mv, p->col_delta) || tmvp_delta_refused("b_merge_decide_col", "cur_delta0", p->cur_delta0) ||
+        tmvp_delta_refused("b_merge_decide_col", "cur_delta1", p->cur_delta1)) return X265HIP_EINVAL;
     return b_merge_decide_run("b_merge_decide_col", &p->base, p->col_mv, p->col_delta, p->cur_delta0, p->cur_delta1, stream);
 }

@@ -6,8 +6,9 @@
 // schedule of the three walks that follow the coding order, and the depth x level dispatch of every launch.
 //
 // Two things stay where they are because sharing them changed the kernels' code for the worse (more instructions, more scalar spills):
-// the "inside the picture and coded before this block" test of intra_picture_kernel and merge_decide_kernel, and the quarter geometry
-// (zof / rx0 / ry0) of inter_sa8d_cost_kernel and b_sa8d_decide_kernel.
+// the "inside the picture and coded before this block" test of intra_picture_kernel, and the quarter geometry (zof / rx0 / ry0) of
+// inter_sa8d_cost_kernel and b_sa8d_decide_kernel.  The two merge kernels share that test, with the rest of their candidate walk, through
+// merge_walk.h: there it kept their code as a lambda that refers to the kernel's own variables (profiles/merge_walk_code_identity.txt).
 #pragma once
 
 namespace x265hip {

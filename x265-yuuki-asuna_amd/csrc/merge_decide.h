@@ -1,28 +1,22 @@
 // merge_decide.h - the merge arm of the sa8d choice of a P picture's blocks, on gfx950 (included at the end of tu_kernels.hip behind
-// inter_sa8d_cost.h: it prices every candidate with that file's sa8d_slots()).
+// inter_sa8d_cost.h and merge_walk.h: it prices every candidate with the former's sa8d_slots() and walks the list of the latter).
 //
 // Analysis::checkMerge2Nx2N_rd0_4 at RD level 0 (source/encoder/analysis.cpp:2787-2838, 2870-2871) and the comparison of
 // Analysis::compressInterCU_rd0_4 (analysis.cpp:1650), per N x N block (N = 8 << level) of the TU stages' grid - one 2Nx2N CU each, CTUs
-// in raster order, blocks in z-order, one slice, a P slice with one reference, no temporal candidate:
-//   list   CUData::getInterMergeCandidates (common/cudata.cpp:1458-1712): A1 (left), B1 (above), B0 (above right), A0 (below left), B2
-//          (above left, only while count < 4); pruned pairs B1-A1, B0-B1, A0-A1, B2-A1, B2-B1 and no other (a B0 equal to A1 stays);
-//          returned once count == max_merge; the rest (0, 0).  A neighbour is available inside the picture and before the block in
-//          coding order; its motion is what it ENDED UP with (its candidate where it merged, its searched vector where it did not).
-//   price  dist = cu[].sa8d(fenc, predInterLumaPixel(fref, clipMv(mv_i))), bits = getTUBits(i, max_merge) = i + (i < max_merge - 1)
-//          (search.h:246-249), cost = dist + ((bits * lambda8 + 128) >> 8); the best with strict <: the lowest index wins a tie
-//   clipMv cudata.cpp:1915-1928 (from Predict::motionCompensation, predict.cpp:92): x into [-((64 + 8 + x0 - 1) << 2), (width + 8 - x0 - 1)
-//          << 2], y alike - for the prediction only; the CU keeps the unclipped vector, which later neighbours inherit.  A clipped vector
-//          reaches at most 71 + 3 samples before the picture and N + 10 behind it: with the planes' margins (96 / 80) the N + 7 rows and
-//          columns of a patch stay inside the padded plane at every level, so the kernel needs no further guard.
+// in raster order, blocks in z-order, one slice, a P slice with one reference; the COL instances (x265hip_merge_decide_col with a field)
+// have the temporal candidate of col_field.h, the others none:
+//   list   CUData::getInterMergeCandidates (common/cudata.cpp:1458-1712): the spatial candidates of merge_walk.h, the temporal one, never
+//          pruned (:1594-1650), returned once count == max_merge; the rest (0, 0).  A neighbour's motion is what it ENDED UP with (its
+//          candidate where it merged, its searched vector where it did not).
+//   price  dist = cu[].sa8d(fenc, predInterLumaPixel(fref, clipMv(mv_i))), rate and comparison of merge_walk.h
 //   choice the block keeps its searched vector iff inter_cost < merge cost (analysis.cpp:1650; a tie stays merge)
 //
 // Mapping: the candidate list reads motion only, never reconstruction, so the walk is the wave schedule of intra_picture.h without its
 // coding chain: wave = cx + 2 cy, one launch per wave, one workgroup of 256 threads per CTU of the wave, the CTU's blocks in z-order.
-// The CTU's motion field sits in LDS with a border of the left CTU's last column, the above CTU's last row and the two corners (read
-// from mv_out, which the earlier waves wrote); the blocks' searched records, inter costs and lambdas are fetched into LDS once, off the serial
-// chain.  Thread 0 builds the list, clips it and keeps one slot per distinct clipped vector -
-// evaluating equal vectors once is exact; the slots go through sa8d_slots() side by side (16 / 4 / 1 per pass at 8x8 / 16x16 / 32x32),
-// thread 0 prices the candidates and decides.
+// The CTU's motion field sits in LDS with its border (read from mv_out, which the earlier waves wrote); the blocks' searched records,
+// inter costs and lambdas are fetched into LDS once, off the serial chain.  Thread 0 builds the list, clips it and keeps one slot per
+// distinct clipped vector - evaluating equal vectors once is exact; the slots go through sa8d_slots() side by side (16 / 4 / 1 per pass
+// at 8x8 / 16x16 / 32x32), thread 0 prices the candidates and decides.
 #pragma once
 
 namespace x265hip {
@@ -42,8 +36,6 @@ struct MergeArgs
     const uint32_t* lambdaByQp;         // optional
     const int32_t* colMv; const int16_t* colDelta; int curDelta;   // the COL instances only: the collocated field (col_field.h)
 };
-
-__device__ __forceinline__ int merge_pack(const int qx, const int qy) { return (qx & 0xffff) | (int)((unsigned)qy << 16); }
 
 // COL: the list has the temporal candidate of col_field.h between B2 and the zero candidates (x265hip_merge_decide_col with a field)
 template <typename Px, int N, bool COL>
@@ -68,26 +60,15 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
     const long rst = a.frefStrideB / BPP, fst = a.fencStrideB / BPP;
 
     // ---- the border of the motion field: the final motion of the blocks around the CTU that earlier waves left in mv_out ----------------
-    if (tid < FW + BPC)
-    {
-        const int rx = tid < FW ? tid - 1 : -1, ry = tid < FW ? -1 : tid - FW;                  // relative to the CTU's first block
-        const int gbx = cxb * BPC + rx, gby = cyb * BPC + ry;
-        int v = 0;
-        if (gbx >= 0 && gby >= 0 && gbx < blocksW)
-        {
-            const int ncx = gbx / BPC, ncy = gby / BPC;
-            v = a.mvOut[(size_t)(ncy * a.ctusW + ncx) * 85 + lbase + ip_zidx(gbx - ncx * BPC, gby - ncy * BPC)].y;
-        }
-        sField[(ry + 1) * FW + rx + 1] = v;
-    }
+    merge_field_border<N, int>(tid, cxb, cyb, a.ctusW, [&](const size_t nctu, const int nz) { return a.mvOut[nctu * 85 + lbase + nz].y; },
+                               [&](const int slot, const int m) { sField[slot] = m; });
     // ---- what the decisions read of the CTU's own blocks, off the serial chain: the searched record, the inter cost, the block's lambda ---
     if (tid < NPU)
     {
         const int z = tid;
         const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
         sSearched[z] = a.mv[(size_t)ctu * 85 + lbase + z];
-        sInter[z] = a.interCost[((size_t)ctu * NPU + z) * a.interCostStride];
-        sLambda[z] = block_lambda8(a.lambda8, a.lambdaByQp, a.qpMap, a.qp, a.depth, a.ctusW, (cxb * 64 + bxz * N) >> 3, (cyb * 64 + byz * N) >> 3);
+        merge_prefetch_block<N>(a, ctu, cxb, cyb, z, sInter, sLambda);
         if constexpr (COL)                                                  // another picture's finished field: off the chain as well
         {
             int cmv = 0, cd = 0;
@@ -104,29 +85,14 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
         const int bxz = ip_zpos(z).x, byz = ip_zpos(z).y;
         const int gbx = cxb * BPC + bxz, gby = cyb * BPC + byz;
         const int x0 = gbx * N, y0 = gby * N;
-        // getPULeft / getPUAbove / getPUAboveRight / getPUBelowLeft / getPUAboveLeft on this grid: inside the picture and already coded
-        auto available = [&](const int nbx, const int nby)
-        {
-            if (nbx < 0 || nby < 0 || nbx >= blocksW || nby >= blocksH) return false;
-            const int ncx = nbx / BPC, ncy = nby / BPC;
-            if (ncx != cxb || ncy != cyb) return ncy * a.ctusW + ncx < ctu;
-            return ip_zidx(nbx - ncx * BPC, nby - ncy * BPC) < z;
-        };
-        auto motion = [&](const int dx, const int dy) { return sField[(byz + dy + 1) * FW + bxz + dx + 1]; };
-        const bool avA1 = available(gbx - 1, gby), avB1 = available(gbx, gby - 1), avB0 = available(gbx + 1, gby - 1);
-        const bool avA0 = available(gbx - 1, gby + 1), avB2 = available(gbx - 1, gby - 1);
-        const int mA1 = avA1 ? motion(-1, 0) : 0, mB1 = avB1 ? motion(0, -1) : 0, mB0 = avB0 ? motion(1, -1) : 0;
-        const int mA0 = avA0 ? motion(-1, 1) : 0, mB2 = avB2 ? motion(-1, -1) : 0;
         const int num = a.maxMerge;
         int count = 0;
-        if (avA1) sCand[count++] = mA1;                                                                  // cudata.cpp:1495-1510
-        if (count < num && avB1 && (!avA1 || mA1 != mB1)) sCand[count++] = mB1;                          // :1517-1532
-        if (count < num && avB0 && (!avB1 || mB1 != mB0)) sCand[count++] = mB0;                          // :1537-1551
-        if (count < num && avA0 && (!avA1 || mA1 != mA0)) sCand[count++] = mA0;                          // :1556-1570
-        if (count < num && count < 4 && avB2 && (!avA1 || mA1 != mB2) && (!avB1 || mB1 != mB2)) sCand[count++] = mB2;   // :1573-1593
+        merge_spatial_candidates<int>(gbx, gby, num, count, merge_available<N>(cxb, cyb, ctu, a.ctusW, blocksW, blocksH, z),
+                                      [&](const int dx, const int dy) { return sField[(byz + dy + 1) * FW + bxz + dx + 1]; },
+                                      [](const int p, const int q) { return p == q; }, [&](const int m) { sCand[count++] = m; });
         if constexpr (COL) { if (count < num && sTemporalOk[z]) sCand[count++] = sTemporal[z]; }          // :1594-1650: never pruned
         while (count < num) sCand[count++] = 0;                                                          // the zero candidates, refIdx 0
-        // clipMv (cudata.cpp:1915-1928)
+        // clipMv: merge_clip() of merge_walk.h, written out
         const int xmin = -((64 + 8 + x0 - 1) << 2), xmax = (width + 8 - x0 - 1) << 2;
         const int ymin = -((64 + 8 + y0 - 1) << 2), ymax = (height + 8 - y0 - 1) << 2;
         int slots = 0;
@@ -161,17 +127,9 @@ __global__ void __launch_bounds__(256) merge_decide_kernel(MergeArgs a, const in
         }
         if (tid == 0)
         {
-            const int lambda8 = sLambda[z];
-            const int num = a.maxMerge;
-            int bestI = 0, bestSad = 0;
-            long long bestCost = 0;
-            for (int i = 0; i < num; i++)
-            {
-                const int sad = sSlotSad[sSlotOf[i]];
-                const int bits = i + (i < num - 1 ? 1 : 0);                                                  // getTUBits, search.h:246-249
-                const long long cost = (long long)sad + rd_sad_rate(bits, lambda8);
-                if (i == 0 || cost < bestCost) { bestI = i; bestSad = sad; bestCost = cost; }                // analysis.cpp:2833
-            }
+            const MergeBest won = merge_price(a.maxMerge, sLambda[z], sSlotSad, sSlotOf);
+            const int bestI = won.i, bestSad = won.sad;
+            const long long bestCost = won.cost;
             const size_t blk = (size_t)ctu * NPU + z, rec = (size_t)ctu * 85 + lbase + z;
             const int2 searched = sSearched[z];
             const int ic = sInter[z];
@@ -197,11 +155,9 @@ namespace x265hip {
 // both entries: colMv / colDelta NULL = the list without a temporal candidate
 static int merge_decide_run(const char* who, const x265hip_merge_decide_params* p, const int32_t* colMv, const int16_t* colDelta, const int curDelta, void* stream)
 {
-    // argument checks first: they need no device (at most 4 bits and lambda8 <= 2^24 keep the rate term below 2^19 and the cost inside int32)
-    if (decision_record_refused(who, p, !p || !p->fenc || !p->fref || !p->mv || !p->inter_cost || !p->merge || !p->merge_idx || !p->mv_out || !p->mv_pred ||
-                                !p->cost)) return X265HIP_EINVAL;
-    if (p->max_merge < 1 || p->max_merge > 5) { set_error("%s: max_merge %d out of 1..5", who, p->max_merge); return X265HIP_EINVAL; }
-    if (inter_cost_stride_refused(who, p->inter_cost_stride)) return X265HIP_EINVAL;
+    // argument checks first: they need no device
+    if (merge_operands_refused(who, p, !p || !p->fenc || !p->fref || !p->mv || !p->inter_cost || !p->merge || !p->merge_idx || !p->mv_out || !p->mv_pred ||
+                               !p->cost)) return X265HIP_EINVAL;
     // the walk reads a block's searched vector from mv and its neighbours' final motion from mv_out: one array for both would change what a
     // second run sees
     if (p->mv_out == p->mv || p->mv_pred == p->mv || p->mv_out == p->mv_pred)
@@ -219,13 +175,9 @@ static int merge_decide_run(const char* who, const x265hip_merge_decide_params* 
     a.cost = (int2*)p->cost; a.best = (int2*)p->best; a.qpMap = p->qp_map; a.lambdaByQp = p->lambda8_by_qp;
     a.colMv = colMv; a.colDelta = colDelta; a.curDelta = curDelta;
     hipStream_t s = (hipStream_t)stream;
-    for_each_wave(a.ctusW, a.ctusH, [&](const int w, const int cyLo, const int n)
+    merge_launch_waves(a.ctusW, a.ctusH, p->depth, p->level, colMv != nullptr, [&](auto px, auto size, auto col, const int n, const int w, const int cyLo)
     {
-        for_depth_level(p->depth, p->level, [&](auto px, auto size)
-        {
-            if (colMv) hipLaunchKernelGGL((merge_decide_kernel<decltype(px), decltype(size)::value, true>), dim3(n), dim3(256), 0, s, a, w, cyLo);
-            else hipLaunchKernelGGL((merge_decide_kernel<decltype(px), decltype(size)::value, false>), dim3(n), dim3(256), 0, s, a, w, cyLo);
-        });
+        hipLaunchKernelGGL((merge_decide_kernel<decltype(px), decltype(size)::value, decltype(col)::value>), dim3(n), dim3(256), 0, s, a, w, cyLo);
     });
     X265HIP_TRY(hipGetLastError());
     return 0;
@@ -242,7 +194,6 @@ extern "C" int x265hip_merge_decide_col(const x265hip_merge_decide_col_params* p
 {
     using namespace x265hip;
     if (!p) { set_error("merge_decide_col: NULL operand"); return X265HIP_EINVAL; }
-    if (!p->col_mv != !p->col_delta) { set_error("merge_decide_col: col_mv and col_delta go together"); return X265HIP_EINVAL; }
-    if (tmvp_delta_refused("merge_decide_col", "cur_delta", p->cur_delta)) return X265HIP_EINVAL;
+    if (col_operands_refused("merge_decide_col", p->col_mv, p->col_delta) || tmvp_delta_refused("merge_decide_col", "cur_delta", p->cur_delta)) return X265HIP_EINVAL;
     return merge_decide_run("merge_decide_col", &p->base, p->col_mv, p->col_delta, p->cur_delta, stream);
 }

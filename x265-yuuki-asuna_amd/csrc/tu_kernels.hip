@@ -1453,9 +1453,12 @@ extern "C" int x265hip_intra_recon_batch(const x265hip_intra_recon_params* p, vo
 // the collocated motion field and the temporal merge candidate read from it (x265hip_col_field_build; the _col merge entries)
 #include "col_field.h"
 
+// the candidate walk both merge stages share: field border, availability, spatial list, clipMv, pricing; their operand checks and launch loop
+#include "merge_walk.h"
+
 // the merge arm of a P picture's sa8d choice (x265hip_merge_decide): sa8d_slots of inter_sa8d_cost.h, the wave schedule of decision_common.h
 #include "merge_decide.h"
 
-// the merge arm of a B picture's sa8d choice (x265hip_b_merge_decide): the walk of merge_decide.h over two-list candidates, the staging
+// the merge arm of a B picture's sa8d choice (x265hip_b_merge_decide): the walk of merge_walk.h over two-list candidates, the staging
 // steps of b_sa8d_decide.h
 #include "b_merge_decide.h"

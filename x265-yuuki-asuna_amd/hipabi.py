@@ -728,17 +728,17 @@ def merge_decide(depth, width, height, level, fenc, fenc_stride, fenc_off, fref,
     device int32 tensor, the block's word at element inter_cost_offset + block * inter_cost_stride (the defaults read the cost word of
     inter_sa8d_cost's pairs); merge / merge_idx: device uint8 [ctu][blocks] out; mv_out / mv_pred: device int32 records out (the CU's motion
     / what the TU stages predict from; neither may be mv); cost (and best): device int32 [ctu][blocks][2] out; qp_map: the LUMA plane of tu_qp."""
-    p = MergeDecideParams()
-    _fill_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge,
-                       merge_idx, mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp)
-    s = current_stream() if stream is None else stream
-    f = lib().x265hip_merge_decide
-    f.argtypes = [ctypes.POINTER(MergeDecideParams), ctypes.c_void_p]
-    check(f(ctypes.byref(p), s), "x265hip_merge_decide")
+    _merge_decide(depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge, merge_idx,
+                  mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp, stream)
 
 
-def _fill_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge,
-                       merge_idx, mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp):
+def _merge_decide(depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge, merge_idx,
+                  mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp, stream, col_mv=None, col_delta=None,
+                  cur_delta=None):
+    """The record of both P entries from their arguments, handed to x265hip_merge_decide_col where cur_delta is given, to
+    x265hip_merge_decide where it is not."""
+    rec = MergeDecideParams() if cur_delta is None else MergeDecideColParams()
+    p = rec if cur_delta is None else rec.base
     es = 1 if depth == 8 else 2
     p.depth, p.width, p.height, p.level, p.qp, p.lambda8, p.max_merge = depth, width, height, level, int(qp), int(lambda8), int(max_merge)
     p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
@@ -746,6 +746,15 @@ def _fill_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fenc_o
     p.mv, p.inter_cost, p.inter_cost_stride = mv.data_ptr(), inter_cost.data_ptr() + 4 * int(inter_cost_offset), int(inter_cost_stride)
     p.qp_map, p.lambda8_by_qp = _p(qp_map), _p(lambda8_by_qp)
     p.merge, p.merge_idx, p.mv_out, p.mv_pred, p.cost, p.best = merge.data_ptr(), merge_idx.data_ptr(), mv_out.data_ptr(), mv_pred.data_ptr(), cost.data_ptr(), _p(best)
+    if cur_delta is not None:
+        rec.col_mv, rec.col_delta, rec.cur_delta = _p(col_mv), _p(col_delta), int(cur_delta)
+    _call_merge_entry("x265hip_merge_decide" if cur_delta is None else "x265hip_merge_decide_col", rec, stream)
+
+
+def _call_merge_entry(name, rec, stream):
+    f = getattr(lib(), name)
+    f.argtypes = [ctypes.POINTER(type(rec)), ctypes.c_void_p]
+    check(f(ctypes.byref(rec), current_stream() if stream is None else stream), name)
 
 
 def merge_decide_col(depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge,
@@ -753,14 +762,8 @@ def merge_decide_col(depth, width, height, level, fenc, fenc_stride, fenc_off, f
                      lambda8_by_qp=None, stream=None):
     """x265hip_merge_decide_col: merge_decide with the temporal candidate between B2 and the zero candidates.  col_mv / col_delta: a
     collocated field (col_field_build; device int32 / int16 [ctu][16]) or both None; cur_delta = curPOC - refPOC, not 0."""
-    p = MergeDecideColParams()
-    _fill_merge_decide(p.base, depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge,
-                       merge_idx, mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp)
-    p.col_mv, p.col_delta, p.cur_delta = _p(col_mv), _p(col_delta), int(cur_delta)
-    s = current_stream() if stream is None else stream
-    f = lib().x265hip_merge_decide_col
-    f.argtypes = [ctypes.POINTER(MergeDecideColParams), ctypes.c_void_p]
-    check(f(ctypes.byref(p), s), "x265hip_merge_decide_col")
+    _merge_decide(depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge, merge_idx,
+                  mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp, stream, col_mv, col_delta, cur_delta)
 
 
 def col_field_build(depth, width, height, level, mv, poc_delta, col_mv, col_delta, intra=None, ref_idx=None, stream=None):
@@ -828,19 +831,18 @@ def b_merge_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1,
     tensor, the block's word at element inter_cost_offset + block * inter_cost_stride (the defaults read word 0 of b_sa8d_decide's cost);
     merge / merge_idx / dir_out: device uint8 [ctu][blocks] out; mv*_out / mv*_pred: device int32 records out (the CU's motion / what the
     two-list TU stages predict from); cost (and best): device int32 [ctu][blocks][2] out; qp_map: the LUMA plane of tu_qp."""
-    p = BMergeDecideParams()
-    _fill_b_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge,
-                         merge_idx, dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best, ref0, ref1, ref_ids, fenc_off, fref_off, inter_cost_stride,
-                         inter_cost_offset, qp, qp_map, lambda8_by_qp)
-    s = current_stream() if stream is None else stream
-    f = lib().x265hip_b_merge_decide
-    f.argtypes = [ctypes.POINTER(BMergeDecideParams), ctypes.c_void_p]
-    check(f(ctypes.byref(p), s), "x265hip_b_merge_decide")
+    _b_merge_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge, merge_idx,
+                    dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best, ref0, ref1, ref_ids, fenc_off, fref_off, inter_cost_stride, inter_cost_offset, qp,
+                    qp_map, lambda8_by_qp, stream)
 
 
-def _fill_b_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge,
-                         merge_idx, dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best, ref0, ref1, ref_ids, fenc_off, fref_off, inter_cost_stride,
-                         inter_cost_offset, qp, qp_map, lambda8_by_qp):
+def _b_merge_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge, merge_idx,
+                    dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best, ref0, ref1, ref_ids, fenc_off, fref_off, inter_cost_stride, inter_cost_offset, qp,
+                    qp_map, lambda8_by_qp, stream, col_mv=None, col_delta=None, cur_deltas=None):
+    """The record of both B entries from their arguments, handed to x265hip_b_merge_decide_col where cur_deltas is given, to
+    x265hip_b_merge_decide where it is not."""
+    rec = BMergeDecideParams() if cur_deltas is None else BMergeDecideColParams()
+    p = rec if cur_deltas is None else rec.base
     es = 1 if depth == 8 else 2
     p.depth, p.width, p.height, p.level, p.qp, p.lambda8, p.max_merge = depth, width, height, level, int(qp), int(lambda8), int(max_merge)
     p.ref_id0, p.ref_id1 = ref_ids
@@ -852,6 +854,9 @@ def _fill_b_merge_decide(p, depth, width, height, level, fenc, fenc_stride, fref
     p.merge, p.merge_idx, p.dir, p.ref0, p.ref1 = merge.data_ptr(), merge_idx.data_ptr(), dir_out.data_ptr(), _p(ref0), _p(ref1)
     p.mv0_out, p.mv1_out, p.mv0_pred, p.mv1_pred = mv0_out.data_ptr(), mv1_out.data_ptr(), mv0_pred.data_ptr(), mv1_pred.data_ptr()
     p.cost, p.best = cost.data_ptr(), _p(best)
+    if cur_deltas is not None:
+        rec.col_mv, rec.col_delta, rec.cur_delta0, rec.cur_delta1 = _p(col_mv), _p(col_delta), int(cur_deltas[0]), int(cur_deltas[1])
+    _call_merge_entry("x265hip_b_merge_decide" if cur_deltas is None else "x265hip_b_merge_decide_col", rec, stream)
 
 
 def b_merge_decide_col(depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge,
@@ -860,15 +865,9 @@ def b_merge_decide_col(depth, width, height, level, fenc, fenc_stride, fref0, fr
     """x265hip_b_merge_decide_col: b_merge_decide with the bi-predictive temporal candidate between B2 and the combined candidates.
     col_mv / col_delta: a collocated field (col_field_build) or both None; cur_deltas = (curPOC - POC(L0[0]), curPOC - POC(L1[0])),
     neither 0."""
-    p = BMergeDecideColParams()
-    _fill_b_merge_decide(p.base, depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge,
-                         merge, merge_idx, dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best, ref0, ref1, ref_ids, fenc_off, fref_off, inter_cost_stride,
-                         inter_cost_offset, qp, qp_map, lambda8_by_qp)
-    p.col_mv, p.col_delta, p.cur_delta0, p.cur_delta1 = _p(col_mv), _p(col_delta), int(cur_deltas[0]), int(cur_deltas[1])
-    s = current_stream() if stream is None else stream
-    f = lib().x265hip_b_merge_decide_col
-    f.argtypes = [ctypes.POINTER(BMergeDecideColParams), ctypes.c_void_p]
-    check(f(ctypes.byref(p), s), "x265hip_b_merge_decide_col")
+    _b_merge_decide(depth, width, height, level, fenc, fenc_stride, fref0, fref1, fref_stride, dir_in, mv0, mv1, inter_cost, lambda8, max_merge, merge, merge_idx,
+                    dir_out, mv0_out, mv1_out, mv0_pred, mv1_pred, cost, best, ref0, ref1, ref_ids, fenc_off, fref_off, inter_cost_stride, inter_cost_offset, qp,
+                    qp_map, lambda8_by_qp, stream, col_mv, col_delta, cur_deltas)
 
 
 def lowres_init(depth, src, src_stride, src_off, planes, stride, org, width, lines, margin_x, margin_y, stream=None):

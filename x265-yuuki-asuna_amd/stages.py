@@ -782,6 +782,14 @@ class _PictureStep:
         for st in list(luma) + list(planes3):
             st.lambda8_by_qp = None if maps is None else lambda8_by_qp
 
+    def _temporal_mvp_run_check(self, col, what, deltas):
+        """run() of a merge step: a field or POC distances (`what` names the argument) without temporal_mvp, or temporal_mvp without them."""
+        name = type(self).__name__
+        if not self.temporal_mvp and (col is not None or deltas is not None):
+            raise ValueError(f"{name}.run: col / {what} need temporal_mvp=True")
+        if self.temporal_mvp and deltas is None:
+            raise ValueError(f"{name}.run: temporal_mvp needs {what}")
+
     def _qp_maps_run_check(self):
         """run() with maps set, in a mode that would not honour them: raise instead of coding with other QPs than asked for."""
         if self.qp_maps is None:
@@ -2014,17 +2022,14 @@ class ColField:
         return {"col_mv": _sum64(self.col_mv), "col_delta": _sum64(self.col_delta)}
 
 
-class MergeDecide:
-    """The merge arm of a P picture's sa8d choice (x265hip_merge_decide; reference Analysis::checkMerge2Nx2N_rd0_4 at RD level 0,
-    analysis.cpp:2787-2838, CUData::getInterMergeCandidates, cudata.cpp:1458-1712, and the comparison of compressInterCU_rd0_4,
-    analysis.cpp:1650): per block, in coding order, the candidates its neighbours' final motion gives, priced by sa8d; the block merges
-    unless its inter candidate is strictly cheaper.  Owns merge / merge_idx uint8 [ctu][blocks], mv_out (the CUs' motion, unclipped) and
-    mv_pred (what the TU stages predict from) int32 [ctu*85][2], cost and best int32 [ctu][blocks][2]."""
+class _MergeStage:
+    """What MergeDecide and BMergeDecide share: the operating point, the grid, merge / merge_idx uint8 [ctu][blocks], cost and best int32
+    [ctu][blocks][2], the optional per-block QP inputs and the skip flags."""
 
-    def __init__(self, nctu, w64, h64, depth, level, device, max_merge=3, lambda8=1024, qp=0):
+    def __init__(self, nctu, w64, h64, depth, level, device, max_merge, lambda8, qp):
         import torch
         if not 1 <= int(max_merge) <= 5:
-            raise ValueError("MergeDecide: max_merge %r outside 1..5" % (max_merge,))
+            raise ValueError("%s: max_merge %r outside 1..5" % (type(self).__name__, max_merge))
         self.nctu, self.w64, self.h64, self.depth, self.level, self.qp = nctu, w64, h64, depth, level, qp
         self.max_merge, self.lambda8 = int(max_merge), int(lambda8)
         self.nblk = (64 >> (3 + level)) ** 2
@@ -2032,27 +2037,13 @@ class MergeDecide:
         nb = nctu * self.nblk
         self.merge = torch.zeros(nb, dtype=torch.uint8, device=device)
         self.merge_idx = torch.zeros(nb, dtype=torch.uint8, device=device)
-        self.mv_out = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device)
-        self.mv_pred = torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device)
         self.cost = torch.zeros(nb * 2, dtype=torch.int32, device=device)
         self.best = torch.zeros(nb * 2, dtype=torch.int32, device=device)
         self.qp_map, self.lambda8_by_qp = None, None          # as InterSa8dCost's
 
-    def run(self, cur: DevicePicture, ref: DevicePicture, mv, inter_cost, stream=None, inter_cost_stride=2, inter_cost_offset=1, col=None, cur_delta=None):
-        """mv: the searched records; inter_cost: InterSa8dCost.cost (the pairs; the defaults read their cost word).  col: a ColField of
-        the collocated picture - the list then has the temporal candidate (x265hip_merge_decide_col) - with cur_delta = curPOC - refPOC."""
-        if col is not None:
-            if cur_delta is None:
-                raise ValueError("MergeDecide.run: a collocated field needs cur_delta")
-            hipabi.merge_decide_col(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, cur.org, ref.t, ref.stride, ref.org, mv, inter_cost,
-                                    self.lambda8, self.max_merge, self.merge, self.merge_idx, self.mv_out, self.mv_pred, self.cost, col.col_mv, col.col_delta,
-                                    cur_delta, best=self.best, inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp,
-                                    qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp, stream=stream)
-            return
-        hipabi.merge_decide(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, cur.org, ref.t, ref.stride, ref.org, mv, inter_cost,
-                            self.lambda8, self.max_merge, self.merge, self.merge_idx, self.mv_out, self.mv_pred, self.cost, best=self.best,
-                            inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map,
-                            lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+    def _records(self, count, device):
+        import torch
+        return (torch.zeros(self.nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device) for _ in range(count))
 
     def skip_flags(self, rc, rc_c=None):
         """uint8 [ctu][blocks]: a merged block none of whose planes has a coded coefficient (encodeResidue sets MODE_SKIP there,
@@ -2062,6 +2053,32 @@ class MergeDecide:
         for r in (rc_c or ()):
             skip = skip & (r.num_sig == 0)
         return skip.to(torch.uint8)
+
+
+class MergeDecide(_MergeStage):
+    """The merge arm of a P picture's sa8d choice (x265hip_merge_decide; reference Analysis::checkMerge2Nx2N_rd0_4 at RD level 0,
+    analysis.cpp:2787-2838, CUData::getInterMergeCandidates, cudata.cpp:1458-1712, and the comparison of compressInterCU_rd0_4,
+    analysis.cpp:1650): per block, in coding order, the candidates its neighbours' final motion gives, priced by sa8d; the block merges
+    unless its inter candidate is strictly cheaper.  Owns merge / merge_idx uint8 [ctu][blocks], mv_out (the CUs' motion, unclipped) and
+    mv_pred (what the TU stages predict from) int32 [ctu*85][2], cost and best int32 [ctu][blocks][2]."""
+
+    def __init__(self, nctu, w64, h64, depth, level, device, max_merge=3, lambda8=1024, qp=0):
+        _MergeStage.__init__(self, nctu, w64, h64, depth, level, device, max_merge, lambda8, qp)
+        self.mv_out, self.mv_pred = self._records(2, device)
+
+    def run(self, cur: DevicePicture, ref: DevicePicture, mv, inter_cost, stream=None, inter_cost_stride=2, inter_cost_offset=1, col=None, cur_delta=None):
+        """mv: the searched records; inter_cost: InterSa8dCost.cost (the pairs; the defaults read their cost word).  col: a ColField of
+        the collocated picture - the list then has the temporal candidate (x265hip_merge_decide_col) - with cur_delta = curPOC - refPOC."""
+        if col is not None and cur_delta is None:
+            raise ValueError("MergeDecide.run: a collocated field needs cur_delta")
+        args = (self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, cur.org, ref.t, ref.stride, ref.org, mv, inter_cost, self.lambda8,
+                self.max_merge, self.merge, self.merge_idx, self.mv_out, self.mv_pred, self.cost)
+        kw = dict(best=self.best, inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map,
+                  lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+        if col is None:
+            hipabi.merge_decide(*args, **kw)
+        else:
+            hipabi.merge_decide_col(*args, col.col_mv, col.col_delta, cur_delta, **kw)
 
     def checksum(self):
         return {"merge": _sum64(self.merge), "merge_idx": _sum64(self.merge_idx), "mv_out": _sum64(self.mv_out), "mv_pred": _sum64(self.mv_pred),
@@ -2093,10 +2110,7 @@ class MergePFramePipeline(_Sa8dPStep):
         mark(name), if given, is called after every stage.  With temporal_mvp: col = the ColField of the collocated picture (the
         reference; None = a picture without motion) and cur_delta = curPOC - refPOC; after the walk self.col is this picture's field."""
         mark = mark or (lambda name: None)
-        if not self.temporal_mvp and (col is not None or cur_delta is not None):
-            raise ValueError("MergePFramePipeline.run: col / cur_delta need temporal_mvp=True")
-        if self.temporal_mvp and cur_delta is None:
-            raise ValueError("MergePFramePipeline.run: temporal_mvp needs cur_delta")
+        self._temporal_mvp_run_check(col, "cur_delta", cur_delta)
         mv = self._search(cur, ref, mark)
         self.ic.run(cur, ref, mv)
         mark("inter_cost")
@@ -2216,7 +2230,7 @@ class Sa8dBFramePipeline(_RefListStep):
         return out
 
 
-class BMergeDecide:
+class BMergeDecide(_MergeStage):
     """The merge arm of a B picture's sa8d choice (x265hip_b_merge_decide; reference Analysis::checkMerge2Nx2N_rd0_4 at RD level 0,
     analysis.cpp:2787-2838, CUData::getInterMergeCandidates with isInterB, cudata.cpp:1458-1712, and the comparisons of
     compressInterCU_rd0_4, analysis.cpp:1650-1655): per block, in coding order, the two-list candidates its neighbours' final motion gives
@@ -2226,22 +2240,13 @@ class BMergeDecide:
 
     def __init__(self, nctu, w64, h64, depth, level, device, max_merge=3, lambda8=1024, qp=0, ref_ids=(0, 1)):
         import torch
-        if not 1 <= int(max_merge) <= 5:
-            raise ValueError("BMergeDecide: max_merge %r outside 1..5" % (max_merge,))
-        self.nctu, self.w64, self.h64, self.depth, self.level, self.qp = nctu, w64, h64, depth, level, qp
-        self.max_merge, self.lambda8, self.ref_ids = int(max_merge), int(lambda8), tuple(ref_ids)
-        self.nblk = (64 >> (3 + level)) ** 2
-        self.waves = hipabi.intra_picture_waves(w64, h64)
+        _MergeStage.__init__(self, nctu, w64, h64, depth, level, device, max_merge, lambda8, qp)
+        self.ref_ids = tuple(ref_ids)
         nb = nctu * self.nblk
-        self.merge = torch.zeros(nb, dtype=torch.uint8, device=device)
-        self.merge_idx = torch.zeros(nb, dtype=torch.uint8, device=device)
         self.dir = torch.zeros(nb, dtype=torch.uint8, device=device)
         self.ref0 = torch.zeros(nb, dtype=torch.int8, device=device)
         self.ref1 = torch.zeros(nb, dtype=torch.int8, device=device)
-        self.mv0_out, self.mv1_out, self.mv0_pred, self.mv1_pred = (torch.zeros(nctu * PUS_PER_CTU * 2, dtype=torch.int32, device=device) for _ in range(4))
-        self.cost = torch.zeros(nb * 2, dtype=torch.int32, device=device)
-        self.best = torch.zeros(nb * 2, dtype=torch.int32, device=device)
-        self.qp_map, self.lambda8_by_qp = None, None          # as InterSa8dCost's
+        self.mv0_out, self.mv1_out, self.mv0_pred, self.mv1_pred = self._records(4, device)
 
     def run(self, cur: DevicePicture, ref0: DevicePicture, ref1: DevicePicture, dir_in, mv0, mv1, inter_cost, stream=None, inter_cost_stride=4,
             inter_cost_offset=0, col=None, cur_deltas=None):
@@ -2249,22 +2254,17 @@ class BMergeDecide:
         word 0).  col: the ColField of the collocated picture (L1[0]) - the list then has the temporal candidate
         (x265hip_b_merge_decide_col) - with cur_deltas = (curPOC - POC(L0[0]), curPOC - POC(L1[0]))."""
         assert ref0.stride == ref1.stride and ref0.org == ref1.org
-        if col is not None:
-            if cur_deltas is None:
-                raise ValueError("BMergeDecide.run: a collocated field needs cur_deltas")
-            hipabi.b_merge_decide_col(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, ref0.t, ref1.t, ref0.stride, dir_in, mv0, mv1, inter_cost,
-                                      self.lambda8, self.max_merge, self.merge, self.merge_idx, self.dir, self.mv0_out, self.mv1_out, self.mv0_pred,
-                                      self.mv1_pred, self.cost, col.col_mv, col.col_delta, cur_deltas, best=self.best, ref0=self.ref0, ref1=self.ref1,
-                                      ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org, inter_cost_stride=inter_cost_stride,
-                                      inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map, lambda8_by_qp=self.lambda8_by_qp, stream=stream)
-            return
-        hipabi.b_merge_decide(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, ref0.t, ref1.t, ref0.stride, dir_in, mv0, mv1, inter_cost,
-                              self.lambda8, self.max_merge, self.merge, self.merge_idx, self.dir, self.mv0_out, self.mv1_out, self.mv0_pred, self.mv1_pred,
-                              self.cost, best=self.best, ref0=self.ref0, ref1=self.ref1, ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org,
-                              inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map,
-                              lambda8_by_qp=self.lambda8_by_qp, stream=stream)
-
-    skip_flags = MergeDecide.skip_flags
+        if col is not None and cur_deltas is None:
+            raise ValueError("BMergeDecide.run: a collocated field needs cur_deltas")
+        args = (self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, ref0.t, ref1.t, ref0.stride, dir_in, mv0, mv1, inter_cost, self.lambda8,
+                self.max_merge, self.merge, self.merge_idx, self.dir, self.mv0_out, self.mv1_out, self.mv0_pred, self.mv1_pred, self.cost)
+        kw = dict(best=self.best, ref0=self.ref0, ref1=self.ref1, ref_ids=self.ref_ids, fenc_off=cur.org, fref_off=ref0.org,
+                  inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map,
+                  lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+        if col is None:
+            hipabi.b_merge_decide(*args, **kw)
+        else:
+            hipabi.b_merge_decide_col(*args, col.col_mv, col.col_delta, cur_deltas, **kw)
 
     def checksum(self):
         return {"merge": _sum64(self.merge), "merge_idx": _sum64(self.merge_idx), "merge_dir": _sum64(self.dir), "mv0_out": _sum64(self.mv0_out),
@@ -2308,10 +2308,7 @@ class MergeBFramePipeline(_RefListStep):
         luma plane of the coded picture; mark(name), if given, is called after every stage.  With temporal_mvp: col = the ColField of
         the collocated picture ref1 (None = a picture without motion: no temporal candidate) and cur_deltas = (curPOC - POC(ref0),
         curPOC - POC(ref1))."""
-        if not self.temporal_mvp and (col is not None or cur_deltas is not None):
-            raise ValueError("MergeBFramePipeline.run: col / cur_deltas need temporal_mvp=True")
-        if self.temporal_mvp and cur_deltas is None:
-            raise ValueError("MergeBFramePipeline.run: temporal_mvp needs cur_deltas")
+        self._temporal_mvp_run_check(col, "cur_deltas", cur_deltas)
         self._qp_maps_run_check()
         mark = mark or (lambda name: None)
         self._alloc_planes(cur)

@@ -529,14 +529,47 @@ __global__ void __launch_bounds__(SURF && BEST ? 768 : 1024, SURF && BEST ? 3 : 
 // 1024 MAD16   the four 8x8 keys of a row are four v_mad_u32_u16 (`half * 256 + sb`, op_sel picks the high half) that read the packed accumulator halves
 //              in place: no v_and / v_bfe unpacking, 32 of the 347 vector instructions of a block of 8 rows (MASK is meaningless then).  Needs CTAB (sb in
 //              an SGPR) and COLMIN (the key is `s << 8 | sb`).  1107 -> 1064 us per 4K launch (profiles/me_tailcut_mad16.txt).
+// 4096 ROWLDS  the row constant `sb` is a VGPR read from the table with a wave-uniform address (the LDS broadcasts it), a pair of rows at a time two rows ahead,
+//              not a v_readlane per row from a per-lane fetch a block ahead; the MAD16 multiplier moves to the one SGPR operand.  A block fetches its own per-lane
+//              64x64 constants pr[] when it starts (no second set of registers, no copies).  Needs CTAB.  Alone it spills four group invariants outside the block
+//              loop (128 registers); with OFFCHAIN it fits (128 registers, no scratch).
+// 8192 OFFCHAIN the LDS address of a block of 8 rows is handed on from block to block (the block before it computed it for its prefetch); the next one is the group's
+//              base + the rows' share (a chain of its own, + 8 rows per block) + the skew of row group by + n, byte n & 3 of a per-lane constant: v_bfe_u32 + two v_add_u32, where every block
+//              rebuilt both offsets with shifts, selects, masks and v_add3.  The offsets are LDS addresses (the window's base is part of them), so no `v_add x, 0, y`
+//              is left behind the opaque copies.  Needs RING.
+//              4096 | 8192 (both in the default set): 315 -> 290 vector instructions per block of 8 rows, 1066 -> 1037 us per 4K launch, the step 1.442 -> 1.411 ms
+//              (profiles/me_emission_rowlds_offchain.txt).
+// (A flag 2048, RSC - the 16x16 sums by a reduce-scatter inside the quad, `quad_perm:[2,3,0,1]` adds of the two packed halves under bank_mask 0x3 / 0xc - was not built:
+// a DPP bank is four consecutive lanes of a row, that is the quad itself, not a lane of every quad, so those masks switch whole quads off and the sums come out wrong.)
 // (A flag 512, TAILCUT - skip the ring slots of candidate rows past 2 R in the last seven window rows - was measured and dropped: the compiler removes those of
 // the 2 / 4 / 6-row tail by itself, the 30 quad-SADs left in the last full block cost one more block instantiation with branches (and spills), and the launch did not get faster.)
 // Results are identical for every FL (tests/test_gpu_me.py runs them all against the oracle).
+// OFFCHAIN: the 32-bit LDS address of a __shared__ object, and three dwords read from such an address (device passes only; the host pass sees stubs)
+__device__ __forceinline__ uint32_t lds_address(const void* p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)(const __attribute__((address_space(3))) uint8_t*)p;
+#else
+    (void)p; return 0;
+#endif
+}
+__device__ __forceinline__ void lds_load3(uint32_t addr, uint32_t (&d)[3])
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const __attribute__((address_space(3))) uint32_t* lp = (const __attribute__((address_space(3))) uint32_t*)addr;
+    d[0] = lp[0]; d[1] = lp[1]; d[2] = lp[2];
+#else
+    (void)addr; d[0] = d[1] = d[2] = 0;
+#endif
+}
 template <int PITCH, int FL>
 __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOff, int groupsPerWg)
 {
     constexpr bool LD64 = (FL & 1) != 0, CTAB = (FL & 2) != 0, PAIR64 = (FL & 4) != 0, DEFERX = (FL & 8) != 0, COLMIN = (FL & 16) != 0, MASK = (FL & 32) != 0;
     constexpr bool RING = (FL & 64) != 0, QUAD64 = (FL & 128) != 0, LDA = (FL & 256) != 0, MAD16 = (FL & 1024) != 0;
+    constexpr bool ROWLDS = (FL & 4096) != 0, OFFCHAIN = (FL & 8192) != 0;
+    static_assert(!ROWLDS || CTAB, "ROWLDS reads the row constants from the table in LDS");
+    static_assert(!OFFCHAIN || RING, "OFFCHAIN carries the three-address-register block offsets of RING");
     static_assert(!LDA || (!LD64 && !RING), "LDA is a window-load scheme of its own");
     static_assert(!MAD16 || (CTAB && COLMIN), "MAD16 builds the per-column keys from an SGPR row constant");
     static_assert(!QUAD64 || (PAIR64 && CTAB), "QUAD64 extends PAIR64 and takes its per-lane row constants from the table");
@@ -595,7 +628,10 @@ __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOf
     const uint32_t selK = 0x0c0c0000u | (uint32_t)((2 * kcol + 1) << 8) | (uint32_t)(2 * kcol);   // v_perm: u16 #kcol of {qhi, qlo}
     const int oddRow = (lane >> 4) & 1;                     // PAIR64: 0 = this lane ends up with row A's 64x64 total, 1 = row B's
     uint32_t c256 = 256u;                                   // MAD16: the multiplier lives in a VGPR (VOP3 reads one SGPR - the row constant - and 256 is no inline constant)
-    if (MAD16) asm volatile("" : "+v"(c256));
+    if (MAD16 && !ROWLDS) asm volatile("" : "+v"(c256));
+    if (MAD16 && ROWLDS) asm volatile("" : "+s"(c256));   // ROWLDS: the row constant is the VGPR operand, the multiplier the one SGPR
+    // OFFCHAIN: the skew of row group by + n is byte n & 3 of this per-lane constant (lds_skew_bytes: 0, 4, 64, 68 bytes by group & 3)
+    const uint32_t skewPack = __builtin_rotateright32(0x44400400u, 8 * (by & 3));
 
     const int T = 2 * R + 8;
     // a launch of few CTUs (a band of the frame-parallel ring, a small picture) deals a CTU's column groups over blockIdx.y workgroups - each stages the window for
@@ -604,7 +640,7 @@ __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOf
     const int gFirst = (int)blockIdx.y * gPer, gEnd = gFirst + gPer < NG ? gFirst + gPer : NG;
     for (int g = gFirst + wave; g < gEnd; g += nwaves)
     {
-        const uint32_t colOff = (uint32_t)((by * 8) * pitch + bx * 8 + 4 * g);
+        const uint32_t colOff = (uint32_t)((by * 8) * pitch + bx * 8 + 4 * g) + (OFFCHAIN ? lds_address(win) : 0u);
         // LDS byte offset of window row t0 of this lane's block column.  LD64 keeps it opaque: ds_read reaches 255 dwords past its address
         // register, so a block of 8 rows is read from THREE address registers (rows 0 - 3, rows 4 - 7, the next block's rows 0 - 1)
         auto block_off = [&](const int t0)
@@ -639,6 +675,11 @@ __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOf
 #pragma unroll
             for (int q = 0; q < 2; q++)
             {
+                if (OFFCHAIN)
+                {   // off is an LDS ADDRESS here (the window's base is part of the carried offset: nothing is added behind the opaque copies)
+                    lds_load3(off + (uint32_t)((p + q) * pitch), d[q]);
+                    continue;
+                }
                 const uint32_t* lp = reinterpret_cast<const uint32_t*>(win + off + (p + q) * pitch);
                 d[q][0] = lp[0]; d[q][1] = lp[1]; d[q][2] = lp[2];
             }
@@ -658,50 +699,74 @@ __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOf
         uint32_t cur[2][3], nxt[2][3];                      // !LD64: round 4's three dwords per row
         uint32_t d3[2][2][3];                               // RING: the same three dwords, two pairs of rows in flight, no copies (slot parity as above)
         (void)buf; (void)cur; (void)nxt; (void)d3;
-        if (LDA) ldpairA(buf[0], block_off(0), 0); else if (LD64) ldpair64(buf[0], block_off(0), 0); else if (RING) ldpair32(d3[0], block_off(0), 0); else ldpair32(cur, block_off(0), 0);
+        uint32_t offCur = block_off(0);                     // OFFCHAIN: the offset of the block about to run, handed on from block to block
+        if (LDA) ldpairA(buf[0], offCur, 0); else if (LD64) ldpair64(buf[0], offCur, 0); else if (RING) ldpair32(d3[0], offCur, 0); else ldpair32(cur, offCur, 0);
 
         // CTAB: a block's row constants, fetched while the block before it runs.  lane l holds the entry of window row t0 + (l & 7)
         // (m = t0 + (l & 7) - 7; the first block only completes m = 0), pr[q] the entry of the row this lane holds after the paired reduction
         // QUAD64: pr[0] / pr[1] = the entries of window rows 0..3 / 4..7 by the lane's 16-lane row, pr[2] / pr[3] = those of a tail pair (rows 0,1 / 4,5)
         uint32_t cbNext = 0, prNext[4] = { 0, 0, 0, 0 };
-        auto fetch_consts = [&](const int t0)
+        // (ROWLDS / OFFCHAIN: only the fetch ahead of the first block can reach before entry 0 - every later one starts at t0 >= 8 - and only that one clamps)
+        // ROWLDS: no cb, and a block fetches its OWN pr[] when it starts (first needed three rows later, one row later in a 2-row tail; the first block needs none): no
+        // second set of registers, no copies
+        auto fetch_consts = [&](const int t0, const bool first, uint32_t& cbDst, uint32_t (&prDst)[4])
         {
+            auto cl = [&](const int i) { return ((ROWLDS || OFFCHAIN) && !first) ? i : (i < 0 ? 0 : i); };
             const int i0 = t0 - 7 + (lane & 7);
-            cbNext = ctab[i0 < 0 ? 0 : i0];
+            if (!ROWLDS) cbDst = ctab[cl(i0)];
             if (QUAD64)
             {
                 const int a0 = t0 - 7 + (lane >> 4), a1 = t0 - 7 + oddRow;
-                prNext[0] = ctab[a0 < 0 ? 0 : a0]; prNext[1] = ctab[a0 + 4 < 0 ? 0 : a0 + 4];
-                prNext[2] = ctab[a1 < 0 ? 0 : a1]; prNext[3] = ctab[a1 + 4 < 0 ? 0 : a1 + 4];
+                prDst[0] = ctab[cl(a0)]; prDst[1] = ctab[cl(a0 + 4)];
+                prDst[2] = ctab[cl(a1)]; prDst[3] = ctab[cl(a1 + 4)];
             }
             else if (PAIR64)
             {
 #pragma unroll
-                for (int q = 0; q < 4; q++) { const int i = t0 - 7 + 2 * q + oddRow; prNext[q] = ctab[i < 0 ? 0 : i]; }
+                for (int q = 0; q < 4; q++) { const int i = t0 - 7 + 2 * q + oddRow; prDst[q] = ctab[cl(i)]; }
             }
         };
-        if (CTAB) fetch_consts(0);
+        if (CTAB && !ROWLDS) fetch_consts(0, true, cbNext, prNext);
+        // ROWLDS: the rows' constants in VGPRs, read from the table with wave-uniform addresses (the LDS broadcasts them; no v_readlane per row).  Two rows ahead, a pair
+        // at a time - four registers live: every even row p fetches the entries of rows p + 2 and p + 3, rows 6 / 7 those of the NEXT block's rows 0 / 1 (the first block
+        // only completes its row 7, m = 0)
+        uint32_t sbv[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+        auto fetch_rows = [&](const int t0, const int p, const bool first)
+        {
+#pragma unroll
+            for (int k = 0; k < 2; k++) { const int i = t0 - 7 + p + 2 + k; sbv[(p + 2 + k) & 7] = ctab[first && i < 0 ? 0 : i]; }
+        };
 
         auto rows8 = [&](auto firstTag, auto nrowsTag, const int t0)
         {
             constexpr bool FIRST = decltype(firstTag)::value;
             constexpr int NROWS = decltype(nrowsTag)::value;
-            const uint32_t bb = block_off(t0), bn = block_off(t0 + 8);
+            uint32_t bb, bn;
+            if (OFFCHAIN)
+            {   // this block's offset is the one the block before it computed for its prefetch; the next one: the group's base, the rows' share (uniform) and the skew byte
+                bb = offCur;
+                bn = colOff + (uint32_t)((t0 + 8) * pitch) + ((skewPack >> ((((t0 >> 3) + 1) & 3) * 8)) & 0xffu);
+                asm volatile("" : "+v"(bn));
+                offCur = bn;
+            }
+            else { bb = block_off(t0); bn = block_off(t0 + 8); }
             uint32_t bb4 = bb + 4 * pitch;
             if (LD64 || RING) asm volatile("" : "+v"(bb4));
             const int mb = t0 - 7;
             uint32_t cb = 0, pr[4] = { 0, 0, 0, 0 };
-            if (CTAB)
+            if (ROWLDS) { if (!FIRST) fetch_consts(t0, false, cb, pr); }
+            else if (CTAB)
             {
                 cb = cbNext;
 #pragma unroll
                 for (int q = 0; q < 4; q++) pr[q] = prNext[q];
-                fetch_consts(t0 + 8);
+                fetch_consts(t0 + 8, false, cbNext, prNext);
             }
             uint32_t v32even = 0, sbEven = 0, pairSum = 0;
 #pragma unroll
             for (int p = 0; p < NROWS; p++)
             {
+                if (ROWLDS && (p & 1) == 0) fetch_rows(t0, p, FIRST);
                 if ((p & 1) == 0)
                 {
                     if (LDA) { if (p + 2 < 8) ldpairA(buf[((p >> 1) + 1) & 1], bb, p + 2); else ldpairA(buf[((p >> 1) + 1) & 1], bn, 0); }
@@ -755,11 +820,18 @@ __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOf
                     const uint32_t v16 = __builtin_amdgcn_perm(qhi, qlo, selK);
                     const uint32_t v32 = (uint32_t)row_sum_of_quads((int)v16);
                     // costY[m] << 8 | m: an SGPR from the block's table entries, or built from round 4's per-row load
-                    const uint32_t sb = CTAB ? (uint32_t)__builtin_amdgcn_readlane((int)cb, p) : (((uint32_t)a.costY[m] << 8) | (uint32_t)m);
+                    const uint32_t sb = ROWLDS ? sbv[p] : CTAB ? (uint32_t)__builtin_amdgcn_readlane((int)cb, p) : (((uint32_t)a.costY[m] << 8) | (uint32_t)m);
                     if (COLMIN)
                     {
                         uint32_t k0, k1, k2, k3;
-                        if (MAD16)
+                        if (MAD16 && ROWLDS)
+                        {
+                            asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(k0) : "v"(lo), "s"(c256), "v"(sb));
+                            asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(k1) : "v"(lo), "s"(c256), "v"(sb));
+                            asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(k2) : "v"(hi), "s"(c256), "v"(sb));
+                            asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(k3) : "v"(hi), "s"(c256), "v"(sb));
+                        }
+                        else if (MAD16)
                         {   // u16 half * 256 + sb: the same value as (s << 8) + sb (s <= 16320)
                             asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(k0) : "v"(lo), "v"(c256), "s"(sb));
                             asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(k1) : "v"(lo), "v"(c256), "s"(sb));
@@ -1294,8 +1366,9 @@ int launch_me_cand(const x265hip_me_params* p, hipStream_t s);       // me_cand_
 
 // the flag set the minima-only 8-bit launch uses by default (-1 = round 4's kernel): what measured fastest on one box, profiles/r05_me_flags_ab.txt
 static const bool W2_DEFAULT = true;          // the 16-bit twin (me_ctu_w2_kernel): 2.60 -> 2.35 ms at 4K, 9.95 -> 8.95 ms at 8K (one box, interleaved: profiles/r05_me10_ab.txt)
-static const int Q2_DEFAULT_FLAGS = 1278;     // CTAB | PAIR64 | DEFERX | COLMIN | MASK | RING | QUAD64 (254: 1.24 ms against round 4's 1.42 at 4K, three interleaved rounds) | MAD16
+static const int Q2_DEFAULT_FLAGS = 13566;    // CTAB | PAIR64 | DEFERX | COLMIN | MASK | RING | QUAD64 (254: 1.24 ms against round 4's 1.42 at 4K, three interleaved rounds) | MAD16
                                               // (1.107 -> 1.064 ms, every step of five alternating pairs below the parent's: profiles/me_tailcut_mad16.txt)
+                                              // | ROWLDS | OFFCHAIN (13566: 1.066 -> 1.037 ms, profiles/me_emission_rowlds_offchain.txt)
 
 // Every A/B switch of the search launches, read ONCE (round-5 advisor: some were read per launch - getenv in a hot path, not thread-safe against setenv in the host
 // process - and x265hip_me_minima_kernel_name re-derived the selection on its own and could disagree with the launch).  x265hip_me_env_refresh() re-reads them: a
@@ -1452,8 +1525,9 @@ static int launch_me(const x265hip_me_params* p, hipStream_t s)
 #define LAUNCH_Q2(FLV) LAUNCH_Q2P(256, FLV)
                     switch (q2Flags)
                     {
-                    /* the single flags, the sets the profile tables name, the default (profiles/r05_me_flags_ab.txt lists more combinations: they were instantiated for the A/B visits) */
-                    LAUNCH_Q2(0) LAUNCH_Q2(1) LAUNCH_Q2(2) LAUNCH_Q2(4) LAUNCH_Q2(8) LAUNCH_Q2(32) LAUNCH_Q2(62) LAUNCH_Q2(254) LAUNCH_Q2(1278) LAUNCH_Q2P(320, 446) LAUNCH_Q2P(320, 256)
+                    /* the single flags, the sets the profile tables name, the default (profiles/r05_me_flags_ab.txt lists more combinations: they were instantiated for the A/B visits);
+                       5374 / 9470 = 1278 | ROWLDS / 1278 | OFFCHAIN alone (tests/test_gpu_me_emission.py) */
+                    LAUNCH_Q2(0) LAUNCH_Q2(1) LAUNCH_Q2(2) LAUNCH_Q2(4) LAUNCH_Q2(8) LAUNCH_Q2(32) LAUNCH_Q2(62) LAUNCH_Q2(254) LAUNCH_Q2(1278) LAUNCH_Q2(5374) LAUNCH_Q2(9470) LAUNCH_Q2(13566) LAUNCH_Q2P(320, 446) LAUNCH_Q2P(320, 256)
                     default: set_error("me_fullsearch: X265HIP_ME_Q2_FLAGS %d is not an instantiated combination", q2Flags); return X265HIP_EINVAL;
                     }
 #undef LAUNCH_Q2

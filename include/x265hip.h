@@ -127,7 +127,10 @@ int x265hip_pixelcmp_batch(int kind, int depth, int w, int h,
  *                PU order) = cost << 32 | (mvy_index * (2*range+1) + mvx_index); must be pre-set to
  *                all-ones by the caller (x265hip_me_best_reset).  Ties resolve to the smallest raster
  *                index, i.e. the reference's scan order with its strict '<'.
- *   cost_x/y   : uint16 [2*range+1] mv bit-cost tables built on the host (bitcost.cpp:51-55).
+ *   cost_x/y   : uint16 [2*range+1] mv bit-cost tables built on the host (bitcost.cpp:51-55).  ANY uint16 values, the two tables
+ *                independent of each other: every kernel of the launch table orders candidates by the exact 32-bit sum (tables of
+ *                65535 on pictures whose SADs are at their maxima included - tests/test_gpu_me_cases.py).  16-bit samples: windows
+ *                up to +-76; +-77 and beyond need more LDS than a workgroup has and return X265HIP_EINVAL with nothing written.
  */
 typedef struct x265hip_me_params
 {

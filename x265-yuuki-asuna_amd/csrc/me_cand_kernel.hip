@@ -383,7 +383,7 @@ __global__ void __launch_bounds__(256, 2) me_ctu_c_kernel(MECandArgs a)
     if (BEST)
     {
         // merge the lanes' running keys: cost << 8 | step << 2 | column  ->  (cost, raster index), minimum over the wavefront, one
-        // 64-bit atomicMin per (wavefront, PU).  8x8 / 16x16 costs fit 18 bits (65280 + 2 * 65535), so with a raster index below
+        // 64-bit atomicMin per (wavefront, PU).  8x8 / 16x16 costs fit 18 bits (65280 + 2 * 65535 = 196350 < 0x3ffff, any uint16 tables), so with a raster index below
         // 2^14 one 32-bit reduction orders both; the three largest levels (and wide windows) reduce cost first, then the index.
         unsigned long long* out = a.best + (size_t)ctu * 85;
         const bool narrow = NC * NC <= 16384;

@@ -319,10 +319,13 @@ __global__ void __launch_bounds__(SURF && BEST ? 768 : 1024, SURF && BEST ? 3 : 
                 d[q][0] = lp[0]; d[q][1] = lp[1]; d[q][2] = lp[2];
             }
         };
-        // Row-local 32-bit keys: inside one column group only the row m varies, so `cost << 10 | m << 2 | k` (8x8,
-        // cost < 2^17) and `cost << 8 | m` (upper levels, cost < 2^22; m < 256) order candidates exactly like
-        // (cost, raster index); they are widened and merged into the 64-bit running minima once per group.
-        // Pad columns (>= 2R+1) get a cost offset no real candidate reaches.
+        // Row-local 32-bit keys: inside one column group only the row m varies, so `cost << 10 | m << 2 | k` (8x8:
+        // the shift leaves the cost 22 bits) and `cost << 8 | m` (upper levels: 24 bits; m < 256) order candidates
+        // exactly like (cost, raster index); they are widened and merged into the 64-bit running minima once per group.
+        // With ANY uint16 tables a real cost is at most 16320 + 2 * 65535 = 147390 < 2^18 (8x8) and
+        // 1044480 + 2 * 65535 = 1175550 < 2^21 (64x64).  Pad columns (>= 2R+1) carry 2^20 (8x8) / 2^23 (upper levels) in
+        // place of costX - above every real cost, and with a full SAD and costY on top still inside 22 / 24 bits
+        // (tests/test_gpu_me_cases.py runs tables of 65535 on flat pictures through every kernel here).
         uint32_t cxk4[4] = { 0, 0, 0, 0 }, cxL = 0;      // (costX << 2 | k) per column; this lane's own column cost
         uint32_t r8 = 0xffffffffu, r16 = 0xffffffffu, r32 = 0xffffffffu, r64 = 0xffffffffu;
         uint32_t r8c[4] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu };      // VAR & 1
@@ -960,7 +963,8 @@ __global__ void __launch_bounds__(1024, 4) me_ctu_q2_kernel(MEArgs a, int ctabOf
 // columns, each window row is 6 dwords (12 pixels: even columns read pixel pairs as stored, odd columns through
 // v_alignbit 16) feeding 8 ring slots x 4 columns x 4 dwords = 128 v_sad_u16; the emission (transposed upper levels,
 // 16-byte group stores, row-local 32-bit keys) is the 8-bit kernel's.  Key widths hold for depth <= 10
-// (64x64 SAD + mv cost < 2^23); 12-bit pictures use the generic kernel.
+// (64x64 SAD + any two uint16 mv costs <= 4190208 + 131070 = 4321278: above 2^22, below the pad columns' 2^23, and a pad column's
+// 2^23 + 4321278 still fits the 24 bits `cost << 8` leaves); 12-bit pictures (64x64: up to 16904190 > 2^24) use the generic kernel.
 template <bool SURF, bool BEST, int PITCH, int VAR = 1>
 __global__ void __launch_bounds__(SURF && BEST ? 768 : 1024, SURF && BEST ? 3 : 4) me_ctu_w_kernel(MEArgs a)
 {

@@ -2015,6 +2015,53 @@ typedef struct x265hip_b_merge_decide_col_params
 } x265hip_b_merge_decide_col_params;
 int x265hip_b_merge_decide_col(const x265hip_b_merge_decide_col_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * AMVP for P pictures (csrc/merge_decide.h): x265hip_merge_decide_col with the inter candidate priced against its predictor.  The walk,
+ * its list, clip, prices, outputs and schedule are x265hip_merge_decide_col's; what changes is the inter cost the block decides against,
+ * and the block's mvp_idx and mvd come out.  One P slice with one reference, every block one 2Nx2N inter CU, RD level <= 2, no frame
+ * parallelism (m_bFrameParallel false in selectMVP), one slice.
+ *   neighbours : A0 = below left, A1 = left, B0 = above right, B1 = above, B2 = above left (CUData::getNeighbourMV, cudata.cpp:1810-1865);
+ *                available exactly as the merge list's neighbours are; a neighbour's motion is its unclipped mv_out.  Every block is inter
+ *                with refIdx 0: getDirectPMV (:1931-1944) is true exactly where the neighbour is available, getIndirectPMV never decides.
+ *   list       : CUData::getPMV (:1715-1807): left = A0 else A1; above = B0 else B1 else B2; two equal candidates count as one
+ *                (:1779-1780); with a collocated field, while fewer than two, the temporal candidate of x265hip_merge_decide_col (same
+ *                positions, same scaling; :1784-1801); the rest (0, 0).  Always two entries.  col_mv / col_delta NULL = no temporal MVP,
+ *                for the merge list and this list alike (the reference's bTemporalMVPEnabled governs both).
+ *   index      : Search::selectMVP (search.cpp:1992-2023): 0 if the two are equal, else the smaller plain SAD (bufSAD over the N x N luma
+ *                block) of predInterLumaPixel(fref, clipMv(amvp[i])), 0 on a tie.  Search::checkBestMVP (:2702-2713, called at :2455)
+ *                then takes the other one iff bitcost(mv, other) < bitcost(mv, chosen): the final index is the cheaper one in bits, and
+ *                selectMVP's choice only where the bits tie.
+ *   rate       : bitcost(mv, mvp) = (uint32_t)(bit_sizes[|qx - px|] + bit_sizes[|qy - py|] + 0.5f) (bitcost.h:54-58); a difference of
+ *                bit_sizes_len or more takes the LAST entry (2 * BC_MAX_MV + 1 = 65537 entries clamp nothing).
+ *                bits = base_bits + bitcost(mv, amvp[mvp_idx]); inter cost = inter_sa8d + ((bits * lambda8 + 128) >> 8) with the block's
+ *                lambda; mvd = mv - amvp[mvp_idx] per component.
+ *   choice     : the block keeps its searched vector iff this inter cost < the best merge cost (a tie stays merge).
+ * Boundary: in the reference the search itself runs around amvp[selectMVP] and charges mv - mvp while it searches.  Here the search is
+ * the picture-parallel one against (0, 0); what this entry makes faithful is everything after motionEstimate returns.
+ * inter_sa8d: the inter candidate's sa8d per block at element block * inter_sa8d_stride (x265hip_inter_sa8d_cost's cost, word 0: pass
+ * cost, stride 2); base_bits, bit_sizes (DEVICE float32): as x265hip_inter_sa8d_cost's.  base.base.inter_cost / inter_cost_stride are
+ * not read (may be NULL / 0).  Outputs besides the walk's, all DEVICE:
+ *   mvp_idx : uint8 [ctu][blocks], for EVERY block (a merged block's is what its inter candidate had)
+ *   mvd     : int32 [ctu][blocks][2] = {dx, dy} (a scaled temporal predictor reaches +-32767: the difference does not fit 16 bits)
+ *   amvp    : optional int32 [ctu][blocks][2]: the two candidates, packed qx | qy << 16
+ *   inter   : int32 [ctu][blocks][2] = {bits, cost} of the inter candidate
+ *   best    : (optional, of the base record) {-1, this inter cost} for an inter block
+ * Refused (X265HIP_EINVAL, before any device call): whatever x265hip_merge_decide_col refuses except the NULL inter_cost; NULL inter_sa8d,
+ * bit_sizes, mvp_idx, mvd or inter; inter_sa8d_stride < 1; base_bits outside [0, 4096]; bit_sizes_len < 1; mvp_idx, mvd, amvp or inter
+ * equal to each other or to another output. */
+typedef struct x265hip_merge_decide_amvp_params
+{
+    x265hip_merge_decide_col_params base;
+    const int32_t* inter_sa8d; intptr_t inter_sa8d_stride;
+    int base_bits;
+    const float* bit_sizes; int bit_sizes_len;
+    uint8_t* mvp_idx;
+    int32_t* mvd;
+    int32_t* amvp;
+    int32_t* inter;
+} x265hip_merge_decide_amvp_params;
+int x265hip_merge_decide_amvp(const x265hip_merge_decide_amvp_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -257,6 +257,13 @@ class MergeDecideColParams(ctypes.Structure):
     _fields_ = [("base", MergeDecideParams), ("col_mv", ctypes.c_void_p), ("col_delta", ctypes.c_void_p), ("cur_delta", ctypes.c_int)]
 
 
+class MergeDecideAmvpParams(ctypes.Structure):
+    """x265hip_merge_decide_amvp_params (include/x265hip.h)."""
+    _fields_ = [("base", MergeDecideColParams), ("inter_sa8d", ctypes.c_void_p), ("inter_sa8d_stride", ctypes.c_ssize_t), ("base_bits", ctypes.c_int),
+                ("bit_sizes", ctypes.c_void_p), ("bit_sizes_len", ctypes.c_int), ("mvp_idx", ctypes.c_void_p), ("mvd", ctypes.c_void_p),
+                ("amvp", ctypes.c_void_p), ("inter", ctypes.c_void_p)]
+
+
 class BMergeDecideColParams(ctypes.Structure):
     """x265hip_b_merge_decide_col_params (include/x265hip.h)."""
     _fields_ = [("base", BMergeDecideParams), ("col_mv", ctypes.c_void_p), ("col_delta", ctypes.c_void_p), ("cur_delta0", ctypes.c_int),
@@ -764,6 +771,29 @@ def merge_decide_col(depth, width, height, level, fenc, fenc_stride, fenc_off, f
     collocated field (col_field_build; device int32 / int16 [ctu][16]) or both None; cur_delta = curPOC - refPOC, not 0."""
     _merge_decide(depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_cost, lambda8, max_merge, merge, merge_idx,
                   mv_out, mv_pred, cost, best, inter_cost_stride, inter_cost_offset, qp, qp_map, lambda8_by_qp, stream, col_mv, col_delta, cur_delta)
+
+
+def merge_decide_amvp(depth, width, height, level, fenc, fenc_stride, fenc_off, fref, fref_stride, fref_off, mv, inter_sa8d, base_bits, bit_sizes, lambda8,
+                      max_merge, merge, merge_idx, mv_out, mv_pred, cost, mvp_idx, mvd, inter, amvp=None, col_mv=None, col_delta=None, cur_delta=1, best=None,
+                      inter_sa8d_stride=2, inter_sa8d_offset=0, qp=0, qp_map=None, lambda8_by_qp=None, stream=None):
+    """x265hip_merge_decide_amvp: merge_decide_col with the inter candidate priced against its AMVP predictor (CUData::getPMV,
+    Search::selectMVP, Search::checkBestMVP).  inter_sa8d: device int32 tensor, the block's sa8d at element inter_sa8d_offset + block *
+    inter_sa8d_stride (the defaults read the sa8d word of inter_sa8d_cost's pairs); base_bits / bit_sizes: as inter_sa8d_cost's; mvp_idx:
+    device uint8 [ctu][blocks] out; mvd, inter (and amvp): device int32 [ctu][blocks][2] out; col_mv / col_delta: a collocated field or
+    both None (no temporal MVP in either list); cur_delta = curPOC - refPOC, not 0."""
+    rec = MergeDecideAmvpParams()
+    p = rec.base.base
+    es = 1 if depth == 8 else 2
+    p.depth, p.width, p.height, p.level, p.qp, p.lambda8, p.max_merge = depth, width, height, level, int(qp), int(lambda8), int(max_merge)
+    p.fenc, p.fenc_stride = fenc.data_ptr() + fenc_off * es, fenc_stride
+    p.fref, p.fref_stride = fref.data_ptr() + fref_off * es, fref_stride
+    p.mv, p.qp_map, p.lambda8_by_qp = mv.data_ptr(), _p(qp_map), _p(lambda8_by_qp)
+    p.merge, p.merge_idx, p.mv_out, p.mv_pred, p.cost, p.best = merge.data_ptr(), merge_idx.data_ptr(), mv_out.data_ptr(), mv_pred.data_ptr(), cost.data_ptr(), _p(best)
+    rec.base.col_mv, rec.base.col_delta, rec.base.cur_delta = _p(col_mv), _p(col_delta), int(cur_delta)
+    rec.inter_sa8d, rec.inter_sa8d_stride = inter_sa8d.data_ptr() + 4 * int(inter_sa8d_offset), int(inter_sa8d_stride)
+    rec.base_bits, rec.bit_sizes, rec.bit_sizes_len = int(base_bits), bit_sizes.data_ptr(), int(bit_sizes.numel())
+    rec.mvp_idx, rec.mvd, rec.amvp, rec.inter = mvp_idx.data_ptr(), mvd.data_ptr(), _p(amvp), inter.data_ptr()
+    _call_merge_entry("x265hip_merge_decide_amvp", rec, stream)
 
 
 def col_field_build(depth, width, height, level, mv, poc_delta, col_mv, col_delta, intra=None, ref_idx=None, stream=None):

@@ -2062,15 +2062,38 @@ class MergeDecide(_MergeStage):
     unless its inter candidate is strictly cheaper.  Owns merge / merge_idx uint8 [ctu][blocks], mv_out (the CUs' motion, unclipped) and
     mv_pred (what the TU stages predict from) int32 [ctu*85][2], cost and best int32 [ctu][blocks][2]."""
 
-    def __init__(self, nctu, w64, h64, depth, level, device, max_merge=3, lambda8=1024, qp=0):
+    def __init__(self, nctu, w64, h64, depth, level, device, max_merge=3, lambda8=1024, qp=0, amvp=False, base_bits=2, rng=57):
+        """amvp: the inter candidate is priced against its AMVP predictor (x265hip_merge_decide_amvp; CUData::getPMV, Search::selectMVP,
+        Search::checkBestMVP; DESIGN.md section 22).  The stage then also owns mvp_idx uint8 [ctu][blocks], mvd, amvp and inter int32
+        [ctu][blocks][2] and the float bit-size table of 2 * BC_MAX_MV + 1 = 65537 entries, which holds every difference of two vectors
+        (rng, the search range, does not bound the table: a predictor may lie anywhere).  base_bits: see InterSa8dCost."""
+        import torch
         _MergeStage.__init__(self, nctu, w64, h64, depth, level, device, max_merge, lambda8, qp)
         self.mv_out, self.mv_pred = self._records(2, device)
+        self.amvp_on, self.base_bits, self.rng = bool(amvp), int(base_bits), int(rng)
+        if self.amvp_on:
+            nb = nctu * self.nblk
+            self.mvp_idx = torch.zeros(nb, dtype=torch.uint8, device=device)
+            self.mvd, self.amvp, self.inter = (torch.zeros(nb * 2, dtype=torch.int32, device=device) for _ in range(3))
+            self.bit_sizes = torch.from_numpy(hipabi.mv_bit_sizes(65537)).to(device)
 
-    def run(self, cur: DevicePicture, ref: DevicePicture, mv, inter_cost, stream=None, inter_cost_stride=2, inter_cost_offset=1, col=None, cur_delta=None):
+    def run(self, cur: DevicePicture, ref: DevicePicture, mv, inter_cost=None, stream=None, inter_cost_stride=2, inter_cost_offset=1, col=None, cur_delta=None,
+            inter_sa8d=None, inter_sa8d_stride=2, inter_sa8d_offset=0):
         """mv: the searched records; inter_cost: InterSa8dCost.cost (the pairs; the defaults read their cost word).  col: a ColField of
-        the collocated picture - the list then has the temporal candidate (x265hip_merge_decide_col) - with cur_delta = curPOC - refPOC."""
+        the collocated picture - the list then has the temporal candidate (x265hip_merge_decide_col) - with cur_delta = curPOC - refPOC.
+        A stage built with amvp takes inter_sa8d instead of inter_cost: InterSa8dCost.cost again (the defaults read the sa8d word)."""
         if col is not None and cur_delta is None:
             raise ValueError("MergeDecide.run: a collocated field needs cur_delta")
+        if self.amvp_on != (inter_sa8d is not None) or self.amvp_on != (inter_cost is None):
+            raise ValueError("MergeDecide.run: inter_sa8d goes with amvp=True, inter_cost with amvp=False")
+        if self.amvp_on:
+            hipabi.merge_decide_amvp(self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, cur.org, ref.t, ref.stride, ref.org, mv, inter_sa8d,
+                                     self.base_bits, self.bit_sizes, self.lambda8, self.max_merge, self.merge, self.merge_idx, self.mv_out, self.mv_pred,
+                                     self.cost, self.mvp_idx, self.mvd, self.inter, amvp=self.amvp, col_mv=None if col is None else col.col_mv,
+                                     col_delta=None if col is None else col.col_delta, cur_delta=1 if cur_delta is None else cur_delta, best=self.best,
+                                     inter_sa8d_stride=inter_sa8d_stride, inter_sa8d_offset=inter_sa8d_offset, qp=self.qp, qp_map=self.qp_map,
+                                     lambda8_by_qp=self.lambda8_by_qp, stream=stream)
+            return
         args = (self.depth, self.w64, self.h64, self.level, cur.t, cur.stride, cur.org, ref.t, ref.stride, ref.org, mv, inter_cost, self.lambda8,
                 self.max_merge, self.merge, self.merge_idx, self.mv_out, self.mv_pred, self.cost)
         kw = dict(best=self.best, inter_cost_stride=inter_cost_stride, inter_cost_offset=inter_cost_offset, qp=self.qp, qp_map=self.qp_map,
@@ -2081,8 +2104,11 @@ class MergeDecide(_MergeStage):
             hipabi.merge_decide_col(*args, col.col_mv, col.col_delta, cur_delta, **kw)
 
     def checksum(self):
-        return {"merge": _sum64(self.merge), "merge_idx": _sum64(self.merge_idx), "mv_out": _sum64(self.mv_out), "mv_pred": _sum64(self.mv_pred),
-                "merge_cost": _sum64(self.cost)}
+        out = {"merge": _sum64(self.merge), "merge_idx": _sum64(self.merge_idx), "mv_out": _sum64(self.mv_out), "mv_pred": _sum64(self.mv_pred),
+               "merge_cost": _sum64(self.cost)}
+        if self.amvp_on:
+            out.update(mvp_idx=_sum64(self.mvp_idx), mvd=_sum64(self.mvd), amvp=_sum64(self.amvp), inter=_sum64(self.inter))
+        return out
 
 
 class MergePFramePipeline(_Sa8dPStep):
@@ -2093,9 +2119,12 @@ class MergePFramePipeline(_Sa8dPStep):
     mean in IntraPFramePipeline; max_merge: --max-merge (the reference's default 3, param.cpp:199)."""
 
     def __init__(self, w64, h64, depth, device, rng=57, subme=2, level=2, qp=27, deblock=False, sao=False, chroma=False, sao_apply=False,
-                 sign_hide=False, sao_rdo=None, lambda8=1024, base_bits=2, max_merge=3, temporal_mvp=False):
+                 sign_hide=False, sao_rdo=None, lambda8=1024, base_bits=2, max_merge=3, temporal_mvp=False, amvp=False):
         _Sa8dPStep.__init__(self, w64, h64, depth, device, rng, subme, level, qp, deblock, sao, chroma, sao_apply, sign_hide, sao_rdo, lambda8, base_bits)
-        self.md = MergeDecide(self.nctu, w64, h64, depth, level, device, max_merge=max_merge, lambda8=lambda8, qp=qp)
+        # amvp: the walk prices the inter candidate against its AMVP predictor and puts out mvp_idx / mvd (DESIGN.md section 22); with
+        # temporal_mvp the predictor list has the temporal candidate too, without it neither list has
+        self.amvp = bool(amvp)
+        self.md = MergeDecide(self.nctu, w64, h64, depth, level, device, max_merge=max_merge, lambda8=lambda8, qp=qp, amvp=self.amvp, base_bits=base_bits, rng=rng)
         self.skip = None
         # temporal_mvp: the merge list has the temporal candidate (DESIGN.md section 21); self.col is then this picture's own field
         self.temporal_mvp = bool(temporal_mvp)
@@ -2114,13 +2143,14 @@ class MergePFramePipeline(_Sa8dPStep):
         mv = self._search(cur, ref, mark)
         self.ic.run(cur, ref, mv)
         mark("inter_cost")
+        cost = dict(inter_sa8d=self.ic.cost) if self.amvp else dict(inter_cost=self.ic.cost)      # the pairs: the walk reads word 0 / word 1
         if self.temporal_mvp:
             if col is self.col:
                 raise ValueError("MergePFramePipeline.run: col is this step's own field, which the run overwrites: hand a copy")
-            self.md.run(cur, ref, mv, self.ic.cost, col=col if col is not None else self.col.clear(), cur_delta=cur_delta)
+            self.md.run(cur, ref, mv, col=col if col is not None else self.col.clear(), cur_delta=cur_delta, **cost)
             self.col.build(self.md.mv_out, self.md.level, cur_delta)
         else:
-            self.md.run(cur, ref, mv, self.ic.cost)
+            self.md.run(cur, ref, mv, **cost)
         mark("merge")
         self._code(cur, ref, self.md.mv_pred, mark)
         self.skip = self.md.skip_flags(self.rc, self.rc_c if self.chroma else None)
